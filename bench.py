@@ -9,8 +9,20 @@ before the timed region.  The renderer carries the K steps in passes of `frame_b
 `frames_in_flight` HIP streams (the reference keeps 3 frames in flight, Renderer.swift:33); every frame is
 rendered in full and the running average is applied in frame order.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs DIR) and prints the line: `value`, `ms_per_step`,
+`config` and the `roofline` of the timed region's own launches (`under_overlap`).  Everything that takes legs of its own — the CPU baseline
+and its parity check, the strict max_bounces=1 figure, the latency leg with the serialised roofline, the on-chip calibration and, for N > 1,
+the `steady` leg — runs only with --full (--no-cpu-baseline / --no-strict / --no-latency / --steady-steps 0 still leave single legs out).
+
+--dump-outputs DIR: what the timed path computed by its last step, written right after the timed region (before any --full leg):
+  accumulation.npy      the (h, w, 4) float32 accumulation buffer the caller reads (warm-up + timed frames; N > 1: the image assembled on
+                        rank 0) — or, above 48 MiB, accumulation_sample.npy + accumulation_sample_index.npy: a fixed, seeded sample of its pixels
+                        and their float64 indices, the two within 48 MiB (all files under 64 MB)
+  ray_counts.npy        float64 [closest, shadow, primary] rays of the timed steps, counted on the device
+Same arguments, same inputs (scene, seeds, frame indices): two builds can be compared output for output.
 
 N > 1: one process per GPU, scene + BVH replicated.  Default `--shard tile` (BASELINE.json north_star): the image is
 sharded by 8x8 screen tile (tile_id % N == rank, total work fixed -> "strong" scaling); `--shard sample`: every rank
@@ -18,7 +30,7 @@ renders full frames of a disjoint Halton index range (per-GPU work fixed -> "wea
 accumulated locally and ONE RCCL reduce of the RGBA32F radiance buffer assembles the image on rank 0 inside the timed
 region.
 
-Prints ONE JSON line on rank 0.  Besides the driver's keys:
+Prints ONE JSON line on rank 0.  Besides the driver's keys (latency, calibration, cpu_baseline and the ALONE roofline with --full only):
   roofline        dominant kernel (bounce + shadow traversal) ALONE on the chip at the default pass size: algorithmic bytes of one
                   8-frame launch / its average launch duration (the kernel's own start/stop events on its launching stream, one
                   stream, nothing else in flight — measured in this run right after the timed region; profiles/ holds rocprofv3's
@@ -73,10 +85,37 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="gloo: rehearsal on one GPU box (ranks share GPUs, reduce on host)")
     ap.add_argument("--group-devices", default=None, help="--gpus N without torch.distributed.run: device ids of the C-ABI device group (default 0..N-1; '0,0' rehearses N = 2 on a one-GPU box)")
     ap.add_argument("--assemble", default="reduce", choices=["reduce", "compact"], help="N > 1, tile sharding: how the image is assembled on rank 0 — the ONE reduce(sum) of the whole RGBA32F buffers (north_star, default) or the compact form: every rank ships only the tiles it owns")
-    ap.add_argument("--steady-steps", type=int, default=240, help="N > 1: after the timed region, one more leg of this many steps (not part of value / ms_per_step) reported as \"steady\": the regime a long run reaches, beside the launch-bound figure of a short --steps (0 = skip)")
+    ap.add_argument("--steady-steps", type=int, default=None, help="N > 1, with --full: after the timed region, one more leg of this many steps (default 240; not part of value / ms_per_step) reported as \"steady\": the regime a long run reaches, beside the launch-bound figure of a short --steps (0 = skip)")
     ap.add_argument("--png", default=None, help="write the tonemapped image here (rank 0)")
     ap.add_argument("--dump-accum", default=None, help="write the assembled RGBA32F accumulation buffer (warm-up + timed frames) here as .npy (rank 0)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path computed by its last step as DIR/<name>.npy (rank 0; see the module docstring)")
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline figure: cpu_baseline + parity, strict, latency + calibration, and the steady leg for N > 1")
+    a = ap.parse_args()
+    if not a.full:          # a plain run: set-up, warm-up, the timed steps, the outputs, the line
+        if a.steady_steps:
+            print(f"bench.py: --steady-steps {a.steady_steps} ignored: the steady leg runs only with --full", file=sys.stderr)
+        a.no_cpu_baseline = a.no_strict = a.no_latency = True
+        a.steady_steps = 0
+    elif a.steady_steps is None:
+        a.steady_steps = 240
+    return a
+
+
+DUMP_MAX_BYTES = 48 << 20      # --dump-outputs: the image files (the whole buffer, or a sample + its float64 indices) stay within this; with the ray counts and the .npy headers, under 64 MB
+
+
+def dump_outputs(d, accum, rays):
+    """--dump-outputs: the accumulation buffer (float32; above DUMP_MAX_BYTES a fixed, seeded sample of its pixels, sample + indices within DUMP_MAX_BYTES) and the timed steps' ray counts (float64)."""
+    os.makedirs(d, exist_ok=True)
+    accum = np.ascontiguousarray(accum, dtype=np.float32)
+    if accum.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(d, "accumulation.npy"), accum)
+    else:
+        px = accum.reshape(-1, accum.shape[-1])
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], DUMP_MAX_BYTES // (px[0].nbytes + 8), replace=False))      # 8: the pixel's float64 index
+        np.save(os.path.join(d, "accumulation_sample.npy"), px[idx])
+        np.save(os.path.join(d, "accumulation_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "ray_counts.npy"), np.asarray(rays, dtype=np.float64))
 
 
 def csrc_hash():
@@ -256,8 +295,12 @@ def main_group(a):
                         "render_wall_ms": round(t_render * 1e3, 4), "gather_wall_ms": round((dt - t_render) * 1e3, 4),
                         "note": "ms_gpu_timed_draw: begin-to-end device time of the timed draw on each device (its own events); the draw's wall time is the slowest rank's plus the enqueue; gather_wall_ms is the one reduce(sum) of the image"},
            "roofline": None, "cpu_baseline": None}
-    if a.dump_accum:
-        np.save(a.dump_accum, g.gather())
+    if a.dump_accum or a.dump_outputs:
+        img = g.gather()
+        if a.dump_accum:
+            np.save(a.dump_accum, img)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, img, (closest, shadow, primary))
     if a.steady_steps > 0 and a.gpus > 1:          # one more leg, not part of value: the regime a long run reaches
         before = g.stats
         torch.cuda.synchronize(); t1 = time.perf_counter()
@@ -377,7 +420,9 @@ def main():
     # ---- N > 1: one more leg, NOT part of value / ms_per_step — the driver's short --steps is launch-bound on a rank of N (a few ms of work in ~20 dependent launches);
     # a long draw shows what the partition itself scales to
     steady = None
-    dump_img = sr.buffer.cpu().numpy().copy() if (world > 1 and rank == 0 and a.dump_accum) else None      # the timed region's image: the steady leg goes on accumulating
+    dump_img = sr.buffer.cpu().numpy().copy() if (world > 1 and rank == 0 and (a.dump_accum or a.dump_outputs)) else None      # the timed region's image: the steady leg goes on accumulating
+    if rank == 0 and a.dump_outputs:     # before any --full leg: the strict leg draws on the same renderer
+        dump_outputs(a.dump_outputs, dump_img if world > 1 else r.accumulation(), (closest, shadow, primary))
     if world > 1 and a.steady_steps > 0:
         if a.shard == "tile":            # the pass size a run of that length takes (ShardedRenderer sized it for warm-up + timed steps); one untimed pass so that the queues are re-sized outside the leg
             from metal_raytracing_amd.distributed import shard_frame_batch

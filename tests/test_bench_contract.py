@@ -87,7 +87,7 @@ def test_committed_driver_command_line_is_reproducible_from_profiles():
 
 @pytest.mark.gpu
 def test_bench_json_contract():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--width", "320", "--height", "180", "--cpu-threads", "4"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--width", "320", "--height", "180", "--cpu-threads", "4", "--full"],
                        capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]
@@ -128,7 +128,7 @@ def test_bench_two_ranks_on_one_gpu_assemble_the_one_rank_image(tmp_path):
     assert p1.returncode == 0, p1.stderr[-2000:]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29541",
-                         os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", *common, "--steady-steps", "12", "--dump-accum", two],
+                         os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", *common, "--full", "--steady-steps", "12", "--dump-accum", two],
                         capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
     assert p2.returncode == 0, p2.stderr[-3000:]
     d = json.loads([l for l in p2.stdout.strip().splitlines() if l.startswith("{")][-1])
@@ -162,7 +162,7 @@ def test_bench_group_path_assembles_the_one_rank_image(tmp_path):
     p1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *common, "--dump-accum", one], capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert p1.returncode == 0, p1.stderr[-2000:]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    p2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--group-devices", "0,0", *common, "--steady-steps", "12", "--assemble", "compact", "--dump-accum", two], capture_output=True, text=True, cwd=ROOT, timeout=600, env=env)
+    p2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--group-devices", "0,0", *common, "--full", "--steady-steps", "12", "--assemble", "compact", "--dump-accum", two], capture_output=True, text=True, cwd=ROOT, timeout=600, env=env)
     assert p2.returncode == 0, p2.stderr[-3000:]
     d = json.loads([l for l in p2.stdout.strip().splitlines() if l.startswith("{")][-1])
     assert d["config"]["reduce_mode"] == 2 and "compact" in d["config"]["reduce"] and d["steady"]["steps"] == 12 and d["steady"]["value"] > 0
@@ -179,3 +179,64 @@ def test_bench_argparse_defaults():
     for flag in ("--gpus", "--steps", "--warmup"):
         assert flag in src
     assert 'default=1)' in src.split('"--gpus"')[1][:60]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_what_the_full_run_computes(tmp_path):
+    """A plain run carries the headline keys and none of the --full legs; --dump-outputs writes the timed path's image and ray counts, the same bits as
+    --dump-accum and as a --full run of the same arguments (whose latency and strict legs come after the dump, the strict one on the same renderer)."""
+    import numpy as np
+    common = ["--steps", "6", "--warmup", "2", "--width", "320", "--height", "180"]
+    plain, full, acc = tmp_path / "plain", tmp_path / "full", str(tmp_path / "acc.npy")
+    p1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *common, "--dump-outputs", str(plain), "--dump-accum", acc], capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert p1.returncode == 0, p1.stderr[-2000:]
+    d1 = json.loads([l for l in p1.stdout.strip().splitlines() if l.startswith("{")][-1])
+    assert d1["steps"] == 6 and d1["warmup"] == 2 and d1["ms_per_step"] > 0 and d1["value"] > 0 and d1["cpu_baseline"] is None
+    assert not {"latency", "calibration", "strict_primary_plus_shadow", "parity", "ms_per_frame", "steady"} & set(d1)
+    p2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *common, "--full", "--no-cpu-baseline", "--dump-outputs", str(full)], capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert p2.returncode == 0, p2.stderr[-2000:]
+    d2 = json.loads([l for l in p2.stdout.strip().splitlines() if l.startswith("{")][-1])
+    assert "latency" in d2 and "strict_primary_plus_shadow" in d2
+    a = np.load(plain / "accumulation.npy")
+    assert a.dtype == np.float32 and a.shape == (180, 320, 4) and np.array_equal(a, np.load(acc)) and np.array_equal(a, np.load(full / "accumulation.npy"))
+    rays = np.load(plain / "ray_counts.npy")
+    rpf = d1["config"]["rays_per_frame"]
+    assert rays.dtype == np.float64 and list(rays) == [rpf["closest"] * 6, rpf["shadow"] * 6, rpf["primary"] * 6] and np.array_equal(rays, np.load(full / "ray_counts.npy"))
+
+
+def test_bench_plain_and_full_arguments_and_output_sample(tmp_path, monkeypatch, capsys):
+    """Without --full the legs beyond the headline are off whatever else is given; with it the --no-* options still take single legs out.  An image larger
+    than the dump limit is written as a fixed, seeded pixel sample with its indices."""
+    import numpy as np
+    monkeypatch.syspath_prepend(ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--steady-steps", "12"])
+    a = bench.parse()
+    assert a.steps == 7 and not a.full and a.no_cpu_baseline and a.no_strict and a.no_latency and a.steady_steps == 0 and a.dump_outputs is None
+    assert "--steady-steps 12 ignored" in capsys.readouterr().err          # an explicit leg that a plain run leaves out is said so
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-strict", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.no_strict and not a.no_cpu_baseline and not a.no_latency and a.steady_steps == 240 and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steady-steps", "12"])
+    assert bench.parse().steady_steps == 12 and capsys.readouterr().err == ""
+
+    def written(d):
+        return sum(f.stat().st_size for f in d.iterdir())
+    # the documented 3840x2160 config (C4): over the image limit, so sampled; sample + indices within DUMP_MAX_BYTES, all files under 64 MB
+    big = np.zeros((2160, 3840, 4), np.float32)
+    bench.dump_outputs(str(tmp_path / "c4"), big, (1, 2, 3))
+    assert not (tmp_path / "c4" / "accumulation.npy").exists() and written(tmp_path / "c4") < 64_000_000
+    assert sum(np.load(tmp_path / "c4" / f).nbytes for f in ("accumulation_sample.npy", "accumulation_sample_index.npy")) <= bench.DUMP_MAX_BYTES
+    del big
+    img = np.random.default_rng(3).random((40, 50, 4), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), img, (1, 2, 3))
+    assert np.array_equal(np.load(tmp_path / "whole" / "accumulation.npy"), img)
+    assert np.load(tmp_path / "whole" / "ray_counts.npy").tolist() == [1.0, 2.0, 3.0]
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", (16 + 8) * 300)
+    for k in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / k), img, (1, 2, 3))
+        assert not (tmp_path / k / "accumulation.npy").exists()
+    s, i = np.load(tmp_path / "s1" / "accumulation_sample.npy"), np.load(tmp_path / "s1" / "accumulation_sample_index.npy")
+    assert s.dtype == np.float32 and s.shape == (300, 4) and i.dtype == np.float64 and len(set(i.tolist())) == 300 and np.all(np.diff(i) > 0)
+    assert s.nbytes + i.nbytes <= bench.DUMP_MAX_BYTES
+    assert np.array_equal(s, img.reshape(-1, 4)[i.astype(np.int64)]) and np.array_equal(s, np.load(tmp_path / "s2" / "accumulation_sample.npy"))
