@@ -311,10 +311,13 @@ int mrt_renderer_write_accum_from_device(MRTRenderer r, const void *device_ptr, 
  * (rank, world) is tile lt * world + rank of the image (8 x 8 tiles, row-major over the image), its pixels row-major, pixels outside the image 0.
  *   _shard_tiles   tiles of this renderer's image that shard (rank, world) owns
  *   _pack_owned    this renderer's accumulation buffer -> the compact buffer of ITS shard (mrt_renderer_set_shard), enqueued on its stream
- *   _unpack_tiles  the compact buffer of shard (rank, world) -> this renderer's accumulation buffer, at those tiles' pixels                                          */
+ *   _unpack_tiles  the compact buffer of shard (rank, world) -> this renderer's accumulation buffer, at those tiles' pixels
+ *   _unpack_tiles_into  the same into `image` instead (device memory, width*height*16 bytes of this renderer's size), enqueued on its stream: the root assembles the
+ *                  image in a buffer of its own and its accumulation buffer keeps its shard (a later draw or reduce would otherwise carry the other shards' pixels)  */
 int mrt_renderer_shard_tiles(MRTRenderer r, int32_t rank, int32_t world, uint64_t *tiles);
 int mrt_renderer_pack_owned_tiles(MRTRenderer r, void *device_ptr, size_t nbytes);
 int mrt_renderer_unpack_tiles(MRTRenderer r, const void *device_ptr, size_t nbytes, int32_t rank, int32_t world);
+int mrt_renderer_unpack_tiles_into(MRTRenderer r, void *image, size_t image_nbytes, const void *device_ptr, size_t nbytes, int32_t rank, int32_t world);
 /* fragmentShader (Shaders.metal:39-52): Reinhard c/(1+c), top row first (flipped), RGBA8.      */
 int mrt_renderer_read_tonemapped_rgba8(MRTRenderer r, uint8_t *rgba, size_t nbytes);
 int mrt_renderer_stats(MRTRenderer r, MRTRenderStats *out);
@@ -328,6 +331,8 @@ int mrt_renderer_kernel_times(MRTRenderer r, MRTKernelTimes *out);   /* waits fo
  * RGBA32F buffer — ncclReduce over xGMI (RCCL is opened when a group of several distinct devices is created), or peer copies + add.
  * The assembled image is bit-identical to the single-device image.                                                                  */
 int mrt_group_create(const int *device_ids, int32_t n, MRTGroup *out);
+/* Destroy the group renderers of a group, and any scene made on one of its contexts (mrt_group_context), before the group: while any is alive
+ * the call is refused — MRT_ERR_STATE, nothing is freed.                                                                                */
 int mrt_group_destroy(MRTGroup g);
 int mrt_group_size(MRTGroup g, int32_t *n);
 int mrt_group_context(MRTGroup g, int32_t rank, MRTContext *ctx);                  /* borrowed: the group owns its contexts            */

@@ -174,6 +174,7 @@ SIGNATURES = {
     "mrt_renderer_shard_tiles": (C.c_int, [_P, _I32, _I32, C.POINTER(C.c_uint64)]),
     "mrt_renderer_pack_owned_tiles": (C.c_int, [_P, _P, _SZ]),
     "mrt_renderer_unpack_tiles": (C.c_int, [_P, _P, _SZ, _I32, _I32]),
+    "mrt_renderer_unpack_tiles_into": (C.c_int, [_P, _P, _SZ, _P, _SZ, _I32, _I32]),
     "mrt_renderer_read_tonemapped_rgba8": (C.c_int, [_P, _P, _SZ]),
     "mrt_renderer_stats": (C.c_int, [_P, C.POINTER(RenderStats)]),
     "mrt_renderer_reset_stats": (C.c_int, [_P]),

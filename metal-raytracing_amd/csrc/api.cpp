@@ -654,6 +654,14 @@ int mrt_renderer_unpack_tiles(MRTRenderer r, const void *dptr, size_t nbytes, in
     return r->r.unpack_tiles(dptr, nbytes, rank, world);
     MRT_CATCH
 }
+int mrt_renderer_unpack_tiles_into(MRTRenderer r, void *image, size_t image_nbytes, const void *dptr, size_t nbytes, int32_t rank, int32_t world) {
+    MRT_TRY
+    RENDERER_PROLOGUE("mrt_renderer_unpack_tiles_into")
+    REQUIRE(dptr || nbytes == 0, "mrt_renderer_unpack_tiles_into: NULL pointer");
+    REQUIRE(image && image_nbytes == (size_t)r->r.width * r->r.height * 16, "mrt_renderer_unpack_tiles_into: image must be width*height*16 bytes of device memory");
+    return mrt::unpack_tiles_into((float4 *)image, r->r.width, r->r.height, dptr, nbytes, rank, world, r->r.stream);
+    MRT_CATCH
+}
 int mrt_renderer_read_tonemapped_rgba8(MRTRenderer r, uint8_t *rgba, size_t nbytes) {
     MRT_TRY
     RENDERER_PROLOGUE("mrt_renderer_read_tonemapped_rgba8")

@@ -130,6 +130,7 @@ struct MRTGroup_ {
     int reduce = MRT_REDUCE_PEER_COPY;
     std::string reduce_note;
     RankPool pool;                        // one host thread per device (rank 0: the caller's)
+    int renderers = 0;                    // group renderers made on this group and not yet destroyed: mrt_group_destroy refuses while any is left
 };
 struct MRTGroupRenderer_ {
     MRTGroup g = nullptr;
@@ -173,6 +174,9 @@ int mrt_group_create(const int *device_ids, int32_t n, MRTGroup *out) {
 }
 int mrt_group_destroy(MRTGroup g) {
     if (!g) return MRT_OK;
+    // a group renderer keeps its group (contexts, streams, rank threads) to the end: destroying the group under it would leave it a dangling pointer and the contexts leaked
+    if (g->renderers != 0) { mrt::set_error("mrt_group_destroy: " + std::to_string(g->renderers) + " group renderer(s) of this group are still alive: destroy them first"); return MRT_ERR_STATE; }
+    for (auto c : g->ctx) if (c->live != 0) { mrt::set_error("mrt_group_destroy: a scene or renderer made on one of this group's contexts (e.g. a group renderer's template scene) is still alive: destroy it first"); return MRT_ERR_STATE; }
     for (size_t i = 0; i < g->comms.size(); i++) if (g->comms[i]) { (void)hipSetDevice(g->devices[i]); (void)g_rccl.CommDestroy(g->comms[i]); }
     for (auto c : g->ctx) mrt_context_destroy(c);
     delete g;
@@ -219,6 +223,7 @@ int mrt_group_renderer_destroy(MRTGroupRenderer gr) {
     for (size_t i = 0; i < gr->done.size(); i++) if (gr->done[i]) { (void)hipSetDevice(gr->g->devices[i]); (void)hipEventDestroy(gr->done[i]); }
     for (size_t i = 0; i < gr->scenes.size(); i++) if (gr->scenes[i]) mrt_scene_destroy(gr->scenes[i]);
     if (!gr->g->devices.empty()) (void)hipSetDevice(gr->g->devices[0]);
+    gr->g->renderers--;
     delete gr;
     return MRT_OK;
 }
@@ -228,7 +233,7 @@ int mrt_group_renderer_create(MRTGroup g, MRTScene scene, int32_t width, int32_t
     *out = nullptr;
     std::unique_ptr<MRTGroupRenderer_> gr(new MRTGroupRenderer_());
     struct Undo { MRTGroupRenderer_ *p; ~Undo() { if (p) mrt_group_renderer_destroy(p); } } undo{gr.get()};
-    gr->g = g; gr->width = width; gr->height = height;
+    gr->g = g; gr->width = width; gr->height = height; g->renderers++;          // (from here on every way out goes through mrt_group_renderer_destroy, which counts it off)
     const int n = (int)g->ctx.size();
     MRTGroupRenderer_ *raw = gr.release();        // from here on the Undo guard owns it
     raw->scenes.assign((size_t)n, nullptr); raw->r.assign((size_t)n, nullptr); raw->done.assign((size_t)n, nullptr);

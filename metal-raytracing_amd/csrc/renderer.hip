@@ -868,6 +868,17 @@ int Renderer::render(int n_frames) {                                   // Render
     fp.tiles_x = (width + 7) / 8; fp.tiles_local = tiles_local; fp.max_bounces = max_bounces;
     const uint32_t grid = std::max<uint32_t>(1u, (uint32_t)tiles_local);
     const bool two_level = sv.num_inst > 0;          // instanced scene: TLAS + BLASes walked by the same kernels (<TWO_LEVEL>)
+    if (tiles_local == 0) {
+        // a shard that owns no tile (more ranks than 8 x 8 tiles: rank 2 of 3 of a 9 x 5 image) has no pixel to render and its buffers stay 0; the launches sized
+        // by its queues would be empty grids (the shading of bounces >= 1: cdiv(capacity x batch, ...) = 0), which HIP refuses.  The frames count as drawn.
+        MRT_HIP(hipEventRecord(ev_begin, stream));
+        frame_index += (uint32_t)n_frames; frames_rendered += (uint64_t)n_frames;
+        ext_used = 0;
+        if (int rc = note_pass(stream)) return rc;
+        MRT_HIP(hipEventRecord(ev_end, stream));
+        pending_timing = true;
+        return MRT_OK;
+    }
     if (alloc_batch != batch_wanted()) {      // option (or the shard, under frame_batch = 0) changed since the buffers were sized
         MRT_HIP(hipStreamSynchronize(stream));
         const uint32_t keep_frame = frame_index; const int keep_cur = cur; const uint64_t keep_rendered = frames_rendered;

@@ -175,19 +175,20 @@ class ShardedRenderer:
         return self.buffer
 
     def _gather_compact(self, dst):
-        r = self.renderer; w, h = r.size
+        # the image is assembled in self.buffer — this rank's own tiles first, then every other shard's unpacked over it — never in the renderer's accumulation
+        # buffer: that must keep holding this rank's shard alone, or the next draw and reduce carry the other shards' pixels along (counted twice)
+        r = self.renderer
         dev = self.buffer.device
+        img, img_bytes = self.buffer.data_ptr(), self.buffer.numel() * 4
         def pack(rank):
             t = torch.empty((r.shard_tiles(rank, self.world) * 64, 4), dtype=torch.float32, device=dev)
             r.pack_owned_tiles(t.data_ptr(), t.numel() * 4); r.wait()
             return t.cpu() if self.backend == "gloo" else t
         def unpack(compact, rank):
             c = compact.to(dev).contiguous()
-            r.unpack_tiles(c.data_ptr(), c.numel() * 4, rank, self.world); r.wait()
-        r.wait()
-        shape = torch.empty((h, w, 4), dtype=torch.float32, device="cpu" if self.backend == "gloo" else dev)          # (only its shape is read when pack / unpack are given)
-        gather_compact(shape, dst, pack=pack, unpack=unpack)
-        r.copy_accum_to(self.buffer.data_ptr(), self.buffer.numel() * 4); r.wait()          # the root's accumulation buffer now holds the whole image
+            r.unpack_tiles_into(img, img_bytes, c.data_ptr(), c.numel() * 4, rank, self.world); r.wait()
+        r.copy_accum_to(img, img_bytes); r.wait()          # (other ranks: their partial buffer, as the reduce leaves it)
+        gather_compact(self.buffer, dst, pack=pack, unpack=unpack)          # (only the shape of self.buffer is read when pack / unpack are given)
         return self.buffer
 
     def close(self):

@@ -255,6 +255,10 @@ class Renderer:
     def unpack_tiles(self, device_ptr, nbytes, rank, world):
         check(lib.mrt_renderer_unpack_tiles(self.handle, C.c_void_p(device_ptr), nbytes, int(rank), int(world)))
 
+    def unpack_tiles_into(self, image_ptr, image_nbytes, device_ptr, nbytes, rank, world):
+        """unpack_tiles into a caller's (h, w, 4) float32 device image instead of this renderer's accumulation buffer."""
+        check(lib.mrt_renderer_unpack_tiles_into(self.handle, C.c_void_p(image_ptr), image_nbytes, C.c_void_p(device_ptr), nbytes, int(rank), int(world)))
+
     @property
     def stats(self):
         s = RenderStats()

@@ -255,8 +255,9 @@ def test_shards_sum_to_full_frame(mrt, orc, gpu_ctx):
 
 def test_shards_in_tile_groups_sum_to_full_frame(mrt, orc, gpu_ctx):
     """A sharded renderer whose passes carry one frame runs them as tile groups (group g of G of rank r of N = shard g N + r of G N): every rank's image is its shard of the
-    oracle's, the shards sum to the full frame and the ray counts add up — also when a rank owns so few tiles that groups are refused (tiles_local < 64)."""
-    for (w, h), world in (((512, 288), 3), ((96, 64), 3)):
+    oracle's, the shards sum to the full frame and the ray counts add up — also when a rank owns so few tiles that groups are refused (tiles_local < 64), and when
+    it owns none (9 x 5 is two tiles: rank 2 of 3 draws nothing, its frames still count)."""
+    for (w, h), world in (((512, 288), 3), ((96, 64), 3), ((9, 5), 3)):
         sc = mrt.CornellScene((w, h))
         full = mrt.Renderer((w, h), sc, ctx=gpu_ctx); full.draw(3, wait=True); f = full.accumulation(); full.close()
         acc = np.zeros_like(f); rays = 0
@@ -264,6 +265,7 @@ def test_shards_in_tile_groups_sum_to_full_frame(mrt, orc, gpu_ctx):
             r = mrt.Renderer((w, h), sc, ctx=gpu_ctx); r.set_shard(rank, world); r.set_option("frame_batch", 1); r.set_option("frames_in_flight", 1)
             r.draw(1, wait=True); r.draw(2, wait=True)
             assert r.get_option("groups_used") == (3 if w == 512 else 1)
+            assert r.stats.frames == 3 and r.framesCompleted == 3
             a = r.accumulation()
             oa, _ = oracle_render(orc, mrt, sc, w, h, 3, shard=(rank, world))
             assert np.array_equal(a, oa)

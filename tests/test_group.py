@@ -65,8 +65,60 @@ def test_group_compact_assemble_is_the_reduce(mrt, gpu_ctx, n):
     own = D.tile_owner_map(w, h, n) == 1
     got = r2.accumulation()
     assert np.array_equal(got[own], acc[own]) and np.array_equal(got[~own], base[~own])
+    # ... and into a caller's image (the root's assembly buffer): the tiles land there and the renderer's own accumulation stays as it was
+    img = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda:0"); torch.cuda.synchronize()
+    r2.unpack_tiles_into(img.data_ptr(), img.numel() * 4, t.data_ptr(), t.numel() * 4, 1, n); r2.wait()
+    into = img.cpu().numpy()
+    assert np.array_equal(into[own], acc[own]) and not into[~own].any() and np.array_equal(r2.accumulation(), got)
+    with pytest.raises(mrt.MRTError): r2.unpack_tiles_into(img.data_ptr(), img.numel() * 4 - 16, t.data_ptr(), t.numel() * 4, 1, n)
+    with pytest.raises(mrt.MRTError): r2.unpack_tiles_into(img.data_ptr(), img.numel() * 4, t.data_ptr(), t.numel() * 4 - 16, 1, n)
     with pytest.raises(mrt.MRTError): r.pack_owned_tiles(t.data_ptr(), t.numel() * 4 - 16)
     r.close(); r2.close()
+
+
+@pytest.mark.parametrize("size", [(203, 117), (9, 5)], ids=["203x117", "9x5"])
+@pytest.mark.parametrize("n", [2, 3])
+def test_group_reduce_mode_switches_between_draws(mrt, gpu_ctx, n, size):
+    """Peer copies + add, then compact, then back, with draws between the gathers: every image is one device's of the same frames, bit for bit — the compact
+    assemble writes the group's own image buffer, never a rank's accumulation.  9 x 5 is two tiles: rank 2 of 3 owns none (empty compact buffer)."""
+    w, h = size
+    sc = mrt.CornellScene((w, h))
+    ref = {f: _plain(mrt, gpu_ctx, sc, w, h, f)[0] for f in (2, 4, 5)}
+    got = []
+    with mrt.GroupRenderer((w, h), sc, [0] * n) as g:
+        assert g.reduce_mode[0] == 1
+        g.draw(2); got.append((2, "peer", g.gather()))
+        g.set_reduce_mode(2); got.append((2, "compact", g.gather()))
+        g.draw(2); got.append((4, "compact after a draw", g.gather()))
+        g.set_reduce_mode(1); g.draw(1); got.append((5, "peer after compact and a draw", g.gather()))
+        assert g.framesCompleted == 5
+    for frames, what, img in got:
+        assert np.array_equal(img.view(np.uint32), ref[frames].view(np.uint32)), (what, frames)
+
+
+def test_group_destroy_is_refused_while_a_group_renderer_lives(mrt, gpu_ctx):
+    """mrt_group_destroy with a live group renderer: MRT_ERR_STATE and nothing freed — the renderer still draws and gathers the one-device image — then
+    the renderer, its template scene and the group go in order."""
+    import ctypes as C
+    from metal_raytracing_amd._ffi import MRT_ERR_STATE, lib
+    w, h = 64, 48
+    sc = mrt.CornellScene((w, h))
+    ref, _ = _plain(mrt, gpu_ctx, sc, w, h, 3)
+    g = mrt.GroupRenderer((w, h), sc, [0, 0])
+    try:
+        assert lib.mrt_group_destroy(g.group) == MRT_ERR_STATE
+        assert b"still alive" in lib.mrt_last_error()
+        g.draw(3)
+        img = g.gather()
+        assert np.array_equal(img.view(np.uint32), ref.view(np.uint32))
+        assert lib.mrt_group_renderer_destroy(g.handle) == 0
+        g.handle = C.c_void_p()
+        assert lib.mrt_group_destroy(g.group) == MRT_ERR_STATE          # the template scene lives on the group's first context
+        g._template.close(); g._template = None
+        assert lib.mrt_group_destroy(g.group) == 0
+        g.group = C.c_void_p()
+    finally:
+        g.close()
 
 
 def test_group_accumulates_across_calls_and_options_reach_every_rank(mrt, gpu_ctx):
