@@ -36,6 +36,12 @@ int mrt_debug_intersect_stream(MRTScene scene, const MRTRay *rays, size_t n, int
 int mrt_debug_wide_histogram(MRTScene scene, uint32_t *out12);
 /* Diagnostics: the 8-wide nodes of a committed scene as they lie in device memory (80 bytes each); out == NULL: only the count.                      */
 int mrt_debug_read_wnodes(MRTScene scene, void *out, size_t nbytes, uint64_t *num_nodes);
+/* Diagnostics: one array of the committed 8-wide layout as it lies in device memory, for the exact box audit of tests/bvh_audit.py.  part: 0 = the 8-wide
+ * nodes (80 B each), 1 = wpackets as the triangle test reads them (v0 | id word, e1, e2: 48 B each), 2 = the instance rows (InstanceDev, 80 B: w2o rows,
+ * node / packet / gid / shading bases, ntri, blas, wroot), 3 = inst_box (64 B per instance: object-space BLAS box lo, hi, padded world box lo, hi),
+ * 4 = wtlas_index (uint32), 5 = a header of 8 uint32 {num_wnodes, tlas_wcap, num_inst, wide_depth, packets, deepest BLAS, wtlas entries, packet stride in
+ * float4}.  *count = elements of the part; out == NULL: only the count; otherwise nbytes must be count x the element size.                            */
+int mrt_debug_read_layout(MRTScene scene, int32_t part, void *out, size_t nbytes, uint64_t *count);
 /* Diagnostics: commits of this scene served by a refit (mrt_scene_update_mesh) since its last build.   */
 int mrt_debug_scene_refits(MRTScene scene, uint32_t *out);
 /* Diagnostics: host wall time (ms) of the last mrt_scene_commit of a flattened scene by phase: {upload staging, device allocations + upload enqueue,

@@ -738,6 +738,28 @@ int mrt_debug_read_wnodes(MRTScene scene, void *out, size_t nbytes, uint64_t *nu
     return MRT_OK;
     MRT_CATCH
 }
+// one array of the committed 8-wide layout as it lies in device memory (tests/bvh_audit.py decodes and checks every box)
+int mrt_debug_read_layout(MRTScene scene, int32_t part, void *out, size_t nbytes, uint64_t *count) {
+    MRT_TRY
+    REQUIRE(scene && count, "mrt_debug_read_layout: bad argument");
+    REQUIRE(part >= 0 && part <= 5, "mrt_debug_read_layout: part must be 0 .. 5");
+    if (!scene->committed) { mrt::set_error("mrt_debug_read_layout: scene not committed"); return MRT_ERR_STATE; }
+    const mrt::DeviceScene &d = scene->dev;
+    const size_t npk = d.wpackets.p ? d.wpackets.n / mrt::WPK : 0, ninst = d.num_inst, nwt = (d.num_inst && d.wtlas_index.p) ? d.wtlas_index.n : 0;
+    uint32_t header[8] = {d.num_wnodes, d.num_inst ? d.tlas_wcap : 0u, d.num_inst, (uint32_t)d.wide_depth, (uint32_t)npk, (uint32_t)d.blas_wdepth, (uint32_t)nwt, mrt::WPK};
+    const size_t elem[6] = {16 * (size_t)mrt::WNODE_STRIDE, 16 * (size_t)mrt::WPK, sizeof(mrt::InstanceDev), 64, 4, 4};
+    const size_t n[6] = {d.num_wnodes, npk, ninst, ninst, nwt, 8};
+    const void *src[6] = {d.wnodes.p, d.wpackets.p, d.inst.p, d.inst_box.p, d.wtlas_index.p, header};
+    *count = n[part];
+    if (out == nullptr) return MRT_OK;
+    REQUIRE(nbytes == n[part] * elem[part], "mrt_debug_read_layout: nbytes must be count x the element size of the part");
+    if (n[part] == 0) return MRT_OK;
+    if (part == 5) { memcpy(out, header, sizeof(header)); return MRT_OK; }
+    int rc = bind_device(scene->ctx); if (rc) return rc;
+    MRT_HIP(hipMemcpy(out, src[part], nbytes, hipMemcpyDeviceToHost));
+    return MRT_OK;
+    MRT_CATCH
+}
 // host wall time of the last commit of a flattened scene by phase (ms): staging, device allocations, topology, 8-wide emit, rope emit, validation
 int mrt_debug_scene_refits(MRTScene scene, uint32_t *out) {
     REQUIRE(scene && out, "mrt_debug_scene_refits: bad argument");

@@ -97,7 +97,7 @@ MRT_DEV bool traverse(const SceneView &s, f3 o, f3 d, float tmin, float tmax, Tr
             float tz0 = __builtin_fmaf(r0.z, iz, noz), tz1 = __builtin_fmaf(r1.z, iz, noz);
             float tn = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fmaxf(fminf(tz0, tz1), tmin));
             float tf = fminf(fminf(fmaxf(tx0, tx1), fmaxf(ty0, ty1)), fmaxf(tz0, tz1)) * 1.0000005f;
-            tf = fminf(tf, h.t);
+            tf = fminf(tf, h.t * 1.0000005f);      // the limit widened like the far side: a box whose entry rounds past the closest hit may still hold a hit at that t (a lower id, an any-hit limit one float past it)
             if (STATS) {      // bottleneck probes (diagnostics only): repeat the box arithmetic / the node fetch
                 for (int r = 0; r < tc->alu_dup; r++) {
                     float e = 1e-9f * (float)(r + 1);

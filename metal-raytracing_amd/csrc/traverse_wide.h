@@ -99,6 +99,7 @@ MRT_DEV void wide_node_test(const float4 n0, const float4 n1, const float4 n2, c
     const uint32_t nry[2] = {ny ? hy0 : ly0, ny ? hy1 : ly1}, fry[2] = {ny ? ly0 : hy0, ny ? ly1 : hy1};
     const uint32_t nrz[2] = {nz ? hz0 : lz0, nz ? hz1 : lz1}, frz[2] = {nz ? lz0 : hz0, nz ? lz1 : hz1};
     const uint32_t meta[2] = {__float_as_uint(n1.z), __float_as_uint(n1.w)};
+    const float tmax_w = tmax * 1.0000005f;      // the limit widened like the far side (SCALED gets it through S): a child whose entry rounds past the closest hit may still hold a hit at that t
     uint32_t nh = 0, th = 0;     // locals, not the reference parameters: `if (..) a |= x; else b |= y;` on references becomes a pointer select -> scratch
 #pragma unroll
     for (int i = 0; i < 8; i++) {
@@ -113,7 +114,7 @@ MRT_DEV void wide_node_test(const float4 n0, const float4 n1, const float4 n2, c
             tn = fmaxf(fmaxf(__builtin_fmaf(ubyte_f(nrx[w], k), ax, bx), __builtin_fmaf(ubyte_f(nry[w], k), ay, by)),
                        fmaxf(__builtin_fmaf(ubyte_f(nrz[w], k), az, bz), tmin));
             tf = fminf(fminf(fminf(__builtin_fmaf(ubyte_f(frx[w], k), ax, bx), __builtin_fmaf(ubyte_f(fry[w], k), ay, by)),
-                             __builtin_fmaf(ubyte_f(frz[w], k), az, bz)) * 1.0000005f, tmax);
+                             __builtin_fmaf(ubyte_f(frz[w], k), az, bz)) * 1.0000005f, tmax_w);
         }
         if (SCALED ? tn < tf : tn <= tf) {
             // no inner branch: an internal child's meta byte is 0 (empty triangle range), a leaf child's imask bit is 0

@@ -48,14 +48,51 @@ bool invert_affine(const float *xf, float rows[3][4]) {
 struct Box { float lo[3], hi[3]; };
 
 // world box of an instance: the corners of its BLAS root box through the object->world matrix; padded like the leaf boxes of
-// bvh_build.hip (1e-5 |coord| + 1e-6) plus the rounding of the ray's trip into object space
-Box instance_box(const float *xf, const float *lo, const float *hi) {
+// bvh_build.hip (1e-5 |coord| + 1e-6) plus the rounding of the ray's trip into object space.  That rounding is bounded per object axis k by
+// delta_k = gamma_4 (sum_j |R_kj| max|X_j| + |w_k|) for the float32 w2o rows (R | w) and world points X in the box: the root box is grown by delta
+// before its corners are mapped (an instance translated 1e4 from the origin needs ~5e-3, far more than the 4e-5 relative pad gives).  The bound covers
+// world points inside the box; the drift of the object-space DIRECTION, which grows with t and with the distance of the ray origin, is not bounded here.
+// Its constants: X and delta taken 10 % larger than computed, at most eight rounds of the fixed point.
+Box instance_box(const float *xf, const float *lo_in, const float *hi_in, const float rows[3][4]) {
+    double lo[3] = {lo_in[0], lo_in[1], lo_in[2]}, hi[3] = {hi_in[0], hi_in[1], hi_in[2]};
+    if (rows) {          // X depends on the box delta grows: iterate (a contraction unless cond(R) gamma_4 nears 1: a few rounds, then 10 % to spare)
+        const double g4 = 4.0 * 0x1p-24 / (1.0 - 4.0 * 0x1p-24);
+        Box cur = instance_box(xf, lo_in, hi_in, nullptr);
+        for (int it = 0; it < 8; it++) {
+            double X[3];
+            for (int j = 0; j < 3; j++) X[j] = 1.1 * std::max(std::fabs((double)cur.lo[j]), std::fabs((double)cur.hi[j]));
+            float glo[3], ghi[3];
+            for (int k = 0; k < 3; k++) {
+                const double dk = 1.1 * g4 * (std::fabs((double)rows[k][0]) * X[0] + std::fabs((double)rows[k][1]) * X[1] + std::fabs((double)rows[k][2]) * X[2] + std::fabs((double)rows[k][3]));
+                lo[k] = (double)lo_in[k] - dk; hi[k] = (double)hi_in[k] + dk;
+                glo[k] = std::nextafter((float)lo[k], -3.0e38f); ghi[k] = std::nextafter((float)hi[k], 3.0e38f);
+            }
+            const Box next = instance_box(xf, glo, ghi, nullptr);
+            bool grew = false;
+            for (int k = 0; k < 3; k++) grew = grew || next.lo[k] < cur.lo[k] || next.hi[k] > cur.hi[k];
+            cur = next;
+            if (!grew && it > 0) break;
+        }
+    }
+    // (with the rows: the corners also through the exact inverse of the float32 rows, the map the traversal's object-space ray really inverts)
+    double mi[3][4] = {};
+    if (rows) {
+        const double a[3][3] = {{rows[0][0], rows[0][1], rows[0][2]}, {rows[1][0], rows[1][1], rows[1][2]}, {rows[2][0], rows[2][1], rows[2][2]}};
+        const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) + a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++)
+            mi[r][c] = (a[(c + 1) % 3][(r + 1) % 3] * a[(c + 2) % 3][(r + 2) % 3] - a[(c + 1) % 3][(r + 2) % 3] * a[(c + 2) % 3][(r + 1) % 3]) / det;
+        for (int r = 0; r < 3; r++) mi[r][3] = -(mi[r][0] * rows[0][3] + mi[r][1] * rows[1][3] + mi[r][2] * rows[2][3]);
+    }
     Box b; for (int k = 0; k < 3; k++) { b.lo[k] = 3.0e38f; b.hi[k] = -3.0e38f; }
     for (int c = 0; c < 8; c++) {
         const double p[3] = {(c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2]};
         for (int k = 0; k < 3; k++) {
             const double w = (double)xf[k] * p[0] + (double)xf[4 + k] * p[1] + (double)xf[8 + k] * p[2] + (double)xf[12 + k];
             b.lo[k] = std::min(b.lo[k], (float)w); b.hi[k] = std::max(b.hi[k], (float)w);
+            if (rows) {
+                const double v = mi[k][0] * p[0] + mi[k][1] * p[1] + mi[k][2] * p[2] + mi[k][3];
+                b.lo[k] = std::min(b.lo[k], std::nextafter((float)v, -3.0e38f)); b.hi[k] = std::max(b.hi[k], std::nextafter((float)v, 3.0e38f));
+            }
         }
     }
     for (int k = 0; k < 3; k++) {
@@ -389,7 +426,7 @@ int update_tlas(const std::vector<HostMesh> &meshes, hipStream_t stream, DeviceS
         const bool ok = invert_affine(xf, rows);
         for (int r = 0; r < 3; r++) d.w2o[r] = ok ? make_float4(rows[r][0], rows[r][1], rows[r][2], rows[r][3]) : make_float4(0, 0, 0, 0);
         if (ok && d.ntri > 0) {
-            boxes[i] = instance_box(xf, &out.blas_lo[3 * (size_t)d.blas], &out.blas_hi[3 * (size_t)d.blas]); live.push_back((uint32_t)i);
+            boxes[i] = instance_box(xf, &out.blas_lo[3 * (size_t)d.blas], &out.blas_hi[3 * (size_t)d.blas], rows); live.push_back((uint32_t)i);
             h_box[4 * i] = make_float4(out.blas_lo[3 * (size_t)d.blas], out.blas_lo[3 * (size_t)d.blas + 1], out.blas_lo[3 * (size_t)d.blas + 2], 0);
             h_box[4 * i + 1] = make_float4(out.blas_hi[3 * (size_t)d.blas], out.blas_hi[3 * (size_t)d.blas + 1], out.blas_hi[3 * (size_t)d.blas + 2], 0);
             h_box[4 * i + 2] = make_float4(boxes[i].lo[0], boxes[i].lo[1], boxes[i].lo[2], 0); h_box[4 * i + 3] = make_float4(boxes[i].hi[0], boxes[i].hi[1], boxes[i].hi[2], 0);

@@ -130,6 +130,27 @@ class DeviceScene:
         check(lib.mrt_debug_stream_stats(self.handle, ptr(rays), rays.shape[0], 1 if any_hit else 0, per_wave, ptr(out), nw))
         return out
 
+    _LAYOUT_PARTS = {"wnodes": 0, "wpackets": 1, "instances": 2, "inst_box": 3, "wtlas_index": 4, "header": 5}
+
+    def read_layout(self, part):
+        """Diagnostics: one array of the committed 8-wide layout (mrt_debug_read_layout) as numpy — "wnodes" (n, 20) uint32, "wpackets" (n, 4 x stride)
+        uint32, "instances" (n, 20) uint32 (InstanceDev), "inst_box" (n, 16) float32, "wtlas_index" (n,) uint32, "header" (8,) uint32."""
+        k = self._LAYOUT_PARTS[part] if isinstance(part, str) else int(part)
+        n = C.c_uint64()
+        check(lib.mrt_debug_read_layout(self.handle, k, None, 0, C.byref(n)))
+        if k == 5:
+            out = np.zeros(8, np.uint32)
+        elif k == 4:
+            out = np.zeros(n.value, np.uint32)
+        else:
+            words = {0: 20, 2: 20, 3: 16}.get(k)
+            if words is None:
+                hdr = self.read_layout(5)
+                words = 4 * int(hdr[7])
+            out = np.zeros((n.value, words), np.float32 if k == 3 else np.uint32)
+        check(lib.mrt_debug_read_layout(self.handle, k, ptr(out), out.nbytes, C.byref(n)))
+        return out
+
     def close(self):
         if self.handle:
             lib.mrt_scene_destroy(self.handle)
