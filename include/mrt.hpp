@@ -187,6 +187,21 @@ class Renderer {                                                     // Renderer
     double option(const char *key) const { double v = 0; check(mrt_renderer_get_option(r_, key, &v)); return v; }
     std::vector<float> accumulation() { std::vector<float> a((size_t)w_ * h_ * 4); check(mrt_renderer_read_accum(r_, a.data(), a.size() * 4)); return a; }
     std::vector<uint8_t> tonemapped() { std::vector<uint8_t> a((size_t)w_ * h_ * 4); check(mrt_renderer_read_tonemapped_rgba8(r_, a.data(), a.size())); return a; }
+    // first-hit guide buffers and the denoiser (setOption("guides", 1) before drawing; no counterpart in the reference — mrt_abi.h)
+    struct Guides { std::vector<float> normalDepth, albedo; std::vector<int32_t> ids; };      // w x h x 4 each, row 0 = bottom
+    Guides guides() {
+        Guides g; const size_t n = (size_t)w_ * h_ * 4;
+        g.normalDepth.resize(n); g.albedo.resize(n); g.ids.resize(n);
+        check(mrt_renderer_read_guide(r_, MRT_GUIDE_NORMAL_DEPTH, g.normalDepth.data(), n * 4));
+        check(mrt_renderer_read_guide(r_, MRT_GUIDE_ALBEDO, g.albedo.data(), n * 4));
+        check(mrt_renderer_read_guide(r_, MRT_GUIDE_IDS, g.ids.data(), n * 4));
+        return g;
+    }
+    std::vector<float> denoise(const MRTDenoiseParams *params = nullptr) {                  // the a-trous filter of the accumulation buffer; nullptr = the defaults
+        check(mrt_renderer_denoise(r_, params));
+        std::vector<float> a((size_t)w_ * h_ * 4); check(mrt_renderer_read_denoised(r_, a.data(), a.size() * 4)); return a;
+    }
+    std::vector<uint8_t> denoisedTonemapped() { std::vector<uint8_t> a((size_t)w_ * h_ * 4); check(mrt_renderer_read_denoised_tonemapped_rgba8(r_, a.data(), a.size())); return a; }
     MRTRenderStats stats() { MRTRenderStats s; check(mrt_renderer_stats(r_, &s)); return s; }
     MRTSceneStats sceneStats() { MRTSceneStats s; check(mrt_scene_stats(scene_, &s)); return s; }
     int width() const { return w_; }

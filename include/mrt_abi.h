@@ -280,7 +280,7 @@ int mrt_renderer_get_uniforms(MRTRenderer r, MRTUniforms *uniforms);
  * per pass, 1..32: larger launches against more queue memory — "lane_bytes" per pass in flight; 0, the default, sizes it by the image: 8 at 1920 x 1080 pixels
  * per device and above, proportionally more for a smaller image or a shard of one, so that a pass always carries about the same number of pixel-frames; reads back as the value in force), "megakernel" (1: one launch
  * per frame, the lowest latency of a single frame; the default pipeline has the higher throughput), "materials" (1: the materials
- * extension — emission, specular lobe, refraction; max_bounces <= 16; the only key that changes the image).  Read-only through
+ * extension — emission, specular lobe, refraction; max_bounces <= 16; the only key that changes the image), "guides" (1: the first-hit guide buffers the denoiser reads, see mrt_renderer_read_guide below).  Read-only through
  * mrt_renderer_get_option: "lanes_used", "lane_bytes".                                                                              */
 int mrt_renderer_set_option(MRTRenderer r, const char *key, double value);
 int mrt_renderer_get_option(MRTRenderer r, const char *key, double *value);
@@ -323,6 +323,58 @@ int mrt_renderer_read_tonemapped_rgba8(MRTRenderer r, uint8_t *rgba, size_t nbyt
 int mrt_renderer_stats(MRTRenderer r, MRTRenderStats *out);
 int mrt_renderer_reset_stats(MRTRenderer r);
 int mrt_renderer_kernel_times(MRTRenderer r, MRTKernelTimes *out);   /* waits for the last render call */
+
+/* ---------------------------------------------------------------- first-hit guide buffers and the denoiser
+ * NOT in the reference: its only outputs are the accumulation target and the tonemap into the drawable (Renderer.swift:284-351); like the
+ * materials extension this is defined here.  With renderer option "guides" = 1 every mrt_renderer_render call also maintains three per-pixel
+ * buffers of the PRIMARY hit, laid out like the accumulation buffer (width*height entries of 16 bytes, row 0 = bottom of the image):
+ *   MRT_GUIDE_NORMAL_DEPTH  4 x float32  xyz: shading normal of the hit (normalised, world space), w: hit distance t
+ *   MRT_GUIDE_ALBEDO        4 x float32  rgb: baseColor of the hit submesh's material, a: 1 (coverage)
+ *   MRT_GUIDE_IDS           4 x int32    {type, instance_id, geometry_id, primitive_id} as MRTIntersection names them; a miss is {0, -1, -1, -1}
+ * A frame whose primary ray misses contributes zeros to the first two, which are running averages over the frames with the accumulation
+ * buffer's own rule and weights (Raytracing.metal:395-401: frameIndex == 0 replaces, otherwise (new + old * frameIndex) / (frameIndex + 1)), so
+ * the coverage is the share of frames that hit; the ids are those of the most recent frame.  The primary ray of a frame is the one its colour
+ * path starts with.  Resize and set_shard clear the guides; pixels a shard does not own stay all-zero.  The guides are complete when
+ * mrt_renderer_wait returns; they cost one more walk of the primary rays per frame, in a kernel of their own, and with "guides" = 0 (default)
+ * nothing is allocated or launched.  Set the option BEFORE frame 0 (or call mrt_renderer_set_frame_index(r, 0) after setting it): switched on at
+ * frame f > 0 the averages start from zero buffers with weight f / (f + 1), so normals, distance and coverage are scaled by about 1 / (f + 1) and
+ * the denoiser's normal term rejects every tap — the image comes back unfiltered.  MRT_ERR_STATE with "guides" = 0 or before a frame was rendered with it on.                           */
+enum { MRT_GUIDE_NORMAL_DEPTH = 0, MRT_GUIDE_ALBEDO = 1, MRT_GUIDE_IDS = 2, MRT_GUIDE_COUNT = 3 };
+int mrt_renderer_read_guide(MRTRenderer r, int32_t which, void *out, size_t nbytes);
+int mrt_renderer_copy_guide_to_device(MRTRenderer r, int32_t which, void *device_ptr, size_t nbytes);
+/* Edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010) of the accumulation buffer, guided by the normal / depth and
+ * albedo buffers, into a separate RGBA32F "denoised" buffer; the accumulation buffer is not modified.  Enqueued on the renderer's stream after
+ * everything rendered so far.  float32 throughout, operations in the order written:
+ *   A_p = max(albedo_p.rgb, 1e-3) per channel if demodulate and the pixel's coverage is not 0, else 1;  I_p = accum_p.rgb / A_p.  A pixel with
+ *   coverage 0 (no frame hit anything) is copied through in every iteration — its output is its accumulation value bit for bit — and is never a
+ *   tap of another pixel.  Iteration i (step = 1 << i, sc = sigma_color / step): over the 25 taps q = p + step * (dx, dy),
+ *   dy outer, dx inner, both -2 .. 2, skipping taps outside the image or of coverage 0; B = {1/16, 1/4, 3/8, 1/4, 1/16}, k(x) = max(0, 1 - x),
+ *   lum(c) = (0.2126 r + 0.7152 g) + 0.0722 b:
+ *     h = B[dy + 2] * B[dx + 2];  xn = (1 - max(0, (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z)) / sigma_normal;
+ *     xz = |t_p - t_q| / ((sigma_depth * t_p) * step);  xc = |lum(I_p) - lum(I_q)| / sc;
+ *     w = ((h * k(xn)^2) * k(xz)^2) * k(xc)^2 — the centre tap takes w = h;  sum += w * I_q, wsum += w;  I'_p = sum / wsum.
+ *   Output rgb = I_last * A_p, alpha 1.  n and t are the averaged guide values as stored.  A covered pixel all of whose taps have weight 0 comes
+ *   back as (h I_p) / h with h = 9/64: its value to two roundings (relative 2^-23 per iteration), not always to the bit.
+ * MRT_ERR_STATE without guides (as above) and on a sharded renderer (mrt_renderer_set_shard with world > 1): the filter needs its neighbours, and
+ * assembling the guides of a device group is not provided.  MRT_ERR_INVALID_ARGUMENT for parameters out of range.                          */
+typedef struct {
+    int32_t iterations;     /* 1..8, default 5: step 1, 2, 4, ...                 */
+    float   sigma_color;    /* > 0, on luminance of the filtered signal           */
+    float   sigma_normal;   /* > 0, on 1 - max(0, n_p . n_q)                      */
+    float   sigma_depth;    /* > 0, on |t_p - t_q| / (t_p * step)                 */
+    int32_t demodulate;     /* 1 (default): filter colour / albedo, multiply back */
+    int32_t _pad[3];
+} MRTDenoiseParams;         /* 32 B; NULL = defaults                              */
+#define MRT_DENOISE_DEFAULT_ITERATIONS   5
+#define MRT_DENOISE_DEFAULT_SIGMA_COLOR  4.0f     /* chosen on the CPU restatement against a 512-frame image (DESIGN.md "Guide buffers and denoiser") */
+#define MRT_DENOISE_DEFAULT_SIGMA_NORMAL 0.25f
+#define MRT_DENOISE_DEFAULT_SIGMA_DEPTH  0.25f
+int mrt_renderer_denoise(MRTRenderer r, const MRTDenoiseParams *params);
+/* The denoised image of the last mrt_renderer_denoise (MRT_ERR_STATE before the first): w*h RGBA32F, row 0 = bottom, as mrt_renderer_read_accum. */
+int mrt_renderer_read_denoised(MRTRenderer r, float *rgba, size_t nbytes);
+int mrt_renderer_copy_denoised_to_device(MRTRenderer r, void *device_ptr, size_t nbytes);
+/* mrt_renderer_read_tonemapped_rgba8 of the denoised image: what a host puts on screen.        */
+int mrt_renderer_read_denoised_tonemapped_rgba8(MRTRenderer r, uint8_t *rgba, size_t nbytes);
 
 /* ---------------------------------------------------------------- device group (multi-GPU, one process)
  * The reference creates ONE device and ONE queue (MTLCreateSystemDefaultDevice + makeCommandQueue, Renderer.swift:46-59); this is that

@@ -112,8 +112,17 @@ class KernelTimes(C.Structure):
 
 KERNEL_CLASSES = ("primary", "shade", "trace", "accumulate")
 
+
+class DenoiseParams(C.Structure):  # MRTDenoiseParams (include/mrt_abi.h; no counterpart in ShaderTypes.h)
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("demodulate", C.c_int32), ("_pad", C.c_int32 * 3)]
+
+
+GUIDE_NORMAL_DEPTH, GUIDE_ALBEDO, GUIDE_IDS = 0, 1, 2
+DENOISE_DEFAULTS = {"iterations": 5, "sigma_color": 4.0, "sigma_normal": 0.25, "sigma_depth": 0.25, "demodulate": 1}      # MRT_DENOISE_DEFAULT_*
+
 assert C.sizeof(Camera) == 64 and C.sizeof(Light) == 128 and C.sizeof(Uniforms) == 96 and C.sizeof(Material) == 64
-assert C.sizeof(Ray) == 32 and C.sizeof(Intersection) == 32
+assert C.sizeof(Ray) == 32 and C.sizeof(Intersection) == 32 and C.sizeof(DenoiseParams) == 32
 
 # ---------------------------------------------------------------- function table: every symbol include/mrt_abi.h declares
 _P, _I32, _U32, _F, _SZ = C.c_void_p, C.c_int32, C.c_uint32, C.c_float, C.c_size_t
@@ -176,6 +185,12 @@ SIGNATURES = {
     "mrt_renderer_unpack_tiles": (C.c_int, [_P, _P, _SZ, _I32, _I32]),
     "mrt_renderer_unpack_tiles_into": (C.c_int, [_P, _P, _SZ, _P, _SZ, _I32, _I32]),
     "mrt_renderer_read_tonemapped_rgba8": (C.c_int, [_P, _P, _SZ]),
+    "mrt_renderer_read_guide": (C.c_int, [_P, _I32, _P, _SZ]),
+    "mrt_renderer_copy_guide_to_device": (C.c_int, [_P, _I32, _P, _SZ]),
+    "mrt_renderer_denoise": (C.c_int, [_P, C.POINTER(DenoiseParams)]),
+    "mrt_renderer_read_denoised": (C.c_int, [_P, _P, _SZ]),
+    "mrt_renderer_copy_denoised_to_device": (C.c_int, [_P, _P, _SZ]),
+    "mrt_renderer_read_denoised_tonemapped_rgba8": (C.c_int, [_P, _P, _SZ]),
     "mrt_renderer_stats": (C.c_int, [_P, C.POINTER(RenderStats)]),
     "mrt_renderer_reset_stats": (C.c_int, [_P]),
     "mrt_renderer_kernel_times": (C.c_int, [_P, C.POINTER(KernelTimes)]),

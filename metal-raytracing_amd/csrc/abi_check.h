@@ -28,4 +28,8 @@ MRT_AT(MRTMaterial, specularExponent, 48); MRT_AT(MRTMaterial, refractionIndex, 
 // query records
 static_assert(sizeof(MRTRay) == 32 && sizeof(MRTIntersection) == 32, "ray / intersection records are 32 bytes");
 MRT_AT(MRTRay, min_distance, 12); MRT_AT(MRTRay, direction, 16); MRT_AT(MRTRay, max_distance, 28);
+// denoiser parameters (no counterpart in ShaderTypes.h)
+static_assert(sizeof(MRTDenoiseParams) == 32, "MRTDenoiseParams is 32 bytes");
+MRT_AT(MRTDenoiseParams, iterations, 0); MRT_AT(MRTDenoiseParams, sigma_color, 4); MRT_AT(MRTDenoiseParams, sigma_normal, 8);
+MRT_AT(MRTDenoiseParams, sigma_depth, 12); MRT_AT(MRTDenoiseParams, demodulate, 16);
 #undef MRT_AT

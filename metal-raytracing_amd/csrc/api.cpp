@@ -510,8 +510,9 @@ int mrt_renderer_set_option(MRTRenderer r, const char *key, double value) {
     else if (k == "sample_offset") { REQUIRE(value >= 0 && value < 4294967296.0, "sample_offset out of range"); r->r.sample_offset = (uint32_t)value; }
     else if (k == "frame_batch") { REQUIRE(value >= 0 && value <= mrt::MAX_FRAME_BATCH, "frame_batch must be in [1,32], or 0 for the default (by image size)"); r->r.frame_batch = (int)value; }
     else if (k == "megakernel") r->r.megakernel = value != 0;
+    else if (k == "guides") { REQUIRE(value == 0 || value == 1, "guides must be 0 or 1"); int rc = bind_device(r->ctx); if (rc) return rc; r->r.stream = r->ctx->stream; rc = r->r.set_guides(value != 0); if (rc) return rc; }
     else if (k == "materials") { REQUIRE(value == 0 || (value == 1 && r->r.max_bounces <= 16), "materials must be 0 or 1 (and max_bounces <= 16: the lobe choice uses Halton dimension 2 + 5 * max_bounces + bounce < 100)"); r->r.materials = value != 0; }
-    else { mrt::set_error("mrt_renderer_set_option: unknown key " + k + " (keys: max_bounces, frames_in_flight, sample_offset, frame_batch, megakernel, materials; the library's A/B switches are behind mrt_debug_renderer_set_option)"); return MRT_ERR_INVALID_ARGUMENT; }
+    else { mrt::set_error("mrt_renderer_set_option: unknown key " + k + " (keys: max_bounces, frames_in_flight, sample_offset, frame_batch, megakernel, materials, guides; the library's A/B switches are behind mrt_debug_renderer_set_option)"); return MRT_ERR_INVALID_ARGUMENT; }
     return MRT_OK;
     MRT_CATCH
 }
@@ -525,6 +526,7 @@ int mrt_renderer_get_option(MRTRenderer r, const char *key, double *value) {
     else if (k == "frame_batch") *value = r->r.batch_wanted();          // (what is in force: under the default, 8 at 1080p and above, up to 32 for smaller images and shards)
     else if (k == "megakernel") *value = r->r.megakernel ? 1 : 0;
     else if (k == "materials") *value = r->r.materials ? 1 : 0;
+    else if (k == "guides") *value = r->r.guides ? 1 : 0;
     else if (k == "lanes_used") *value = r->r.lanes_used;
     else if (k == "lane_bytes") *value = (double)r->r.lane_bytes();
     else { mrt::set_error("mrt_renderer_get_option: unknown key " + k); return MRT_ERR_INVALID_ARGUMENT; }
@@ -667,6 +669,48 @@ int mrt_renderer_read_tonemapped_rgba8(MRTRenderer r, uint8_t *rgba, size_t nbyt
     RENDERER_PROLOGUE("mrt_renderer_read_tonemapped_rgba8")
     REQUIRE(rgba, "mrt_renderer_read_tonemapped_rgba8: NULL buffer");
     return r->r.read_tonemapped(rgba, nbytes);
+    MRT_CATCH
+}
+// ---- first-hit guide buffers and the denoiser (no counterpart in the reference; include/mrt_abi.h)
+int mrt_renderer_read_guide(MRTRenderer r, int32_t which, void *out, size_t nbytes) {
+    MRT_TRY
+    RENDERER_PROLOGUE("mrt_renderer_read_guide")
+    REQUIRE(out, "mrt_renderer_read_guide: NULL buffer");
+    return r->r.read_guide(which, out, nbytes);
+    MRT_CATCH
+}
+int mrt_renderer_copy_guide_to_device(MRTRenderer r, int32_t which, void *dptr, size_t nbytes) {
+    MRT_TRY
+    RENDERER_PROLOGUE("mrt_renderer_copy_guide_to_device")
+    REQUIRE(dptr, "mrt_renderer_copy_guide_to_device: NULL pointer");
+    return r->r.copy_guide_to_device(which, dptr, nbytes);
+    MRT_CATCH
+}
+int mrt_renderer_denoise(MRTRenderer r, const MRTDenoiseParams *params) {
+    MRT_TRY
+    RENDERER_PROLOGUE("mrt_renderer_denoise")
+    return r->r.enqueue_denoise(params);
+    MRT_CATCH
+}
+int mrt_renderer_read_denoised(MRTRenderer r, float *rgba, size_t nbytes) {
+    MRT_TRY
+    RENDERER_PROLOGUE("mrt_renderer_read_denoised")
+    REQUIRE(rgba, "mrt_renderer_read_denoised: NULL buffer");
+    return r->r.read_denoised(rgba, nbytes);
+    MRT_CATCH
+}
+int mrt_renderer_copy_denoised_to_device(MRTRenderer r, void *dptr, size_t nbytes) {
+    MRT_TRY
+    RENDERER_PROLOGUE("mrt_renderer_copy_denoised_to_device")
+    REQUIRE(dptr, "mrt_renderer_copy_denoised_to_device: NULL pointer");
+    return r->r.copy_denoised_to_device(dptr, nbytes);
+    MRT_CATCH
+}
+int mrt_renderer_read_denoised_tonemapped_rgba8(MRTRenderer r, uint8_t *rgba, size_t nbytes) {
+    MRT_TRY
+    RENDERER_PROLOGUE("mrt_renderer_read_denoised_tonemapped_rgba8")
+    REQUIRE(rgba, "mrt_renderer_read_denoised_tonemapped_rgba8: NULL buffer");
+    return r->r.read_denoised_tonemapped(rgba, nbytes);
     MRT_CATCH
 }
 int mrt_renderer_stats(MRTRenderer r, MRTRenderStats *out) {

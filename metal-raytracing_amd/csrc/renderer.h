@@ -100,6 +100,24 @@ struct Renderer {
     hipEvent_t ev_fork = nullptr;
     DevBuf<unsigned long long> totals;   // [0] closest rays, [1] shadow rays, [2] primary rays
 
+    // first-hit guide buffers and the denoiser (renderer option guides; include/mrt_abi.h MRT_GUIDE_*, guides.h, denoise.hip).  Not queue memory: lane_bytes() does not count them
+    bool guides = false;
+    bool guides_valid = false;           // a frame has been rendered with the option on since the buffers were last cleared
+    bool guides_keep = false;            // resize() on behalf of a new frame_batch: the guides survive as the accumulation buffer does
+    DevBuf<float4> guide_nd, guide_albedo; DevBuf<int4> guide_ids;
+    hipStream_t guide_stream = nullptr;  // the guide launch of a render call runs beside the pass lanes
+    hipEvent_t guide_fork = nullptr, guide_done = nullptr;
+    DevBuf<float4> dn_scratch[2], denoised; bool denoised_valid = false;
+    int set_guides(bool on);
+    int ensure_guides();                 // buffers (zeroed) and stream, on the main stream ahead of the fork
+    int clear_guides();
+    int read_guide(int which, void *out, size_t nbytes);
+    int copy_guide_to_device(int which, void *dptr, size_t nbytes);
+    int enqueue_denoise(const MRTDenoiseParams *params);          // (not `denoise`: include/mrt.hpp has an inline mrt::Renderer::denoise of that signature, and a host program's copy of the symbol would be bound in its place)
+    int read_denoised(float *rgba, size_t nbytes);
+    int copy_denoised_to_device(void *dptr, size_t nbytes);
+    int read_denoised_tonemapped(uint8_t *rgba, size_t nbytes);
+
     int light_count_limit = 0;           // > 0: the kernels see only the first n lights (Uniforms.lightCount, ShaderTypes.h:93; 0 = all the scene's lights)
     // completion without blocking (the reference is told per frame, Renderer.swift:285-287): one pooled event per pass, recorded after its
     // k_accumulate; passes complete in order (each accumulate waits for the previous one)
@@ -150,5 +168,7 @@ int probe_halton(hipStream_t stream, const int32_t *i, const int32_t *d, size_t 
 int probe_hemisphere(hipStream_t stream, const float *u2, const float *n3, size_t n, float *out3);
 int probe_seeds(hipStream_t stream, uint32_t seed, int w, int h, uint32_t *out);
 int calibrate(hipStream_t stream, size_t table_bytes, double *out3);   // calibrate.hip
+// denoise.hip: the a-trous filter of `accum` guided by `nd` / `albedo` into `out`, all width x height float4; s0 / s1: two scratch images of that size
+int denoise_enqueue(hipStream_t stream, int width, int height, const float4 *accum, const float4 *nd, const float4 *albedo, float4 *s0, float4 *s1, float4 *out, const MRTDenoiseParams &p);
 
 }  // namespace mrt

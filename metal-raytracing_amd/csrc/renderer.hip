@@ -302,6 +302,7 @@ __global__ void __launch_bounds__(64, MRT_WIDE_STREAM_WAVES) k_trace_mixed_wide_
 }
 
 #include "megakernel.h"            // k_megakernel: one launch per frame
+#include "guides.h"                // k_guides: first-hit guide buffers (renderer option guides)
 
 // Primary rays on the wide layout with lane refill (experiment: the rope kernel is VALU-bound on primary rays; measured
 // equal on the full frame, 7 % slower on the primary + shadow workload).
@@ -701,6 +702,9 @@ Renderer::~Renderer() {
     for (auto &e : ev_ext) { if (e.a) (void)hipEventDestroy(e.a); if (e.b) (void)hipEventDestroy(e.b); }
     for (auto &pd : passes_pending) (void)hipEventDestroy(pd.ev);
     for (auto e : pass_events_free) (void)hipEventDestroy(e);
+    if (guide_stream) { (void)hipStreamSynchronize(guide_stream); (void)hipStreamDestroy(guide_stream); }
+    if (guide_done) (void)hipEventDestroy(guide_done);
+    if (guide_fork) (void)hipEventDestroy(guide_fork);
     for (auto &L : lanes) {
         if (L.stream) { (void)hipStreamSynchronize(L.stream); (void)hipStreamDestroy(L.stream); }
         if (L.accumulated) (void)hipEventDestroy(L.accumulated);
@@ -733,6 +737,13 @@ int Renderer::resize(int w, int h) {                                   // Render
     frames_rendered = 0;
     for (auto &pd : passes_pending) pass_events_free.push_back(pd.ev);      // the caller synchronised (mrt_renderer_resize)
     passes_pending.clear(); frames_completed_known = 0;
+    denoised_valid = false;
+    if (guides && !guides_keep) {          // the guides restart with the accumulation (new size: new buffers at the next draw)
+        if (guide_nd.p && guide_nd.n != npix) { guide_nd.release(); guide_albedo.release(); guide_ids.release(); }
+        for (auto &b : dn_scratch) b.release();
+        denoised.release();
+        if (int rc = clear_guides()) return rc;
+    }
     return alloc_queues();
 }
 
@@ -851,7 +862,90 @@ int Renderer::set_shard(int rank, int world) {
     MRT_HIP(hipMemsetAsync(accum[0].p, 0, accum[0].bytes(), stream));
     MRT_HIP(hipMemsetAsync(accum[1].p, 0, accum[1].bytes(), stream));
     frame_index = 0; cur = 0;
+    if (int rc = clear_guides()) return rc;
     return alloc_queues();
+}
+
+// ---- guide buffers (guides.h)
+int Renderer::clear_guides() {
+    guides_valid = false; denoised_valid = false;
+    if (guide_nd.p) {
+        MRT_HIP(hipMemsetAsync(guide_nd.p, 0, guide_nd.bytes(), stream)); MRT_HIP(hipMemsetAsync(guide_albedo.p, 0, guide_albedo.bytes(), stream));
+        MRT_HIP(hipMemsetAsync(guide_ids.p, 0, guide_ids.bytes(), stream));
+    }
+    return MRT_OK;
+}
+int Renderer::set_guides(bool on) {
+    if (on == guides) return MRT_OK;
+    guides = on;
+    if (!on) {          // off: nothing stays allocated
+        MRT_HIP(hipStreamSynchronize(stream));
+        guide_nd.release(); guide_albedo.release(); guide_ids.release(); denoised.release();
+        for (auto &b : dn_scratch) b.release();
+        guides_valid = false; denoised_valid = false;
+    }
+    return MRT_OK;
+}
+int Renderer::ensure_guides() {
+    const size_t npix = (size_t)width * height;
+    if (!guide_stream) { MRT_HIP(hipStreamCreateWithFlags(&guide_stream, hipStreamNonBlocking)); MRT_HIP(hipEventCreateWithFlags(&guide_done, hipEventDisableTiming)); MRT_HIP(hipEventCreateWithFlags(&guide_fork, hipEventDisableTiming)); }
+    if (guide_nd.p && guide_nd.n == npix) return MRT_OK;
+    MRT_HIP(guide_nd.alloc(npix)); MRT_HIP(guide_albedo.alloc(npix)); MRT_HIP(guide_ids.alloc(npix));
+    return clear_guides();
+}
+int Renderer::read_guide(int which, void *out, size_t nbytes) {
+    if (which < 0 || which >= MRT_GUIDE_COUNT) { set_error("read_guide: which must be MRT_GUIDE_NORMAL_DEPTH, MRT_GUIDE_ALBEDO or MRT_GUIDE_IDS"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (nbytes != (size_t)width * height * 16) { set_error("read_guide: nbytes must be width*height*16"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (!guides || !guides_valid) { set_error("read_guide: no guide buffers (renderer option guides = 1, then render)"); return MRT_ERR_STATE; }
+    int rc = wait(); if (rc) return rc;
+    MRT_HIP(hipMemcpy(out, which == MRT_GUIDE_NORMAL_DEPTH ? (const void *)guide_nd.p : which == MRT_GUIDE_ALBEDO ? (const void *)guide_albedo.p : (const void *)guide_ids.p, nbytes, hipMemcpyDeviceToHost));
+    return MRT_OK;
+}
+int Renderer::copy_guide_to_device(int which, void *dptr, size_t nbytes) {
+    if (which < 0 || which >= MRT_GUIDE_COUNT) { set_error("copy_guide_to_device: which must be MRT_GUIDE_NORMAL_DEPTH, MRT_GUIDE_ALBEDO or MRT_GUIDE_IDS"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (nbytes != (size_t)width * height * 16) { set_error("copy_guide_to_device: nbytes must be width*height*16"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (!guides || !guides_valid) { set_error("copy_guide_to_device: no guide buffers (renderer option guides = 1, then render)"); return MRT_ERR_STATE; }
+    MRT_HIP(hipMemcpyAsync(dptr, which == MRT_GUIDE_NORMAL_DEPTH ? (const void *)guide_nd.p : which == MRT_GUIDE_ALBEDO ? (const void *)guide_albedo.p : (const void *)guide_ids.p, nbytes, hipMemcpyDeviceToDevice, stream));
+    return MRT_OK;
+}
+int Renderer::enqueue_denoise(const MRTDenoiseParams *params) {
+    MRTDenoiseParams p{};
+    if (params) p = *params;
+    else { p.iterations = MRT_DENOISE_DEFAULT_ITERATIONS; p.sigma_color = MRT_DENOISE_DEFAULT_SIGMA_COLOR; p.sigma_normal = MRT_DENOISE_DEFAULT_SIGMA_NORMAL; p.sigma_depth = MRT_DENOISE_DEFAULT_SIGMA_DEPTH; p.demodulate = 1; }
+    if (p.iterations < 1 || p.iterations > 8) { set_error("denoise: iterations must be in [1,8]"); return MRT_ERR_INVALID_ARGUMENT; }
+    const float big = 3.0e38f;
+    if (!(p.sigma_color > 0.0f && p.sigma_color < big) || !(p.sigma_normal > 0.0f && p.sigma_normal < big) || !(p.sigma_depth > 0.0f && p.sigma_depth < big)) { set_error("denoise: sigma_color, sigma_normal and sigma_depth must be finite and > 0"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (p.demodulate != 0 && p.demodulate != 1) { set_error("denoise: demodulate must be 0 or 1"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (!guides || !guides_valid) { set_error("denoise: no guide buffers (renderer option guides = 1, then render)"); return MRT_ERR_STATE; }
+    if (shard_world > 1) { set_error("denoise: a sharded renderer holds only its own tiles and the filter needs a pixel's neighbours"); return MRT_ERR_STATE; }
+    const size_t npix = (size_t)width * height;
+    for (auto &b : dn_scratch) MRT_HIP(b.alloc(npix));
+    MRT_HIP(denoised.alloc(npix));
+    if (int rc = denoise_enqueue(stream, width, height, accum[cur].p, guide_nd.p, guide_albedo.p, dn_scratch[0].p, dn_scratch[1].p, denoised.p, p)) return rc;
+    denoised_valid = true;
+    return MRT_OK;
+}
+int Renderer::read_denoised(float *rgba, size_t nbytes) {
+    if (nbytes != (size_t)width * height * 16) { set_error("read_denoised: nbytes must be width*height*16"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (!denoised_valid) { set_error("read_denoised: no denoised image (mrt_renderer_denoise first)"); return MRT_ERR_STATE; }
+    int rc = wait(); if (rc) return rc;
+    MRT_HIP(hipMemcpy(rgba, denoised.p, nbytes, hipMemcpyDeviceToHost));
+    return MRT_OK;
+}
+int Renderer::copy_denoised_to_device(void *dptr, size_t nbytes) {
+    if (nbytes != (size_t)width * height * 16) { set_error("copy_denoised_to_device: nbytes must be width*height*16"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (!denoised_valid) { set_error("copy_denoised_to_device: no denoised image (mrt_renderer_denoise first)"); return MRT_ERR_STATE; }
+    MRT_HIP(hipMemcpyAsync(dptr, denoised.p, nbytes, hipMemcpyDeviceToDevice, stream));
+    return MRT_OK;
+}
+int Renderer::read_denoised_tonemapped(uint8_t *rgba, size_t nbytes) {
+    if (nbytes != (size_t)width * height * 4) { set_error("read_denoised_tonemapped: nbytes must be width*height*4"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (!denoised_valid) { set_error("read_denoised_tonemapped: no denoised image (mrt_renderer_denoise first)"); return MRT_ERR_STATE; }
+    DevBuf<uchar4> tmp; MRT_HIP(tmp.alloc((size_t)width * height));
+    hipLaunchKernelGGL(k_tonemap, dim3(cdiv(width, 16), cdiv(height, 16)), dim3(16, 16), 0, stream, (const float4 *)denoised.p, width, height, tmp.p);
+    int rc = wait(); if (rc) return rc;
+    MRT_HIP(hipMemcpy(rgba, tmp.p, nbytes, hipMemcpyDeviceToHost));
+    return MRT_OK;
 }
 
 int Renderer::render(int n_frames) {                                   // Renderer.draw(in:) :284-351, n times
@@ -871,6 +965,7 @@ int Renderer::render(int n_frames) {                                   // Render
     if (tiles_local == 0) {
         // a shard that owns no tile (more ranks than 8 x 8 tiles: rank 2 of 3 of a 9 x 5 image) has no pixel to render and its buffers stay 0; the launches sized
         // by its queues would be empty grids (the shading of bounces >= 1: cdiv(capacity x batch, ...) = 0), which HIP refuses.  The frames count as drawn.
+        if (guides) { if (int rc = ensure_guides()) return rc; guides_valid = true; }
         MRT_HIP(hipEventRecord(ev_begin, stream));
         frame_index += (uint32_t)n_frames; frames_rendered += (uint64_t)n_frames;
         ext_used = 0;
@@ -887,7 +982,11 @@ int Renderer::render(int n_frames) {                                   // Render
         const MRTCamera keep_cam = camera;
         unsigned long long keep_totals[3] = {0, 0, 0};
         MRT_HIP(hipMemcpy(keep_totals, totals.p, sizeof keep_totals, hipMemcpyDeviceToHost));
-        int rc = resize(width, height); if (rc) return rc;
+        const bool keep_denoised = denoised_valid;
+        guides_keep = true;
+        int rc = resize(width, height);
+        guides_keep = false; denoised_valid = keep_denoised;
+        if (rc) return rc;
         MRT_HIP(hipMemcpyAsync(totals.p, keep_totals, sizeof keep_totals, hipMemcpyHostToDevice, stream));
         MRT_HIP(hipMemcpyAsync(accum[keep_cur].p, keep.p, keep.bytes(), hipMemcpyDeviceToDevice, stream));
         MRT_HIP(hipStreamSynchronize(stream));
@@ -944,6 +1043,15 @@ int Renderer::render(int n_frames) {                                   // Render
         return MRT_ERR_UNSUPPORTED;
     }
     const bool mega = megakernel;
+    // the guide buffers of the call's frames (guides.h): what can fail on the host happens here, the launch follows the pass loop — no error return of the
+    // loop leaves a guide kernel in flight that the main stream has not joined
+    FrameParams gp = fp;
+    gp.frameIndex = frame_index; gp.sampleIndex = frame_index + sample_offset; gp.npix = (uint32_t)((size_t)width * height); gp.capacity = capacity; gp.batch = 1;
+    if (guides) {
+        if (int rc = ensure_guides()) return rc;
+        MRT_HIP(hipEventRecord(guide_fork, stream));       // the guide stream starts behind whatever the caller queued on the main stream (the clears of ensure_guides included), not behind the passes
+        MRT_HIP(hipStreamWaitEvent(guide_stream, guide_fork, 0));
+    }
     // passes larger than the default (sharded renderers ask for up to 32 frames so that a shard's launches stay large) never take more than a third of the draw:
     // a short draw keeps about three passes to run side by side (a rank of eight over 20 frames: 7.1 Grays/s as 7 + 7 + 6, 6.0 as one pass of 20)
     const int batch_cap = alloc_batch > DEFAULT_FRAME_BATCH ? std::min(alloc_batch, std::max(DEFAULT_FRAME_BATCH, (n_frames + 2) / 3)) : alloc_batch;
@@ -1229,6 +1337,21 @@ int Renderer::render(int n_frames) {                                   // Render
     }
     // join: the main stream continues after every lane has drained
     for (int k = 0; k < (G > 1 ? std::min(Fp, pass) * G : std::min(F, pass)); k++) MRT_HIP(hipStreamWaitEvent(stream, lanes[k].accumulated, 0));
+    if (guides) {
+        // one launch over this renderer's own pixels and all the call's frames, on a stream of its own beside the passes just enqueued; joined like a lane
+        const size_t lds = sv.num_wnodes ? (size_t)scene->wide_depth * WIDE_STACK_LEVEL_BYTES : 0;
+        const dim3 gg(grid), gb(64);
+        if (two_level && sv.num_wnodes) hipLaunchKernelGGL(k_guides<3>, gg, gb, lds, guide_stream, sv, gp, (const uint32_t *)seeds.p, (uint32_t)n_frames, guide_nd.p, guide_albedo.p, guide_ids.p);
+        else if (two_level) hipLaunchKernelGGL(k_guides<0>, gg, gb, 0, guide_stream, sv, gp, (const uint32_t *)seeds.p, (uint32_t)n_frames, guide_nd.p, guide_albedo.p, guide_ids.p);
+        else if (sv.num_wnodes) hipLaunchKernelGGL(k_guides<2>, gg, gb, lds, guide_stream, sv, gp, (const uint32_t *)seeds.p, (uint32_t)n_frames, guide_nd.p, guide_albedo.p, guide_ids.p);
+        else hipLaunchKernelGGL(k_guides<1>, gg, gb, 0, guide_stream, sv, gp, (const uint32_t *)seeds.p, (uint32_t)n_frames, guide_nd.p, guide_albedo.p, guide_ids.p);
+        const hipError_t le = hipGetLastError();
+        // the join comes whatever the launch said: nothing on this stream outlives the call unjoined
+        (void)hipEventRecord(guide_done, guide_stream);
+        (void)hipStreamWaitEvent(stream, guide_done, 0);
+        if (le != hipSuccess) return hip_fail(le, "k_guides launch", __FILE__, __LINE__);
+        guides_valid = true;
+    }
     if (G > 1) { if (int rc = note_pass(stream)) return rc; }      // (tile groups: completion is reported per draw)
     if (tail.n > 0) {
         EvPair *ev = nullptr;

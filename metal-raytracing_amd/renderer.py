@@ -217,7 +217,7 @@ class Renderer:
         return v.value
 
     # the host's knobs (include/mrt_abi.h mrt_renderer_set_option); every other key is one of the library's A/B switches (mrt_debug_renderer_set_option: tests, tools/, bench.py --opt)
-    PUBLIC_OPTIONS = ("max_bounces", "frames_in_flight", "sample_offset", "frame_batch", "megakernel", "materials", "lanes_used", "lane_bytes")
+    PUBLIC_OPTIONS = ("max_bounces", "frames_in_flight", "sample_offset", "frame_batch", "megakernel", "materials", "guides", "lanes_used", "lane_bytes")
 
     def set_option(self, key, value):
         fn = lib.mrt_renderer_set_option if key in self.PUBLIC_OPTIONS else lib.mrt_debug_renderer_set_option
@@ -263,6 +263,45 @@ class Renderer:
 
     def write_accum_from(self, device_ptr, nbytes):
         check(lib.mrt_renderer_write_accum_from_device(self.handle, C.c_void_p(device_ptr), nbytes))
+
+    # -- first-hit guide buffers and the denoiser (set_option("guides", 1) before drawing; no counterpart in the reference)
+    def guides(self):
+        """{"normal_depth": (h, w, 4) float32 — shading normal | hit distance of the primary hit, "albedo": (h, w, 4) float32 — baseColor | coverage,
+        "ids": (h, w, 4) int32 — type, instance_id, geometry_id, primitive_id of the last frame}; row 0 = bottom, as accumulation()."""
+        from ._ffi import GUIDE_ALBEDO, GUIDE_IDS, GUIDE_NORMAL_DEPTH
+        out = {}
+        for name, which, dt in (("normal_depth", GUIDE_NORMAL_DEPTH, np.float32), ("albedo", GUIDE_ALBEDO, np.float32), ("ids", GUIDE_IDS, np.int32)):
+            a = np.empty((self.size[1], self.size[0], 4), dt)
+            check(lib.mrt_renderer_read_guide(self.handle, which, ptr(a), a.nbytes))
+            out[name] = a
+        return out
+
+    def copy_guide_to(self, which, device_ptr, nbytes):
+        check(lib.mrt_renderer_copy_guide_to_device(self.handle, int(which), C.c_void_p(device_ptr), nbytes))
+
+    def denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None, demodulate=None, read=True):
+        """The edge-avoiding a-trous filter of the accumulation buffer (mrt_renderer_denoise) -> (h, w, 4) float32, row 0 = bottom
+        (None with read=False: the image stays on the device for denoised_tonemapped() / copy_denoised_to())."""
+        from ._ffi import DENOISE_DEFAULTS, DenoiseParams
+        given = dict(iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_depth=sigma_depth, demodulate=demodulate)
+        v = {k: (DENOISE_DEFAULTS[k] if x is None else x) for k, x in given.items()}
+        p = DenoiseParams(int(v["iterations"]), float(v["sigma_color"]), float(v["sigma_normal"]), float(v["sigma_depth"]), int(v["demodulate"]))
+        check(lib.mrt_renderer_denoise(self.handle, C.byref(p)))
+        return self.denoised() if read else None
+
+    def denoised(self):
+        out = np.empty((self.size[1], self.size[0], 4), np.float32)
+        check(lib.mrt_renderer_read_denoised(self.handle, ptr(out), out.nbytes))
+        return out
+
+    def denoised_tonemapped(self):
+        """tonemapped() of the denoised image: (h, w, 4) uint8, top row first."""
+        out = np.empty((self.size[1], self.size[0], 4), np.uint8)
+        check(lib.mrt_renderer_read_denoised_tonemapped_rgba8(self.handle, ptr(out), out.nbytes))
+        return out
+
+    def copy_denoised_to(self, device_ptr, nbytes):
+        check(lib.mrt_renderer_copy_denoised_to_device(self.handle, C.c_void_p(device_ptr), nbytes))
 
     def shard_tiles(self, rank, world):
         """8 x 8 tiles of this image that shard (rank, world) owns (a compact buffer of that shard is tiles x 64 RGBA32F pixels)."""
