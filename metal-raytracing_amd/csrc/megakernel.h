@@ -27,13 +27,12 @@ __global__ void __launch_bounds__(64, 4) k_megakernel(SceneView s, FrameParams f
     uint32_t pix = 0, pslot = 0; int bounce = 0;      // pixel (accumulation targets) and slot (seed table) of the lane's path
     f3 thr = mk3(1, 1, 1), rad = mk3(0, 0, 0), con = mk3(0, 0, 0), ndir = mk3(0, 1, 0);
     uint32_t n_closest = 0, n_shadow = 0;
-    // ray + traversal state (traverse_wide_stream)
-    f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1); float ix = 0, iy = 0, iz = 0; bool nx = false, ny = false, nz = false; uint32_t oct = 0;
+    // ray + traversal state: the steps of traverse_wide.h
+    f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1); RayBox rb = {};
     float best_t = 0.0f; uint32_t best_pk = 0xFFFFFFFFu;
     uint32_t g_base = 0, g_mask = 0, t_base = 0, t_mask = 0;
     auto start_ray = [&](f3 ro, f3 rd, float tmax) {
-        o = ro; d = rd; ix = box_inv(rd.x); iy = box_inv(rd.y); iz = box_inv(rd.z);
-        nx = rd.x < 0.0f; ny = rd.y < 0.0f; nz = rd.z < 0.0f; oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
+        o = ro; d = rd; rb = ray_box(rd);
         best_t = tmax; best_pk = 0xFFFFFFFFu;
         g_base = 0; g_mask = s.num_wnodes != 0 ? 0x100u : 0u; t_base = 0; t_mask = 0;
         live = true;
@@ -51,13 +50,10 @@ __global__ void __launch_bounds__(64, 4) k_megakernel(SceneView s, FrameParams f
                     else end_path = true;
                 } else if (best_pk == 0xFFFFFFFFu) end_path = true;                                // :246-247 miss terminates the path
                 else {
-                    // hit record of the winning triangle (recomputed: same arithmetic as the traversal's test)
-                    const float4 *__restrict__ pk = s.wpackets + WPK * (size_t)best_pk;
-                    const float4 q0 = pk[0];
-                    float t_, U, V, ad;
-                    (void)tri_test(q0, pk[1], pk[2], o, d, 0.0f, __builtin_inff(), t_, U, V, ad);
-                    const uint32_t gid = __float_as_uint(q0.w);
-                    const float bu = U / ad, bv = V / ad;
+                    TravHit h;          // hit record of the winning triangle
+                    retest_winner<false>(s, best_pk, 0u, o, d, h);
+                    const uint32_t gid = h.gid;
+                    const float bu = h.U / h.ad, bv = h.V / h.ad;
                     const uint4 ts = s.tri_shade[gid];
                     const uint32_t inst = ts.w >> 16, geom = ts.w & 0xFFFFu;
                     const f3 P = o + d * best_t;                                                   // :261
@@ -165,57 +161,36 @@ __global__ void __launch_bounds__(64, 4) k_megakernel(SceneView s, FrameParams f
             if (__ballot(has_path) == 0ull) { if (!more) break; else continue; }
             if (__ballot(live) == 0ull) continue;      // everybody was serviced into a finished state again (cannot happen: a serviced lane is live or pathless)
         }
-        // ---- traversal step: traverse_wide_stream's iteration (one memory round trip: node and triangle fetched together)
+        // ---- traversal step, from the shared steps of traverse_wide.h: traverse_wide_stream's iteration without its extras (one memory round trip: node and triangle fetched together)
         const bool has_tri = live && t_mask != 0;
         const uint32_t t_rest = t_mask & (t_mask - 1u);
         bool want_node = live && t_rest == 0u;
         uint32_t pending_node = 0, tri_pk = 0;
-        if (want_node) {
-            if ((g_mask & 0xFF00u) == 0) {
-                const uint32_t sp = g_mask >> 16;
-                if (sp == 0) { want_node = false; if (!has_tri) live = false; }
-                else { wstack_pop(stack, sp - 1u, lane, g_base, g_mask); g_mask |= (sp - 1u) << 16; }
-            }
-            if (want_node) {
-                const uint32_t hits = (g_mask >> 8) & 0xFFu;
-                const uint32_t b = (uint32_t)__ffs((int)hits) - 1u;
-                g_mask &= ~(0x100u << b);
-                const uint32_t slot = b ^ oct;
-                pending_node = g_base + (uint32_t)__popc(g_mask & 0xFFu & ((1u << slot) - 1u));
-            }
-        }
+        if (want_node && next_node<false>(stack, lane, g_base, g_mask, rb.oct, pending_node) != NEXT_NODE) { want_node = false; if (!has_tri) live = false; }
         float4 r0, r1, r2, n0, n1, n2, n3, n4;
-        asm volatile("" : "=v"(r0.x), "=v"(r0.y), "=v"(r0.z), "=v"(r0.w), "=v"(r1.x), "=v"(r1.y), "=v"(r1.z), "=v"(r2.x), "=v"(r2.y), "=v"(r2.z));
-        asm volatile("" : "=v"(n0.x), "=v"(n0.y), "=v"(n0.z), "=v"(n0.w), "=v"(n1.x), "=v"(n1.y), "=v"(n1.z), "=v"(n1.w), "=v"(n2.x), "=v"(n2.y), "=v"(n2.z), "=v"(n2.w));
-        asm volatile("" : "=v"(n3.x), "=v"(n3.y), "=v"(n3.z), "=v"(n3.w), "=v"(n4.x), "=v"(n4.y), "=v"(n4.z), "=v"(n4.w));
-        r1.w = 0.0f; r2.w = 0.0f;
+        MRT_DECLARE_UNLOADED(r0, r1, r2, n0, n1, n2, n3, n4);
         if (has_tri) {
             tri_pk = t_base + (uint32_t)__ffs((int)t_mask) - 1u;
             t_mask = t_rest;
-            const float4 *__restrict__ pk = s.wpackets + WPK * (size_t)tri_pk;
-            r0 = pk[0]; r1 = pk[1]; r2 = pk[2];
+            MRT_LOAD_PACKET(s, tri_pk, r0, r1, r2);
         }
         if (want_node) {
-            const float4 *__restrict__ nd = s.wnodes + WNODE_STRIDE * (size_t)pending_node;
-            n0 = nd[0]; n1 = nd[1]; n2 = nd[2]; n3 = nd[3]; n4 = nd[4];
+            MRT_LOAD_NODE(s, pending_node, n0, n1, n2, n3, n4);
         }
         if (has_tri) {
             float t, U, V, ad;
             if (tri_test(r0, r1, r2, o, d, 0.0f, best_t, t, U, V, ad)) {
                 if (is_shadow) { best_pk = tri_pk; live = false; }                                 // any hit: done
                 else {
-                    bool better = t < best_t || best_pk == 0xFFFFFFFFu;
-                    if (!better) better = __float_as_uint(r0.w) < __float_as_uint(s.wpackets[WPK * (size_t)best_pk].w);   // ties go to the lowest id
+                    MRT_CLOSER_HIT(better, t, best_t, best_pk, true, __float_as_uint(r0.w), packet_id(s, best_pk));
                     if (better) { best_t = t; best_pk = tri_pk; }
                 }
             }
         }
         if (want_node && live) {
             uint32_t node_hits, tri_hits;
-            wide_node_test(n0, n1, n2, n3, n4, o, ix, iy, iz, nx, ny, nz, oct, 0.0f, best_t, node_hits, tri_hits);      // (the scaled form needs one more register: 128 -> spills)
-            uint32_t sp = g_mask >> 16;
-            if ((g_mask & 0xFF00u) != 0) { wstack_push(stack, sp, lane, g_base, g_mask & 0xFFFFu); sp++; }
-            g_base = __float_as_uint(n1.x); g_mask = (sp << 16) | (node_hits << 8) | (__float_as_uint(n0.w) >> 24);
+            wide_node_test(n0, n1, n2, n3, n4, o, rb.ix, rb.iy, rb.iz, rb.nx, rb.ny, rb.nz, rb.oct, 0.0f, best_t, node_hits, tri_hits);      // (the scaled form needs one more register: 128 -> spills)
+            enter_node<false>(stack, lane, g_base, g_mask, n0, n1, node_hits);
             t_base = __float_as_uint(n1.y); t_mask = tri_hits;
         }
     }

@@ -125,6 +125,131 @@ MRT_DEV void wide_node_test(const float4 n0, const float4 n1, const float4 n2, c
     node_hits = nh; tri_hits = th;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The steps of one 8-wide traversal iteration that the walks share, each written once: traverse_wide_lane, traverse_wide_lane_two_level, traverse_wide_stream below and
+// k_megakernel (megakernel.h) are built from them.  All of them inline away; their shapes (values in, small struct or references to plain locals out) are the ones that leave
+// the flattened kernels' assembly exactly as it was (tools/isa_diff.py; docs/HISTORY.md §18 lists the shapes that do not).
+// what the box tests need of a ray's direction: 1 / d per axis, the sign per axis, the octant (child slots are visited in slot ^ octant order)
+struct RayBox { float ix, iy, iz; bool nx, ny, nz; uint32_t oct; };
+MRT_DEV RayBox ray_box(const f3 d) {
+    RayBox b; b.ix = box_inv(d.x); b.iy = box_inv(d.y); b.iz = box_inv(d.z); b.nx = d.x < 0.0f; b.ny = d.y < 0.0f; b.nz = d.z < 0.0f;
+    b.oct = (b.nx ? 1u : 0u) | (b.ny ? 2u : 0u) | (b.nz ? 4u : 0u);
+    return b;
+}
+
+// The nearest remaining hit child of a node group, in (slot ^ octant) order: its bit is cleared, its node index returned (a node's internal children are stored densely).
+// g_mask: imask | permuted hit bits << 8 (| stack depth << 16 | the depth at which the BLAS was entered << 24 in the walks that keep them there)
+MRT_DEV uint32_t take_nearest_child(uint32_t g_base, uint32_t &g_mask, uint32_t oct) {
+    const uint32_t hits = (g_mask >> 8) & 0xFFu;
+    const uint32_t b = (uint32_t)__ffs((int)hits) - 1u;
+    g_mask &= ~(0x100u << b);
+    const uint32_t slot = b ^ oct;
+    return g_base + (uint32_t)__popc(g_mask & 0xFFu & ((1u << slot) - 1u));
+}
+// A tested node (n0, n1: its first two quads) becomes the lane's node group; the siblings still to visit are pushed first.  The node's triangles are the caller's.
+template <bool TWO_LEVEL>
+MRT_DEV void enter_node(uint32_t *stack, uint32_t lane, uint32_t &g_base, uint32_t &g_mask, const float4 n0, const float4 n1, uint32_t node_hits) {
+    uint32_t sp = TWO_LEVEL ? (g_mask >> 16) & 0xFFu : g_mask >> 16;
+    const uint32_t isp = TWO_LEVEL ? g_mask & 0xFF000000u : 0u;
+    if ((g_mask & 0xFF00u) != 0) { wstack_push(stack, sp, lane, g_base, g_mask & 0xFFFFu); sp++; }
+    g_base = __float_as_uint(n1.x); g_mask = isp | (sp << 16) | (node_hits << 8) | (__float_as_uint(n0.w) >> 24);
+}
+
+// A walk loads its packet (r0..r2) and its node (n0..n4) under has_tri / want_node and uses them under the same predicates; an empty asm "defines" them on the other
+// paths without the 28 v_mov a zero initialiser costs per iteration.
+#define MRT_DECLARE_UNLOADED(r0, r1, r2, n0, n1, n2, n3, n4) do { \
+    asm volatile("" : "=v"(r0.x), "=v"(r0.y), "=v"(r0.z), "=v"(r0.w), "=v"(r1.x), "=v"(r1.y), "=v"(r1.z), "=v"(r2.x), "=v"(r2.y), "=v"(r2.z)); \
+    asm volatile("" : "=v"(n0.x), "=v"(n0.y), "=v"(n0.z), "=v"(n0.w), "=v"(n1.x), "=v"(n1.y), "=v"(n1.z), "=v"(n1.w), "=v"(n2.x), "=v"(n2.y), "=v"(n2.z), "=v"(n2.w)); \
+    asm volatile("" : "=v"(n3.x), "=v"(n3.y), "=v"(n3.z), "=v"(n3.w), "=v"(n4.x), "=v"(n4.y), "=v"(n4.z), "=v"(n4.w)); \
+    r1.w = 0.0f; r2.w = 0.0f; } while (0)
+// ... and loads them: macros, because a function with reference parameters changes the flattened kernels' code; MRT_BOUND inside, so that every walk is checked
+#define MRT_LOAD_PACKET(s, pk_index, r0, r1, r2) do { MRT_BOUND(pk_index, (s).num_wpackets, 2); \
+    const float4 *__restrict__ pk_ = (s).wpackets + WPK * (size_t)(pk_index); r0 = pk_[0]; r1 = pk_[1]; r2 = pk_[2]; } while (0)
+#define MRT_LOAD_NODE(s, node, n0, n1, n2, n3, n4) do { MRT_BOUND(node, (s).num_wnodes, 1); \
+    const float4 *__restrict__ nd_ = (s).wnodes + WNODE_STRIDE * (size_t)(node); n0 = nd_[0]; n1 = nd_[1]; n2 = nd_[2]; n3 = nd_[3]; n4 = nd_[4]; } while (0)
+// Closest-hit order, the one place it is written: a hit at t replaces the closest hit so far when it is closer, or the first, or as close (`tie`: t == best_t; a triangle
+// test bounded by best_t passes `true`) and of the lower id.  A macro: the incumbent's id (a packet re-read, a hit word in LDS, global ids of two instances) is only
+// evaluated on a tie, and a function taking it as a callable changes the flattened kernels' code.
+#define MRT_CLOSER_HIT(better, t, best_t, best_pk, tie, cand_id, incumbent_id) \
+    bool better = (t) < (best_t) || (best_pk) == 0xFFFFFFFFu; \
+    if (!better && (tie)) better = (cand_id) < (incumbent_id)
+MRT_DEV uint32_t packet_id(const SceneView &s, uint32_t pk) { return __float_as_uint(s.wpackets[WPK * (size_t)pk].w); }
+
+// Hit words: U, V, |det| and triangle id (bits) of a lane's closest hit so far in four words of LDS ([4][64] per wave), so that the winner need not be tested again at the end
+MRT_DEV void hit_words_store(float *hw, uint32_t lane, float U, float V, float ad, float id_bits) { hw[lane] = U; hw[64u + lane] = V; hw[128u + lane] = ad; hw[192u + lane] = id_bits; }
+MRT_DEV void hit_words_store(float *hw, uint32_t lane, const TravHit &h) { hw[lane] = h.U; hw[64u + lane] = h.V; hw[128u + lane] = h.ad; hw[192u + lane] = __uint_as_float(h.gid); }
+MRT_DEV uint32_t hit_words_id(const float *hw, uint32_t lane) { return __float_as_uint(hw[192u + lane]); }
+MRT_DEV void hit_words_load(const float *hw, uint32_t lane, TravHit &h) { h.U = hw[lane]; h.V = hw[64u + lane]; h.ad = hw[128u + lane]; h.gid = hit_words_id(hw, lane); }
+// Without hit words: U, V, |det| and id of the winning packet for the ray it was found with, recomputed (same arithmetic as the walk's test) instead of living in four
+// registers through the loop.  TWO_LEVEL: (o, d) is the world ray and the test runs in the object space of `inst`, the winner's instance; the id is the global one.
+template <bool TWO_LEVEL>
+MRT_DEV void retest_winner(const SceneView &s, uint32_t best_pk, uint32_t inst, f3 o, f3 d, TravHit &h) {
+    const float4 *__restrict__ pk = s.wpackets + WPK * (size_t)best_pk;
+    const float4 q0 = pk[0];
+    uint32_t gid_base = 0;
+    if (TWO_LEVEL) { const InstanceDev &I = s.inst[inst]; const f3 oo = to_object_point(I, o), dd = to_object_dir(I, d); o = oo; d = dd; gid_base = I.gid_base; }
+    float t_;
+    (void)tri_test(q0, pk[1], pk[2], o, d, 0.0f, __builtin_inff(), t_, h.U, h.V, h.ad);
+    h.gid = gid_base + __float_as_uint(q0.w);
+}
+// the instance behind slot `tl_slot` of a TLAS leaf (two-level walks)
+MRT_DEV uint32_t tlas_instance(const SceneView &s, uint32_t tl_slot) {
+    MRT_BOUND(tl_slot, s.num_wtlas, 3);
+    uint32_t id = s.wtlas_index[tl_slot]; MRT_BOUND(id, s.num_inst, 4);
+    return id;
+}
+// The node a lane visits next: the nearest hit child of its group, or of the group on top of its stack when the group is used up (NEXT_NODE: `node` is it).
+// NEXT_END: nothing on the stack, the ray ends with the triangles it still has pending.  NEXT_LEAVE (TWO_LEVEL): the stack is back at the depth at which the BLAS was
+// entered — its last triangle is tested in this iteration, the lane leaves the instance in the next.
+enum NextNode { NEXT_NODE, NEXT_END, NEXT_LEAVE };
+template <bool TWO_LEVEL>
+MRT_DEV NextNode next_node(const uint32_t *stack, uint32_t lane, uint32_t &g_base, uint32_t &g_mask, uint32_t oct, uint32_t &node) {
+    if ((g_mask & 0xFF00u) == 0) {
+        const uint32_t sp = TWO_LEVEL ? (g_mask >> 16) & 0xFFu : g_mask >> 16, isp = TWO_LEVEL ? g_mask >> 24 : 0u;
+        if (TWO_LEVEL && isp != 0u && sp == isp) return NEXT_LEAVE;
+        if (sp == 0) return NEXT_END;
+        wstack_pop(stack, sp - 1u, lane, g_base, g_mask); g_mask |= ((sp - 1u) << 16) | (isp << 24);
+    }
+    node = take_nearest_child(g_base, g_mask, oct);
+    return NEXT_NODE;
+}
+// World <-> object switch of the two-level walks.  insts = instance being walked | instance of the closest hit << 16; tl_pack = the TLAS leaf's remaining instances while the
+// lane is inside a BLAS: tri_base << 8 | mask; g_mask carries the depth at which the BLAS was entered in bits 24.. (0 = at the TLAS level).
+// Enter the next instance of the TLAS leaf: park the TLAS group on the stack (always, also without siblings left: the exit pops it), take the ray into object space (direction
+// not renormalised: t stays the world distance), no group yet at the entry depth.  True: `node` is the BLAS root, fetched in this same iteration.  False: a BLAS of at most
+// eight triangles (a wall, the floor) has no node to test: its packets are the pending set.
+MRT_DEV bool enter_instance(const SceneView &s, uint32_t *stack, uint32_t lane, f3 &o, f3 &d, RayBox &rb, uint32_t &g_base, uint32_t &g_mask, uint32_t &t_base, uint32_t &t_mask,
+                            uint32_t &insts, uint32_t &tl_pack, uint32_t &node) {
+    const uint32_t k = (uint32_t)__ffs((int)t_mask) - 1u;
+    t_mask &= t_mask - 1u;
+    const uint32_t id = tlas_instance(s, t_base + k);
+    const InstanceDev &I = s.inst[id];
+    tl_pack = (t_base << 8) | t_mask;
+    uint32_t sp = (g_mask >> 16) & 0xFFu;
+    wstack_push(stack, sp, lane, g_base, g_mask & 0xFFFFu); sp++;
+    const f3 oo = to_object_point(I, o), dd = to_object_dir(I, d);
+    o = oo; d = dd; rb = ray_box(dd);
+    g_base = 0; g_mask = (sp << 24) | (sp << 16);
+    t_base = 0; t_mask = 0;
+    insts = (insts & 0xFFFF0000u) | id;
+    if (I.ntri <= 8u) { t_base = I.packet_base; t_mask = (1u << I.ntri) - 1u; return false; }
+    node = I.wroot;
+    return true;
+}
+// Nothing of the BLAS left (no triangle pending, no hit child, stack back at the entry depth): back to the world ray (wo, wd: the lane walk has it in registers, the stream
+// walk parked in LDS) and to the TLAS group parked at entry.  False: the lane is not at that point.
+MRT_DEV bool blas_done(uint32_t g_mask, uint32_t t_mask) {
+    const uint32_t sp = (g_mask >> 16) & 0xFFu, isp = g_mask >> 24;
+    return isp != 0u && t_mask == 0u && (g_mask & 0xFF00u) == 0u && sp == isp;
+}
+MRT_DEV void leave_instance(const uint32_t *stack, uint32_t lane, const f3 wo, const f3 wd, uint32_t tl_pack, f3 &o, f3 &d, RayBox &rb,
+                            uint32_t &g_base, uint32_t &g_mask, uint32_t &t_base, uint32_t &t_mask) {
+    const uint32_t sp = (g_mask >> 16) & 0xFFu;
+    o = wo; d = wd; rb = ray_box(wd);
+    wstack_pop(stack, sp - 1u, lane, g_base, g_mask); g_mask |= (sp - 1u) << 16;
+    t_base = tl_pack >> 8; t_mask = tl_pack & 0xFFu;
+}
+
 // stack: depth x WIDE_STACK_LEVEL_BYTES of LDS for the wave (depth = the scene's wide-tree depth, <= WIDE_STACK)
 template <bool ANY, bool STATS = false, bool RUNTIME_ANY = false>
 MRT_DEV bool traverse_wide(const SceneView &s, f3 o, f3 d, float tmin, float tmax, TravHit &h, uint32_t *stack /* depth x WIDE_STACK_LEVEL_BYTES in LDS */, TravCounters *tc = nullptr, bool any_rt = false, uint32_t root = 0 /* the node the walk starts at: a BLAS root of a two-level scene, with the ray in that instance's object space */) {
@@ -146,11 +271,7 @@ MRT_DEV bool traverse_wide(const SceneView &s, f3 o, f3 d, float tmin, float tma
                 sp--;
                 wstack_pop(stack, sp, lane, g_base, g_mask);
             }
-            const uint32_t hits = g_mask >> 8;
-            const uint32_t b = (uint32_t)__ffs((int)hits) - 1u;       // nearest remaining child in (slot ^ octant) order
-            g_mask &= ~(0x100u << b);
-            const uint32_t slot = b ^ oct;
-            pending = g_base + (uint32_t)__popc(g_mask & 0xFFu & ((1u << slot) - 1u));
+            pending = take_nearest_child(g_base, g_mask, oct);
             have_pending = true;
         }
         if (STATS) { if (do_tri) tc->tris++; else tc->steps++; if ((int)lane == __ffsll((long long)__ballot(1)) - 1) tc->wave_iters++; }
@@ -194,17 +315,16 @@ MRT_DEV bool traverse_wide(const SceneView &s, f3 o, f3 d, float tmin, float tma
 // refill: for COHERENT rays — the primary rays of an 8x8 tile, traced inside k_shade<.., TRACE0 = 2> — whose lanes stay in step by themselves.
 // SEED: `seed_pk` is a packet the caller has already tested (distance in tmax); the walk starts with it as its closest hit.  h.pk = packet of the final hit.
 #ifndef MRT_LANE_HIT_LDS
-#define MRT_LANE_HIT_LDS 1      // 1: the lane walk keeps U, V, |det|, id of its closest hit in four words of LDS (`hitw`, [4][64] behind the caller's stack) instead of testing the winner again at the end
+#define MRT_LANE_HIT_LDS 1      // 1: the lane walk keeps the hit words of its closest hit in LDS (`hitw`, [4][64] behind the caller's stack) instead of testing the winner again at the end
 #endif
 template <bool SEED>
-MRT_DEV bool traverse_wide_lane(const SceneView &s, const f3 o, const f3 d, float tmax, uint32_t seed_pk, TravHit &h, uint32_t *stack /* depth x WIDE_STACK_LEVEL_BYTES of LDS, this wave's */, float *hitw = nullptr, const TravHit *seed_hit = nullptr) {
+MRT_DEV bool traverse_wide_lane(const SceneView &s, const f3 o, const f3 d, float tmax, uint32_t seed_pk, TravHit &h, uint32_t *stack /* depth x WIDE_STACK_LEVEL_BYTES of LDS, this wave's */,
+                                float *hitw = nullptr, const TravHit *seed_hit = nullptr) {
     const uint32_t lane = threadIdx.x & 63;
-    const float ix = box_inv(d.x), iy = box_inv(d.y), iz = box_inv(d.z);
-    const bool nx = d.x < 0.0f, ny = d.y < 0.0f, nz = d.z < 0.0f;
-    const uint32_t oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
+    const RayBox rb = ray_box(d);
     float best_t = tmax; uint32_t best_pk = SEED ? seed_pk : 0xFFFFFFFFu;
     if (MRT_LANE_HIT_LDS && hitw) {          // the seed's own U, V, |det|, id (the caller tested it) are the closest hit so far
-        if (SEED && seed_hit && seed_pk != 0xFFFFFFFFu) { hitw[lane] = seed_hit->U; hitw[64u + lane] = seed_hit->V; hitw[128u + lane] = seed_hit->ad; hitw[192u + lane] = __uint_as_float(seed_hit->gid); }
+        if (SEED && seed_hit && seed_pk != 0xFFFFFFFFu) hit_words_store(hitw, lane, *seed_hit);
     }
     uint32_t g_base = 0, g_mask = s.num_wnodes != 0 ? 0x100u : 0u, t_base = 0, t_mask = 0;      // the root as the only hit child of a pseudo group; g_mask: imask | hit bits << 8 | stack depth << 16
     for (;;) {
@@ -212,62 +332,43 @@ MRT_DEV bool traverse_wide_lane(const SceneView &s, const f3 o, const f3 d, floa
         const uint32_t t_rest = t_mask & (t_mask - 1u);
         bool want_node = t_rest == 0u;
         uint32_t pending = 0;
-        if (want_node) {
+        if (want_node) {        // (next_node<false>, written out: the call changes k_shade_primary<2>)
             if ((g_mask & 0xFF00u) == 0) {
                 const uint32_t sp = g_mask >> 16;
                 if (sp == 0) { want_node = false; if (!has_tri) break; }
                 else { wstack_pop(stack, sp - 1u, lane, g_base, g_mask); g_mask |= (sp - 1u) << 16; }
             }
-            if (want_node) {
-                const uint32_t hits = (g_mask >> 8) & 0xFFu;
-                const uint32_t b = (uint32_t)__ffs((int)hits) - 1u;       // nearest remaining child in (slot ^ octant) order
-                g_mask &= ~(0x100u << b);
-                const uint32_t slot = b ^ oct;
-                pending = g_base + (uint32_t)__popc(g_mask & 0xFFu & ((1u << slot) - 1u));
-            }
+            if (want_node) pending = take_nearest_child(g_base, g_mask, rb.oct);
         }
         float4 r0, r1, r2, n0, n1, n2, n3, n4;
-        asm volatile("" : "=v"(r0.x), "=v"(r0.y), "=v"(r0.z), "=v"(r0.w), "=v"(r1.x), "=v"(r1.y), "=v"(r1.z), "=v"(r2.x), "=v"(r2.y), "=v"(r2.z));
-        asm volatile("" : "=v"(n0.x), "=v"(n0.y), "=v"(n0.z), "=v"(n0.w), "=v"(n1.x), "=v"(n1.y), "=v"(n1.z), "=v"(n1.w), "=v"(n2.x), "=v"(n2.y), "=v"(n2.z), "=v"(n2.w));
-        asm volatile("" : "=v"(n3.x), "=v"(n3.y), "=v"(n3.z), "=v"(n3.w), "=v"(n4.x), "=v"(n4.y), "=v"(n4.z), "=v"(n4.w));
-        r1.w = 0.0f; r2.w = 0.0f;
+        MRT_DECLARE_UNLOADED(r0, r1, r2, n0, n1, n2, n3, n4);
         uint32_t tri_pk = 0;
         if (has_tri) {
             tri_pk = t_base + (uint32_t)__ffs((int)t_mask) - 1u; t_mask = t_rest;
-            const float4 *__restrict__ pk = s.wpackets + WPK * (size_t)tri_pk;
-            r0 = pk[0]; r1 = pk[1]; r2 = pk[2];
+            MRT_LOAD_PACKET(s, tri_pk, r0, r1, r2);
         }
         if (want_node) {
-            const float4 *__restrict__ nd = s.wnodes + WNODE_STRIDE * (size_t)pending;
-            n0 = nd[0]; n1 = nd[1]; n2 = nd[2]; n3 = nd[3]; n4 = nd[4];
+            MRT_LOAD_NODE(s, pending, n0, n1, n2, n3, n4);
         }
         if (has_tri) {
             float t, U, V, ad;
             if (tri_test(r0, r1, r2, o, d, 0.0f, best_t, t, U, V, ad)) {
-                bool better = t < best_t || best_pk == 0xFFFFFFFFu;
-                if (!better) better = (MRT_LANE_HIT_LDS && hitw) ? __float_as_uint(r0.w) < __float_as_uint(hitw[192u + lane]) : __float_as_uint(r0.w) < __float_as_uint(s.wpackets[WPK * (size_t)best_pk].w);      // t == best_t: ties go to the lowest id
-                if (better) { best_t = t; best_pk = tri_pk; if (MRT_LANE_HIT_LDS && hitw) { hitw[lane] = U; hitw[64u + lane] = V; hitw[128u + lane] = ad; hitw[192u + lane] = r0.w; } }
+                MRT_CLOSER_HIT(better, t, best_t, best_pk, true, __float_as_uint(r0.w), (MRT_LANE_HIT_LDS && hitw) ? hit_words_id(hitw, lane) : packet_id(s, best_pk));
+                if (better) { best_t = t; best_pk = tri_pk; if (MRT_LANE_HIT_LDS && hitw) hit_words_store(hitw, lane, U, V, ad, r0.w); }
             }
         }
         if (want_node) {
             uint32_t node_hits, tri_hits;
-            wide_node_test<MRT_WIDE_SCALED != 0>(n0, n1, n2, n3, n4, o, ix, iy, iz, nx, ny, nz, oct, 0.0f, best_t, node_hits, tri_hits);
-            uint32_t sp = g_mask >> 16;
-            if ((g_mask & 0xFF00u) != 0) { wstack_push(stack, sp, lane, g_base, g_mask & 0xFFFFu); sp++; }     // siblings still to visit
-            g_base = __float_as_uint(n1.x); g_mask = (sp << 16) | (node_hits << 8) | (__float_as_uint(n0.w) >> 24);
+            wide_node_test<MRT_WIDE_SCALED != 0>(n0, n1, n2, n3, n4, o, rb.ix, rb.iy, rb.iz, rb.nx, rb.ny, rb.nz, rb.oct, 0.0f, best_t, node_hits, tri_hits);
+            enter_node<false>(stack, lane, g_base, g_mask, n0, n1, node_hits);
             t_base = __float_as_uint(n1.y); t_mask = tri_hits;
         }
         else if (t_rest == 0u) break;        // no node left and this was the last pending triangle
     }
     h.t = best_t; h.U = 0.0f; h.V = 0.0f; h.ad = 1.0f; h.gid = 0xFFFFFFFFu; h.pk = best_pk;
     if (best_pk == 0xFFFFFFFFu) return false;
-    if (MRT_LANE_HIT_LDS && hitw) { h.U = hitw[lane]; h.V = hitw[64u + lane]; h.ad = hitw[128u + lane]; h.gid = __float_as_uint(hitw[192u + lane]); return true; }
-    // id and barycentrics of the winning triangle: recomputed (same arithmetic) instead of living in four registers through the loop
-    const float4 *__restrict__ pk = s.wpackets + WPK * (size_t)best_pk;
-    const float4 q0 = pk[0];
-    float t_;
-    (void)tri_test(q0, pk[1], pk[2], o, d, 0.0f, __builtin_inff(), t_, h.U, h.V, h.ad);
-    h.gid = __float_as_uint(q0.w);
+    if (MRT_LANE_HIT_LDS && hitw) { hit_words_load(hitw, lane, h); return true; }
+    retest_winner<false>(s, best_pk, 0u, o, d, h);
     return true;
 }
 
@@ -280,24 +381,13 @@ template <bool SEED>
 MRT_DEV bool traverse_wide_lane_two_level(const SceneView &s, const f3 wo, const f3 wd, float tmax, uint32_t seed, TravHit &h, uint32_t *stack) {
     const uint32_t lane = threadIdx.x & 63;
     f3 o = wo, d = wd;
-    float ix = box_inv(d.x), iy = box_inv(d.y), iz = box_inv(d.z);
-    bool nx = d.x < 0.0f, ny = d.y < 0.0f, nz = d.z < 0.0f;
-    uint32_t oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
+    RayBox rb = ray_box(d);
     float best_t = tmax; uint32_t best_pk = 0xFFFFFFFFu;
-    uint32_t insts = 0;                                   // instance being walked | instance of the closest hit << 16
+    uint32_t insts = 0, tl_pack = 0;                      // (enter_instance)
     if (SEED && seed != 0xFFFFFFFFu) { best_pk = seed & 0xFFFFFFu; insts = (seed >> 24) << 16; }
-    uint32_t tl_pack = 0;                                 // the TLAS leaf's remaining instances while inside a BLAS: tri_base << 8 | mask
     uint32_t g_base = 0, g_mask = s.num_wnodes != 0 ? 0x100u : 0u, t_base = 0, t_mask = 0;
     for (;;) {
-        {   // nothing of the BLAS left (no triangle pending, no hit child, stack back at the entry depth): back to world space and to the TLAS group parked at entry
-            const uint32_t sp = (g_mask >> 16) & 0xFFu, isp = g_mask >> 24;
-            if (isp != 0u && t_mask == 0u && (g_mask & 0xFF00u) == 0u && sp == isp) {
-                o = wo; d = wd; ix = box_inv(d.x); iy = box_inv(d.y); iz = box_inv(d.z);
-                nx = d.x < 0.0f; ny = d.y < 0.0f; nz = d.z < 0.0f; oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
-                wstack_pop(stack, sp - 1u, lane, g_base, g_mask); g_mask |= (sp - 1u) << 16;
-                t_base = tl_pack >> 8; t_mask = tl_pack & 0xFFu;
-            }
-        }
+        if (blas_done(g_mask, t_mask)) leave_instance(stack, lane, wo, wd, tl_pack, o, d, rb, g_base, g_mask, t_base, t_mask);
         const bool in_blas = (g_mask >> 24) != 0u;
         const bool has_inst = t_mask != 0u && !in_blas;          // at the TLAS level a pending "triangle" is an instance to enter
         bool has_tri = t_mask != 0u && !has_inst;
@@ -305,78 +395,39 @@ MRT_DEV bool traverse_wide_lane_two_level(const SceneView &s, const f3 wo, const
         bool want_node = t_rest == 0u && !has_inst;
         uint32_t pending = 0, tri_pk = 0;
         if (has_inst) {
-            const uint32_t k = (uint32_t)__ffs((int)t_mask) - 1u;
-            t_mask &= t_mask - 1u;
-            const uint32_t id = s.wtlas_index[t_base + k];
-            const InstanceDev &I = s.inst[id];
-            tl_pack = (t_base << 8) | t_mask;
-            uint32_t sp = (g_mask >> 16) & 0xFFu;
-            wstack_push(stack, sp, lane, g_base, g_mask & 0xFFFFu); sp++;          // parked always, also without siblings left: the exit pops it
-            const f3 oo = to_object_point(I, o), dd = to_object_dir(I, d);
-            o = oo; d = dd; ix = box_inv(d.x); iy = box_inv(d.y); iz = box_inv(d.z);
-            nx = d.x < 0.0f; ny = d.y < 0.0f; nz = d.z < 0.0f; oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
-            g_base = 0; g_mask = (sp << 24) | (sp << 16);
-            t_base = 0; t_mask = 0;
-            insts = (insts & 0xFFFF0000u) | id;
-            if (I.ntri <= 8u) { t_base = I.packet_base; t_mask = (1u << I.ntri) - 1u; t_rest = t_mask & (t_mask - 1u); has_tri = true; }      // a wall, the floor: its packets are the pending set
-            else { pending = I.wroot; want_node = true; }
+            if (enter_instance(s, stack, lane, o, d, rb, g_base, g_mask, t_base, t_mask, insts, tl_pack, pending)) want_node = true;
+            else { t_rest = t_mask & (t_mask - 1u); has_tri = true; }
         }
         else if (want_node) {
-            if ((g_mask & 0xFF00u) == 0) {
-                const uint32_t sp = (g_mask >> 16) & 0xFFu, isp = g_mask >> 24;
-                if (isp != 0u && sp == isp) want_node = false;          // the BLAS's last triangle is tested in this iteration; the lane leaves in the next
-                else if (sp == 0) { want_node = false; if (!has_tri) break; }
-                else { wstack_pop(stack, sp - 1u, lane, g_base, g_mask); g_mask |= ((sp - 1u) << 16) | (isp << 24); }
-            }
-            if (want_node) {
-                const uint32_t hits = (g_mask >> 8) & 0xFFu;
-                const uint32_t b = (uint32_t)__ffs((int)hits) - 1u;
-                g_mask &= ~(0x100u << b);
-                const uint32_t slot = b ^ oct;
-                pending = g_base + (uint32_t)__popc(g_mask & 0xFFu & ((1u << slot) - 1u));
-            }
+            const NextNode nn = next_node<true>(stack, lane, g_base, g_mask, rb.oct, pending);
+            if (nn != NEXT_NODE) { want_node = false; if (nn == NEXT_END && !has_tri) break; }
         }
         float4 r0, r1, r2, n0, n1, n2, n3, n4;
-        asm volatile("" : "=v"(r0.x), "=v"(r0.y), "=v"(r0.z), "=v"(r0.w), "=v"(r1.x), "=v"(r1.y), "=v"(r1.z), "=v"(r2.x), "=v"(r2.y), "=v"(r2.z));
-        asm volatile("" : "=v"(n0.x), "=v"(n0.y), "=v"(n0.z), "=v"(n0.w), "=v"(n1.x), "=v"(n1.y), "=v"(n1.z), "=v"(n1.w), "=v"(n2.x), "=v"(n2.y), "=v"(n2.z), "=v"(n2.w));
-        asm volatile("" : "=v"(n3.x), "=v"(n3.y), "=v"(n3.z), "=v"(n3.w), "=v"(n4.x), "=v"(n4.y), "=v"(n4.z), "=v"(n4.w));
-        r1.w = 0.0f; r2.w = 0.0f;
+        MRT_DECLARE_UNLOADED(r0, r1, r2, n0, n1, n2, n3, n4);
         if (has_tri) {
             tri_pk = t_base + (uint32_t)__ffs((int)t_mask) - 1u; t_mask = t_rest;
-            const float4 *__restrict__ pk = s.wpackets + WPK * (size_t)tri_pk;
-            r0 = pk[0]; r1 = pk[1]; r2 = pk[2];
+            MRT_LOAD_PACKET(s, tri_pk, r0, r1, r2);
         }
         if (want_node) {
-            const float4 *__restrict__ nd = s.wnodes + WNODE_STRIDE * (size_t)pending;
-            n0 = nd[0]; n1 = nd[1]; n2 = nd[2]; n3 = nd[3]; n4 = nd[4];
+            MRT_LOAD_NODE(s, pending, n0, n1, n2, n3, n4);
         }
         if (has_tri) {
             float t, U, V, ad;
             if (tri_test(r0, r1, r2, o, d, 0.0f, best_t, t, U, V, ad)) {
-                bool better = t < best_t || best_pk == 0xFFFFFFFFu;
-                if (!better) better = s.inst[insts & 0xFFFFu].gid_base + __float_as_uint(r0.w) < s.inst[insts >> 16].gid_base + __float_as_uint(s.wpackets[WPK * (size_t)best_pk].w);      // t == best_t: lowest global id
+                MRT_CLOSER_HIT(better, t, best_t, best_pk, true, s.inst[insts & 0xFFFFu].gid_base + __float_as_uint(r0.w), s.inst[insts >> 16].gid_base + packet_id(s, best_pk));
                 if (better) { best_t = t; best_pk = tri_pk; insts = (insts & 0xFFFFu) | (insts << 16); }
             }
         }
         if (want_node) {
             uint32_t node_hits, tri_hits;
-            wide_node_test<MRT_WIDE_SCALED != 0>(n0, n1, n2, n3, n4, o, ix, iy, iz, nx, ny, nz, oct, 0.0f, best_t, node_hits, tri_hits);
-            uint32_t sp = (g_mask >> 16) & 0xFFu;
-            const uint32_t isp = g_mask & 0xFF000000u;
-            if ((g_mask & 0xFF00u) != 0) { wstack_push(stack, sp, lane, g_base, g_mask & 0xFFFFu); sp++; }
-            g_base = __float_as_uint(n1.x); g_mask = isp | (sp << 16) | (node_hits << 8) | (__float_as_uint(n0.w) >> 24);
+            wide_node_test<MRT_WIDE_SCALED != 0>(n0, n1, n2, n3, n4, o, rb.ix, rb.iy, rb.iz, rb.nx, rb.ny, rb.nz, rb.oct, 0.0f, best_t, node_hits, tri_hits);
+            enter_node<true>(stack, lane, g_base, g_mask, n0, n1, node_hits);
             t_base = __float_as_uint(n1.y); t_mask = tri_hits;
         }
     }
     h.t = best_t; h.U = 0.0f; h.V = 0.0f; h.ad = 1.0f; h.gid = 0xFFFFFFFFu; h.pk = 0xFFFFFFFFu;
     if (best_pk == 0xFFFFFFFFu) return false;
-    // id and barycentrics of the winning triangle, in the object space of its instance (the walk's own arithmetic)
-    const InstanceDev &I = s.inst[insts >> 16];
-    const float4 *__restrict__ pk = s.wpackets + WPK * (size_t)best_pk;
-    const float4 q0 = pk[0];
-    float t_;
-    (void)tri_test(q0, pk[1], pk[2], to_object_point(I, wo), to_object_dir(I, wd), 0.0f, __builtin_inff(), t_, h.U, h.V, h.ad);
-    h.gid = I.gid_base + __float_as_uint(q0.w);
+    retest_winner<true>(s, best_pk, insts >> 16, wo, wd, h);      // in the object space of its instance (the walk's own arithmetic)
     h.pk = best_pk | ((insts >> 16) << 24);
     return true;
 }
@@ -540,7 +591,54 @@ template <bool HIT> struct StreamExt {
     uint32_t *root = nullptr;      // MRT_ROOT_AT_FETCH: [2][64] words of this wave: the root's {internal-child hits, leaf-triangle hits} of the prefetched batch's rays
 };
 constexpr uint32_t HIT_LDS_WORDS = 256u + (MRT_ROOT_AT_FETCH ? 128u : 0u);      // per wave, in front of its stack
-//
+
+// Diagnostics of the stream walk (tools/build_variant.sh NAME "-DMRT_WAVE_TIMES" / "-DMRT_STATS_PROBE=1" / "=2"): hooks called once per iteration.  In the product build
+// they are empty MACROS, not empty functions: the loop's text has no #ifdef, and the arguments are not even evaluated — with empty functions the flattened stream
+// kernels' instructions come out in another order (tools/isa_diff.py).
+#ifdef MRT_WAVE_TIMES      // per-iteration clocks, and what the last live lanes of a draining wave still hold (StreamStats above)
+MRT_DEV void hook_wave_times(StreamStats *ss, bool TWO_LEVEL, bool draining, bool live, uint32_t g_mask, uint32_t t_mask, uint32_t u_mask, const uint32_t *stack, uint32_t lane) {
+    if (!ss) return;
+    if (draining) {
+        const uint32_t nl_ = (uint32_t)__popcll(__ballot(live)); ss->drain_iters++; ss->drain_live += nl_; if (nl_ <= 8u) ss->drain_le8++;
+        if (!TWO_LEVEL && nl_ <= 16u) {   // (flattened scenes) every live lane's pending work, summed over the wave by ballots / shuffles; lane 0's copy of `ss` is the one reported
+            const uint32_t sp_ = live ? g_mask >> 16 : 0u;
+            uint32_t kids_ = live ? (uint32_t)__popc((g_mask >> 8) & 0xFFu) : 0u;
+            for (uint32_t l_ = 0; l_ < sp_; l_++) kids_ += (uint32_t)__popc(stack[l_ * (WIDE_STACK_LEVEL_BYTES / 4u) + lane] & 0xFFu);
+            uint32_t tris_ = live ? (uint32_t)__popc(t_mask) + (uint32_t)__popc(u_mask) : 0u;
+            for (int o_ = 32; o_ > 0; o_ >>= 1) { kids_ += (uint32_t)__shfl_xor((int)kids_, o_); tris_ += (uint32_t)__shfl_xor((int)tris_, o_); }
+            for (int c_ = 0; c_ < 2; c_++) if (c_ == 0 || nl_ <= 4u) {
+                for (uint32_t d_ = 0; d_ < 6u; d_++) ss->dr_hist[c_][d_] += (uint32_t)__popcll(__ballot(live && (d_ < 5u ? sp_ == d_ : sp_ >= 5u)));
+                ss->dr_kids[c_] += kids_; ss->dr_tris[c_] += tris_; ss->dr_n[c_] += nl_;
+            }
+        }
+    }
+    const unsigned long long now_ = wall_clock64(); const uint32_t dt_ = (uint32_t)(now_ - ss->prev);
+    if (ss->prev != 0ull && dt_ > ss->maxdt) ss->maxdt = dt_;
+    ss->prev = now_; if (draining && ss->drain_t0 == 0ull) ss->drain_t0 = now_;
+}
+#else
+#define hook_wave_times(...) ((void)0)
+#endif
+#ifdef MRT_STATS_PROBE     // = 1: node fetches by tree level; = 2: pending triangles per iteration (pend = the lane's, both groups)
+MRT_DEV void hook_stats_probe(StreamStats *ss, bool has_tri, bool want_node, uint32_t node, uint32_t pend) {
+    if (!ss) return;
+#if MRT_STATS_PROBE == 1
+    for (int k = 0; k < 3; k++) ss->probe[k] += (uint32_t)__popcll(__ballot(want_node && node < ss->level_end[k]));
+#elif MRT_STATS_PROBE == 2
+    uint32_t tot = pend;
+    for (int o_ = 32; o_ > 0; o_ >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o_);
+    ss->probe[0] += tot; ss->probe[1] += (uint32_t)__popcll(__ballot(pend >= 2u)); ss->probe[2] += __popcll(__ballot(has_tri)) < 16 ? 1u : 0u;
+#endif
+}
+#else
+#define hook_stats_probe(...) ((void)0)
+#endif
+
+// the lane's ray in world space while it walks a BLAS (TWO_LEVEL): [6][64] words of LDS in front of the wave's stack
+MRT_DEV void world_ray_store(float *w, uint32_t l, f3 o, f3 d) { w[l] = o.x; w[64 + l] = o.y; w[128 + l] = o.z; w[192 + l] = d.x; w[256 + l] = d.y; w[320 + l] = d.z; }
+MRT_DEV f3 world_ray_o(const float *wray, uint32_t lane) { return mk3(wray[lane], wray[64 + lane], wray[128 + lane]); }
+MRT_DEV f3 world_ray_d(const float *wray, uint32_t lane) { return mk3(wray[192 + lane], wray[256 + lane], wray[320 + lane]); }
+
 // TWO_LEVEL (scenes committed with instancing = 1, two_level.hip): wnodes[0 ..] is an 8-wide TLAS whose leaf children are single instances
 // (the "packet" tri_base + k is an entry of wtlas_index), followed by the BLASes' nodes with absolute indices.  The same loop walks both levels on
 // the same stack: a lane whose pending "triangle" is an instance parks the TLAS group it came from on the stack, takes its ray into object space
@@ -550,6 +648,10 @@ constexpr uint32_t HIT_LDS_WORDS = 256u + (MRT_ROOT_AT_FETCH ? 128u : 0u);      
 // SEED (primary rays with a hint, k_trace_primary_wide_stream): `fetch` also returns a candidate hit — a packet (| instance << 24) whose distance it has already put
 // into the ray's limit word — and the walk starts with it as its closest hit so far; TravHit::pk at emit time is the final hit in the same encoding.
 // ROOTS (with TWO_LEVEL = false): `fetch` also returns the node the ray's walk starts at (the root of its instance's BLAS in the shared node array) instead of node 0.
+// ids as the stream walk's tie-break compares them (MRT_CLOSER_HIT evaluates them on a tie only; they name the walk's locals): global ones in a two-level scene — the
+// candidate is a triangle of the instance being walked
+#define MRT_GLOBAL_ID(id) (TWO_LEVEL ? s.inst[insts & 0xFFFFu].gid_base + (id) : (id))
+#define MRT_INCUMBENT_ID (TWO_LEVEL ? s.inst[insts >> 16].gid_base + packet_id(s, best_pk) : Ext::hit_lds ? hit_words_id(ext.hit, lane) : packet_id(s, best_pk))
 template <bool TWO_LEVEL = false, bool SEED = false, bool ROOTS = false, class Pairs = NoPairs, class Ext = NoExt, class Chunks, class RayFetch, class Emit>
 MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_t *stack, RayFetch fetch, Emit emit, StreamStats *ss = nullptr, Pairs pq = Pairs{}, Ext ext = Ext{}) {
     static_assert(!Ext::hit_lds || (!TWO_LEVEL && !SEED), "hit_lds: flattened scenes, rays without a seed hit");
@@ -571,7 +673,7 @@ MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_
     // live ray
     bool live = false, unreported = false;            // unreported: the lane's ray is finished, its result not yet emitted
     uint32_t tagw = 0;                                // tag | any-hit flag << 31
-    f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1); float ix = 0, iy = 0, iz = 0; bool nx = false, ny = false, nz = false; uint32_t oct = 0;
+    f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1); RayBox rb = {};
     float best_t = 0.0f; uint32_t best_pk = 0xFFFFFFFFu;     // closest hit so far: distance and packet (0xFFFFFFFF = none); id, U, V are re-read at emit time
     uint32_t g_base = 0, g_mask = 0, t_base = 0, t_mask = 0;   // g_mask: imask | permuted hit bits << 8 | stack depth << 16
     // Node visits ahead of the triangle tests (flattened scenes).  A node's leaf children leave up to 32 pending triangles, tested one per iteration; a lane
@@ -588,22 +690,19 @@ MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_
         const unsigned long long m_idle = __ballot(!live);
         const uint32_t n_idle = (uint32_t)__popcll(m_idle);
         if (n_idle >= (uint32_t)WIDE_REFILL_AT || m_idle == ~0ull) {
+            // ---- 1. report: the finished rays, by all idle lanes together
             if (unreported) {
                 const bool was_any = (tagw >> 31) != 0, was_hit = best_pk != 0xFFFFFFFFu;
                 TravHit h; h.t = best_t; h.U = 0.0f; h.V = 0.0f; h.ad = 1.0f; h.gid = 0xFFFFFFFFu;
                 if constexpr (Ext::hit_lds) {
-                    if (!was_any && was_hit) { h.U = ext.hit[lane]; h.V = ext.hit[64u + lane]; h.ad = ext.hit[128u + lane]; h.gid = __float_as_uint(ext.hit[192u + lane]); }      // kept since the hit was found
+                    if (!was_any && was_hit) hit_words_load(ext.hit, lane, h);      // kept since the hit was found
                 }
                 else if (!was_any && was_hit) {      // id and barycentrics of the winning triangle: recomputed here (same arithmetic) instead of living in 4 registers
-                    const float4 *__restrict__ pk = s.wpackets + WPK * (size_t)best_pk;
-                    const float4 q0 = pk[0];
-                    float t_;
-                    if (TWO_LEVEL) {            // in the object space of the hit's instance, from the parked world ray
-                        const InstanceDev &I = s.inst[insts >> 16];
-                        const f3 wo = mk3(wray[lane], wray[64 + lane], wray[128 + lane]), wd = mk3(wray[192 + lane], wray[256 + lane], wray[320 + lane]);
-                        (void)tri_test(q0, pk[1], pk[2], to_object_point(I, wo), to_object_dir(I, wd), 0.0f, __builtin_inff(), t_, h.U, h.V, h.ad);
-                        h.gid = I.gid_base + __float_as_uint(q0.w);
-                    } else {
+                    if (TWO_LEVEL) retest_winner<true>(s, best_pk, insts >> 16, world_ray_o(wray, lane), world_ray_d(wray, lane), h);      // from the parked world ray
+                    else {
+                        const float4 *__restrict__ pk = s.wpackets + WPK * (size_t)best_pk;
+                        const float4 q0 = pk[0];
+                        float t_;
                         (void)tri_test(q0, pk[1], pk[2], o, d, 0.0f, __builtin_inff(), t_, h.U, h.V, h.ad);
                         h.gid = __float_as_uint(q0.w);
                     }
@@ -611,7 +710,8 @@ MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_
                 if (SEED) h.pk = was_hit ? (best_pk | (TWO_LEVEL ? (insts >> 16) << 24 : 0u)) : 0xFFFFFFFFu;
                 emit(tagw & 0x7FFFFFFFu, was_any, was_hit, h); unreported = false;
             }
-            if (batch_used >= batch_n) {                        // prefetch the next (up to) 64 rays (coalesced), all lanes
+            // ---- 2. prefetch the next (up to) 64 rays (coalesced), all lanes
+            if (batch_used >= batch_n) {
                 if (cur >= end && more) more = next_chunk(cur, end);
                 batch_n = cur < end ? min(64u, end - cur) : 0u; batch_used = 0;
                 if (Pairs::on) batch_first = cur;
@@ -626,16 +726,16 @@ MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_
                         const float4 r0_ = nd[0], r1_ = nd[1], r2_ = nd[2], r3_ = nd[3], r4_ = nd[4];
                         if (lane < batch_n) {
                             const f3 o_ = mk3(pA.x, pA.y, pA.z);
-                            const float ix_ = box_inv(pB.x), iy_ = box_inv(pB.y), iz_ = box_inv(pB.z);
-                            const bool nx_ = pB.x < 0.0f, ny_ = pB.y < 0.0f, nz_ = pB.z < 0.0f;
+                            const RayBox b_ = ray_box(mk3(pB.x, pB.y, pB.z));
                             uint32_t nh_, th_;
-                            wide_node_test<MRT_WIDE_SCALED != 0>(r0_, r1_, r2_, r3_, r4_, o_, ix_, iy_, iz_, nx_, ny_, nz_, (nx_ ? 1u : 0u) | (ny_ ? 2u : 0u) | (nz_ ? 4u : 0u), 0.0f, pA.w, nh_, th_);
+                            wide_node_test<MRT_WIDE_SCALED != 0>(r0_, r1_, r2_, r3_, r4_, o_, b_.ix, b_.iy, b_.iz, b_.nx, b_.ny, b_.nz, b_.oct, 0.0f, pA.w, nh_, th_);
                             ext.root[lane] = nh_; ext.root[64u + lane] = th_;
                         }
                     }
                 }
                 cur += batch_n;
             }
+            // ---- 3. refill: the idle lanes take the prefetched rays
             const uint32_t avail = batch_n - batch_used;
             if (avail == 0) { if (m_idle == ~0ull) break; draining = true; }
             else {
@@ -647,12 +747,12 @@ MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_
                 const float bx_ = __shfl(pB.x, sl), by_ = __shfl(pB.y, sl), bz_ = __shfl(pB.z, sl), bw_ = __shfl(pB.w, sl);
                 const uint32_t seed_ = (SEED || ROOTS) ? (uint32_t)__shfl((int)pS, sl) : 0xFFFFFFFFu;
                 if (take) {
-                    o = mk3(ax_, ay_, az_); d = mk3(bx_, by_, bz_); ix = box_inv(bx_); iy = box_inv(by_); iz = box_inv(bz_);
-                    nx = d.x < 0.0f; ny = d.y < 0.0f; nz = d.z < 0.0f; oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
+                    o = mk3(ax_, ay_, az_); d = mk3(bx_, by_, bz_); rb = ray_box(d);
                     best_t = aw_; best_pk = 0xFFFFFFFFu;
                     tagw = __float_as_uint(bw_);
                     // enter the root as the only "hit child" of a pseudo group: base 0, no internal-child bits -> node 0; empty stack
-                    g_base = ROOTS ? seed_ : 0u; g_mask = s.num_wnodes != 0 ? 0x100u : 0u; t_base = 0; t_mask = 0;      // (the pseudo group has no internal-child bits: its one "hit child" is node g_base itself)
+                    // (the pseudo group has no internal-child bits: its one "hit child" is node g_base itself)
+                    g_base = ROOTS ? seed_ : 0u; g_mask = s.num_wnodes != 0 ? 0x100u : 0u; t_base = 0; t_mask = 0;
                     if constexpr (Ext::root_pre) {
                         if (s.num_wnodes != 0) {          // the root was tested when the batch was fetched: its children are the lane's first group
                             const float4 q1_ = s.wnodes[1];
@@ -664,39 +764,17 @@ MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_
                     live = true;
                     if (Pairs::on) qi = batch_first + (uint32_t)sl;
                     if (TWO_LEVEL) {
-                        wray[lane] = ax_; wray[64 + lane] = ay_; wray[128 + lane] = az_; wray[192 + lane] = bx_; wray[256 + lane] = by_; wray[320 + lane] = bz_;
+                        world_ray_store(wray, lane, o, d);
                         insts = 0; tl_pack = 0;
                     }
                     if (SEED && seed_ != 0xFFFFFFFFu) { best_pk = TWO_LEVEL ? (seed_ & 0xFFFFFFu) : seed_; if (TWO_LEVEL) insts = (seed_ >> 24) << 16; }
                 }
                 batch_used += min(avail, n_idle);
-#ifndef MRT_STATS_BOTH
                 if (ss) { ss->refills++; ss->refill_lanes += min(avail, n_idle); }
-#endif
                 continue;
             }
         }
-#ifdef MRT_WAVE_TIMES
-        if (ss) {
-            if (draining) {
-                const uint32_t nl_ = (uint32_t)__popcll(__ballot(live)); ss->drain_iters++; ss->drain_live += nl_; if (nl_ <= 8u) ss->drain_le8++;
-                if (!TWO_LEVEL && nl_ <= 16u) {          // (flattened scenes) every live lane's pending work, summed over the wave by ballots / shuffles; lane 0's copy of `ss` is the one reported
-                    const uint32_t sp_ = live ? g_mask >> 16 : 0u;
-                    uint32_t kids_ = live ? (uint32_t)__popc((g_mask >> 8) & 0xFFu) : 0u;
-                    for (uint32_t l_ = 0; l_ < sp_; l_++) kids_ += (uint32_t)__popc(stack[l_ * (WIDE_STACK_LEVEL_BYTES / 4u) + lane] & 0xFFu);
-                    uint32_t tris_ = live ? (uint32_t)__popc(t_mask) + (uint32_t)__popc(u_mask) : 0u;
-                    for (int o_ = 32; o_ > 0; o_ >>= 1) { kids_ += (uint32_t)__shfl_xor((int)kids_, o_); tris_ += (uint32_t)__shfl_xor((int)tris_, o_); }
-                    for (int c_ = 0; c_ < 2; c_++) if (c_ == 0 || nl_ <= 4u) {
-                        for (uint32_t d_ = 0; d_ < 6u; d_++) ss->dr_hist[c_][d_] += (uint32_t)__popcll(__ballot(live && (d_ < 5u ? sp_ == d_ : sp_ >= 5u)));
-                        ss->dr_kids[c_] += kids_; ss->dr_tris[c_] += tris_; ss->dr_n[c_] += nl_;
-                    }
-                }
-            }
-            const unsigned long long now_ = wall_clock64(); const uint32_t dt_ = (uint32_t)(now_ - ss->prev);
-            if (ss->prev != 0ull && dt_ > ss->maxdt) ss->maxdt = dt_;
-            ss->prev = now_; if (draining && ss->drain_t0 == 0ull) ss->drain_t0 = now_;
-        }
-#endif
+        hook_wave_times(ss, TWO_LEVEL, draining, live, g_mask, t_mask, u_mask, stack, lane);
         if (ss) { ss->iters++; ss->live_sum += (uint32_t)__popcll(__ballot(live)); }
         // One memory round trip per iteration.  A lane with at most one triangle left to test already knows the next node
         // it will visit (the nearest remaining hit child, or the top of its stack), so it fetches that node (80 B) together
@@ -704,20 +782,12 @@ MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_
         // (Measured, full frame: node-or-triangle per iteration 6.90, node then triangle with two round trips 7.24,
         // this loop 7.44 Grays/s.)
         if (SPEC && t_mask == 0u && u_mask != 0u) { t_base = u_base; t_mask = u_mask; u_mask = 0u; }      // the first group is used up: the second takes its place
-        if (TWO_LEVEL) {
-            // a lane inside a BLAS with nothing of it left (no triangle pending, no hit child, stack back at the entry depth) returns to world
-            // space and to the TLAS group parked at entry — in this same iteration it goes on to its next instance or TLAS node
-            const uint32_t sp = (g_mask >> 16) & 0xFFu, isp = g_mask >> 24;
-            if (live && isp != 0u && t_mask == 0u && (g_mask & 0xFF00u) == 0u && sp == isp) {
-                o = mk3(wray[lane], wray[64 + lane], wray[128 + lane]); d = mk3(wray[192 + lane], wray[256 + lane], wray[320 + lane]);
-                ix = box_inv(d.x); iy = box_inv(d.y); iz = box_inv(d.z);
-                nx = d.x < 0.0f; ny = d.y < 0.0f; nz = d.z < 0.0f; oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
-                wstack_pop(stack, sp - 1u, lane, g_base, g_mask); g_mask |= (sp - 1u) << 16;
-                t_base = tl_pack >> 8; t_mask = tl_pack & 0xFFu;
-            }
+        // ---- 4. leave-BLAS
+        if (TWO_LEVEL) {     // ... and in this same iteration the lane goes on to its next instance or TLAS node
+            if (live && blas_done(g_mask, t_mask)) leave_instance(stack, lane, world_ray_o(wray, lane), world_ray_d(wray, lane), tl_pack, o, d, rb, g_base, g_mask, t_base, t_mask);
         }
         const bool in_blas = TWO_LEVEL && (g_mask >> 24) != 0u;
-        // Drain phase (rocprofv3 / tools/archive/wave_times.py: the last 30 % of a launch run on < 2 % of the waves, each walking one or two grazing rays
+        // ---- 5. drain-help (rocprofv3 / tools/archive/wave_times.py: the last 30 % of a launch run on < 2 % of the waves, each walking one or two grazing rays
         // that test 100-200 triangles one per iteration).  The finished lanes help: the pending triangles of ONE such ray are tested by idle
         // lanes in this same iteration — lane k (or k + 32) takes triangle t_base + k with the owner's ray — and folded back into the owner.
         bool helping = false; int owner = -1; uint32_t help_pk = 0;
@@ -732,15 +802,18 @@ MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_
                 helping = !live && !unreported && ((o_tm >> bit) & 1u) != 0u && (lane < 32u || ((f_lo >> bit) & 1u) == 0u);
                 // the owner's ray is read HERE, where the whole wave is on: the owner is not among the helpers, and inside `if (helping)` a register the compiler had to reload would
                 // hold the owner's lane no more (a reload covers the active lanes only — two variant builds with more scratch rendered wrong images, tests/test_kernel_resources.py)
-                const f3 o_o = mk3(__uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(o.x), owner)), __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(o.y), owner)),
+                const f3 o_o = mk3(__uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(o.x), owner)),
+                                   __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(o.y), owner)),
                                    __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(o.z), owner)));
-                const f3 o_d = mk3(__uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(d.x), owner)), __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(d.y), owner)),
+                const f3 o_d = mk3(__uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(d.x), owner)),
+                                   __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(d.y), owner)),
                                    __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(d.z), owner)));
                 const float o_bt = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(best_t), owner));
                 if (helping) { o = o_o; d = o_d; best_t = o_bt; help_pk = o_tb + bit; }
                 if ((int)lane == owner) t_mask &= ~((f_lo | f_hi) & o_tm);      // these are being tested now
             }
         }
+        // ---- 6. pair push
         if constexpr (Pairs::on) {
             // TLAS pass: every LARGE instance among the lane's pending ones goes to the pair queue now (a short divergent loop: at most eight trips); the small ones stay pending and are
             // entered in place, one per iteration, as without a queue.  A lane whose pending instances were all large goes on to its next node in this same iteration.
@@ -748,10 +821,7 @@ MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_
                 uint32_t rest = t_mask, keep = 0u;
                 while (rest != 0u) {
                     const uint32_t k = (uint32_t)__ffs((int)rest) - 1u; rest &= rest - 1u;
-                    uint32_t tl_slot = t_base + k;
-                    MRT_BOUND(tl_slot, s.num_wtlas, 3);
-                    uint32_t id = s.wtlas_index[tl_slot];
-                    MRT_BOUND(id, s.num_inst, 4);
+                    const uint32_t id = tlas_instance(s, t_base + k);
                     if (s.inst[id].ntri > 8u && !pq_refused) {
                         const bool pushed = pq.push(qi, id, best_t, tagw);
                         if (!pushed) { pq_refused = true; keep |= 1u << k; }      // refused (the queue is full): this lane walks its large instances in place from here on
@@ -761,6 +831,7 @@ MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_
                 t_mask = keep;
             }
         }
+        // ---- 7. choose: this iteration's triangle and node
         const bool has_inst = TWO_LEVEL && live && t_mask != 0 && !in_blas;      // at the TLAS level a pending "triangle" is an instance to enter
         bool has_tri = live && t_mask != 0 && !has_inst;
         uint32_t t_rest = t_mask & (t_mask - 1u);               // triangles left after this iteration's first one
@@ -768,29 +839,10 @@ MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_
         uint32_t pending = 0, tri_pk = 0;
         bool last_step = false;         // flattened scenes: nothing but this iteration's triangle is left of the ray — it is finished when the test is done
         if (TWO_LEVEL && has_inst) {
-            // enter the next instance of the TLAS leaf: park the TLAS group (always, also without siblings left: the exit pops it), take the ray
-            // into object space, and fetch the BLAS root in this same iteration
-            const uint32_t k = (uint32_t)__ffs((int)t_mask) - 1u;
-            t_mask &= t_mask - 1u;
-            uint32_t tl_slot = t_base + k;
-            MRT_BOUND(tl_slot, s.num_wtlas, 3);
-            uint32_t id = s.wtlas_index[tl_slot];
-            MRT_BOUND(id, s.num_inst, 4);
-            const InstanceDev &I = s.inst[id];
-            tl_pack = (t_base << 8) | t_mask;
-            uint32_t sp = (g_mask >> 16) & 0xFFu;
-            wstack_push(stack, sp, lane, g_base, g_mask & 0xFFFFu); sp++;
-            const f3 oo = to_object_point(I, o), dd = to_object_dir(I, d);
-            o = oo; d = dd; ix = box_inv(d.x); iy = box_inv(d.y); iz = box_inv(d.z);
-            nx = d.x < 0.0f; ny = d.y < 0.0f; nz = d.z < 0.0f; oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
-            g_base = 0; g_mask = (sp << 24) | (sp << 16);          // no group yet: the root's children become the first one
-            t_base = 0; t_mask = 0;
-            insts = (insts & 0xFFFF0000u) | id;
-            if (I.ntri <= 8u) {          // a BLAS of a few triangles (a wall, a floor): no node to test, its packets are the pending set, the first one is tested now
-                t_base = I.packet_base; t_mask = (1u << I.ntri) - 1u; t_rest = t_mask & (t_mask - 1u); has_tri = true;
-            } else { pending = I.wroot; want_node = true; }
+            if (enter_instance(s, stack, lane, o, d, rb, g_base, g_mask, t_base, t_mask, insts, tl_pack, pending)) want_node = true;
+            else { t_rest = t_mask & (t_mask - 1u); has_tri = true; }      // a small BLAS: its first packet is tested now
         }
-        else if (want_node) {
+        else if (want_node) {       // (next_node<TWO_LEVEL>, written out: the call changes the flattened stream kernels)
             if ((g_mask & 0xFF00u) == 0) {
                 const uint32_t sp = TWO_LEVEL ? (g_mask >> 16) & 0xFFu : g_mask >> 16, isp = TWO_LEVEL ? g_mask >> 24 : 0u;
                 if (TWO_LEVEL && isp != 0u && sp == isp) want_node = false;      // the BLAS's last triangle is tested in this iteration; the lane leaves in the next
@@ -801,65 +853,37 @@ MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_
                 }
                 else { wstack_pop(stack, sp - 1u, lane, g_base, g_mask); g_mask |= ((sp - 1u) << 16) | (isp << 24); }
             }
-            if (want_node) {
-                const uint32_t hits = (g_mask >> 8) & 0xFFu;
-                const uint32_t b = (uint32_t)__ffs((int)hits) - 1u;       // nearest remaining child in (slot ^ octant) order
-                g_mask &= ~(0x100u << b);
-                const uint32_t slot = b ^ oct;
-                pending = g_base + (uint32_t)__popc(g_mask & 0xFFu & ((1u << slot) - 1u));
-            }
+            if (want_node) pending = take_nearest_child(g_base, g_mask, rb.oct);
         }
         if (ss) { ss->tri_sum += (uint32_t)__popcll(__ballot(has_tri)); ss->node_sum += (uint32_t)__popcll(__ballot(want_node)); }
-#if defined(MRT_STATS_PROBE) && MRT_STATS_PROBE == 1
-        if (ss) for (int k = 0; k < 3; k++) ss->probe[k] += (uint32_t)__popcll(__ballot(want_node && pending < ss->level_end[k]));
-#elif defined(MRT_STATS_PROBE) && MRT_STATS_PROBE == 2
-        if (ss) {
-            const uint32_t pend = live ? (uint32_t)__popc(t_mask) + (SPEC ? (uint32_t)__popc(u_mask) : 0u) : 0u;
-            uint32_t tot = pend;
-            for (int o_ = 32; o_ > 0; o_ >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o_);
-            ss->probe[0] += tot; ss->probe[1] += (uint32_t)__popcll(__ballot(pend >= 2u)); ss->probe[2] += __popcll(__ballot(has_tri)) < 16 ? 1u : 0u;
-        }
-#endif
-#ifdef MRT_STATS_BOTH      // diagnostics build (tools/archive/two_level_probe.py): in place of the refill counters, lane-iterations that do a triangle AND a node / that enter an instance
-        if (ss) { ss->refills += (uint32_t)__popcll(__ballot(has_tri && want_node)); ss->refill_lanes += (uint32_t)__popcll(__ballot(TWO_LEVEL && has_inst)); }
-#endif
-        float4 r0, r1, r2, n0, n1, n2, n3, n4;        // loaded under has_tri / want_node and used under the same predicates;
-        // an empty asm "defines" them on the other paths without the 28 v_mov a zero initialiser costs per iteration
-        asm volatile("" : "=v"(r0.x), "=v"(r0.y), "=v"(r0.z), "=v"(r0.w), "=v"(r1.x), "=v"(r1.y), "=v"(r1.z), "=v"(r2.x), "=v"(r2.y), "=v"(r2.z));
-        asm volatile("" : "=v"(n0.x), "=v"(n0.y), "=v"(n0.z), "=v"(n0.w), "=v"(n1.x), "=v"(n1.y), "=v"(n1.z), "=v"(n1.w), "=v"(n2.x), "=v"(n2.y), "=v"(n2.z), "=v"(n2.w));
-        asm volatile("" : "=v"(n3.x), "=v"(n3.y), "=v"(n3.z), "=v"(n3.w), "=v"(n4.x), "=v"(n4.y), "=v"(n4.z), "=v"(n4.w));
-        r1.w = 0.0f; r2.w = 0.0f;
+        hook_stats_probe(ss, has_tri, want_node, pending, live ? (uint32_t)__popc(t_mask) + (SPEC ? (uint32_t)__popc(u_mask) : 0u) : 0u);
+        // ---- 8. fetch
+        float4 r0, r1, r2, n0, n1, n2, n3, n4;
+        MRT_DECLARE_UNLOADED(r0, r1, r2, n0, n1, n2, n3, n4);
         if (has_tri || helping) {
             if (has_tri) { tri_pk = t_base + (uint32_t)__ffs((int)t_mask) - 1u; t_mask = t_rest; }
             else tri_pk = help_pk;
-            MRT_BOUND(tri_pk, s.num_wpackets, 2);
-            const float4 *__restrict__ pk = s.wpackets + WPK * (size_t)tri_pk;
-            r0 = pk[0]; r1 = pk[1]; r2 = pk[2];
+            MRT_LOAD_PACKET(s, tri_pk, r0, r1, r2);
         }
         if (want_node) {
-            MRT_BOUND(pending, s.num_wnodes, 1);
-            const float4 *__restrict__ nd = s.wnodes + WNODE_STRIDE * (size_t)pending;
-            n0 = nd[0]; n1 = nd[1]; n2 = nd[2]; n3 = nd[3]; n4 = nd[4];
+            MRT_LOAD_NODE(s, pending, n0, n1, n2, n3, n4);
         }
+        // ---- 9. triangle
         auto consider = [&](const float4 q0, const float4 q1, const float4 q2, const uint32_t pk_index) {
             float t, U, V, ad;
             if (tri_test(q0, q1, q2, o, d, 0.0f, best_t, t, U, V, ad)) {
                 if ((tagw >> 31) != 0) { best_pk = pk_index; live = false; unreported = true; }   // any-hit ray: done
                 else {
-                    bool better = t < best_t || best_pk == 0xFFFFFFFFu;
-                    if (!better) {                                      // t == best_t: ties go to the lowest (global) id (rare)
-                        if (TWO_LEVEL) better = s.inst[insts & 0xFFFFu].gid_base + __float_as_uint(q0.w) < s.inst[insts >> 16].gid_base + __float_as_uint(s.wpackets[WPK * (size_t)best_pk].w);
-                        else if (Ext::hit_lds) better = __float_as_uint(q0.w) < __float_as_uint(ext.hit[192u + lane]);
-                        else better = __float_as_uint(q0.w) < __float_as_uint(s.wpackets[WPK * (size_t)best_pk].w);
-                    }
+                    MRT_CLOSER_HIT(better, t, best_t, best_pk, true, MRT_GLOBAL_ID(__float_as_uint(q0.w)), MRT_INCUMBENT_ID);      // (ties are rare)
                     if (better) {
                         best_t = t; best_pk = pk_index; if (TWO_LEVEL) insts = (insts & 0xFFFFu) | (insts << 16);
-                        if (Ext::hit_lds) { ext.hit[lane] = U; ext.hit[64u + lane] = V; ext.hit[128u + lane] = ad; ext.hit[192u + lane] = q0.w; }
+                        if (Ext::hit_lds) hit_words_store(ext.hit, lane, U, V, ad, q0.w);
                     }
                 }
             }
         };
         if (has_tri) consider(r0, r1, r2, tri_pk);
+        // ---- 10. fold-back of the helpers' hits into the owner
         if (owner >= 0) {                                        // wave-uniform
             float h_t = 0.0f; bool h_hit = false;
             float U_ = 0.0f, V_ = 0.0f, ad_ = 1.0f;
@@ -870,31 +894,29 @@ MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_
                 const int l = __ffsll((long long)m) - 1;
                 const float t_ = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(h_t), l));
                 const uint32_t g_ = (uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(r0.w), l), p_ = (uint32_t)__builtin_amdgcn_readlane((int)tri_pk, l);
-                if (t_ < bt || (t_ == bt && g_ < bgid)) { bt = t_; bgid = g_; bpk = p_; bl = l; }
+                if (t_ < bt || (t_ == bt && g_ < bgid)) { bt = t_; bgid = g_; bpk = p_; bl = l; }      // (wave-uniform min over (t, id): as a shared function it changed the flattened kernels)
             }
             // hit_lds: the winning helper's U, V, |det| travel to the owner with its distance
-            const float wU = Ext::hit_lds ? __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(U_), bl)) : 0.0f, wV = Ext::hit_lds ? __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(V_), bl)) : 0.0f,
+            const float wU = Ext::hit_lds ? __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(U_), bl)) : 0.0f,
+                        wV = Ext::hit_lds ? __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(V_), bl)) : 0.0f,
                         wA = Ext::hit_lds ? __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(ad_), bl)) : 1.0f;
             // (the owner may have run out of nodes in this very iteration — it then waits for its report with these hits folded in)
             if ((int)lane == owner && bpk != 0xFFFFFFFFu) {
                 if ((tagw >> 31) != 0) { best_pk = bpk; live = false; unreported = true; }
                 else {
-                    bool better = bt < best_t || best_pk == 0xFFFFFFFFu;
-                    if (!better && bt == best_t) {
-                        if (TWO_LEVEL) better = s.inst[insts & 0xFFFFu].gid_base + bgid < s.inst[insts >> 16].gid_base + __float_as_uint(s.wpackets[WPK * (size_t)best_pk].w);
-                        else if (Ext::hit_lds) better = bgid < __float_as_uint(ext.hit[192u + lane]);
-                        else better = bgid < __float_as_uint(s.wpackets[WPK * (size_t)best_pk].w);
-                    }
+                    MRT_CLOSER_HIT(better, bt, best_t, best_pk, bt == best_t, MRT_GLOBAL_ID(bgid), MRT_INCUMBENT_ID);
                     if (better) {
                         best_t = bt; best_pk = bpk; if (TWO_LEVEL) insts = (insts & 0xFFFFu) | (insts << 16);
-                        if (Ext::hit_lds) { ext.hit[lane] = wU; ext.hit[64u + lane] = wV; ext.hit[128u + lane] = wA; ext.hit[192u + lane] = __uint_as_float(bgid); }
+                        if (Ext::hit_lds) hit_words_store(ext.hit, lane, wU, wV, wA, __uint_as_float(bgid));
                     }
                 }
             }
         }
+        // ---- 11. node
         if (want_node && live) {
             uint32_t node_hits, tri_hits;
-            wide_node_test<MRT_WIDE_SCALED != 0>(n0, n1, n2, n3, n4, o, ix, iy, iz, nx, ny, nz, oct, 0.0f, best_t, node_hits, tri_hits);
+            wide_node_test<MRT_WIDE_SCALED != 0>(n0, n1, n2, n3, n4, o, rb.ix, rb.iy, rb.iz, rb.nx, rb.ny, rb.nz, rb.oct, 0.0f, best_t, node_hits, tri_hits);
+            // (enter_node<TWO_LEVEL>, written out: the call changes the order of the flattened stream kernels' instructions)
             uint32_t sp = TWO_LEVEL ? (g_mask >> 16) & 0xFFu : g_mask >> 16;
             const uint32_t isp = TWO_LEVEL ? g_mask & 0xFF000000u : 0u;
             if ((g_mask & 0xFF00u) != 0) { wstack_push(stack, sp, lane, g_base, g_mask & 0xFFFFu); sp++; }     // siblings still to visit
@@ -903,13 +925,10 @@ MRT_DEV void traverse_wide_stream(const SceneView &s, Chunks next_chunk, uint32_
             else { t_base = __float_as_uint(n1.y); t_mask = tri_hits; }
         }
         if (last_step && live) { live = false; unreported = true; }
-#ifdef MRT_PROBE_EXTRA_VALU      // diagnostics build: N more full-rate VALU instructions per iteration, on a scratch register (how much of the loop's time is VALU issue?)
-        { float sink_; asm volatile("v_mov_b32 %0, %1" : "=v"(sink_) : "v"(best_t));
-#pragma unroll
-          for (int k_ = 0; k_ < MRT_PROBE_EXTRA_VALU; k_++) asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(sink_)); }
-#endif
     }
 }
+#undef MRT_GLOBAL_ID
+#undef MRT_INCUMBENT_ID
 
 }  // namespace
 }  // namespace mrt
