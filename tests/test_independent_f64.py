@@ -96,34 +96,43 @@ def test_oracle_image_matches_float64_restatement_on_a_cornell_crop(orc, mrt):
         assert ref.max() > 0.5 and (ref.sum(1) > 0).mean() > 0.5       # the crop is lit: the comparison is not vacuous
 
 
-def _crop_against_f64(orc, mrt, sc, W, H, x0, y0, frames=2, side=16):
+def _crop_against_f64(orc, mrt, sc, W, H, x0, y0, frames=2, side=16, materials=False, max_bounces=3, image=None):
     """The oracle's fp32 image of `sc` against tests/f64_reference.render_frame on a side x side block, `frames` accumulated frames; the tolerance rule of the
-    Cornell crop above, scaled with the radiance range.  Returns (f64 radiance of frame 0, margin, oracle scene, triangles) for the callers' own checks."""
+    Cornell crop above, scaled with the radiance range.  `materials`: the extension of docs/HISTORY.md §10 on both sides.  `image(f)`: the (H, W, 4) accumulation after
+    frame f from another renderer of the same definition (the GPU's) in place of the oracle's.
+    Returns (f64 radiance of frame 0, margin, triangles, pixels, per-path branch tally summed over the frames) for the callers' own checks."""
     flat = mrt.flatten_scene(sc)
-    osc = orc.OracleScene(flat, sc.lights)
-    r = orc.OracleRenderer(osc, W, H, seed=1, max_bounces=3, camera=sc.camera)
     tris = F.Triangles(flat)
-    assert len(tris) == osc.triangles
+    if image is None:
+        osc = orc.OracleScene(flat, sc.lights)
+        r = orc.OracleRenderer(osc, W, H, seed=1, max_bounces=max_bounces, camera=sc.camera)
+        r.set_materials(materials)
+        assert len(tris) == osc.triangles
+        def image(f):
+            r.render(1)
+            return r.accumulation().copy()
     seeds = np.array([orc.seed_hash(1, i) for i in range(W * H)], np.int64).reshape(H, W)
     pix = [(x, y) for y in range(y0, y0 + side) for x in range(x0, x0 + side)]
     ys, xs = np.array([p[1] for p in pix]), np.array([p[0] for p in pix])
-    ref, margin, first = None, np.full(len(pix), np.inf), None
+    ref, margin, first, tally = None, np.full(len(pix), np.inf), None, 0
     for f in range(frames):
-        r.render(1)
-        img = r.accumulation().copy()
-        ff, m = F.render_frame(tris, sc.lights, sc.camera, W, H, seeds, f, pix)
+        img = image(f)
+        ff, m, t = F.render_frame(tris, sc.lights, sc.camera, W, H, seeds, f, pix, max_bounces=max_bounces, materials=materials, tally=True)
         first = ff if first is None else first
         ref = ff if f == 0 else (ff + ref * float(f)) / float(f + 1)          # Raytracing.metal:394-401
-        margin = np.minimum(margin, m)
+        margin = np.minimum(margin, m); tally = tally + t
         got = img[ys, xs, :3].astype(np.float64)
         assert np.all(img[ys, xs, 3] == 1.0)
         d = np.abs(got - ref).max(1)
         safe = margin > 1e-3
         scale = max(1.0, float(ref.max()))
+        print(f"crop ({x0}, {y0}) frame {f}: safe {safe.mean():.3f}, max over safe pixels {d[safe].max():.3g}, median {np.median(d):.3g}, scale {scale:.3g}")
         assert safe.mean() > 0.5, safe.mean()
+        # measured with materials on the Cornell box of tests/material_scenes.py (glass + gold-like spheres, 4 bounces): max 1.6e-6 over the safe pixels of the WHOLE
+        # 64 x 48 frame, scale 2.5 — curved glass does not need a wider bound than the plain crops
         assert (d[safe] <= 2e-5 * scale).mean() >= 0.97, f"frame {f}: {(d[safe] > 2e-5 * scale).sum()} of {safe.sum()} safe pixels differ by more than {2e-5 * scale:.1e} (max {d[safe].max():.3g})"
         assert np.median(d) < 2e-6 * scale
-    return first, margin, tris, pix
+    return first, margin, tris, pix, tally
 
 
 def _without_light(lights, k):
@@ -151,7 +160,7 @@ def test_oracle_image_matches_float64_on_a_dragonscene_crop_spot_light_rotated_t
             self.models = [mo if mo.name != "dragon" else mrt.Model(name="train", position=dr.position, rotation=dr.rotation, scale=0.3 * dr.scale) for mo in full]
     sc = S((W, H))
     assert [l.type for l in sc.lights] == [4, 2] and sc.models[1].rotation[1] != 0
-    f0, margin, tris, pix = _crop_against_f64(orc, mrt, sc, W, H, 40, 12)
+    f0, margin, tris, pix, _ = _crop_against_f64(orc, mrt, sc, W, H, 40, 12)
     # not vacuous: the spot light carries a visible part of the crop, and the crop sees many submeshes of both trains
     seeds = np.array([orc.seed_hash(1, i) for i in range(W * H)], np.int64).reshape(H, W)
     dark, _ = F.render_frame(tris, _without_light(sc.lights, 1), sc.camera, W, H, seeds, 0, pix)
@@ -181,7 +190,7 @@ def test_oracle_image_matches_float64_on_a_garden_crop_sun_and_spot(orc, mrt):
             self.lights = g.lights
     sc = S((W, H))
     assert [l.type for l in sc.lights] == [2, 1] and len(sc.models) == 5
-    f0, margin, tris, pix = _crop_against_f64(orc, mrt, sc, W, H, 50, 7)
+    f0, margin, tris, pix, _ = _crop_against_f64(orc, mrt, sc, W, H, 50, 7)
     seeds = np.array([orc.seed_hash(1, i) for i in range(W * H)], np.int64).reshape(H, W)
     for k in (0, 1):          # each of the two lights carries a visible part of the crop
         dark, _ = F.render_frame(tris, _without_light(sc.lights, k), sc.camera, W, H, seeds, 0, pix)
@@ -195,8 +204,122 @@ def test_oracle_image_matches_float64_on_a_cornell_crop_with_point_and_spot_ligh
     sc.lights = [mrt.Light.pointLight(position=[0.3, 1.6, 0.4], color=[2.0, 1.5, 1.0]),
                  mrt.Light.spotLight(position=[-0.6, 1.8, 0.8], direction=[0.5, -1.0, -0.6], coneAngle=np.float32(18.0 / 180.0 * np.pi), color=[5, 5, 6])]
     assert [l.type for l in sc.lights] == [3, 2]
-    f0, margin, tris, pix = _crop_against_f64(orc, mrt, sc, W, H, 24, 20)
+    f0, margin, tris, pix, _ = _crop_against_f64(orc, mrt, sc, W, H, 24, 20)
     seeds = np.array([orc.seed_hash(1, i) for i in range(W * H)], np.int64).reshape(H, W)
     for k in (0, 1):
         dark, _ = F.render_frame(tris, _without_light(sc.lights, k), sc.camera, W, H, seeds, 0, pix)
         assert ((f0 - dark).max(1) > 0.02).mean() > 0.1, (k, ((f0 - dark).max(1) > 0.02).mean())
+
+
+# ---------------------------------------------------------------- the materials extension (docs/HISTORY.md §10)
+MATERIAL_CROPS = [(16, 8), (28, 8)]          # 64 x 48 frame: over the right half of the glass sphere and its silhouette; over the gold-like sphere's top and left silhouette
+
+
+def materials_crop_is_not_vacuous(tally):
+    """the crop holds paths through every kind of event the extension adds (the float64 side knows what each of its paths did)"""
+    t = dict(zip(F.BRANCHES, tally.sum(0)))
+    assert t["reflect"] >= 3 and t["refract"] >= 50 and t["specular"] >= 30 and t["emitter"] >= 3 and t["diffuse"] >= 500 and t["absorbed"] >= 1, t
+
+
+@pytest.mark.parametrize("x0,y0", MATERIAL_CROPS)
+def test_oracle_materials_match_float64_physics_on_a_cornell_crop(orc, mrt, x0, y0):
+    """The oracle's `if (materials)` against the float64 restatement of docs/HISTORY.md §10 (Householder reflection, refraction by angles, the lobe through arccos):
+    Cornell box with a glass sphere (dissolve 0.15, Ni 1.5), a gold-like sphere (Ks 0.8 / Ns 96) and an emissive panel, 4 bounces, two accumulated frames."""
+    from material_scenes import cornell_with_materials
+    W, H = 64, 48
+    sc = cornell_with_materials(mrt, (W, H))
+    _, margin, _, _, tally = _crop_against_f64(orc, mrt, sc, W, H, x0, y0, materials=True, max_bounces=4)
+    materials_crop_is_not_vacuous(tally)
+
+
+# pure-function checks of the float64 helpers: what the restatement is itself pinned by
+def _unit(rng, n):
+    v = rng.normal(size=(n, 3))
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def _incident(rng, n, lo_deg=3.0, hi_deg=87.0):
+    """unit normals and unit directions arriving at them (d.n < 0) at angles of incidence in [lo, hi] degrees"""
+    nn = _unit(rng, n)
+    t = _unit(rng, n); t -= (t * nn).sum(1, keepdims=True) * nn; t /= np.linalg.norm(t, axis=1, keepdims=True)
+    th = np.radians(rng.uniform(lo_deg, hi_deg, n))
+    return nn, -np.cos(th)[:, None] * nn + np.sin(th)[:, None] * t, th
+
+
+def test_f64_reflection_is_the_mirror_image():
+    rng = np.random.default_rng(21)
+    n, d, th = _incident(rng, 200)
+    r = F.householder(n, d)
+    assert np.allclose((r * n).sum(1), -(d * n).sum(1), atol=1e-14) and np.allclose(r - (r * n).sum(1, keepdims=True) * n, d - (d * n).sum(1, keepdims=True) * n, atol=1e-14)
+    assert np.allclose(np.linalg.norm(r, axis=1), 1.0, atol=1e-14) and np.allclose(F.householder(-n, d), r, atol=1e-15) and np.allclose(F.householder(n, r), d, atol=1e-14)
+    assert np.allclose(F.householder([[0.0, 1.0, 0.0]], [[0.6, -0.8, 0.0]]), [[0.6, 0.8, 0.0]], atol=1e-16)
+
+
+@pytest.mark.parametrize("ni", [1.5, 2.4, 1.0, 0.67])
+def test_f64_refraction_obeys_snell_and_stays_in_the_plane_of_incidence(ni):
+    rng = np.random.default_rng(22)
+    n, d, th = _incident(rng, 400)
+    for flip in (False, True):                       # entering (d.n < 0, eta = 1 / ni) and leaving (the same rays against -n, eta = ni)
+        r = F.dielectric(d, -n if flip else n, ni)
+        eta = ni if flip else 1.0 / ni
+        assert (r["entering"] != flip).all() and np.allclose(r["eta"], eta) and np.allclose(r["theta_i"], th, atol=1e-13)
+        assert np.array_equal(r["tir"], eta * np.sin(th) >= 1.0)
+        ok = ~r["tir"]
+        assert ok.sum() > 50                             # leaving a medium of index 2.4: only below the critical angle of 24.6 degrees
+        t = r["refracted"][ok]
+        assert np.abs(np.linalg.norm(t, axis=1) - 1.0).max() < 1e-12
+        sin_t = np.linalg.norm(np.cross(t, n[ok]), axis=1)
+        assert np.abs(sin_t - eta * np.sin(th[ok])).max() < 1e-12                                        # Snell
+        assert np.abs(np.einsum("ki,ki->k", np.cross(d[ok], n[ok]), t)).max() < 1e-12                  # coplanar with d and n
+        assert ((t * n[ok]).sum(1) < 0).all()                                                          # goes on through the surface ...
+        tang = lambda v: v - (v * n[ok]).sum(1, keepdims=True) * n[ok]
+        assert ((tang(t) * tang(d[ok])).sum(1) > 0).all()                                              # ... on the same side of the normal
+        if ni == 1.0:
+            assert np.abs(t - d[ok]).max() < 1e-12 and np.abs(r["F"][ok] - (1.0 - np.cos(th[ok])) ** 5).max() < 1e-12                    # Ni 1 bends nothing
+
+
+def test_f64_refraction_in_and_out_through_parallel_faces_returns_the_direction():
+    rng = np.random.default_rng(23)
+    for ni in (1.5, 2.4, 0.67, 1.0):
+        n, d, th = _incident(rng, 300)
+        a = F.dielectric(d, n, ni)
+        ok = ~a["tir"]
+        b = F.dielectric(a["refracted"][ok], -n[ok], ni)             # the far face of a slab: its normal points out of the medium, the other way
+        assert not b["entering"].any() and not b["tir"].any()
+        assert np.abs(b["refracted"] - d[ok]).max() < 1e-12
+        assert np.abs(b["F"] - a["F"][ok]).max() < 1e-12               # §10: the transmitted cosine when leaving == the incident cosine when entering
+
+
+def test_f64_schlick_limits():
+    n = np.array([[0.0, 1.0, 0.0]])
+    for ni in (1.5, 2.4, 0.67):
+        r0 = ((1 - ni) / (1 + ni)) ** 2
+        assert abs(F.dielectric([[0.0, -1.0, 0.0]], n, ni)["F"][0] - r0) < 1e-15                        # normal incidence, entering
+        assert abs(F.dielectric([[0.0, 1.0, 0.0]], n, ni)["F"][0] - r0) < 1e-15                         # and leaving
+        th = np.radians(np.array([30.0, 60.0, 80.0, 89.0, 89.9, 89.999]))
+        r = F.dielectric(np.c_[np.sin(th), -np.cos(th), 0 * th], np.repeat(n, len(th), 0), ni)
+        f = r["F"]
+        if ni > 1.0:
+            assert (np.diff(f) > 0).all() and f[0] > r0 and 1.0 - f[-1] < 1e-3 and (f <= 1.0).all()     # tends to 1 at grazing incidence
+        else:                                            # into a thinner medium: total internal reflection beyond arcsin(0.67) = 42 degrees
+            assert r["tir"].tolist() == [False] + [True] * 5 and r0 < f[0] < 1.0 and (f[1:] == 1.0).all()
+    c = 0.5 ** 0.5
+    assert abs(F.dielectric([[c, -c, 0.0]], n, 1.5)["F"][0] - (0.04 + 0.96 * (1 - c) ** 5)) < 1e-15
+
+
+def test_f64_specular_half_vector_distribution():
+    """theta = arccos sqrt((1 - v) / (1 + (a2 - 1) v)) inverts the GGX cumulative: v = 0 is the normal itself, v -> 1 grazing, the median half angle has tan^2 = a2; the frame is the diffuse branch's."""
+    rng = np.random.default_rng(24)
+    nw = _unit(rng, 50)
+    u = rng.random(50)
+    for Ns in (0.01, 30.0, 1e6):
+        a2 = 2.0 / (Ns + 2.0)
+        h0 = F.specular_half_vector(u, np.zeros(50), Ns, nw)
+        assert np.abs(h0 - nw).max() < 1e-12
+        hm = F.specular_half_vector(u, np.full(50, 0.5), Ns, nw)
+        cos2 = (hm * nw).sum(1) ** 2
+        assert np.abs((1 - cos2) / cos2 - a2).max() < 1e-9 * max(1.0, a2) and np.abs(np.linalg.norm(hm, axis=1) - 1).max() < 1e-12
+    y = np.array([[0.0, 1.0, 0.0]])
+    h = F.specular_half_vector(np.array([0.0]), np.array([0.5]), 0.0, y)[0]       # Ns = 0: a2 = 1, cos^2 = 1 - v; phi = 0 lies along `right` = normalize(y x (0.0072, 1, 0.0034))
+    right = np.cross(y[0], [0.0072, 1.0, 0.0034]); right /= np.linalg.norm(right)
+    assert np.allclose(h, np.sqrt(0.5) * right + np.sqrt(0.5) * y[0], atol=1e-15)
