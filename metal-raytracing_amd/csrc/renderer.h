@@ -2,6 +2,7 @@
 #pragma once
 #include "scene_device.h"
 #include "host_geometry.h"
+#include <algorithm>
 #include <array>
 #include <deque>
 #include <vector>
@@ -33,6 +34,46 @@ constexpr int MAX_TILE_GROUPS = 4;
 struct TileGroup { int rank = 0, world = 1, tiles_local = 0; uint32_t capacity = 0; uint64_t owned = 0; const uint32_t *seeds = nullptr; };
 constexpr int MAX_FRAME_BATCH = 32;
 constexpr int DEFAULT_FRAME_BATCH = 8;
+
+// What a draw of n_frames comes to, decided before anything is enqueued (Renderer::plan_draw: host arithmetic only).  The rule that splits a draw into passes lives here and
+// nowhere else (distributed.pass_sizes restates it for bench.py's launch plan).
+struct DrawPlan {
+    int n_frames = 0;
+    bool mega = false;                   // one launch per frame: passes of one frame
+    bool equal = true, tail = true;      // the options equal_passes, tail_accumulate
+    int batch_max = 1;                   // frames per pass at most
+    int n_passes = 0;
+    int G = 1;                           // tile groups per pass
+    int lanes = 1;                       // lanes wanted; after settle(): lanes the draw runs on
+    int lanes_plain = 1;                 // lanes of the draw without tile groups (frames_in_flight)
+    int Fp = 1;                          // passes in flight
+    int tail_from = 0;                   // passes from here on (each on a lane of its own) are accumulated together after the join (tile groups: every group accumulates its own pixels as it ends — nothing to serialise)
+    bool long_call = false;              // every lane gets several passes (n_passes >= 2 x lanes): the persistent grids take half the wave slots
+    // the draw's frames in passes of equal size (20 frames at frame_batch 8: 7 + 7 + 6, not 8 + 8 + 4 — the passes of a short draw run side by side and end together); equal = 0: full passes first
+    int pass_size(int p) const { return equal ? n_frames / n_passes + (p < n_frames % n_passes ? 1 : 0) : std::min(batch_max, n_frames - p * batch_max); }
+    void settle(int lanes_ready);        // the lanes the device had memory for: G, lanes, Fp, tail_from, long_call as the draw will run
+};
+
+// What one pass of B frames over one tile group launches (Renderer::plan_pass): kernels, grids, LDS sizes.  The enqueue steps read it and decide nothing.
+enum class PrimaryForm { none, stream, lane_wide, rope };          // none: traced inside shade(0); the 8-wide stream kernel with lane refill; one ray per lane on the 8-wide layout; the rope walk
+enum class TraceForm { pairs, pull_x, pull, static_x, static_split, rope };      // TLAS pass + BLAS pass; persistent waves pulling chunks (x: hit words in LDS); the static split (x: likewise); the rope kernel
+struct PullGrid { uint32_t chunk = 0, waves = 0; size_t grid_slots = 0; };      // rays per pull, waves launched, wave slots the launch may use
+struct PassPlan {
+    int B = 0;
+    uint32_t grid_tiles = 1, grid_shade = 1;          // one workgroup per tile of the group / per SHADE_THREADS slots
+    bool two_level = false, on_wide = false, chain = false, planes = false, pairs = false, tl_flat = false, prim_rope = false;
+    bool trace0_pass = false, trace0_wide = false, trace0_hint = false, primary_hinted = false, bundle = false, pull = false, strided = false;
+    PrimaryForm primary = PrimaryForm::none;
+    TraceForm trace = TraceForm::rope;
+    size_t stack_bytes = 0, trace_lds = 0, pair_cap = 0;
+    uint32_t pair_cap_used = 0, rpw_p = 0, rpw_m = 0, pack_range = 0;
+    int wave_slots = 0;                  // what the traversal grids are sized for: the option, or the chip's for the pulling kernel
+    PullGrid pg;                         // pairs, pull_x, pull
+    uint32_t even = 0, static_grid = 0;  // static_x, static_split
+    uint32_t mega_waves = 0;             // DrawPlan::mega
+};
+struct SlotCache { size_t lds_bytes = ~(size_t)0; int per_cu = 0; };      // resident 64-thread workgroups of a kernel per compute unit at this LDS size (renderer.hip wave_slots_for)
+struct DrawCtx;                          // renderer.hip: what the enqueue steps of one draw share
 
 struct Renderer {
     hipStream_t stream = nullptr;
@@ -73,18 +114,17 @@ struct Renderer {
     int lanes_ready = 0;                 // lanes [0, lanes_ready) hold queues and sample buffers
     int alloc_batch = 0;                 // batch the queues / sample buffers / seed table are sized for
     bool megakernel = false;             // one launch per frame (k_megakernel): lowest latency of a single frame; the wavefront pipeline has the higher throughput
-    int mega_slots = 0; size_t mega_slots_for_stack = ~(size_t)0;
     bool materials = false;              // the materials extension: emission, specular lobe, dielectric refraction (shade_entry<MATERIALS>); off = the reference's diffuse-only kernel
     int primary_wide = 2;                // primary rays of a flattened scene: 2 = one ray per lane on the 8-wide layout (inside shade(0) or in their own launch; default), 1 = the 8-wide stream kernel with lane refill (own launch), 0 = the rope walk (scene option rope = 1)
     int persistent = 2;                  // bounce / shadow traversal as persistent waves pulling chunks of rays from a shared counter: 0 never, 1 always, 2 by launch size
     int xcd_counters = 1;                  // pulling traversal launches: 1 = one work counter and one eighth of every sub-frame's rays per XCD (traverse_wide.h XcdRegions), 0 = one counter for all
     int hit_lds = 1;                     // pulling traversal launches of flattened scenes: a lane's closest hit keeps U, V, |det| and id in LDS; a finished ray is reported without re-testing its triangle (traverse_wide.h StreamExt)
     int shade_pack = 1;                  // k_shade of bounces >= 1 compacts the hits of its queue in LDS and shades them on full waves (k_shade_pack)
-    int wave_slots_x = 0; int slots_x_key = -1;      // wave slots of that kernel (k_trace_mixed_wide_persist_x), and the LDS size they were computed for
-    int persist_chunk = 256;             // rays per pull (upper bound; small queues pull less, see render())
+    int persist_chunk = 256;             // rays per pull (upper bound; small queues pull less, see pull_grid())
     int wave_slots = 7168;               // resident waves the persistent launch is sized for (occupancy query at the first draw)
     bool wave_slots_user = false;        // set through the option: keep it
-    size_t slots_for_stack = ~(size_t)0;
+    mutable SlotCache mega_cache, persist_cache, persist_x_cache;      // k_megakernel, k_trace_mixed_wide_persist, k_trace_mixed_wide_persist_x
+    mutable int cu_count = 0;            // compute units of the device (looked up once)
     int alloc_planes(FrameLane &L);
     bool tail_accumulate = true;         // the last passes of a draw (one per lane) are accumulated in one launch after the join instead of one after the other
     int fuse_primary = 1;                // the primary rays are generated, traced and shaded in ONE launch (k_shade_primary): no hit / direction records, one launch less per pass
@@ -125,7 +165,7 @@ struct Renderer {
     std::deque<PassDone> passes_pending;
     std::vector<hipEvent_t> pass_events_free;
     uint64_t frames_completed_known = 0; // frames (since create / resize) whose accumulate is known to have finished
-    int note_pass(hipStream_t st);       // render(): after a pass's accumulate
+    int note_pass(hipStream_t st);       // after a pass's accumulate
     int poll_completed(uint64_t *out);   // hipEventQuery only; never waits
 
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
@@ -146,6 +186,24 @@ struct Renderer {
     size_t lane_bytes() const;           // device bytes of one lane's queues + sample buffer at the current size and batch
     int set_shard(int rank, int world);
     int render(int n_frames);
+    // render() decides first: host arithmetic only (the one HIP call is the cached occupancy lookup of plan_pass) ...
+    DrawPlan plan_draw(int n_frames) const;
+    int plan_pass(const DrawPlan &dp, const SceneView &sv, const TileGroup &TG, int B, PassPlan &pp) const;
+    PullGrid pull_grid(size_t slots, size_t slots_of_chip, size_t min_chunk, bool long_call) const;
+    // ... and enqueues then, step by step in the order a pass runs
+    int draw_nothing(int n_frames);
+    int rebuild_for_batch();
+    int ensure_lanes(int want);
+    void begin_draw(DrawCtx &d) const;
+    int prepare_lane(FrameLane &L, const TileGroup &TG, const PassPlan &pp);
+    int enqueue_pass(DrawCtx &d, FrameLane &L, const TileGroup &TG, const PassPlan &pp, int pass, int g);
+    int enqueue_megakernel_pass(DrawCtx &d, FrameLane &L, const TileGroup &TG, const PassPlan &pp);
+    void enqueue_primary(DrawCtx &d, FrameLane &L, const TileGroup &TG, const PassPlan &pp);
+    void enqueue_shade(DrawCtx &d, FrameLane &L, const TileGroup &TG, const PassPlan &pp, int b);
+    void enqueue_trace(DrawCtx &d, FrameLane &L, const TileGroup &TG, const PassPlan &pp, int b);
+    int enqueue_accumulate(DrawCtx &d, FrameLane &L, const TileGroup &TG, const PassPlan &pp, int pass, int g);
+    int enqueue_guides(DrawCtx &d);
+    EvPair *timed(int kind);             // the next pair of ev_ext for a launch of this kind (nullptr: all taken)
     int wait();
     int read_accum(float *rgba, size_t nbytes);
     int copy_accum_to_device(void *dptr, size_t nbytes);

@@ -821,10 +821,10 @@ int Renderer::alloc_planes(FrameLane &L) {
 }
 int Renderer::alloc_lane(FrameLane &L) {
     const size_t qcap = (size_t)capacity * (size_t)std::max(1, alloc_batch);      // a batch of frames shares one set of queues
-    const bool need_thr = !(throughput_chain && !materials && max_bounces <= 3);      // else on demand (render())
+    const bool need_thr = !(throughput_chain && !materials && max_bounces <= 3);      // else on demand (prepare_lane)
     for (int k = 0; k < 2; k++) { MRT_HIP(L.rayA[k].alloc(qcap)); MRT_HIP(L.rayB[k].alloc(qcap)); if (need_thr) MRT_HIP(L.thr[k].alloc(qcap)); }
     MRT_HIP(L.hits.alloc(qcap)); MRT_HIP(L.srayA.alloc(qcap)); MRT_HIP(L.srayB.alloc(qcap));
-    if (need_thr || !shadow_planes) MRT_HIP(L.scon.alloc(qcap));          // the contribution queue: with shadow planes only the passes they do not cover need it (allocated then, render())
+    if (need_thr || !shadow_planes) MRT_HIP(L.scon.alloc(qcap));          // the contribution queue: with shadow planes only the passes they do not cover need it (allocated then, prepare_lane)
     MRT_HIP(L.sample.alloc((size_t)std::max<uint32_t>(capacity, 1u) * (size_t)std::max(1, alloc_batch)));
     MRT_HIP(hipMemsetAsync(L.sample.p, 0, L.sample.bytes(), stream));
     if (shadow_planes && !need_thr) { if (int rc = alloc_planes(L)) return rc; }
@@ -948,70 +948,215 @@ int Renderer::read_denoised_tonemapped(uint8_t *rgba, size_t nbytes) {
     return MRT_OK;
 }
 
-int Renderer::render(int n_frames) {                                   // Renderer.draw(in:) :284-351, n times
-    if (!scene) { set_error("renderer has no scene"); return MRT_ERR_STATE; }
-    SceneView sv = scene->view();
-    if (sv.light_count < 1) { set_error("scene has no lights (lightCount must be >= 1, Raytracing.metal:273)"); return MRT_ERR_STATE; }
-    FrameParams fp{};
-    fp.width = width; fp.height = height; fp.lightCount = light_count_limit > 0 ? std::min(light_count_limit, sv.light_count) : sv.light_count;
-    fp.cam_pos = make_float4(camera.position.x, camera.position.y, camera.position.z, 0);
-    fp.cam_right = make_float4(camera.right.x, camera.right.y, camera.right.z, 0);
-    fp.cam_up = make_float4(camera.up.x, camera.up.y, camera.up.z, 0);
-    fp.cam_fwd = make_float4(camera.forward.x, camera.forward.y, camera.forward.z, 0);
-    fp.shard_rank = shard_rank; fp.shard_world = shard_world;
-    fp.tiles_x = (width + 7) / 8; fp.tiles_local = tiles_local; fp.max_bounces = max_bounces;
-    const uint32_t grid = std::max<uint32_t>(1u, (uint32_t)tiles_local);
-    const bool two_level = sv.num_inst > 0;          // instanced scene: TLAS + BLASes walked by the same kernels (<TWO_LEVEL>)
-    if (tiles_local == 0) {
-        // a shard that owns no tile (more ranks than 8 x 8 tiles: rank 2 of 3 of a 9 x 5 image) has no pixel to render and its buffers stay 0; the launches sized
-        // by its queues would be empty grids (the shading of bounces >= 1: cdiv(capacity x batch, ...) = 0), which HIP refuses.  The frames count as drawn.
-        if (guides) { if (int rc = ensure_guides()) return rc; guides_valid = true; }
-        MRT_HIP(hipEventRecord(ev_begin, stream));
-        frame_index += (uint32_t)n_frames; frames_rendered += (uint64_t)n_frames;
-        ext_used = 0;
-        if (int rc = note_pass(stream)) return rc;
-        MRT_HIP(hipEventRecord(ev_end, stream));
-        pending_timing = true;
+// ---- the frame driver (Renderer.draw(in:) :284-351, n times).  A draw is decided first — plan_draw: passes, lanes, tile groups; plan_pass: kernels, grids, what it can be refused
+// for — by host arithmetic alone, and enqueued then: the enqueue_* steps read the plans and decide nothing.
+#ifdef MRT_DIAGNOSTICS
+// measuring aid of the diagnostics build only (tools/build_variant.sh diag "-DMRT_DIAGNOSTICS"; tools/archive/gpu_stage_ablation.sh): MRT_ABLATE=1 skips the primary launches, =2 the
+// bounce / shadow traversal launches — the other kernels then run on the stale but well-formed queues of an earlier pass, so their load is realistic and the frame time shows
+// what the skipped stage costs under overlap.  Images are garbage; the release library does not read the variable.
+static inline int ablate_mask() { static const int mask = getenv("MRT_ABLATE") ? atoi(getenv("MRT_ABLATE")) : 0; return mask; }
+#else
+static constexpr int ablate_mask() { return 0; }
+#endif
+// MRT_WAVE_TIMES builds: a traversal launch carries its bounce in the top byte of its chunk / rays-per-wave argument
+static inline uint32_t tag_bounce(uint32_t arg, int b) {
+#ifdef MRT_WAVE_TIMES
+    return arg | ((uint32_t)b << 24);
+#else
+    (void)b; return arg;
+#endif
+}
+
+// What the steps of one draw share: the plans, the uniforms of the pass being enqueued, and what a pass hands to the next
+struct DrawCtx {
+    SceneView sv;
+    DrawPlan dp;
+    FrameParams fp;                      // begin_draw: the draw's uniforms on the renderer's own shard; enqueue_pass sets the pass's and the tile group's fields
+    FrameParams gp;                      // the guide launch's (the call's first frame)
+    hipEvent_t last_acc, last_acc_g[MAX_TILE_GROUPS];      // the accumulate that the next one waits for (tile groups: the same group's of the pass before)
+    AccGroup tail;                       // the passes accumulated together after the join
+};
+
+// Resident 64-thread workgroups of `kernel` per compute unit at this LDS size (0: it does not fit); x cu_count = the wave slots of the chip for it.  One occupancy query per
+// LDS size, one device lookup per renderer.
+template <class K>
+static int wave_slots_for(K kernel, size_t lds_bytes, SlotCache &cache, int &cu_count) {
+    if (cu_count == 0) { int dev = 0; hipDeviceProp_t prop; MRT_HIP(hipGetDevice(&dev)); MRT_HIP(hipGetDeviceProperties(&prop, dev)); cu_count = prop.multiProcessorCount; }
+    if (cache.lds_bytes != lds_bytes) { MRT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&cache.per_cu, kernel, 64, lds_bytes)); cache.lds_bytes = lds_bytes; }
+    return MRT_OK;
+}
+
+// traversal launches carry their own start/stop events (hipExtLaunchKernelGGL: the dispatch packet's timestamps, the
+// same clock rocprofv3 reads): plain hipEventRecord pairs on a stream also count the time a launch waits behind the
+// other frames in flight (+12 % at 12 frames)
+EvPair *Renderer::timed(int kind) { if (ext_used >= (int)ev_ext.size()) return nullptr; ev_ext[ext_used].kind = kind; return &ev_ext[ext_used++]; }
+
+DrawPlan Renderer::plan_draw(int n_frames) const {
+    DrawPlan dp;
+    dp.n_frames = n_frames; dp.mega = megakernel; dp.equal = equal_passes != 0; dp.tail = tail_accumulate;
+    // passes larger than the default (sharded renderers ask for up to 32 frames so that a shard's launches stay large) never take more than a third of the draw:
+    // a short draw keeps about three passes to run side by side (a rank of eight over 20 frames: 7.1 Grays/s as 7 + 7 + 6, 6.0 as one pass of 20)
+    const int batch_cap = alloc_batch > DEFAULT_FRAME_BATCH ? std::min(alloc_batch, std::max(DEFAULT_FRAME_BATCH, (n_frames + 2) / 3)) : alloc_batch;
+    dp.batch_max = megakernel ? 1 : batch_cap;
+    dp.n_passes = (n_frames + dp.batch_max - 1) / dp.batch_max;
+    dp.lanes = dp.lanes_plain = std::max(1, std::min(frames_in_flight, MAX_FRAMES_IN_FLIGHT));
+    // tile groups: a pass as G groups of tiles on G lanes (renderer.h TileGroup); the one-launch-per-frame mode has no passes to split.
+    if (!megakernel && tile_groups != 1 && tiles_local >= 64) {
+        const int in_flight = std::max(1, std::min(dp.lanes, dp.n_passes));
+        // by the draw (0): only passes of ONE frame — the launch-bound regimes: a frame alone 1.53 -> 1.42 ms as two or three groups (four: 1.53), three one-frame passes in flight
+        // 0.85-0.91 -> 0.82-0.83 ms per frame as two groups each; a pass of seven or eight frames is better left whole (the driver's 20 frames as 3 x 2 groups: -4 %; profiles/r05_tile_groups.txt)
+        const int by_draw = tile_groups >= 2 ? tile_groups : dp.batch_max > 1 ? 1 : in_flight == 1 ? 3 : in_flight <= 3 ? 2 : 1;
+        dp.G = std::max(1, std::min(by_draw, std::min(MAX_FRAMES_IN_FLIGHT / in_flight, tiles_local / 32)));
+        if (dp.G > 1) dp.lanes = in_flight * dp.G;          // lanes this draw runs on: G per pass in flight
+    }
+    return dp;
+}
+
+void DrawPlan::settle(int lanes_ready) {
+    if (G > 1 && lanes_ready < lanes) { G = 1; lanes = lanes_plain; }      // not enough memory for the groups' lanes: the plain form
+    lanes = std::min(lanes, lanes_ready);
+    Fp = G > 1 ? lanes / G : lanes;
+    tail_from = (tail && G == 1) ? n_passes - std::min(lanes, n_passes) : n_passes;
+    long_call = n_passes >= 2 * lanes;
+}
+
+// The grid of a pulling launch.  Rays per pull: at least four pulls per wave slot on a queue of this size (so that the launch ends evenly), at most
+// persist_chunk; 128-ray pulls of a one-frame launch are ~78 atomics per microsecond on the one counter word (limit ~88)
+PullGrid Renderer::pull_grid(size_t slots, size_t slots_of_chip, size_t min_chunk, bool long_call) const {
+    PullGrid pg;
+    pg.chunk = (uint32_t)std::min<size_t>((size_t)persist_chunk, std::max<size_t>(min_chunk, slots / (slots_of_chip * 4) / 64 * 64));
+    // a long call (every lane gets several passes) runs its traversal launches on HALF the wave slots: the other passes' shade, primary
+    // and accumulate blocks then find free slots instead of queueing behind persistent waves that only leave when their queue is empty
+    // (measured, 240 steps: 4 lanes 9.86 -> 10.06, 6 lanes 10.08 -> 10.32, 12 lanes 10.38 -> 10.55 Grays/s; a 20-step call, whose five
+    // passes move in lock step, loses 3 % and keeps the full grid)
+    pg.grid_slots = (!wave_slots_user && long_call) ? std::max<size_t>(1, slots_of_chip / 2) : slots_of_chip;
+    pg.waves = (uint32_t)std::max<size_t>(1, std::min<size_t>(cdiv(slots, pg.chunk), pg.grid_slots));
+    return pg;
+}
+
+int Renderer::plan_pass(const DrawPlan &dp, const SceneView &sv, const TileGroup &TG, int B, PassPlan &pp) const {
+    pp = PassPlan{};
+    pp.B = B; pp.two_level = sv.num_inst > 0;          // instanced scene: TLAS + BLASes walked by the same kernels (<TWO_LEVEL>)
+    pp.grid_tiles = std::max<uint32_t>(1u, (uint32_t)TG.tiles_local); pp.grid_shade = std::max<uint32_t>(1u, cdiv(TG.capacity, SHADE_THREADS));
+    pp.wave_slots = wave_slots;
+    const bool two_level = pp.two_level;
+    const size_t wide_stack = (size_t)scene->wide_depth * WIDE_STACK_LEVEL_BYTES;
+    if (dp.mega) {
+        if (two_level || materials || sv.num_wnodes == 0) {          // the one-launch-per-frame mode exists for flattened scenes on the 8-wide layout, diffuse kernel: say so instead of quietly rendering through the pipeline
+            set_error(std::string("megakernel = 1 renders flattened scenes with the 8-wide layout and the reference's diffuse kernel only; this renderer has ") + (two_level ? "a two-level scene (scene option instancing = 1)" : materials ? "materials = 1" : "a scene without the 8-wide layout") + ": set megakernel = 0");
+            return MRT_ERR_UNSUPPORTED;
+        }
+        pp.stack_bytes = wide_stack;
+        if (int rc = wave_slots_for(k_megakernel, wide_stack, mega_cache, cu_count)) return rc;
+        pp.mega_waves = (uint32_t)std::min<size_t>(std::max<size_t>(1, cdiv(TG.capacity, 64)), (size_t)(std::max(1, mega_cache.per_cu) * cu_count));
         return MRT_OK;
     }
-    if (alloc_batch != batch_wanted()) {      // option (or the shard, under frame_batch = 0) changed since the buffers were sized
-        MRT_HIP(hipStreamSynchronize(stream));
-        const uint32_t keep_frame = frame_index; const int keep_cur = cur; const uint64_t keep_rendered = frames_rendered;
-        DevBuf<float4> keep; MRT_HIP(keep.alloc(accum[cur].n));
-        MRT_HIP(hipMemcpyAsync(keep.p, accum[cur].p, accum[cur].bytes(), hipMemcpyDeviceToDevice, stream));
-        const MRTCamera keep_cam = camera;
-        unsigned long long keep_totals[3] = {0, 0, 0};
-        MRT_HIP(hipMemcpy(keep_totals, totals.p, sizeof keep_totals, hipMemcpyDeviceToHost));
-        const bool keep_denoised = denoised_valid;
-        guides_keep = true;
-        int rc = resize(width, height);
-        guides_keep = false; denoised_valid = keep_denoised;
-        if (rc) return rc;
-        MRT_HIP(hipMemcpyAsync(totals.p, keep_totals, sizeof keep_totals, hipMemcpyHostToDevice, stream));
-        MRT_HIP(hipMemcpyAsync(accum[keep_cur].p, keep.p, keep.bytes(), hipMemcpyDeviceToDevice, stream));
-        MRT_HIP(hipStreamSynchronize(stream));
-        frame_index = keep_frame; cur = keep_cur; frames_rendered = keep_rendered; frames_completed_known = keep_rendered; camera = keep_cam;
-        return render(n_frames);
+    // the pipeline: primary trace -> per bounce { shade, trace } ; bounce rays and shadow rays of a shade share one traversal launch
+    pp.on_wide = wide_bounce && sv.num_wnodes > 0;          // no 8-wide layout (scene option wide = 0, a tree deeper than WIDE_STACK_MAX): the rope kernels
+    // two-level scenes walk TLAS and BLASes with the same kernels (traverse_wide_stream<true>); their LDS also parks the lanes' world rays
+    pp.stack_bytes = wide_stack + (two_level ? WIDE_WORLD_RAY_BYTES : 0);
+    if (pp.on_wide && persistent != 0) {       // wave slots of the chip for this kernel at this LDS size
+        if (int rc = two_level ? wave_slots_for(k_trace_mixed_wide_persist<true>, pp.stack_bytes, persist_cache, cu_count) : wave_slots_for(k_trace_mixed_wide_persist<false>, pp.stack_bytes, persist_cache, cu_count)) return rc;
+        if (!wave_slots_user) pp.wave_slots = std::max(1, persist_cache.per_cu) * cu_count;
     }
-    // the first draw sizes the lanes in use.  A lane's queues take ~163 B x pixels x frame_batch (1080p, 8-frame passes: 2.7 GB); when the
-    // device cannot hold all the lanes asked for, the renderer runs on the ones it got (>= 1) instead of failing in the middle of a draw
-    int F = std::max(1, std::min(frames_in_flight, MAX_FRAMES_IN_FLIGHT));
-    // tile groups: a pass as G groups of tiles on G lanes (renderer.h TileGroup); the one-launch-per-frame mode has no passes to split.
-    int G = 1;
-    {
-        const int cap0 = alloc_batch > DEFAULT_FRAME_BATCH ? std::min(alloc_batch, std::max(DEFAULT_FRAME_BATCH, (n_frames + 2) / 3)) : alloc_batch;
-        const int np0 = (n_frames + std::max(1, cap0) - 1) / std::max(1, cap0), in_flight = std::max(1, std::min(F, np0));
-        if (!megakernel && tile_groups != 1 && tiles_local >= 64) {
-            const int lanes_target = std::max(F, 6);
-            // by the draw (0): only passes of ONE frame — the launch-bound regimes: a frame alone 1.53 -> 1.42 ms as two or three groups (four: 1.53), three one-frame passes in flight
-            // 0.85-0.91 -> 0.82-0.83 ms per frame as two groups each; a pass of seven or eight frames is better left whole (the driver's 20 frames as 3 x 2 groups: -4 %; profiles/r05_tile_groups.txt)
-            G = tile_groups >= 2 ? tile_groups : cap0 > 1 ? 1 : in_flight == 1 ? 3 : in_flight <= 3 ? 2 : 1;
-            (void)lanes_target;
-            G = std::max(1, std::min(G, std::min(MAX_FRAMES_IN_FLIGHT / in_flight, tiles_local / 32)));
-        }
-        if (G > 1) F = in_flight * G;          // lanes this draw runs on: G per pass in flight
+    pp.chain = throughput_chain && !materials && max_bounces <= 3 && (uint64_t)scene->stats.instances * (uint64_t)std::max(1, scene->stats.max_submeshes) <= 65536ull;
+    const size_t slots = 2 * (size_t)TG.capacity * B;          // the combined queue [next-bounce rays | shadow rays] of a bounce
+    pp.rpw_p = stream_rays_per_wave((size_t)TG.capacity * B); pp.rpw_m = stream_rays_per_wave(slots);
+    // shadow planes: contribution per pixel and bounce + one byte per shadow ray that got through, instead of the contribution queue and the read-modify-write of the sample buffer
+    pp.planes = shadow_planes != 0 && pp.chain && pp.on_wide && !materials && max_bounces <= PLANES_MAX_BOUNCES && !ablate_mask();
+    // two-level scenes: the binned walk (TLAS pass + BLAS pass over (ray, instance) pairs) for the bounce / shadow rays of planes passes
+    pp.pairs = two_level && pp.planes && tl_pairs != 0 && sv.tri_packet != nullptr;
+    pp.pair_cap = 2 * (size_t)capacity * (size_t)std::max(1, alloc_batch);          // one pair per virtual ray of the combined queue; a push beyond it walks its instance in place
+    // few instances: the TLAS pass has no tree (every lane visits every instance: nothing diverges; two_level_passes.h k_tl_top_flat)
+    pp.tl_flat = pp.pairs && sv.num_inst <= TL_FLAT_MAX_INSTANCES && tl_pairs != 2;
+    pp.pair_cap_used = (uint32_t)std::min<size_t>(tl_pair_cap > 0 ? std::min<size_t>((size_t)tl_pair_cap, pp.pair_cap) : pp.pair_cap, 0xFFFFFFFFu);
+    // the primary trace inside shade(0): flattened scenes, planes passes
+    // (not for one frame alone on the chip, fuse_primary = 1: there the primary kernel's 48 registers and 64-thread workgroups fill the chip better than shade's 76 and 256 — 1.71 against 1.81 ms;
+    // fuse_primary = 2 fuses always)
+    // which layout the primary rays of a flattened scene walk: the 8-wide one when the scene has it (primary_wide = 2, default: one ray per lane inside shade(0) or in its own launch;
+    // = 1: the stream kernel with lane refill, A/B), the rope layout otherwise — or on request (primary_wide = 0; needs scene option rope = 1)
+    pp.prim_rope = !two_level && (!sv.num_wnodes || primary_wide == 0);
+    if (pp.prim_rope && sv.num_nodes == 0 && sv.num_tris != 0) { set_error("primary_wide = 0 walks the rope layout: commit the scene with scene option rope = 1"); return MRT_ERR_STATE; }
+    if (!pp.on_wide && !two_level && sv.num_nodes == 0 && sv.num_tris != 0) { set_error("wide_bounce = 0 walks the rope layout: commit the scene with scene option rope = 1"); return MRT_ERR_STATE; }
+    pp.trace0_pass = pp.planes && fuse_primary != 0 && primary_wide != 1 && !(two_level && primary_wide == 0) && (fuse_primary == 2 || dp.lanes > 1 || B > 1 || two_level);      // (two-level scenes always: their own-launch form is the stream kernel, 0.88 ms for one 1080p frame of dragon x 4)
+    pp.trace0_wide = pp.trace0_pass && !pp.prim_rope;          // (planes implies the 8-wide layout)
+    // the hint of two-level scenes is (packet | instance << 24): scenes of at most 255 instances and 2^24 packets
+    pp.trace0_hint = primary_hint && (!two_level || (sv.num_inst <= 255u && scene->wpackets.n / WPK < ((size_t)1 << 24)));
+    pp.primary = ((ablate_mask() & 1) || pp.trace0_pass) ? PrimaryForm::none
+               : ((two_level && pp.on_wide) || (primary_wide == 1 && sv.num_wnodes && !two_level)) ? PrimaryForm::stream
+               : (two_level || pp.prim_rope) ? PrimaryForm::rope : PrimaryForm::lane_wide;
+    pp.primary_hinted = pp.trace0_hint && !(two_level && pp.primary == PrimaryForm::rope);          // (k_trace_primary<true> takes no hint)
+    pp.bundle = frame_bundle && pp.trace0_wide && B > 1;
+    // entries per packing workgroup: SHADE_PACK_RANGE when the queue is long, less when that would leave fewer than ~2048 workgroups (a one-frame pass, a tile group, a shard) — never less than two rounds' worth
+    pp.pack_range = (uint32_t)std::min<size_t>(SHADE_PACK_RANGE, std::max<size_t>(2 * SHADE_THREADS, (size_t)TG.capacity * B / 2048 / SHADE_THREADS * SHADE_THREADS));
+    // persistent = 2 (auto): pull chunks when every wave slot would otherwise own >= 1024 rays (4-frame passes at 1080p: +7...+11 % with
+    // one stream, +2.5 % with 12); one-frame launches keep the static split (384 rays per wave, no atomics: 3 frames in flight 6.5 vs 5.4 Grays/s)
+    // [r3] smaller launches pull as well when five or more passes are in flight (6 lanes x one-frame passes: 9.33 against 8.76 Grays/s; a rank of eight over 240 frames
+    // in 8-frame passes: 9.43 against 8.56); with one to three passes in flight they do better on the even static split (one frame alone 1.51 against 1.76 ms, 3 x 1 frame
+    // 7.63 against 7.20 Grays/s, a rank of eight over the driver's 20 frames 6.65 against 5.73): stream_even below
+    pp.pull = persistent == 1 || (persistent == 2 && (slots >= (size_t)pp.wave_slots * 1024 || (std::min(dp.lanes, dp.G > 1 ? dp.Fp * dp.G : dp.n_passes) >= 5 && slots >= (size_t)pp.wave_slots * 256)));      // (below 256 slots per wave slot — Cornell 256^2 in 8-frame passes — the even split: 6.46 against 5.40 Grays/s)
+    const bool takes_x = !two_level && pp.planes && hit_lds;          // the kernels with the hit words in LDS; k_trace_mixed_wide_stream_x is also the one kernel that deals batches round-robin (BatchStride)
+    pp.trace = pp.pairs ? TraceForm::pairs : !pp.on_wide ? TraceForm::rope : pp.pull ? (takes_x ? TraceForm::pull_x : TraceForm::pull) : (takes_x ? TraceForm::static_x : TraceForm::static_split);
+    pp.trace_lds = pp.trace == TraceForm::rope ? 0 : pp.stack_bytes + (takes_x ? (size_t)HIT_LDS_WORDS * 4 : 0);
+    if (pp.trace == TraceForm::pairs) pp.pg = pull_grid(slots, (size_t)pp.wave_slots, 64, dp.long_call);
+    else if (pp.trace == TraceForm::pull) pp.pg = pull_grid(slots, (size_t)pp.wave_slots, 128, dp.long_call);
+    else if (pp.trace == TraceForm::pull_x) {
+        // the variant with the hit words in LDS: its own LDS size, hence its own count of wave slots
+        if (int rc = wave_slots_for(k_trace_mixed_wide_persist_x, pp.trace_lds, persist_x_cache, cu_count)) return rc;
+        if (persist_x_cache.per_cu < 1) { set_error("hit_lds: the traversal kernel does not fit a compute unit with " + std::to_string(pp.trace_lds) + " bytes of LDS"); return MRT_ERR_UNSUPPORTED; }
+        pp.pg = pull_grid(slots, wave_slots_user ? (size_t)pp.wave_slots : (size_t)(persist_x_cache.per_cu * cu_count), 128, dp.long_call);
     }
-    for (; lanes_ready < F; lanes_ready++) {
+    else if (pp.trace != TraceForm::rope) {
+        // a shard's launches (a rank of eight over the driver's 20 frames: three passes of its 1/8 of the tiles in flight) do better with ONE round of waves that take the queue's
+        // 64-ray batches round-robin — every rank of eight timed: 2.00 against 2.21 ms on average, the slowest 2.13-2.18 against 2.46-2.50 (profiles/r05_shard_stride.txt); a whole
+        // image's one-frame launches do not (one frame alone 1.38 = 1.38 ms, three in flight 0.775 against 0.765)
+        const bool shard_auto = stream_stride == 2 && stream_even == 200 && shard_world > 1 && dp.G == 1 && takes_x;          // (one round of waves was measured with the strided deal only)
+        pp.strided = stream_stride == 1 || shard_auto;
+        const int even_pct = shard_auto ? 100 : stream_even;
+        pp.even = even_pct > 0 ? (uint32_t)std::max<size_t>(1, std::min<size_t>(cdiv(slots, 64), (size_t)pp.wave_slots * (size_t)even_pct / 100)) : 0u;     // stream_even: percent of the wave slots
+        pp.static_grid = pp.even ? pp.even : cdiv(slots, pp.rpw_m);
+    }
+    return MRT_OK;
+}
+
+// a shard that owns no tile (more ranks than 8 x 8 tiles: rank 2 of 3 of a 9 x 5 image) has no pixel to render and its buffers stay 0; the launches sized
+// by its queues would be empty grids (the shading of bounces >= 1: cdiv(capacity x batch, ...) = 0), which HIP refuses.  The frames count as drawn.
+int Renderer::draw_nothing(int n_frames) {
+    if (guides) { if (int rc = ensure_guides()) return rc; guides_valid = true; }
+    MRT_HIP(hipEventRecord(ev_begin, stream));
+    frame_index += (uint32_t)n_frames; frames_rendered += (uint64_t)n_frames;
+    ext_used = 0;
+    if (int rc = note_pass(stream)) return rc;
+    MRT_HIP(hipEventRecord(ev_end, stream));
+    pending_timing = true;
+    return MRT_OK;
+}
+
+// the frame_batch option (or the shard, under frame_batch = 0) changed since the buffers were sized: size them again; image, frame count, totals and guides survive
+int Renderer::rebuild_for_batch() {
+    MRT_HIP(hipStreamSynchronize(stream));
+    const uint32_t keep_frame = frame_index; const int keep_cur = cur; const uint64_t keep_rendered = frames_rendered;
+    DevBuf<float4> keep; MRT_HIP(keep.alloc(accum[cur].n));
+    MRT_HIP(hipMemcpyAsync(keep.p, accum[cur].p, accum[cur].bytes(), hipMemcpyDeviceToDevice, stream));
+    const MRTCamera keep_cam = camera;
+    unsigned long long keep_totals[3] = {0, 0, 0};
+    MRT_HIP(hipMemcpy(keep_totals, totals.p, sizeof keep_totals, hipMemcpyDeviceToHost));
+    const bool keep_denoised = denoised_valid;
+    guides_keep = true;
+    int rc = resize(width, height);
+    guides_keep = false; denoised_valid = keep_denoised;
+    if (rc) return rc;
+    MRT_HIP(hipMemcpyAsync(totals.p, keep_totals, sizeof keep_totals, hipMemcpyHostToDevice, stream));
+    MRT_HIP(hipMemcpyAsync(accum[keep_cur].p, keep.p, keep.bytes(), hipMemcpyDeviceToDevice, stream));
+    MRT_HIP(hipStreamSynchronize(stream));
+    frame_index = keep_frame; cur = keep_cur; frames_rendered = keep_rendered; frames_completed_known = keep_rendered; camera = keep_cam;
+    return MRT_OK;
+}
+
+// the first draw sizes the lanes in use.  A lane's queues take ~163 B x pixels x frame_batch (1080p, 8-frame passes: 2.7 GB); when the
+// device cannot hold all the lanes asked for, the renderer runs on the ones it got (>= 1) instead of failing in the middle of a draw
+int Renderer::ensure_lanes(int want) {
+    for (; lanes_ready < want; lanes_ready++) {
         const size_t need = lane_bytes() + (lanes_ready == 0 && !halton_tab.p ? (size_t)HALTON_TAB_DIMS * HALTON_TAB_SPAN * sizeof(float) : 0);      // (+ the renderer's one Halton table, allocated at its first bundled draw)
         size_t free_b = 0, total_b = 0;
         const bool fits = hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b > need + (size_t(1) << 30);      // keep 1 GiB of slack for the caller
@@ -1020,343 +1165,274 @@ int Renderer::render(int n_frames) {                                   // Render
         if (rc == MRT_ERR_OUT_OF_MEMORY) { set_error("not enough device memory for one pass in flight: " + std::to_string(need >> 20) + " MiB of ray queues needed (" + std::to_string(width) + "x" + std::to_string(height) + ", frame_batch " + std::to_string(alloc_batch) + "); lower frame_batch"); return rc; }
         if (rc) return rc;
     }
-    if (G > 1 && lanes_ready < F) { G = 1; F = std::max(1, std::min(std::min(frames_in_flight, MAX_FRAMES_IN_FLIGHT), lanes_ready)); }      // not enough memory for the groups' lanes: the plain form
-    F = std::min(F, lanes_ready); lanes_used = F; groups_used = G;
-    if (G > 1) { if (int rc = ensure_tile_groups(G)) return rc; }
-    const int Fp = G > 1 ? F / G : F;          // passes in flight
+    return MRT_OK;
+}
+
+// the draw's uniforms on the renderer's own shard (updateUniforms :216-229), and the guide launch's: the call's first frame
+void Renderer::begin_draw(DrawCtx &d) const {
+    FrameParams &fp = d.fp;
+    fp = FrameParams{};
+    fp.width = width; fp.height = height; fp.lightCount = light_count_limit > 0 ? std::min(light_count_limit, d.sv.light_count) : d.sv.light_count;
+    fp.cam_pos = make_float4(camera.position.x, camera.position.y, camera.position.z, 0);
+    fp.cam_right = make_float4(camera.right.x, camera.right.y, camera.right.z, 0);
+    fp.cam_up = make_float4(camera.up.x, camera.up.y, camera.up.z, 0);
+    fp.cam_fwd = make_float4(camera.forward.x, camera.forward.y, camera.forward.z, 0);
+    fp.shard_rank = shard_rank; fp.shard_world = shard_world;
+    fp.tiles_x = (width + 7) / 8; fp.tiles_local = tiles_local; fp.max_bounces = max_bounces;
+    d.gp = fp;
+    d.gp.frameIndex = frame_index; d.gp.sampleIndex = frame_index + sample_offset; d.gp.npix = (uint32_t)((size_t)width * height); d.gp.capacity = capacity; d.gp.batch = 1;
+    fp.npix = (uint32_t)((size_t)width * height); fp.capacity = capacity;
+    d.last_acc = nullptr;
+    for (hipEvent_t &e : d.last_acc_g) e = nullptr;
+    d.tail.n = 0;
+}
+
+// the buffers that only some passes need, allocated by the first such pass on the lane (a lane's buffers are sized for the renderer's whole shard, whatever tile group uses it now)
+int Renderer::prepare_lane(FrameLane &L, const TileGroup &TG, const PassPlan &pp) {
+    const size_t shard_qcap = (size_t)capacity * (size_t)std::max(1, alloc_batch);
+    if (!pp.chain && !L.thr[0].p) {           // this draw needs the throughput queues after all (materials, more than three bounces, a very large resource table)
+        for (int k = 0; k < 2; k++) MRT_HIP(L.thr[k].alloc(shard_qcap));
+    }
+    if (pp.planes) {
+        if (!L.f_lit.p) { if (int rc = alloc_planes(L)) return rc; }
+        MRT_HIP(hipMemsetAsync(L.f_lit.p, 0, 4 * (size_t)TG.capacity * (size_t)pp.B, L.stream));
+    }
+    if (pp.pairs && !L.pairs.p) MRT_HIP(L.pairs.alloc(std::max<size_t>(PairQueue::WORDS * pp.pair_cap, 1)));
+    if (!pp.planes && !L.scon.p) MRT_HIP(L.scon.alloc(shard_qcap));
+    return MRT_OK;
+}
+
+// one launch per frame on the pass's stream; frames are sequential (a path's last act is the running average with the previous target)
+int Renderer::enqueue_megakernel_pass(DrawCtx &d, FrameLane &L, const TileGroup &TG, const PassPlan &pp) {
+    FrameParams &fp = d.fp;
+    uint32_t *work = reinterpret_cast<uint32_t *>(L.bounce_counts.p + 64);      // its own word: the pipeline's per-bounce work counters must stay zero between passes
+    for (int sub = 0; sub < pp.B; sub++) {
+        fp.frameIndex = frame_index + (uint32_t)sub; fp.sampleIndex = frame_index + (uint32_t)sub + sample_offset; fp.batch = 1;
+        if (d.last_acc) { MRT_HIP(hipStreamWaitEvent(L.stream, d.last_acc, 0)); d.last_acc = nullptr; }
+        MRT_HIP(hipMemsetAsync(work, 0, 4, L.stream));
+        launch_timed(timed(MRT_KERNEL_TRACE), k_megakernel, dim3(pp.mega_waves), dim3(64), pp.stack_bytes, L.stream, d.sv, fp, TG.seeds, accum[cur].p, accum[1 - cur].p, work, totals.p, (uint32_t)TG.owned);
+        cur = 1 - cur;
+    }
+    MRT_HIP(hipEventRecord(L.accumulated, L.stream));
+    d.last_acc = L.accumulated;
+    frame_index += (uint32_t)pp.B; frames_rendered += (uint64_t)pp.B;
+    return note_pass(L.stream);
+}
+
+// the primary rays in a launch of their own (PrimaryForm::none: shade(0) traces them)
+void Renderer::enqueue_primary(DrawCtx &d, FrameLane &L, const TileGroup &TG, const PassPlan &pp) {
+    if (pp.primary == PrimaryForm::none) return;
+    float4 *const dirs = L.rayB[1].p;
+    uint32_t *const hint_p = pp.primary_hinted ? hint.p : nullptr;
+    if (pp.primary == PrimaryForm::stream) {
+        const auto kernel = pp.two_level ? (pp.primary_hinted ? k_trace_primary_wide_stream<true, true> : k_trace_primary_wide_stream<true, false>)
+                                         : (pp.primary_hinted ? k_trace_primary_wide_stream<false, true> : k_trace_primary_wide_stream<false, false>);
+        launch_timed(timed(MRT_KERNEL_PRIMARY), kernel, dim3(cdiv(TG.capacity, pp.rpw_p), pp.B), dim3(64), pp.stack_bytes, L.stream, d.sv, d.fp, TG.seeds, L.hits.p, dirs, TG.capacity, pp.rpw_p, hint_p);
+        return;
+    }
+    const bool lane_wide = pp.primary == PrimaryForm::lane_wide;
+    auto kernel = k_trace_primary<true>;
+    if (!pp.two_level) kernel = lane_wide ? k_trace_primary<false, true> : k_trace_primary<false>;
+    launch_timed(timed(MRT_KERNEL_PRIMARY), kernel, dim3(pp.grid_tiles, pp.B), dim3(64), lane_wide ? pp.stack_bytes : 0, L.stream, d.sv, d.fp, TG.seeds, L.hits.p, dirs, hint_p);
+}
+
+using ShadeKernel = void (*)(SceneView, FrameParams, const uint32_t *, const float4 *, const float4 *, const float4 *, const float4 *, const unsigned long long *, uint32_t, float4 *, float4 *, float4 *, float4 *, float4 *, float4 *,
+                             unsigned long long *, float4 *, float4 *, uint32_t *);
+static ShadeKernel shade_kernel_for(const PassPlan &pp, bool materials, bool pack, int b) {
+    if (pack) return materials ? (ShadeKernel)k_shade_pack<true, false, false, false>
+                   : pp.pairs ? (ShadeKernel)k_shade_pack<false, true, true, true>
+                   : pp.planes ? (ShadeKernel)k_shade_pack<false, true, true, false>
+                   : pp.chain ? (ShadeKernel)k_shade_pack<false, true, false, false> : (ShadeKernel)k_shade_pack<false, false, false, false>;
+    return materials ? (ShadeKernel)k_shade<true, false, false, false>
+         : (pp.pairs && b > 0) ? (ShadeKernel)k_shade<false, true, true, true>
+         : (pp.trace0_wide && b == 0 && pp.two_level) ? (ShadeKernel)k_shade_primary<3>
+         : (pp.trace0_wide && b == 0) ? (ShadeKernel)k_shade_primary<2>
+         : (pp.trace0_pass && b == 0) ? (ShadeKernel)k_shade_primary<1>
+         : pp.planes ? (ShadeKernel)k_shade<false, true, true, false>
+         : pp.chain ? (ShadeKernel)k_shade<false, true, false, false> : (ShadeKernel)k_shade<false, false, false, false>;
+}
+
+// shade(b) reads the queue shade(b - 1) wrote (b & 1 ^ 1) and writes next rays into queue b & 1
+void Renderer::enqueue_shade(DrawCtx &d, FrameLane &L, const TileGroup &TG, const PassPlan &pp, int b) {
+    FrameParams &fp = d.fp;
+    const int q = b & 1, B = pp.B;
+    unsigned long long *const bc = L.bounce_counts.p;                     // [bounce] {next rays (lo), shadow rays (hi)}, zero at frame start
+    fp.bounce = b;
+    // bounce 0 reads no ray queue (it regenerates the primary ray); bounce b > 0 reads the queue shade(b-1) wrote
+    // bounce 0: one grid row per sub-frame of the batch over the primary slots; later bounces: the compact queue of the whole batch
+    const bool pack = shade_pack && b > 0;          // bounces >= 1 read a queue half of whose rays missed: its hits are compacted in LDS and shaded on full waves (k_shade_pack)
+    fp.pack_range = pp.pack_range;
+    fp.frame_bundle = (pp.bundle && b == 0) ? 1 : 0;
+    if (fp.frame_bundle) {
+        fp.bundle_groups = ((uint32_t)B + 7u) / 8u; fp.bundle_w = ((uint32_t)B + fp.bundle_groups - 1u) / fp.bundle_groups;
+        fp.bundle_per_wave = 64u / fp.bundle_w; fp.bundle_magic = (65536u + fp.bundle_w - 1u) / fp.bundle_w;
+    }
+    fp.halton_tab = nullptr; fp.halton_w0 = 0; fp.halton_n = 0;
+    if (fp.frame_bundle && fp.bundle_w >= 4u && halton_table && halton_tab.p) {          // a wave reads bundle_w consecutive values per load: the table pays from four on (indices outside its window: the recurrence)
+        fp.halton_tab = halton_tab.p; fp.halton_w0 = halton_w0; fp.halton_n = HALTON_TAB_SPAN;
+    }
+    const dim3 gs = b == 0 ? (fp.frame_bundle ? dim3(cdiv(cdiv((size_t)TG.capacity * fp.bundle_groups, fp.bundle_per_wave) * 64, SHADE_THREADS), 1) : dim3(pp.grid_shade, B)) : dim3(cdiv((size_t)TG.capacity * B, pack ? fp.pack_range : (uint32_t)SHADE_THREADS));
+    float4 *const con_b = !pp.planes ? L.scon.p : b == 0 ? L.sample.p : L.f_con[b - 1].p;         // PLANES: this bounce's contribution plane in place of the queue
+    const size_t shade_lds = (pp.trace0_wide && b == 0) ? (size_t)SHADE_WAVES * (scene->wide_depth * WIDE_STACK_LEVEL_BYTES + (MRT_LANE_HIT_LDS ? 1024 : 0)) : 0;
+    // (two-level, binned, b > 0: L.hits holds the 64-bit keys of the TLAS / BLAS passes)
+    launch_timed(timed(MRT_KERNEL_SHADE), shade_kernel_for(pp, materials, pack, b), gs, dim3(SHADE_THREADS), shade_lds, L.stream, d.sv, fp, TG.seeds, L.rayA[1 - q].p, L.rayB[1 - q].p, L.thr[1 - q].p, L.hits.p,
+                 b == 0 ? nullptr : bc + (b - 1), TG.capacity, L.rayA[q].p, L.rayB[q].p, L.thr[q].p, L.srayA.p, L.srayB.p, con_b, bc + b, b == 0 ? L.sample.p : nullptr, L.sample.p,
+                 (b == 0 && pp.trace0_pass && pp.trace0_hint) ? hint.p : nullptr);
+}
+
+// the bounce rays and the shadow rays that shade(b) queued, in one traversal launch (pairs: two)
+void Renderer::enqueue_trace(DrawCtx &d, FrameLane &L, const TileGroup &TG, const PassPlan &pp, int b) {
+    if (ablate_mask() & 2) return;
+    const int q = b & 1;
+    hipStream_t st = L.stream;
+    unsigned long long *const bc = L.bounce_counts.p;
+    const unsigned long long *const counts = bc + b;
+    uint32_t *const work = reinterpret_cast<uint32_t *>(bc + WORK_COUNTERS + (size_t)b * WORK_COUNTERS_PER_BOUNCE);
+    uint8_t *const lit_b = pp.planes ? L.f_lit.p + b : nullptr;
+    const float4 *const rayA = L.rayA[q].p, *const rayB = L.rayB[q].p, *const srayA = L.srayA.p, *const srayB = L.srayB.p;
+    const uint32_t xcd_frames = xcd_counters ? (uint32_t)pp.B : 0u;
+    switch (pp.trace) {
+    case TraceForm::pairs: {
+        unsigned long long *const keys = reinterpret_cast<unsigned long long *>(L.hits.p);
+        uint32_t *const pc = reinterpret_cast<uint32_t *>(bc + 65 + b);          // two-level, binned: {pairs queued, work counter of the BLAS pass}
+        const uint32_t stack_words = (uint32_t)(pp.stack_bytes / 4);
+        // few instances: the TLAS pass without a tree; many: the stream walk of the 8-wide TLAS
+        if (pp.tl_flat) launch_timed(timed(MRT_KERNEL_TRACE), k_tl_top_flat, dim3((uint32_t)std::max<size_t>(1, std::min<size_t>(cdiv(2 * (size_t)TG.capacity * pp.B, 64), 2 * pp.pg.grid_slots))), dim3(64), pp.stack_bytes + 8, st, d.sv, rayA, rayB, keys, srayA, srayB,
+                                     counts, lit_b, L.pairs.p, pc, pp.pair_cap_used, stack_words);
+        else launch_timed(timed(MRT_KERNEL_TRACE), k_tl_top, dim3(pp.pg.waves), dim3(64), pp.stack_bytes + 8, st, d.sv, rayA, rayB, keys, srayA, srayB,
+                          counts, reinterpret_cast<uint32_t *>(bc + 32 + b), pp.pg.chunk, lit_b, L.pairs.p, pc, pp.pair_cap_used, stack_words);
+        // the pairs' count is on the device: the launch has the wave slots it may use and the surplus leaves at once
+        launch_timed(timed(MRT_KERNEL_TRACE), k_tl_blas, dim3((uint32_t)pp.pg.grid_slots), dim3(64), (size_t)scene->wide_depth * WIDE_STACK_LEVEL_BYTES, st, d.sv, rayA, rayB, keys, srayA, srayB,
+                     counts, pc + 1, 256u, lit_b, (const uint4 *)L.pairs.p, (const uint32_t *)pc, pp.pair_cap_used);
+        break;
+    }
+    case TraceForm::pull_x:
+        launch_timed(timed(MRT_KERNEL_TRACE), k_trace_mixed_wide_persist_x, dim3(pp.pg.waves), dim3(64), pp.trace_lds, st, d.sv, rayA, rayB, L.hits.p, srayA, srayB, counts, work, pp.pg.chunk, lit_b, xcd_frames);
+        break;
+    case TraceForm::pull:
+        launch_timed(timed(MRT_KERNEL_TRACE), pp.two_level ? k_trace_mixed_wide_persist<true> : k_trace_mixed_wide_persist<false>, dim3(pp.pg.waves), dim3(64), pp.trace_lds, st, d.sv, rayA, rayB, L.hits.p, srayA, srayB, L.scon.p,
+                     counts, L.sample.p, work, tag_bounce(pp.pg.chunk, b), lit_b, xcd_frames);
+        break;
+    case TraceForm::static_x:
+        launch_timed(timed(MRT_KERNEL_TRACE), k_trace_mixed_wide_stream_x, dim3(pp.static_grid), dim3(64), pp.trace_lds, st, d.sv, rayA, rayB, L.hits.p, srayA, srayB, counts, tag_bounce(pp.rpw_m, b), lit_b, pp.even | (pp.strided ? 0x80000000u : 0u));
+        break;
+    case TraceForm::static_split:
+        launch_timed(timed(MRT_KERNEL_TRACE), pp.two_level ? k_trace_mixed_wide_stream<true> : k_trace_mixed_wide_stream<false>, dim3(pp.static_grid), dim3(64), pp.trace_lds, st, d.sv, rayA, rayB, L.hits.p, srayA, srayB, L.scon.p,
+                     counts, L.sample.p, pp.rpw_m, lit_b, pp.even);
+        break;
+    case TraceForm::rope:
+        launch_timed(timed(MRT_KERNEL_TRACE), pp.two_level ? k_trace_mixed<true> : k_trace_mixed<false>, dim3(2 * pp.grid_tiles * (uint32_t)pp.B), dim3(64), 0, st, d.sv, rayA, rayB, L.hits.p, srayA, srayB, L.scon.p, counts, L.sample.p);
+        break;
+    }
+}
+
+// accumulation is the only frame-to-frame dependency (prev target = the previous frame's output)
+int Renderer::enqueue_accumulate(DrawCtx &d, FrameLane &L, const TileGroup &TG, const PassPlan &pp, int pass, int g) {
+    const int B = pp.B;
+    hipStream_t st = L.stream;
+    unsigned long long *const bc = L.bounce_counts.p;
+    const uint32_t primary = (uint32_t)(TG.owned * (uint64_t)B);
+    if (pp.planes && pass >= d.dp.tail_from && d.tail.n < MAX_FRAMES_IN_FLIGHT) {          // deferred: with the draw's other last passes, after the join
+        AccPass &P = d.tail.p[d.tail.n++];
+        P.con0 = L.sample.p; P.con1 = L.f_con[0].p; P.con2 = L.f_con[1].p; P.lit = L.f_lit.p; P.counts = bc; P.frameIndex = d.fp.frameIndex; P.batch = B; P.primary = primary; P.pad = 0;
+        MRT_HIP(hipEventRecord(L.accumulated, st));       // (here: traced — the join below waits for it, the accumulation follows on the main stream)
+        frame_index += (uint32_t)B; frames_rendered += (uint64_t)B;
+        return MRT_OK;
+    }
+    const bool grouped = d.dp.G > 1;
+    if (grouped) { if (d.last_acc_g[g] && d.last_acc_g[g] != L.accumulated) MRT_HIP(hipStreamWaitEvent(st, d.last_acc_g[g], 0)); }      // this group's pixels of the previous target: written by the same group of the pass before
+    else if (d.last_acc) MRT_HIP(hipStreamWaitEvent(st, d.last_acc, 0));
+    if (pp.planes) launch_timed(timed(MRT_KERNEL_ACCUMULATE), k_accumulate_planes, dim3(pp.grid_tiles), dim3(64), 0, st, d.fp, L.sample.p, L.f_con[0].p, L.f_con[1].p, L.f_lit.p, accum[cur].p, accum[1 - cur].p, bc, totals.p, primary);
+    else launch_timed(timed(MRT_KERNEL_ACCUMULATE), k_accumulate, dim3(pp.grid_tiles), dim3(64), 0, st, d.fp, L.sample.p, accum[cur].p, accum[1 - cur].p, bc, totals.p, primary);
+    MRT_HIP(hipEventRecord(L.accumulated, st));
+    if (grouped) { d.last_acc_g[g] = L.accumulated; return MRT_OK; }          // (render() swaps the targets and counts the frames once every group of the pass is enqueued)
+    d.last_acc = L.accumulated;
+    cur = 1 - cur;                                                  // ping-pong swap :332-334 (once per batch: the batch's frames are applied in one kernel)
+    frame_index += (uint32_t)B; frames_rendered += (uint64_t)B;
+    return note_pass(st);
+}
+
+// one pass of pp.B frames over the tiles of TG (G = 1: the renderer's own shard) on lane L
+int Renderer::enqueue_pass(DrawCtx &d, FrameLane &L, const TileGroup &TG, const PassPlan &pp, int pass, int g) {
+    FrameParams &fp = d.fp;
+    fp.batch = pp.B;
+    fp.frameIndex = frame_index;                                    // updateUniforms :216-229 (first frame of the batch)
+    fp.sampleIndex = frame_index + sample_offset;
+    fp.shard_rank = TG.rank; fp.shard_world = TG.world; fp.tiles_local = TG.tiles_local; fp.capacity = TG.capacity;
+    if (d.dp.mega) return enqueue_megakernel_pass(d, L, TG, pp);
+    if (int rc = prepare_lane(L, TG, pp)) return rc;
+    fp.bounce = 0; fp.chain = pp.chain ? 1 : 0;
+    fp.wide_stack_words = (uint32_t)((size_t)scene->wide_depth * WIDE_STACK_LEVEL_BYTES / 4);
+    enqueue_primary(d, L, TG, pp);
+    for (int b = 0; b < max_bounces; b++) { enqueue_shade(d, L, TG, pp, b); enqueue_trace(d, L, TG, pp, b); }
+    return enqueue_accumulate(d, L, TG, pp, pass, g);
+}
+
+// one launch over this renderer's own pixels and all the call's frames, on a stream of its own beside the passes just enqueued; joined like a lane
+int Renderer::enqueue_guides(DrawCtx &d) {
+    const bool two_level = d.sv.num_inst > 0;
+    const size_t lds = d.sv.num_wnodes ? (size_t)scene->wide_depth * WIDE_STACK_LEVEL_BYTES : 0;
+    const auto kernel = two_level ? (d.sv.num_wnodes ? k_guides<3> : k_guides<0>) : (d.sv.num_wnodes ? k_guides<2> : k_guides<1>);
+    hipLaunchKernelGGL(kernel, dim3(std::max<uint32_t>(1u, (uint32_t)tiles_local)), dim3(64), lds, guide_stream, d.sv, d.gp, (const uint32_t *)seeds.p, (uint32_t)d.dp.n_frames, guide_nd.p, guide_albedo.p, guide_ids.p);
+    const hipError_t le = hipGetLastError();
+    // the join comes whatever the launch said: nothing on this stream outlives the call unjoined
+    (void)hipEventRecord(guide_done, guide_stream);
+    (void)hipStreamWaitEvent(stream, guide_done, 0);
+    if (le != hipSuccess) return hip_fail(le, "k_guides launch", __FILE__, __LINE__);
+    guides_valid = true;
+    return MRT_OK;
+}
+
+int Renderer::render(int n_frames) {
+    if (!scene) { set_error("renderer has no scene"); return MRT_ERR_STATE; }
+    DrawCtx d;
+    d.sv = scene->view();
+    if (d.sv.light_count < 1) { set_error("scene has no lights (lightCount must be >= 1, Raytracing.metal:273)"); return MRT_ERR_STATE; }
+    if (tiles_local == 0) return draw_nothing(n_frames);
+    if (alloc_batch != batch_wanted()) { if (int rc = rebuild_for_batch()) return rc; return render(n_frames); }
+    // decide: the passes, the lanes the device has memory for, and what each pass launches.  All passes but the last have the size of the first, so two rows of plans
+    // serve the draw.  What a draw can be refused for is found here: nothing is enqueued and no lane forked yet
+    DrawPlan &dp = d.dp;
+    dp = plan_draw(n_frames);
+    if (int rc = ensure_lanes(dp.lanes)) return rc;
+    dp.settle(lanes_ready);
+    lanes_used = dp.lanes; groups_used = dp.G;
+    if (dp.G > 1) { if (int rc = ensure_tile_groups(dp.G)) return rc; }
+    const TileGroup self_group{shard_rank, shard_world, tiles_local, capacity, owned_pixels, seeds.p};
+    PassPlan plans[2][MAX_TILE_GROUPS];
+    for (int k = 0; k < 2; k++)
+        for (int g = 0; g < dp.G; g++) { if (int rc = plan_pass(dp, d.sv, dp.G > 1 ? tgroups[g] : self_group, dp.pass_size(k == 0 ? 0 : dp.n_passes - 1), plans[k][g])) return rc; }
+    wave_slots = plans[0][0].wave_slots;          // (the option reads back what the grids were sized for)
+    begin_draw(d);
     ext_used = 0;
     if (halton_table && frame_bundle && !megakernel && n_frames > 1) { if (int rc = ensure_halton_table(frame_index + sample_offset, (uint32_t)n_frames)) return rc; }      // (ahead of the fork: see there)
     MRT_HIP(hipEventRecord(ev_begin, stream));
     // fork: every lane starts after whatever the caller queued on the main stream (resize, camera, ...)
     MRT_HIP(hipEventRecord(ev_fork, stream));
-    for (int k = 0; k < F; k++) MRT_HIP(hipStreamWaitEvent(lanes[k].stream, ev_fork, 0));
-#ifdef MRT_DIAGNOSTICS
-    // measuring aid of the diagnostics build only (tools/build_variant.sh diag "-DMRT_DIAGNOSTICS"; tools/archive/gpu_stage_ablation.sh): MRT_ABLATE=1 skips the primary launches, =2 the
-    // bounce / shadow traversal launches — the other kernels then run on the stale but well-formed queues of an earlier pass, so their load is realistic and the frame time shows
-    // what the skipped stage costs under overlap.  Images are garbage; the release library does not read the variable.
-    static const int ablate = getenv("MRT_ABLATE") ? atoi(getenv("MRT_ABLATE")) : 0;
-#else
-    constexpr int ablate = 0;
-#endif
-    if (megakernel && (two_level || materials || sv.num_wnodes == 0)) {          // the one-launch-per-frame mode exists for flattened scenes on the 8-wide layout, diffuse kernel: say so instead of quietly rendering through the pipeline
-        set_error(std::string("megakernel = 1 renders flattened scenes with the 8-wide layout and the reference's diffuse kernel only; this renderer has ") + (two_level ? "a two-level scene (scene option instancing = 1)" : materials ? "materials = 1" : "a scene without the 8-wide layout") + ": set megakernel = 0");
-        return MRT_ERR_UNSUPPORTED;
-    }
-    const bool mega = megakernel;
+    for (int k = 0; k < dp.lanes; k++) MRT_HIP(hipStreamWaitEvent(lanes[k].stream, ev_fork, 0));
     // the guide buffers of the call's frames (guides.h): what can fail on the host happens here, the launch follows the pass loop — no error return of the
     // loop leaves a guide kernel in flight that the main stream has not joined
-    FrameParams gp = fp;
-    gp.frameIndex = frame_index; gp.sampleIndex = frame_index + sample_offset; gp.npix = (uint32_t)((size_t)width * height); gp.capacity = capacity; gp.batch = 1;
     if (guides) {
         if (int rc = ensure_guides()) return rc;
         MRT_HIP(hipEventRecord(guide_fork, stream));       // the guide stream starts behind whatever the caller queued on the main stream (the clears of ensure_guides included), not behind the passes
         MRT_HIP(hipStreamWaitEvent(guide_stream, guide_fork, 0));
     }
-    // passes larger than the default (sharded renderers ask for up to 32 frames so that a shard's launches stay large) never take more than a third of the draw:
-    // a short draw keeps about three passes to run side by side (a rank of eight over 20 frames: 7.1 Grays/s as 7 + 7 + 6, 6.0 as one pass of 20)
-    const int batch_cap = alloc_batch > DEFAULT_FRAME_BATCH ? std::min(alloc_batch, std::max(DEFAULT_FRAME_BATCH, (n_frames + 2) / 3)) : alloc_batch;
-    const int batch_max = mega ? 1 : batch_cap;
-    fp.npix = (uint32_t)((size_t)width * height); fp.capacity = capacity;
-    hipEvent_t last_acc = nullptr;
-    int pass = 0;
-    const int n_passes = (n_frames + batch_max - 1) / batch_max;
-    const int tail_from = (tail_accumulate && G == 1) ? n_passes - std::min(F, n_passes) : n_passes;      // passes from here on (each on a lane of its own) are accumulated together after the join (tile groups: every group accumulates its own pixels as it ends — nothing to serialise)
-    hipEvent_t last_acc_g[MAX_TILE_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
-    const TileGroup self_group{shard_rank, shard_world, tiles_local, capacity, owned_pixels, seeds.p};
-    AccGroup tail{}; tail.n = 0;
-    for (int f = 0; f < n_frames; pass++) {
-        // the draw's frames in passes of equal size (20 frames at frame_batch 8: 7 + 7 + 6, not 8 + 8 + 4 — the passes of a short draw run side by side and end together)
-        int B = equal_passes ? std::min(batch_max, (n_frames - f + (n_passes - pass) - 1) / std::max(1, n_passes - pass)) : std::min(batch_max, n_frames - f);
-        f += B;
-        fp.batch = B;
-        for (int g = 0; g < G; g++) {
-        const TileGroup &TG = G > 1 ? tgroups[g] : self_group;
-        if (G > 1 && TG.capacity == 0) continue;
-        FrameLane &L = lanes[G > 1 ? (pass % Fp) * G + g : pass % F];
-        hipStream_t st = L.stream;
-        unsigned long long *bc = L.bounce_counts.p;                     // [bounce] {next rays (lo), shadow rays (hi)}, zero at frame start
-        fp.frameIndex = frame_index;                                    // updateUniforms :216-229 (first frame of the batch)
-        fp.sampleIndex = frame_index + sample_offset;
-        // this group's tiles (G = 1: the renderer's own shard)
-        fp.shard_rank = TG.rank; fp.shard_world = TG.world; fp.tiles_local = TG.tiles_local; fp.capacity = TG.capacity;
-        const uint32_t capacity = TG.capacity, grid = std::max<uint32_t>(1u, (uint32_t)TG.tiles_local), grid_shade = std::max<uint32_t>(1u, cdiv(TG.capacity, SHADE_THREADS));
-        const uint64_t owned_pixels = TG.owned;
-        const uint32_t *const seeds_p = TG.seeds;
-        bool used_planes = false;
-        if (mega) {
-            // one launch per frame on the pass's stream; frames are sequential (a path's last act is the running average with the previous target)
-            const size_t stack_bytes = (size_t)scene->wide_depth * WIDE_STACK_LEVEL_BYTES;
-            if (mega_slots_for_stack != stack_bytes) {
-                int per_cu = 0, dev = 0; hipDeviceProp_t prop;
-                MRT_HIP(hipGetDevice(&dev)); MRT_HIP(hipGetDeviceProperties(&prop, dev));
-                MRT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_megakernel, 64, stack_bytes));
-                mega_slots = std::max(1, per_cu) * prop.multiProcessorCount; mega_slots_for_stack = stack_bytes;
-            }
-            uint32_t *work = reinterpret_cast<uint32_t *>(bc + 64);      // its own word: the pipeline's per-bounce work counters must stay zero between passes
-            for (int sub = 0; sub < B; sub++) {
-                fp.frameIndex = frame_index + (uint32_t)sub; fp.sampleIndex = frame_index + (uint32_t)sub + sample_offset; fp.batch = 1;
-                if (last_acc) { MRT_HIP(hipStreamWaitEvent(st, last_acc, 0)); last_acc = nullptr; }
-                MRT_HIP(hipMemsetAsync(work, 0, 4, st));
-                EvPair *ev = nullptr;
-                if (ext_used < (int)ev_ext.size()) { ev_ext[ext_used].kind = MRT_KERNEL_TRACE; ev = &ev_ext[ext_used++]; }
-                const uint32_t waves = (uint32_t)std::min<size_t>(std::max<size_t>(1, cdiv(capacity, 64)), (size_t)mega_slots);
-                launch_timed(ev, k_megakernel, dim3(waves), dim3(64), stack_bytes, st, sv, fp, seeds_p, accum[cur].p, accum[1 - cur].p, work, totals.p, (uint32_t)owned_pixels);
-                cur = 1 - cur;
-            }
-            MRT_HIP(hipEventRecord(L.accumulated, st));
-            last_acc = L.accumulated;
-            frame_index += (uint32_t)B; frames_rendered += (uint64_t)B;
-            if (int rc = note_pass(st)) return rc;
-            continue;
+    for (int pass = 0; pass < dp.n_passes; pass++) {
+        const int B = dp.pass_size(pass);
+        for (int g = 0; g < dp.G; g++) {
+            const TileGroup &TG = dp.G > 1 ? tgroups[g] : self_group;
+            if (dp.G > 1 && TG.capacity == 0) continue;
+            FrameLane &L = lanes[dp.G > 1 ? (pass % dp.Fp) * dp.G + g : pass % dp.lanes];
+            if (int rc = enqueue_pass(d, L, TG, plans[B == plans[0][g].B ? 0 : 1][g], pass, g)) return rc;
         }
-        {
-            // the pipeline: primary trace -> per bounce { shade, trace } ; bounce rays and shadow rays of a shade share one traversal launch
-            const uint32_t grid_mixed = 2 * grid * (uint32_t)B;
-            const bool on_wide = wide_bounce && sv.num_wnodes > 0;          // no 8-wide layout (scene option wide = 0, a tree deeper than WIDE_STACK_MAX): the rope kernels
-            // two-level scenes walk TLAS and BLASes with the same kernels (traverse_wide_stream<true>); their LDS also parks the lanes' world rays
-            const size_t stack_bytes = (size_t)scene->wide_depth * WIDE_STACK_LEVEL_BYTES + (two_level ? WIDE_WORLD_RAY_BYTES : 0);
-            if (on_wide && persistent != 0 && slots_for_stack != stack_bytes) {       // wave slots of the chip for this kernel at this LDS size
-                int per_cu = 0, dev = 0; hipDeviceProp_t prop;
-                MRT_HIP(hipGetDevice(&dev)); MRT_HIP(hipGetDeviceProperties(&prop, dev));
-                if (two_level) MRT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trace_mixed_wide_persist<true>, 64, stack_bytes));
-                else MRT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trace_mixed_wide_persist<false>, 64, stack_bytes));
-                if (!wave_slots_user) wave_slots = std::max(1, per_cu) * prop.multiProcessorCount;
-                slots_for_stack = stack_bytes;
-            }
-            // traversal launches carry their own start/stop events (hipExtLaunchKernelGGL: the dispatch packet's timestamps, the
-            // same clock rocprofv3 reads): plain hipEventRecord pairs on a stream also count the time a launch waits behind the
-            // other frames in flight (+12 % at 12 frames)
-            auto timed = [&](int kind) -> EvPair * { if (ext_used >= (int)ev_ext.size()) return nullptr; ev_ext[ext_used].kind = kind; return &ev_ext[ext_used++]; };
-            fp.bounce = 0;
-            fp.chain = (throughput_chain && !materials && max_bounces <= 3 && (uint64_t)scene->stats.instances * (uint64_t)std::max(1, scene->stats.max_submeshes) <= 65536ull) ? 1 : 0;
-            if (!fp.chain && !L.thr[0].p) {           // this draw needs the throughput queues after all (materials, more than three bounces, a very large resource table)
-                const size_t qcap = (size_t)this->capacity * (size_t)std::max(1, alloc_batch);          // (a lane's buffers are sized for the renderer's whole shard, whatever tile group uses it now)
-                for (int k = 0; k < 2; k++) MRT_HIP(L.thr[k].alloc(qcap));
-            }
-            const uint32_t rpw_p = stream_rays_per_wave((size_t)capacity * B), rpw_m = stream_rays_per_wave(2 * (size_t)capacity * B);
-            float4 *const dirs = L.rayB[1].p;
-            // shadow planes: contribution per pixel and bounce + one byte per shadow ray that got through, instead of the contribution queue and the read-modify-write of the sample buffer
-            const bool planes_pass = shadow_planes != 0 && fp.chain && on_wide && !materials && max_bounces <= PLANES_MAX_BOUNCES && !ablate;
-            if (planes_pass) {
-                if (!L.f_lit.p) { if (int rc = alloc_planes(L)) return rc; }
-                MRT_HIP(hipMemsetAsync(L.f_lit.p, 0, 4 * (size_t)capacity * (size_t)B, st));
-            }
-            used_planes = planes_pass;
-            // two-level scenes: the binned walk (TLAS pass + BLAS pass over (ray, instance) pairs) for the bounce / shadow rays of planes passes
-            const bool pairs_pass = two_level && planes_pass && tl_pairs != 0 && sv.tri_packet != nullptr;
-            const size_t pair_cap = 2 * (size_t)this->capacity * (size_t)std::max(1, alloc_batch);          // one pair per virtual ray of the combined queue; a push beyond it walks its instance in place
-            if (pairs_pass && !L.pairs.p) MRT_HIP(L.pairs.alloc(std::max<size_t>(PairQueue::WORDS * pair_cap, 1)));
-            // few instances: the TLAS pass has no tree (every lane visits every instance: nothing diverges; two_level_passes.h k_tl_top_flat)
-            const bool tl_flat = pairs_pass && sv.num_inst <= TL_FLAT_MAX_INSTANCES && tl_pairs != 2;
-            const uint32_t pair_cap_used = (uint32_t)std::min<size_t>(tl_pair_cap > 0 ? std::min<size_t>((size_t)tl_pair_cap, pair_cap) : pair_cap, 0xFFFFFFFFu);
-            // the primary trace inside shade(0): flattened scenes, planes passes
-            // (not for one frame alone on the chip, fuse_primary = 1: there the primary kernel's 48 registers and 64-thread workgroups fill the chip better than shade's 76 and 256 — 1.71 against 1.81 ms;
-            // fuse_primary = 2 fuses always)
-            // which layout the primary rays of a flattened scene walk: the 8-wide one when the scene has it (primary_wide = 2, default: one ray per lane inside shade(0) or in its own launch;
-            // = 1: the stream kernel with lane refill, A/B), the rope layout otherwise — or on request (primary_wide = 0; needs scene option rope = 1)
-            const bool prim_rope = !two_level && (!sv.num_wnodes || primary_wide == 0);
-            if (prim_rope && sv.num_nodes == 0 && sv.num_tris != 0) { set_error("primary_wide = 0 walks the rope layout: commit the scene with scene option rope = 1"); return MRT_ERR_STATE; }
-            if (!on_wide && !two_level && sv.num_nodes == 0 && sv.num_tris != 0) { set_error("wide_bounce = 0 walks the rope layout: commit the scene with scene option rope = 1"); return MRT_ERR_STATE; }
-            const bool trace0_pass = planes_pass && fuse_primary != 0 && primary_wide != 1 && !(two_level && primary_wide == 0) && (fuse_primary == 2 || F > 1 || B > 1 || two_level);      // (two-level scenes always: their own-launch form is the stream kernel, 0.88 ms for one 1080p frame of dragon x 4)
-            const bool trace0_wide = trace0_pass && !prim_rope;          // (planes_pass implies the 8-wide layout)
-            const bool trace0_hint = primary_hint && (!two_level || (sv.num_inst <= 255u && scene->wpackets.n / WPK < ((size_t)1 << 24)));      // two-level: the hint is (packet | instance << 24)
-            fp.wide_stack_words = (uint32_t)((size_t)scene->wide_depth * WIDE_STACK_LEVEL_BYTES / 4);
-            if (!planes_pass && !L.scon.p) MRT_HIP(L.scon.alloc((size_t)this->capacity * (size_t)std::max(1, alloc_batch)));
-            if ((ablate & 1) || trace0_pass) {}
-            else if (two_level && on_wide) {
-                // the hint of two-level scenes is (packet | instance << 24): scenes of at most 255 instances and 2^24 packets
-                const bool seeded = primary_hint && sv.num_inst <= 255u && scene->wpackets.n / WPK < ((size_t)1 << 24);
-                if (seeded) launch_timed(timed(MRT_KERNEL_PRIMARY), k_trace_primary_wide_stream<true, true>, dim3(cdiv(capacity, rpw_p), B), dim3(64), stack_bytes, st, sv, fp, seeds_p, L.hits.p, dirs, capacity, rpw_p, hint.p);
-                else launch_timed(timed(MRT_KERNEL_PRIMARY), k_trace_primary_wide_stream<true, false>, dim3(cdiv(capacity, rpw_p), B), dim3(64), stack_bytes, st, sv, fp, seeds_p, L.hits.p, dirs, capacity, rpw_p, (uint32_t *)nullptr);
-            }
-            else if (primary_wide == 1 && sv.num_wnodes && !two_level) {
-                if (primary_hint) launch_timed(timed(MRT_KERNEL_PRIMARY), k_trace_primary_wide_stream<false, true>, dim3(cdiv(capacity, rpw_p), B), dim3(64), stack_bytes, st, sv, fp, seeds_p, L.hits.p, dirs, capacity, rpw_p, hint.p);
-                else launch_timed(timed(MRT_KERNEL_PRIMARY), k_trace_primary_wide_stream<false, false>, dim3(cdiv(capacity, rpw_p), B), dim3(64), stack_bytes, st, sv, fp, seeds_p, L.hits.p, dirs, capacity, rpw_p, (uint32_t *)nullptr);
-            }
-            else if (two_level) launch_timed(timed(MRT_KERNEL_PRIMARY), k_trace_primary<true>, dim3(grid, B), dim3(64), 0, st, sv, fp, seeds_p, L.hits.p, dirs, (uint32_t *)nullptr);
-            else if (!prim_rope) launch_timed(timed(MRT_KERNEL_PRIMARY), k_trace_primary<false, true>, dim3(grid, B), dim3(64), (size_t)scene->wide_depth * WIDE_STACK_LEVEL_BYTES, st, sv, fp, seeds_p, L.hits.p, dirs, primary_hint ? hint.p : (uint32_t *)nullptr);
-            else launch_timed(timed(MRT_KERNEL_PRIMARY), k_trace_primary<false>, dim3(grid, B), dim3(64), 0, st, sv, fp, seeds_p, L.hits.p, dirs, primary_hint ? hint.p : (uint32_t *)nullptr);
-            int q = 0;                                                  // shade(b) writes next rays into queue q
-            for (int b = 0; b < max_bounces; b++) {
-                fp.bounce = b;
-                const unsigned long long *cin = b == 0 ? nullptr : bc + (b - 1);
-                // bounce 0 reads no ray queue (it regenerates the primary ray); bounce b > 0 reads the queue shade(b-1) wrote
-                // bounce 0: one grid row per sub-frame of the batch over the primary slots; later bounces: the compact queue of the whole batch
-                const bool pack = shade_pack && b > 0;          // bounces >= 1 read a queue half of whose rays missed: its hits are compacted in LDS and shaded on full waves (k_shade_pack)
-                // entries per packing workgroup: SHADE_PACK_RANGE when the queue is long, less when that would leave fewer than ~2048 workgroups (a one-frame pass, a tile group, a shard) — never less than two rounds' worth
-                fp.pack_range = (uint32_t)std::min<size_t>(SHADE_PACK_RANGE, std::max<size_t>(2 * SHADE_THREADS, (size_t)capacity * B / 2048 / SHADE_THREADS * SHADE_THREADS));
-                fp.frame_bundle = (frame_bundle && b == 0 && trace0_wide && B > 1) ? 1 : 0;
-                if (fp.frame_bundle) {
-                    fp.bundle_groups = ((uint32_t)B + 7u) / 8u; fp.bundle_w = ((uint32_t)B + fp.bundle_groups - 1u) / fp.bundle_groups;
-                    fp.bundle_per_wave = 64u / fp.bundle_w; fp.bundle_magic = (65536u + fp.bundle_w - 1u) / fp.bundle_w;
-                }
-                fp.halton_tab = nullptr; fp.halton_w0 = 0; fp.halton_n = 0;
-                if (b == 0 && fp.frame_bundle && fp.bundle_w >= 4u && halton_table && halton_tab.p) {          // a wave reads bundle_w consecutive values per load: the table pays from four on (indices outside its window: the recurrence)
-                    fp.halton_tab = halton_tab.p; fp.halton_w0 = halton_w0; fp.halton_n = HALTON_TAB_SPAN;
-                }
-                const dim3 gs = b == 0 ? (fp.frame_bundle ? dim3(cdiv(cdiv((size_t)capacity * fp.bundle_groups, fp.bundle_per_wave) * 64, SHADE_THREADS), 1) : dim3(grid_shade, B)) : dim3(cdiv((size_t)capacity * B, pack ? fp.pack_range : (uint32_t)SHADE_THREADS));
-                using ShadeKernel = void (*)(SceneView, FrameParams, const uint32_t *, const float4 *, const float4 *, const float4 *, const float4 *, const unsigned long long *, uint32_t, float4 *, float4 *, float4 *, float4 *, float4 *, float4 *,
-                                             unsigned long long *, float4 *, float4 *, uint32_t *);
-                const bool trace0_tl = trace0_wide && b == 0 && two_level;
-                const ShadeKernel shade_kernel = pack ? (materials ? (ShadeKernel)k_shade_pack<true, false, false, false>
-                                                          : pairs_pass ? (ShadeKernel)k_shade_pack<false, true, true, true>
-                                                          : planes_pass ? (ShadeKernel)k_shade_pack<false, true, true, false>
-                                                          : fp.chain ? (ShadeKernel)k_shade_pack<false, true, false, false> : (ShadeKernel)k_shade_pack<false, false, false, false>)
-                                                  : materials ? (ShadeKernel)k_shade<true, false, false, false>
-                                                  : (pairs_pass && b > 0) ? (ShadeKernel)k_shade<false, true, true, true>
-                                                  : trace0_tl ? (ShadeKernel)k_shade_primary<3>
-                                                  : (trace0_wide && b == 0) ? (ShadeKernel)k_shade_primary<2>
-                                                  : (trace0_pass && b == 0) ? (ShadeKernel)k_shade_primary<1>
-                                                  : planes_pass ? (ShadeKernel)k_shade<false, true, true, false>
-                                                  : fp.chain ? (ShadeKernel)k_shade<false, true, false, false> : (ShadeKernel)k_shade<false, false, false, false>;
-                float4 *const con_b = !planes_pass ? L.scon.p : b == 0 ? L.sample.p : L.f_con[b - 1].p;         // PLANES: this bounce's contribution plane in place of the queue
-                uint8_t *const lit_b = planes_pass ? L.f_lit.p + b : nullptr;
-                ShadeIO io{};
-                io.seeds = seeds_p; io.rayA = L.rayA[1 - q].p; io.rayB = L.rayB[1 - q].p; io.thr = L.thr[1 - q].p; io.hits = L.hits.p;          // (two-level, binned, b > 0: the 64-bit keys of the TLAS / BLAS passes, in the hit buffer)
-                io.count_in = cin; io.capacity = capacity;
-                io.nrayA = L.rayA[q].p; io.nrayB = L.rayB[q].p; io.nthr = L.thr[q].p; io.srayA = L.srayA.p; io.srayB = L.srayB.p; io.scon = con_b; io.count_out = bc + b;
-                io.sample_primary = b == 0 ? L.sample.p : nullptr; io.sample = L.sample.p; io.hint = (b == 0 && trace0_pass && trace0_hint) ? hint.p : nullptr;
-                uint32_t *const pc = reinterpret_cast<uint32_t *>(bc + 65 + b);          // two-level, binned: {pairs queued, work counter of the BLAS pass}
-                const size_t shade_lds = (trace0_wide && b == 0) ? (size_t)SHADE_WAVES * (scene->wide_depth * WIDE_STACK_LEVEL_BYTES + (MRT_LANE_HIT_LDS ? 1024 : 0)) : 0;
-                launch_timed(timed(MRT_KERNEL_SHADE), shade_kernel, gs, dim3(SHADE_THREADS), shade_lds, st, sv, fp, io.seeds, io.rayA, io.rayB, io.thr, io.hits, io.count_in, io.capacity, io.nrayA, io.nrayB, io.nthr, io.srayA, io.srayB, io.scon,
-                             io.count_out, io.sample_primary, io.sample, io.hint);
-                // persistent = 2 (auto): pull chunks when every wave slot would otherwise own >= 1024 rays (4-frame passes at 1080p: +7...+11 % with
-                // one stream, +2.5 % with 12); one-frame launches keep the static split (384 rays per wave, no atomics: 3 frames in flight 6.5 vs 5.4 Grays/s)
-                // [r3] smaller launches pull as well when five or more passes are in flight (6 lanes x one-frame passes: 9.33 against 8.76 Grays/s; a rank of eight over 240 frames
-                // in 8-frame passes: 9.43 against 8.56); with one to three passes in flight they do better on the even static split (one frame alone 1.51 against 1.76 ms, 3 x 1 frame
-                // 7.63 against 7.20 Grays/s, a rank of eight over the driver's 20 frames 6.65 against 5.73): stream_even below
-                const bool pull = persistent == 1 || (persistent == 2 && (2 * (size_t)capacity * B >= (size_t)wave_slots * 1024 || (std::min(F, G > 1 ? Fp * G : n_passes) >= 5 && 2 * (size_t)capacity * B >= (size_t)wave_slots * 256)));      // (below 256 slots per wave slot — Cornell 256^2 in 8-frame passes — the even split: 6.46 against 5.40 Grays/s)
-                if (ablate & 2) {}
-                else if (pairs_pass) {
-                    const size_t slots = 2 * (size_t)capacity * B;
-                    const uint32_t chunk = (uint32_t)std::min<size_t>((size_t)persist_chunk, std::max<size_t>(64, slots / ((size_t)wave_slots * 4) / 64 * 64));
-                    const size_t grid_slots = (!wave_slots_user && (n_frames + batch_max - 1) / batch_max >= 2 * F) ? (size_t)std::max(1, wave_slots / 2) : (size_t)wave_slots;
-                    const uint32_t waves = (uint32_t)std::max<size_t>(1, std::min<size_t>(cdiv(slots, chunk), grid_slots));
-                    unsigned long long *const keys = reinterpret_cast<unsigned long long *>(L.hits.p);
-                    // few instances: the TLAS pass without a tree; many: the stream walk of the 8-wide TLAS
-                    if (tl_flat)
-                        launch_timed(timed(MRT_KERNEL_TRACE), k_tl_top_flat, dim3((uint32_t)std::max<size_t>(1, std::min<size_t>(cdiv(slots, 64), 2 * grid_slots))), dim3(64), stack_bytes + 8, st, sv, L.rayA[q].p, L.rayB[q].p, keys, L.srayA.p, L.srayB.p,
-                                     (const unsigned long long *)(bc + b), lit_b, L.pairs.p, pc, pair_cap_used, (uint32_t)(stack_bytes / 4));
-                    else
-                    launch_timed(timed(MRT_KERNEL_TRACE), k_tl_top, dim3(waves), dim3(64), stack_bytes + 8, st, sv, L.rayA[q].p, L.rayB[q].p, keys, L.srayA.p, L.srayB.p,
-                                 (const unsigned long long *)(bc + b), reinterpret_cast<uint32_t *>(bc + 32 + b), chunk, lit_b, L.pairs.p, pc, pair_cap_used, (uint32_t)(stack_bytes / 4));
-                    // the pairs' count is on the device: the launch has the wave slots it may use and the surplus leaves at once
-                    launch_timed(timed(MRT_KERNEL_TRACE), k_tl_blas, dim3((uint32_t)grid_slots), dim3(64), (size_t)scene->wide_depth * WIDE_STACK_LEVEL_BYTES, st, sv, L.rayA[q].p, L.rayB[q].p, keys, L.srayA.p, L.srayB.p,
-                                 (const unsigned long long *)(bc + b), pc + 1, 256u, lit_b, (const uint4 *)L.pairs.p, (const uint32_t *)pc, pair_cap_used);
-                }
-                else if (on_wide && pull) {
-                    // rays per pull: at least four pulls per wave slot on a queue of this size (so that the launch ends evenly), at most
-                    // persist_chunk; 128-ray pulls of a one-frame launch are ~78 atomics per microsecond on the one counter word (limit ~88)
-                    const size_t slots = 2 * (size_t)capacity * B;
-                    const uint32_t chunk = (uint32_t)std::min<size_t>((size_t)persist_chunk, std::max<size_t>(128, slots / ((size_t)wave_slots * 4) / 64 * 64));
-                    // a long call (every lane gets several passes) runs its traversal launches on HALF the wave slots: the other passes' shade, primary
-                    // and accumulate blocks then find free slots instead of queueing behind persistent waves that only leave when their queue is empty
-                    // (measured, 240 steps: 4 lanes 9.86 -> 10.06, 6 lanes 10.08 -> 10.32, 12 lanes 10.38 -> 10.55 Grays/s; a 20-step call, whose five
-                    // passes move in lock step, loses 3 % and keeps the full grid)
-                    const size_t grid_slots = (!wave_slots_user && (n_frames + batch_max - 1) / batch_max >= 2 * F) ? (size_t)std::max(1, wave_slots / 2) : (size_t)wave_slots;
-                    const uint32_t waves = (uint32_t)std::min<size_t>(cdiv(slots, chunk), grid_slots);
-#ifdef MRT_WAVE_TIMES
-                    const uint32_t chunk_arg = chunk | ((uint32_t)b << 24);
-#else
-                    const uint32_t chunk_arg = chunk;
-#endif
-                    if (!two_level && planes_pass && hit_lds) {
-                        // the variant with the hit words in LDS: its own LDS size, hence its own count of wave slots
-                        const size_t lds_x = (size_t)HIT_LDS_WORDS * 4 + stack_bytes;
-                        const int key = (int)(lds_x & 0xFFFFFF);
-                        if (slots_x_key != key) {
-                            int per_cu = 0, dev = 0; hipDeviceProp_t prop;
-                            MRT_HIP(hipGetDevice(&dev)); MRT_HIP(hipGetDeviceProperties(&prop, dev));
-                            MRT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trace_mixed_wide_persist_x, 64, lds_x));
-                            if (per_cu < 1) { set_error("hit_lds: the traversal kernel does not fit a compute unit with " + std::to_string(lds_x) + " bytes of LDS"); return MRT_ERR_UNSUPPORTED; }
-                            wave_slots_x = per_cu * prop.multiProcessorCount; slots_x_key = key;
-                        }
-                        const size_t ws = wave_slots_user ? (size_t)wave_slots : (size_t)wave_slots_x;
-                        const uint32_t chunk_x = (uint32_t)std::min<size_t>((size_t)persist_chunk, std::max<size_t>(128, slots / (ws * 4) / 64 * 64));
-                        const size_t grid_slots_x = (!wave_slots_user && (n_frames + batch_max - 1) / batch_max >= 2 * F) ? std::max<size_t>(1, ws / 2) : ws;
-                        const uint32_t waves_x = (uint32_t)std::max<size_t>(1, std::min<size_t>(cdiv(slots, chunk_x), grid_slots_x));
-                        launch_timed(timed(MRT_KERNEL_TRACE), k_trace_mixed_wide_persist_x, dim3(waves_x), dim3(64), lds_x, st, sv, (const float4 *)L.rayA[q].p, (const float4 *)L.rayB[q].p, L.hits.p, (const float4 *)L.srayA.p, (const float4 *)L.srayB.p,
-                                     (const unsigned long long *)(bc + b), reinterpret_cast<uint32_t *>(bc + WORK_COUNTERS + (size_t)b * WORK_COUNTERS_PER_BOUNCE), chunk_x, lit_b, xcd_counters ? (uint32_t)B : 0u);
-                    }
-                    else if (two_level) launch_timed(timed(MRT_KERNEL_TRACE), k_trace_mixed_wide_persist<true>, dim3(std::max(1u, waves)), dim3(64), stack_bytes, st, sv, L.rayA[q].p, L.rayB[q].p, L.hits.p, L.srayA.p, L.srayB.p, L.scon.p,
-                                 (const unsigned long long *)(bc + b), L.sample.p, reinterpret_cast<uint32_t *>(bc + WORK_COUNTERS + (size_t)b * WORK_COUNTERS_PER_BOUNCE), chunk_arg, lit_b, xcd_counters ? (uint32_t)B : 0u);
-                    else launch_timed(timed(MRT_KERNEL_TRACE), k_trace_mixed_wide_persist<false>, dim3(std::max(1u, waves)), dim3(64), stack_bytes, st, sv, L.rayA[q].p, L.rayB[q].p, L.hits.p, L.srayA.p, L.srayB.p, L.scon.p,
-                                 (const unsigned long long *)(bc + b), L.sample.p, reinterpret_cast<uint32_t *>(bc + WORK_COUNTERS + (size_t)b * WORK_COUNTERS_PER_BOUNCE), chunk_arg, lit_b, xcd_counters ? (uint32_t)B : 0u);
-                }
-                else if (on_wide) {
-                    const size_t slots_m = 2 * (size_t)capacity * B;
-                    // a shard's launches (a rank of eight over the driver's 20 frames: three passes of its 1/8 of the tiles in flight) do better with ONE round of waves that take the queue's
-                    // 64-ray batches round-robin — every rank of eight timed: 2.00 against 2.21 ms on average, the slowest 2.13-2.18 against 2.46-2.50 (profiles/r05_shard_stride.txt); a whole
-                    // image's one-frame launches do not (one frame alone 1.38 = 1.38 ms, three in flight 0.775 against 0.765)
-                    const bool takes_x = !two_level && planes_pass && hit_lds;          // k_trace_mixed_wide_stream_x: the one kernel that deals batches round-robin (BatchStride)
-                    const bool shard_auto = stream_stride == 2 && stream_even == 200 && this->shard_world > 1 && G == 1 && takes_x;          // (one round of waves was measured with the strided deal only)
-                    const bool strided = stream_stride == 1 || shard_auto;
-                    const int even_pct = shard_auto ? 100 : stream_even;
-                    const uint32_t even = even_pct > 0 ? (uint32_t)std::max<size_t>(1, std::min<size_t>(cdiv(slots_m, 64), (size_t)wave_slots * (size_t)even_pct / 100)) : 0u;     // stream_even: percent of the wave slots
-                    const dim3 grid_s(even ? even : cdiv(slots_m, rpw_m));
-#ifdef MRT_WAVE_TIMES
-                    const uint32_t rpw_m_arg = rpw_m | ((uint32_t)b << 24);
-#else
-                    const uint32_t rpw_m_arg = rpw_m;
-#endif
-                    if (takes_x) launch_timed(timed(MRT_KERNEL_TRACE), k_trace_mixed_wide_stream_x, grid_s, dim3(64), stack_bytes + HIT_LDS_WORDS * 4, st, sv, (const float4 *)L.rayA[q].p, (const float4 *)L.rayB[q].p, L.hits.p, (const float4 *)L.srayA.p, (const float4 *)L.srayB.p, (const unsigned long long *)(bc + b), rpw_m_arg, lit_b, even | (strided ? 0x80000000u : 0u));
-                    else if (two_level) launch_timed(timed(MRT_KERNEL_TRACE), k_trace_mixed_wide_stream<true>, grid_s, dim3(64), stack_bytes, st, sv, L.rayA[q].p, L.rayB[q].p, L.hits.p, L.srayA.p, L.srayB.p, L.scon.p, (const unsigned long long *)(bc + b), L.sample.p, rpw_m, lit_b, even);
-                    else launch_timed(timed(MRT_KERNEL_TRACE), k_trace_mixed_wide_stream<false>, grid_s, dim3(64), stack_bytes, st, sv, L.rayA[q].p, L.rayB[q].p, L.hits.p, L.srayA.p, L.srayB.p, L.scon.p, (const unsigned long long *)(bc + b), L.sample.p, rpw_m, lit_b, even);
-                }
-                else if (two_level) launch_timed(timed(MRT_KERNEL_TRACE), k_trace_mixed<true>, dim3(grid_mixed), dim3(64), 0, st, sv, L.rayA[q].p, L.rayB[q].p, L.hits.p, L.srayA.p, L.srayB.p, L.scon.p, (const unsigned long long *)(bc + b), L.sample.p);
-                else launch_timed(timed(MRT_KERNEL_TRACE), k_trace_mixed<false>, dim3(grid_mixed), dim3(64), 0, st, sv, L.rayA[q].p, L.rayB[q].p, L.hits.p, L.srayA.p, L.srayB.p, L.scon.p, (const unsigned long long *)(bc + b), L.sample.p);
-                q = 1 - q;
-            }
-        }
-        // accumulation is the only frame-to-frame dependency (prev target = the previous frame's output)
-        const bool deferred = used_planes && pass >= tail_from && tail.n < MAX_FRAMES_IN_FLIGHT;
-        if (deferred) {
-            AccPass &P = tail.p[tail.n++];
-            P.con0 = L.sample.p; P.con1 = L.f_con[0].p; P.con2 = L.f_con[1].p; P.lit = L.f_lit.p; P.counts = bc; P.frameIndex = fp.frameIndex; P.batch = B; P.primary = (uint32_t)(owned_pixels * (uint64_t)B); P.pad = 0;
-            MRT_HIP(hipEventRecord(L.accumulated, st));       // (here: traced — the join below waits for it, the accumulation follows on the main stream)
-            frame_index += (uint32_t)B; frames_rendered += (uint64_t)B;
-            continue;
-        }
-        if (G > 1) { if (last_acc_g[g] && last_acc_g[g] != L.accumulated) MRT_HIP(hipStreamWaitEvent(st, last_acc_g[g], 0)); }      // this group's pixels of the previous target: written by the same group of the pass before
-        else if (last_acc) MRT_HIP(hipStreamWaitEvent(st, last_acc, 0));
-        {
-            EvPair *ev = nullptr;
-            if (ext_used < (int)ev_ext.size()) { ev_ext[ext_used].kind = MRT_KERNEL_ACCUMULATE; ev = &ev_ext[ext_used++]; }
-            if (used_planes) launch_timed(ev, k_accumulate_planes, dim3(grid), dim3(64), 0, st, fp, (const float4 *)L.sample.p, (const float4 *)L.f_con[0].p, (const float4 *)L.f_con[1].p, (const uint8_t *)L.f_lit.p,
-                                          (const float4 *)accum[cur].p, accum[1 - cur].p, bc, totals.p, (uint32_t)(owned_pixels * (uint64_t)B));
-            else launch_timed(ev, k_accumulate, dim3(grid), dim3(64), 0, st, fp, L.sample.p, accum[cur].p, accum[1 - cur].p, bc, totals.p, (uint32_t)(owned_pixels * (uint64_t)B));
-        }
-        MRT_HIP(hipEventRecord(L.accumulated, st));
-        if (G > 1) { last_acc_g[g] = L.accumulated; continue; }
-        last_acc = L.accumulated;
-        cur = 1 - cur;                                                  // ping-pong swap :332-334 (once per batch: the batch's frames are applied in one kernel)
-        frame_index += (uint32_t)B; frames_rendered += (uint64_t)B;
-        if (int rc = note_pass(st)) return rc;
-        }       // tile groups of the pass
-        if (G > 1) { cur = 1 - cur; frame_index += (uint32_t)B; frames_rendered += (uint64_t)B; }      // every group read accum[cur] and wrote accum[1 - cur] at its own pixels
+        if (dp.G > 1) { cur = 1 - cur; frame_index += (uint32_t)B; frames_rendered += (uint64_t)B; }      // every group read accum[cur] and wrote accum[1 - cur] at its own pixels
     }
     // join: the main stream continues after every lane has drained
-    for (int k = 0; k < (G > 1 ? std::min(Fp, pass) * G : std::min(F, pass)); k++) MRT_HIP(hipStreamWaitEvent(stream, lanes[k].accumulated, 0));
-    if (guides) {
-        // one launch over this renderer's own pixels and all the call's frames, on a stream of its own beside the passes just enqueued; joined like a lane
-        const size_t lds = sv.num_wnodes ? (size_t)scene->wide_depth * WIDE_STACK_LEVEL_BYTES : 0;
-        const dim3 gg(grid), gb(64);
-        if (two_level && sv.num_wnodes) hipLaunchKernelGGL(k_guides<3>, gg, gb, lds, guide_stream, sv, gp, (const uint32_t *)seeds.p, (uint32_t)n_frames, guide_nd.p, guide_albedo.p, guide_ids.p);
-        else if (two_level) hipLaunchKernelGGL(k_guides<0>, gg, gb, 0, guide_stream, sv, gp, (const uint32_t *)seeds.p, (uint32_t)n_frames, guide_nd.p, guide_albedo.p, guide_ids.p);
-        else if (sv.num_wnodes) hipLaunchKernelGGL(k_guides<2>, gg, gb, lds, guide_stream, sv, gp, (const uint32_t *)seeds.p, (uint32_t)n_frames, guide_nd.p, guide_albedo.p, guide_ids.p);
-        else hipLaunchKernelGGL(k_guides<1>, gg, gb, 0, guide_stream, sv, gp, (const uint32_t *)seeds.p, (uint32_t)n_frames, guide_nd.p, guide_albedo.p, guide_ids.p);
-        const hipError_t le = hipGetLastError();
-        // the join comes whatever the launch said: nothing on this stream outlives the call unjoined
-        (void)hipEventRecord(guide_done, guide_stream);
-        (void)hipStreamWaitEvent(stream, guide_done, 0);
-        if (le != hipSuccess) return hip_fail(le, "k_guides launch", __FILE__, __LINE__);
-        guides_valid = true;
-    }
-    if (G > 1) { if (int rc = note_pass(stream)) return rc; }      // (tile groups: completion is reported per draw)
-    if (tail.n > 0) {
-        EvPair *ev = nullptr;
-        if (ext_used < (int)ev_ext.size()) { ev_ext[ext_used].kind = MRT_KERNEL_ACCUMULATE; ev = &ev_ext[ext_used++]; }
-        launch_timed(ev, k_accumulate_planes_group, dim3(grid), dim3(64), 0, stream, fp, tail, (const float4 *)accum[cur].p, accum[1 - cur].p, totals.p);
+    for (int k = 0; k < (dp.G > 1 ? std::min(dp.Fp, dp.n_passes) * dp.G : std::min(dp.lanes, dp.n_passes)); k++) MRT_HIP(hipStreamWaitEvent(stream, lanes[k].accumulated, 0));
+    if (guides) { if (int rc = enqueue_guides(d)) return rc; }
+    if (dp.G > 1) { if (int rc = note_pass(stream)) return rc; }      // (tile groups: completion is reported per draw)
+    if (d.tail.n > 0) {          // the draw's last passes, accumulated in one launch over the shard's tiles
+        launch_timed(timed(MRT_KERNEL_ACCUMULATE), k_accumulate_planes_group, dim3(std::max<uint32_t>(1u, (uint32_t)tiles_local)), dim3(64), 0, stream, d.fp, d.tail, accum[cur].p, accum[1 - cur].p, totals.p);
         cur = 1 - cur;
         if (int rc = note_pass(stream)) return rc;
     }

@@ -30,7 +30,7 @@ def shard_frame_batch(world, frames_total=None, base=DEFAULT_FRAME_BATCH):
     """Frames per pass of one rank of a `world`-GPU tile-sharded run.  A rank owns 1/world of the pixels of every frame, so it carries
     proportionally more frames per pass to keep its launches large (base x world, at most 32) — but never more than a third of the run's frames (and never
     fewer than the 1-GPU default): a short run keeps about three passes to overlap.  mrt_group_renderer_create applies the first half of the rule, and
-    Renderer::render the second to every draw (csrc/renderer.hip `batch_cap`), so both launch paths agree."""
+    Renderer::plan_draw the second to every draw (csrc/renderer.hip, `batch_cap` there), so both launch paths agree."""
     if world <= 1:
         return base
     fb = min(MAX_FRAME_BATCH, base * world)
@@ -40,7 +40,7 @@ def shard_frame_batch(world, frames_total=None, base=DEFAULT_FRAME_BATCH):
 
 
 def pass_sizes(n_frames, frame_batch, base=DEFAULT_FRAME_BATCH):
-    """How Renderer::render (csrc/renderer.hip) splits a draw of n_frames into passes: passes larger than the default take at most a third of the draw,
+    """How the library splits a draw of n_frames into passes (csrc/renderer.hip Renderer::plan_draw: batch_max and n_passes; csrc/renderer.h DrawPlan::pass_size: the size of pass p): passes larger than the default take at most a third of the draw,
     and the draw's frames go in ceil(n / batch) passes of (almost) equal size — 20 frames at frame_batch 8 = 7 + 7 + 6."""
     cap = min(frame_batch, max(base, (n_frames + 2) // 3)) if frame_batch > base else frame_batch
     n_passes = (n_frames + cap - 1) // cap

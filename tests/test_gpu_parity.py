@@ -406,7 +406,8 @@ def test_1080p_accumulation_identity(mrt, gpu_ctx, dragon1080):
 @pytest.mark.parametrize("backend", ["default", "rope_only", "wide_primary_stream", "rope_primary_in_shade", "rope_bounce", "one_frame_in_flight", "eight_frames_in_flight", "one_frame_per_pass", "three_frames_per_pass", "eight_frames_per_pass",
                                      "no_primary_hint", "persistent_always", "persistent_never", "small_persistent_grid", "one_work_counter",
                                      "no_hit_lds", "no_hit_lds_static_split", "hit_lds_small_grid", "unpacked_shade", "packed_shade_one_frame_passes", "no_frame_bundle", "no_halton_table", "frame_bundle_passes_of_three", "frame_bundle_no_hint",
-                                     "stream_stride_static_split"])
+                                     "stream_stride_static_split",
+                                     "static_split_by_capacity", "static_split_one_round", "no_tail_accumulate", "unequal_passes", "no_shadow_planes", "no_throughput_chain"])
 def test_traversal_backends_agree_with_oracle(mrt, orc, gpu_ctx, backend):
     """Every path a scene or option can reach must give the oracle's image: the default (every ray on the 8-wide layout; primary rays traced inside
     shade(0)), a scene without the 8-wide layout (rope kernels for everything), the primary rays on the 8-wide stream kernel / on the rope layout
@@ -439,6 +440,13 @@ def test_traversal_backends_agree_with_oracle(mrt, orc, gpu_ctx, backend):
     if backend == "unpacked_shade": r.set_option("shade_pack", 0)          # one queue entry per thread, hit or miss (round 4's form)
     if backend == "no_hit_lds_static_split": r.set_option("persistent", 0); r.set_option("hit_lds", 0)              # the static split without them (persistent_never runs it with them: the default)
     if backend == "hit_lds_small_grid": r.set_option("persistent", 1); r.set_option("persist_chunk", 64); r.set_option("wave_slots", 96)      # few waves: a long drain phase, where idle lanes help a straggler and hand their hit to its owner
+    # options the frame driver branches on that nothing above sets
+    if backend == "static_split_by_capacity": r.set_option("persistent", 0); r.set_option("stream_even", 0)      # rays_per_wave rays each, the grid sized for the queue's capacity (default 200: twice the wave slots, an even split)
+    if backend == "static_split_one_round": r.set_option("persistent", 0); r.set_option("stream_even", 100)      # one round of waves
+    if backend == "no_tail_accumulate": r.set_option("tail_accumulate", 0); r.set_option("frame_batch", 1); r.set_option("frames_in_flight", 3)      # several passes end together, each accumulated by its own launch
+    if backend == "unequal_passes": r.set_option("equal_passes", 0); r.set_option("frame_batch", 3)          # full passes first: 3 + 2
+    if backend == "no_shadow_planes": r.set_option("shadow_planes", 0)          # the contribution queue and the read-modify-write of the sample buffer
+    if backend == "no_throughput_chain": r.set_option("throughput_chain", 0)    # bounce rays carry a throughput record
     if backend == "one_frame_in_flight": r.set_option("frames_in_flight", 1)
     if backend == "eight_frames_in_flight": r.set_option("frames_in_flight", 8)
     if backend.endswith("_per_pass"): r.set_option("frame_batch", {"one": 1, "three": 3, "eight": 8}[backend.split("_")[0]])   # default 8: 5 frames = one pass; three: 3 + 2
