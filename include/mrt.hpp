@@ -108,6 +108,11 @@ struct Scene {                                                       // Scene.sw
         lights = {light1, light3};                                   // Scene.swift:30
     }
     virtual ~Scene() = default;
+    // Stream-ordered queries of a committed MRTScene on device buffers (mrt_scene_intersect_closest_device / _any_device): n x MRTRay in, n x MRTIntersection or
+    // n x int32 out, all in device memory; hipStream is a hipStream_t taken literally (nullptr = HIP's null stream; Renderer::stream() is the context's).
+    // Nothing is allocated, copied or synchronised; keep the buffers alive until the stream has passed the call.
+    static void intersectClosestDevice(MRTScene committed, const void *deviceRays, size_t n, void *deviceOut, void *hipStream) { check(mrt_scene_intersect_closest_device(committed, deviceRays, n, deviceOut, hipStream)); }
+    static void intersectAnyDevice(MRTScene committed, const void *deviceRays, size_t n, void *deviceOccluded, void *hipStream) { check(mrt_scene_intersect_any_device(committed, deviceRays, n, deviceOccluded, hipStream)); }
     void updateUniforms(int width, int height) { camera = setupCamera(width, height); }   // Scene.swift:36-38
     static Camera setupCamera(int width, int height) { Camera c; check(mrt_default_camera(width, height, &c)); return c; }   // :40-57
     static Light setupLight() {                                      // :59-67
@@ -182,6 +187,11 @@ class Renderer {                                                     // Renderer
         updateMesh(meshId, positions.data(), normals.data(), positions.size() / 3);
     }
     void commit() { check(mrt_scene_commit(scene_)); }
+    // the committed scene's stream-ordered queries on device buffers (Scene::intersectClosestDevice) and the context's stream to order them with the draws
+    MRTScene sceneHandle() const { return scene_; }
+    void *stream() const { void *s = nullptr; check(mrt_context_get_stream(ctx_, &s)); return s; }
+    void intersectClosestDevice(const void *deviceRays, size_t n, void *deviceOut, void *hipStream) { Scene::intersectClosestDevice(scene_, deviceRays, n, deviceOut, hipStream); }
+    void intersectAnyDevice(const void *deviceRays, size_t n, void *deviceOccluded, void *hipStream) { Scene::intersectAnyDevice(scene_, deviceRays, n, deviceOccluded, hipStream); }
     // implementation knobs (mrt_abi.h): "frames_in_flight" (HIP streams, default 12), "frame_batch" (frames per pass, default 4), ...
     void setOption(const char *key, double value) { check(mrt_renderer_set_option(r_, key, value)); }
     double option(const char *key) const { double v = 0; check(mrt_renderer_get_option(r_, key, &v)); return v; }

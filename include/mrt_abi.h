@@ -175,6 +175,9 @@ int mrt_context_create(int device_id, MRTContext *out);
 int mrt_context_destroy(MRTContext ctx);
 /* Use an existing hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL = own stream */
 int mrt_context_set_stream(MRTContext ctx, void *hip_stream);
+/* The stream the context's work is enqueued on: its own, or the one mrt_context_set_stream gave it.  What a C host passes to the
+ * mrt_scene_intersect_*_device entries to have a query ordered with the context's other work.                                   */
+int mrt_context_get_stream(MRTContext ctx, void **hip_stream);
 int mrt_context_device_name(MRTContext ctx, char *buf, size_t buflen);
 
 /* ---------------------------------------------------------------- scene / geometry
@@ -234,6 +237,21 @@ int mrt_scene_instance_transform(MRTScene scene, int32_t mesh_id, float out_colm
  * (Raytracing.metal:244 closest, :367 any).  Host arrays in, host arrays out.                  */
 int mrt_scene_intersect_closest(MRTScene scene, const MRTRay *rays, size_t n, MRTIntersection *out);
 int mrt_scene_intersect_any(MRTScene scene, const MRTRay *rays, size_t n, int32_t *occluded);
+/* The same two queries on DEVICE buffers, ordered on a stream of the caller's: d_rays is n x MRTRay (32 B each), d_out n x MRTIntersection (32 B each),
+ * d_occluded n x int32, all in device memory of the scene's device.  A call enqueues its kernels on hip_stream and returns: it allocates nothing, copies
+ * nothing and synchronises neither the stream nor the device; the work runs after whatever that stream already holds.  A launch that fails is still
+ * reported (MRT_ERR_HIP).  Every record is written; a miss is {0, -1.0f, -1, -1, -1, 0, 0, 0} as the host entries write it.
+ *   hip_stream is taken literally: 0 is HIP's null stream (what torch.cuda.current_stream().cuda_stream is for torch's default stream), NOT the
+ *   context's stream — a C host that wants that one asks for it with mrt_context_get_stream.
+ *   The caller owes: buffers that stay alive until the stream has passed the call; no mrt_scene_commit of this scene while a query is in flight;
+ *   pointers on the scene's device.
+ *   Domain: finite origin and direction, 0 <= min_distance <= max_distance, max_distance may be +inf.  Inside it every field of every record has the
+ *   bits mrt_scene_intersect_closest / _any return for the same ray and scene; outside it the record is unspecified, and the call still terminates.
+ *   Which walk: rays with min_distance == 0 on a scene with the 8-wide layout take the render kernels' walk (lane refill, both levels of a two-level
+ *   scene); the others, and every ray of a scene without that layout (scene option wide = 0), take the host entries' one-ray-per-lane walk.
+ * MRT_ERR_STATE: the scene is not committed.  MRT_ERR_INVALID_ARGUMENT: NULL scene, NULL buffers with n > 0, n >= 2^31.  n == 0: MRT_OK, nothing is launched. */
+int mrt_scene_intersect_closest_device(MRTScene scene, const void *d_rays, size_t n, void *d_out, void *hip_stream);
+int mrt_scene_intersect_any_device(MRTScene scene, const void *d_rays, size_t n, void *d_occluded, void *hip_stream);
 
 /* ---------------------------------------------------------------- host-side geometry helpers
  * (no GPU needed) — the library's OBJ/MTL reader standing in for ModelIO (Model.swift:16-21,

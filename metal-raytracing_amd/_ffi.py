@@ -133,6 +133,7 @@ SIGNATURES = {
     "mrt_context_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "mrt_context_destroy": (C.c_int, [_P]),
     "mrt_context_set_stream": (C.c_int, [_P, _P]),
+    "mrt_context_get_stream": (C.c_int, [_P, C.POINTER(_P)]),
     "mrt_context_device_name": (C.c_int, [_P, C.c_char_p, _SZ]),
     "mrt_scene_create": (C.c_int, [_P, C.POINTER(_P)]),
     "mrt_scene_destroy": (C.c_int, [_P]),
@@ -150,6 +151,8 @@ SIGNATURES = {
     "mrt_scene_instance_transform": (C.c_int, [_P, _I32, _PF]),
     "mrt_scene_intersect_closest": (C.c_int, [_P, _P, _SZ, _P]),
     "mrt_scene_intersect_any": (C.c_int, [_P, _P, _SZ, _P]),
+    "mrt_scene_intersect_closest_device": (C.c_int, [_P, _P, _SZ, _P, _P]),
+    "mrt_scene_intersect_any_device": (C.c_int, [_P, _P, _SZ, _P, _P]),
     "mrt_obj_load": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "mrt_dragon_proxy": (C.c_int, [C.POINTER(_P)]),
     "mrt_dragon_proxy_irregular": (C.c_int, [C.POINTER(_P)]),

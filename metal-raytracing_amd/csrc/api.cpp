@@ -69,6 +69,11 @@ int mrt_context_set_stream(MRTContext ctx, void *hip_stream) {
     return MRT_OK;
     MRT_CATCH
 }
+int mrt_context_get_stream(MRTContext ctx, void **hip_stream) {
+    REQUIRE(ctx && hip_stream, "mrt_context_get_stream: bad argument");
+    *hip_stream = (void *)ctx->stream;
+    return MRT_OK;
+}
 int mrt_context_device_name(MRTContext ctx, char *buf, size_t buflen) {
     REQUIRE(ctx && buf && buflen, "mrt_context_device_name: bad argument");
     snprintf(buf, buflen, "%s", ctx->name);
@@ -304,6 +309,25 @@ int mrt_scene_intersect_any(MRTScene scene, const MRTRay *rays, size_t n, int32_
     if (!scene->committed) { mrt::set_error("mrt_scene_intersect_any: scene not committed"); return MRT_ERR_STATE; }
     int rc = bind_device(scene->ctx); if (rc) return rc;
     return mrt::query_any(scene->dev, scene->ctx->stream, rays, n, occluded);
+    MRT_CATCH
+}
+// The stream-ordered forms: device buffers, the caller's stream (0 = HIP's null stream), two launches and nothing else.
+static int intersect_device(const char *who, MRTScene scene, const void *d_rays, size_t n, void *d_out, void *hip_stream, bool any) {
+    if (!(scene && (n == 0 || (d_rays && d_out)))) { mrt::set_error(std::string(who) + ": bad argument"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (n >= (size_t(1) << 31)) { mrt::set_error(std::string(who) + ": too many rays (n must be below 2^31)"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (!scene->committed) { mrt::set_error(std::string(who) + ": scene not committed"); return MRT_ERR_STATE; }
+    if (n == 0) return MRT_OK;
+    int rc = bind_device(scene->ctx); if (rc) return rc;
+    return any ? mrt::query_any_device(scene->dev, (hipStream_t)hip_stream, d_rays, n, d_out) : mrt::query_closest_device(scene->dev, (hipStream_t)hip_stream, d_rays, n, d_out);
+}
+int mrt_scene_intersect_closest_device(MRTScene scene, const void *d_rays, size_t n, void *d_out, void *hip_stream) {
+    MRT_TRY
+    return intersect_device("mrt_scene_intersect_closest_device", scene, d_rays, n, d_out, hip_stream, false);
+    MRT_CATCH
+}
+int mrt_scene_intersect_any_device(MRTScene scene, const void *d_rays, size_t n, void *d_occluded, void *hip_stream) {
+    MRT_TRY
+    return intersect_device("mrt_scene_intersect_any_device", scene, d_rays, n, d_occluded, hip_stream, true);
     MRT_CATCH
 }
 

@@ -219,6 +219,9 @@ uint32_t shard_tiles(int width, int height, int rank, int world);               
 int unpack_tiles_into(float4 *image, int width, int height, const void *compact, size_t nbytes, int rank, int world, hipStream_t st);
 int query_closest(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, MRTIntersection *out);
 int query_any(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, int32_t *out);
+// the stream-ordered forms on caller device buffers: two launches on `stream`, no allocation, copy or synchronisation (renderer.hip)
+int query_closest_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_out);
+int query_any_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_occluded);
 int query_stats(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, int any, uint32_t *out4);
 int query_stream(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, int any, MRTIntersection *out);
 int query_stream_stats(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, int any, uint32_t per_wave, uint32_t *out8, size_t nwaves);

@@ -628,6 +628,61 @@ __global__ void __launch_bounds__(64) k_query_stream(SceneView s, const MRTRay *
         });
 }
 
+// ------------------------------------------------------------------ stream-ordered queries on caller buffers (mrt_scene_intersect_*_device)
+// Two launches on the caller's stream, no allocation, no copy, no synchronisation.  Every ray is answered by exactly one of them, and both decide with the same
+// expression (min_distance != 0), so every record is written exactly once whatever the rays hold:
+//   k_query_stream_device   rays with min_distance == 0 on the 8-wide layout: the render kernels' walk (traverse_wide_stream, lane refill, both levels of a two-level
+//                           scene on one stack).  Its scaled node test has tmin = 0 built in, so a ray with another min_distance enters the loop as the inert ray of a
+//                           partial-tile slot (tmax < 0 -> miss: one refill slot, no node visit) and its result is not written.
+//   k_query_lane_device     the other rays — and all rays of a scene without the 8-wide layout — one per lane with the walks of mrt_scene_intersect_closest / _any,
+//                           which carry tmin.  A lane whose ray the stream kernel answered leaves after reading min_distance.
+MRT_DEV MRTIntersection closest_record(const SceneView &s, bool two_level, bool hit, const TravHit &h) {
+    MRTIntersection o;
+    o._pad = 0; o.type = 0; o.distance = -1.0f; o.instance_id = o.geometry_id = o.primitive_id = -1; o.u = o.v = 0.0f;
+    if (hit) {
+        uint32_t inst, geom;
+        if (two_level) { inst = instance_of_gid(s, h.gid); const InstanceDev &I = s.inst[inst]; geom = s.tri_shade[I.ts_base + (h.gid - I.gid_base)].w & 0xFFFFu; }
+        else { const uint4 ts = s.tri_shade[h.gid]; inst = ts.w >> 16; geom = ts.w & 0xFFFFu; }
+        o.type = 1; o.distance = h.t; o.instance_id = (int32_t)inst; o.geometry_id = (int32_t)geom;
+        o.primitive_id = (int32_t)(h.gid - s.geom_base[inst * (uint32_t)s.max_sub + geom]);
+        o.u = h.U / h.ad; o.v = h.V / h.ad;
+    }
+    return o;
+}
+constexpr uint32_t QUERY_STREAM_RAYS = 256;      // rays per wave of the static split, as k_query_stream
+template <bool TWO_LEVEL, bool ANY>
+__global__ void __launch_bounds__(64, TWO_LEVEL ? MRT_TWO_LEVEL_WAVES : MRT_WIDE_STREAM_WAVES) k_query_stream_device(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, void *__restrict__ out) {
+    extern __shared__ uint32_t stk_dyn[];
+    const uint32_t begin = blockIdx.x * QUERY_STREAM_RAYS;
+    if (begin >= n) return;
+    traverse_wide_stream<TWO_LEVEL>(s, OneRange{begin, min(n, begin + QUERY_STREAM_RAYS)}, stk_dyn,
+        [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) {
+            const MRTRay r = rays[i]; tag = i; is_any = ANY ? 1u : 0u;
+            if (r.min_distance != 0.0f) { A = make_float4(0.0f, 0.0f, 0.0f, -1.0f); B = make_float4(0.0f, 0.0f, 1.0f, 0.0f); }      // the lane kernel's ray: inert here (tmax < 0 -> miss)
+            else { A = make_float4(r.origin[0], r.origin[1], r.origin[2], r.max_distance); B = make_float4(r.direction[0], r.direction[1], r.direction[2], 0.0f); }
+        },
+        [&](uint32_t i, bool, bool hit, const TravHit &h) {
+            if (rays[i].min_distance != 0.0f) return;
+            if (ANY) static_cast<int32_t *>(out)[i] = hit ? 1 : 0;
+            else static_cast<MRTIntersection *>(out)[i] = closest_record(s, TWO_LEVEL, hit, h);
+        });
+}
+template <bool WIDE, bool ANY>
+__global__ void __launch_bounds__(64) k_query_lane_device(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, void *__restrict__ out) {
+    extern __shared__ uint32_t stk[];      // WIDE: the scene's wide-tree depth x WIDE_STACK_LEVEL_BYTES, sized by the host
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    const bool mine = i < n && (s.num_wnodes == 0 || rays[i].min_distance != 0.0f);      // without the 8-wide layout no stream kernel ran: every ray is answered here
+    if (__ballot(mine) == 0ull) return;      // nothing for this wave: a uniform branch to the end
+    if (!mine) return;
+    const MRTRay r = rays[i];
+    TravHit h;
+    const f3 ro = mk3(r.origin[0], r.origin[1], r.origin[2]), rd = mk3(r.direction[0], r.direction[1], r.direction[2]);
+    const bool hit = s.num_inst ? traverse_instanced<ANY>(s, ro, rd, r.min_distance, r.max_distance, h)
+                   : WIDE ? traverse_wide<ANY>(s, ro, rd, r.min_distance, r.max_distance, h, stk) : traverse<ANY>(s, ro, rd, r.min_distance, r.max_distance, h);
+    if (ANY) static_cast<int32_t *>(out)[i] = hit ? 1 : 0;
+    else static_cast<MRTIntersection *>(out)[i] = closest_record(s, s.num_inst != 0, hit, h);
+}
+
 // ------------------------------------------------------------------ device-function probes
 __global__ void k_probe_halton(const int32_t *i, const int32_t *d, uint32_t n, float *out) {
     uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1618,6 +1673,25 @@ int query_stream(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, 
     MRT_HIP(hipGetLastError());
     return check_bounds_record();
 }
+
+// The stream-ordered entries (mrt_scene_intersect_closest_device / _any_device): both launches on the caller's stream, nothing else.
+template <bool ANY>
+static int query_device_t(const DeviceScene &sc, hipStream_t stream, const MRTRay *d_rays, size_t n, void *d_out) {
+    const SceneView sv = sc.view();
+    const uint32_t n32 = (uint32_t)n;
+    if (sc.num_wnodes) {
+        const size_t lds = (size_t)sc.wide_depth * WIDE_STACK_LEVEL_BYTES + (sc.num_inst ? WIDE_WORLD_RAY_BYTES : 0);
+        if (sc.num_inst) hipLaunchKernelGGL((k_query_stream_device<true, ANY>), dim3(cdiv(n, QUERY_STREAM_RAYS)), dim3(64), lds, stream, sv, d_rays, n32, d_out);
+        else hipLaunchKernelGGL((k_query_stream_device<false, ANY>), dim3(cdiv(n, QUERY_STREAM_RAYS)), dim3(64), lds, stream, sv, d_rays, n32, d_out);
+        MRT_HIP(hipGetLastError());
+    }
+    if (sc.num_wnodes) hipLaunchKernelGGL((k_query_lane_device<true, ANY>), dim3(cdiv(n, 64)), dim3(64), (size_t)sc.wide_depth * WIDE_STACK_LEVEL_BYTES, stream, sv, d_rays, n32, d_out);
+    else hipLaunchKernelGGL((k_query_lane_device<false, ANY>), dim3(cdiv(n, 64)), dim3(64), 0, stream, sv, d_rays, n32, d_out);
+    MRT_HIP(hipGetLastError());
+    return MRT_OK;
+}
+int query_closest_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_out) { return query_device_t<false>(sc, stream, static_cast<const MRTRay *>(d_rays), n, d_out); }
+int query_any_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_occluded) { return query_device_t<true>(sc, stream, static_cast<const MRTRay *>(d_rays), n, d_occluded); }
 
 int probe_halton(hipStream_t stream, const int32_t *i, const int32_t *d, size_t n, float *out) {
     if (n == 0) return MRT_OK;

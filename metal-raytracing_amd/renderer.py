@@ -31,6 +31,13 @@ class Context:
     def set_stream(self, hip_stream):
         check(lib.mrt_context_set_stream(self.handle, C.c_void_p(hip_stream) if hip_stream else None))
 
+    @property
+    def stream(self):
+        """The hipStream_t handle (an int) the context's work is enqueued on: its own, or the one set_stream gave it."""
+        s = C.c_void_p()
+        check(lib.mrt_context_get_stream(self.handle, C.byref(s)))
+        return s.value or 0
+
     def close(self):
         if self.handle:
             lib.mrt_context_destroy(self.handle)
@@ -115,6 +122,37 @@ class DeviceScene:
         check(lib.mrt_debug_intersect_stream(self.handle, ptr(rays), rays.shape[0], 1 if any_hit else 0, ptr(out)))
         return out
 
+    def _device_query(self, fn, rays, out, stream, out_shape):
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        if not isinstance(rays, torch.Tensor) or rays.device != dev:
+            raise ValueError(f"rays must be a torch tensor on {dev}")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("rays must be a contiguous torch.float32 tensor of shape (n, 8): [ox, oy, oz, tmin, dx, dy, dz, tmax]")
+        shape = (rays.shape[0], *out_shape)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous torch.int32 tensor of shape {shape} on {dev}")
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        elif isinstance(stream, torch.cuda.Stream):
+            stream = stream.cuda_stream
+        n = rays.shape[0]
+        check(fn(self.handle, C.c_void_p(rays.data_ptr() if n else None), n, C.c_void_p(out.data_ptr() if n else None), C.c_void_p(int(stream))))
+        return out
+
+    def intersect_closest_device(self, rays, out=None, stream=None):
+        """Closest hits of rays that live on the GPU, ordered on a stream: rays is a contiguous torch.float32 (n, 8) tensor on the context's device
+        ([ox, oy, oz, tmin, dx, dy, dz, tmax]); returns torch.int32 (n, 8), one MRTIntersection per row (unpack_intersections gives the fields).  Nothing is
+        allocated (but `out` when it is None), copied or synchronised.  stream: None = torch's current stream of that device; an integer handle (0 = the
+        null stream) or a torch.cuda.Stream.  Keep rays and out alive until the stream has passed the call."""
+        return self._device_query(lib.mrt_scene_intersect_closest_device, rays, out, stream, (8,))
+
+    def intersect_any_device(self, rays, out=None, stream=None):
+        """Any-hit form of intersect_closest_device: torch.int32 (n,), 1 = occluded."""
+        return self._device_query(lib.mrt_scene_intersect_any_device, rays, out, stream, ())
+
     def traversal_stats(self, rays, any_hit=False, alu_dup=0, mem_dup=0):
         """Diagnostics: (n, 8) uint32 {node visits, leaf visits, triangle tests, hit gid, t0, t1, 0, 0} per ray."""
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
@@ -159,6 +197,13 @@ class DeviceScene:
 
 INTERSECTION_DTYPE = np.dtype([("type", np.int32), ("distance", np.float32), ("instance_id", np.int32), ("geometry_id", np.int32),
                                ("primitive_id", np.int32), ("u", np.float32), ("v", np.float32), ("_pad", np.int32)])
+
+
+def unpack_intersections(t):
+    """Views of the fields of a torch.int32 (n, 8) tensor of MRTIntersection records (DeviceScene.intersect_closest_device): no copy."""
+    import torch
+    return {"type": t[:, 0], "distance": t[:, 1].view(torch.float32), "instance_id": t[:, 2], "geometry_id": t[:, 3], "primitive_id": t[:, 4],
+            "u": t[:, 5].view(torch.float32), "v": t[:, 6].view(torch.float32)}
 
 
 class Renderer:
