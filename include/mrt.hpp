@@ -113,6 +113,13 @@ struct Scene {                                                       // Scene.sw
     // Nothing is allocated, copied or synchronised; keep the buffers alive until the stream has passed the call.
     static void intersectClosestDevice(MRTScene committed, const void *deviceRays, size_t n, void *deviceOut, void *hipStream) { check(mrt_scene_intersect_closest_device(committed, deviceRays, n, deviceOut, hipStream)); }
     static void intersectAnyDevice(MRTScene committed, const void *deviceRays, size_t n, void *deviceOccluded, void *hipStream) { check(mrt_scene_intersect_any_device(committed, deviceRays, n, deviceOccluded, hipStream)); }
+    // Stream-ordered deformation of a committed flattened MRTScene (mrt_scene_update_mesh_device / mrt_scene_refit_device): strided float3 positions and normals in device
+    // memory replace one mesh's vertices, then the resident tree is refitted, all on hipStream; updatesRejected() blocks and counts the updates refused for a NaN or an infinity.
+    static void updateMeshDevice(MRTScene committed, int32_t meshId, const void *devicePositions, size_t positionStrideBytes, const void *deviceNormals, size_t normalStrideBytes, size_t vertexCount, void *hipStream) {
+        check(mrt_scene_update_mesh_device(committed, meshId, devicePositions, positionStrideBytes, deviceNormals, normalStrideBytes, vertexCount, hipStream));
+    }
+    static void refitDevice(MRTScene committed, void *hipStream) { check(mrt_scene_refit_device(committed, hipStream)); }
+    static uint64_t deviceUpdatesRejected(MRTScene scene) { uint64_t n = 0; check(mrt_scene_device_updates_rejected(scene, &n)); return n; }
     void updateUniforms(int width, int height) { camera = setupCamera(width, height); }   // Scene.swift:36-38
     static Camera setupCamera(int width, int height) { Camera c; check(mrt_default_camera(width, height, &c)); return c; }   // :40-57
     static Light setupLight() {                                      // :59-67
@@ -192,6 +199,12 @@ class Renderer {                                                     // Renderer
     void *stream() const { void *s = nullptr; check(mrt_context_get_stream(ctx_, &s)); return s; }
     void intersectClosestDevice(const void *deviceRays, size_t n, void *deviceOut, void *hipStream) { Scene::intersectClosestDevice(scene_, deviceRays, n, deviceOut, hipStream); }
     void intersectAnyDevice(const void *deviceRays, size_t n, void *deviceOccluded, void *hipStream) { Scene::intersectAnyDevice(scene_, deviceRays, n, deviceOccluded, hipStream); }
+    // deformation from device buffers on a stream (Scene::updateMeshDevice): packed or strided float3 rows; refitDevice() after one or more updates
+    void updateMeshDevice(int32_t meshId, const void *devicePositions, size_t positionStrideBytes, const void *deviceNormals, size_t normalStrideBytes, size_t vertexCount, void *hipStream) {
+        Scene::updateMeshDevice(scene_, meshId, devicePositions, positionStrideBytes, deviceNormals, normalStrideBytes, vertexCount, hipStream);
+    }
+    void refitDevice(void *hipStream) { Scene::refitDevice(scene_, hipStream); }
+    uint64_t deviceUpdatesRejected() const { return Scene::deviceUpdatesRejected(scene_); }
     // implementation knobs (mrt_abi.h): "frames_in_flight" (HIP streams, default 12), "frame_batch" (frames per pass, default 4), ...
     void setOption(const char *key, double value) { check(mrt_renderer_set_option(r_, key, value)); }
     double option(const char *key) const { double v = 0; check(mrt_renderer_get_option(r_, key, &v)); return v; }

@@ -252,6 +252,29 @@ int mrt_scene_intersect_any(MRTScene scene, const MRTRay *rays, size_t n, int32_
  * MRT_ERR_STATE: the scene is not committed.  MRT_ERR_INVALID_ARGUMENT: NULL scene, NULL buffers with n > 0, n >= 2^31.  n == 0: MRT_OK, nothing is launched. */
 int mrt_scene_intersect_closest_device(MRTScene scene, const void *d_rays, size_t n, void *d_out, void *hip_stream);
 int mrt_scene_intersect_any_device(MRTScene scene, const void *d_rays, size_t n, void *d_occluded, void *hip_stream);
+/* Deforming geometry from DEVICE buffers, ordered on a stream of the caller's: the other half of the loop "move vertices -> refit -> query or draw" on one stream.
+ * mrt_scene_update_mesh_device replaces the vertices of one mesh of a COMMITTED flattened scene with vertex_count strided float3 positions and normals read from
+ * device memory (strides >= 12, multiples of 4: a row of a torch view of 16 or 32 bytes is fine; 4-byte aligned pointers), in every flattened instance of that mesh;
+ * mrt_scene_refit_device then refits whatever layouts are resident (the 8-wide tree, the rope layout, or both) exactly as the commit after mrt_scene_update_mesh does:
+ * same kernels, same tree, same bits.  Several updates may precede one refit.  Both calls enqueue kernels on hip_stream (taken literally, as the query entries above
+ * take it: 0 is HIP's null stream) and return.  The FIRST update or refit after a build creates the scene's refit workspace (about 80 B per triangle + 32 B per 8-wide
+ * node; it allocates and may block) and keeps it until the next build or mrt_scene_destroy; every later call allocates nothing, copies nothing from host memory and
+ * synchronises neither the stream nor the device.
+ *   Validation happens on the device: a call whose positions or normals hold a NaN or an infinity writes NOTHING (the scene goes on answering with what it had, as
+ *   mrt_scene_update_mesh promises) and is counted; mrt_scene_device_updates_rejected reads that count (it blocks until the calls enqueued so far have run).
+ *   The caller owes: buffers that stay alive until the stream has passed the call; pointers on the scene's device; no query, draw or commit of this scene in flight on
+ *   ANOTHER stream unless the caller has ordered it behind the refit (work on hip_stream itself is ordered by the stream; the renderer draws on the context's stream
+ *   and on streams of its own: wait for the refit, or hand the context's stream to both, before drawing).
+ *   The host side stays truthful: mrt_scene_stats (which then blocks on the last refit) reports refits, wide_cost, sah_cost, leaf_growth and build_ms as the host path
+ *   would; a later mrt_scene_commit builds or refits from the vertices the device holds (it reads them back first; an update that no mrt_scene_refit_device followed
+ *   counts as a vertex change, so a commit with nothing else changed refits); mrt_scene_update_mesh on such a mesh simply replaces them.  Scene option "refit_max_cost_ratio" is NOT acted on here — that would take a read-back; the statistics carry the signal and the next mrt_scene_commit may act.
+ * MRT_ERR_STATE: the scene is not committed, or host-side changes wait for a commit.  MRT_ERR_INVALID_ARGUMENT: NULL scene, NULL or misaligned buffers, bad strides,
+ * mesh_id out of range or an instance (update its source), vertex_count other than the mesh's.  MRT_ERR_UNSUPPORTED: a two-level scene (instancing = 1), scene option
+ * refit = 0, or a resident tree the refit cannot take (an empty scene).                                                                                              */
+int mrt_scene_update_mesh_device(MRTScene scene, int32_t mesh_id, const void *d_positions, size_t pos_stride_bytes,
+                                 const void *d_normals, size_t nrm_stride_bytes, size_t vertex_count, void *hip_stream);
+int mrt_scene_refit_device(MRTScene scene, void *hip_stream);
+int mrt_scene_device_updates_rejected(MRTScene scene, uint64_t *count);
 
 /* ---------------------------------------------------------------- host-side geometry helpers
  * (no GPU needed) — the library's OBJ/MTL reader standing in for ModelIO (Model.swift:16-21,

@@ -23,6 +23,26 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line) {
 
 static int bind_device(MRTContext ctx) { MRT_HIP(hipSetDevice(ctx->device)); return MRT_OK; }
 
+// HostMesh copies brought up to date (download_stale_meshes).  A mesh updated on the device and never refitted there is a vertex change like mrt_scene_update_mesh's: where nothing
+// else changed since the commit, the next commit refits instead of building.
+static int sync_host_meshes(MRTScene scene) {
+    bool pending = false;
+    int rc = mrt::download_stale_meshes(scene->meshes, scene->dev, &pending);
+    if (!rc && pending && scene->committed) scene->only_vertices_changed = true;
+    return rc;
+}
+
+// The meshes' host copies as the device has them now (a scene whose vertices were replaced by mrt_scene_update_mesh_device): for readers of MRTScene_::meshes outside this file.
+// Leaves the calling thread's current device as it found it.
+int mrt_scene_sync_host_meshes(MRTScene scene) {
+    if (!scene->dev.refit_ws) return MRT_OK;
+    int before = 0; MRT_HIP(hipGetDevice(&before));
+    int rc = bind_device(scene->ctx);
+    if (!rc) rc = sync_host_meshes(scene);
+    (void)hipSetDevice(before);
+    return rc;
+}
+
 extern "C" {
 
 const char *mrt_last_error(void) { return mrt::g_err.c_str(); }
@@ -231,6 +251,10 @@ int mrt_scene_commit(MRTScene scene) {
     MRT_TRY
     REQUIRE(scene, "mrt_scene_commit: scene is NULL");
     int rc = bind_device(scene->ctx); if (rc) return rc;
+    // vertices replaced on the device since the last commit (mrt_scene_update_mesh_device): the statistics of those refits are read first (a refit below chains on them), then the
+    // meshes' host copies, which everything below reads, are brought up to date
+    rc = mrt::resolve_device_refits(scene->dev, scene->opt, scene->ctx->stream); if (rc) return rc;
+    rc = sync_host_meshes(scene); if (rc) return rc;
     if (scene->only_transforms_changed && scene->opt.instancing && scene->dev.num_inst == scene->meshes.size())
         rc = mrt::update_tlas(scene->meshes, scene->ctx->stream, scene->dev);         // instance rows + TLAS; the BLASes stay (the refit of an animated scene)
     else if (scene->only_vertices_changed && scene->opt.instancing && scene->opt.refit && (rc = mrt::refit_two_level(scene->meshes, scene->opt, scene->ctx->stream, scene->dev)) != MRT_ERR_UNSUPPORTED) {}      // the changed meshes' BLASes refitted in place + the TLAS
@@ -238,6 +262,10 @@ int mrt_scene_commit(MRTScene scene) {
     if (rc) return rc;
     scene->only_transforms_changed = false; scene->only_vertices_changed = false;
     for (auto &m : scene->meshes) m.dirty = false;
+    if (scene->dev.refit_ws) {          // a refit kept the tree and with it the workspace of the stream-ordered refit: its chained leaf_growth goes on from this commit's, its dirty marks are spent
+        MRT_HIP(hipMemcpy(scene->dev.refit_ws->leaf_growth.p, &scene->dev.stats.leaf_growth, 4, hipMemcpyHostToDevice));
+        MRT_HIP(hipMemset(scene->dev.refit_ws->inst_dirty.p, 0, scene->dev.refit_ws->inst_dirty.bytes()));
+    }
     rc = mrt::upload_lights(scene->lights.data(), (int)scene->lights.size(), scene->ctx->stream, scene->dev); if (rc) return rc;
     scene->committed = true;
     return MRT_OK;
@@ -257,6 +285,7 @@ int mrt_scene_update_mesh(MRTScene scene, int32_t mesh_id, const float *position
         const float *n = (const float *)((const char *)normals + i * nrm_stride);
         for (int k = 0; k < 3; k++) { m.positions[i * 3 + k] = p[k]; m.normals[i * 3 + k] = n[k]; }
     }
+    if (scene->dev.refit_ws && (size_t)mesh_id < scene->dev.refit_ws->host_stale.size()) scene->dev.refit_ws->host_stale[(size_t)mesh_id] = 0;      // (replaced on the device before: this copy is the newer one now)
     // a committed scene in which nothing else changes until the next commit keeps its tree: that commit refits (flattened scenes with the 8-wide layout; others build again)
     m.dirty = true;
     if (scene->committed) scene->only_vertices_changed = true;                         // the first change since the commit
@@ -284,6 +313,10 @@ int mrt_scene_set_instance_transform(MRTScene scene, int32_t mesh_id, const floa
 int mrt_scene_stats(MRTScene scene, MRTSceneStats *out) {
     REQUIRE(scene && out, "mrt_scene_stats: bad argument");
     if (!scene->committed) { mrt::set_error("mrt_scene_stats: scene not committed"); return MRT_ERR_STATE; }
+    if (scene->dev.refit_ws && scene->dev.refit_ws->unresolved) {          // refits enqueued by mrt_scene_refit_device: wait for the last one and read what it left (the only place this blocks)
+        int rc = bind_device(scene->ctx); if (rc) return rc;
+        rc = mrt::resolve_device_refits(scene->dev, scene->opt, scene->ctx->stream); if (rc) return rc;
+    }
     *out = scene->dev.stats;
     out->wide_layout = scene->dev.num_wnodes > 0 ? 1 : 0; out->wide_depth = scene->dev.wide_depth;
     return MRT_OK;
@@ -328,6 +361,46 @@ int mrt_scene_intersect_closest_device(MRTScene scene, const void *d_rays, size_
 int mrt_scene_intersect_any_device(MRTScene scene, const void *d_rays, size_t n, void *d_occluded, void *hip_stream) {
     MRT_TRY
     return intersect_device("mrt_scene_intersect_any_device", scene, d_rays, n, d_occluded, hip_stream, true);
+    MRT_CATCH
+}
+
+// The stream-ordered refit: vertices from device buffers, the refit kernels on the caller's stream (0 = HIP's null stream), nothing of the host in between.
+static int device_refit_prologue(const char *who, MRTScene scene) {
+    if (!scene) { mrt::set_error(std::string(who) + ": scene is NULL"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (!scene->committed) {
+        mrt::set_error(std::string(who) + (scene->only_vertices_changed || scene->only_transforms_changed ? ": host-side changes are pending (mrt_scene_commit first)" : ": scene not committed"));
+        return MRT_ERR_STATE;
+    }
+    if (int rc = mrt::device_refit_supported(scene->dev, scene->opt, who)) return rc;
+    return bind_device(scene->ctx);
+}
+int mrt_scene_update_mesh_device(MRTScene scene, int32_t mesh_id, const void *d_positions, size_t pos_stride, const void *d_normals, size_t nrm_stride, size_t nverts, void *hip_stream) {
+    MRT_TRY
+    const char *who = "mrt_scene_update_mesh_device";
+    if (int rc = device_refit_prologue(who, scene)) return rc;
+    REQUIRE(d_positions && d_normals, "mrt_scene_update_mesh_device: NULL buffers");
+    REQUIRE(mesh_id >= 0 && (size_t)mesh_id < scene->meshes.size(), "mrt_scene_update_mesh_device: mesh_id out of range");
+    REQUIRE(pos_stride >= 12 && nrm_stride >= 12 && pos_stride % 4 == 0 && nrm_stride % 4 == 0, "mrt_scene_update_mesh_device: strides must be multiples of 4 and >= 12");
+    REQUIRE((uintptr_t)d_positions % 4 == 0 && (uintptr_t)d_normals % 4 == 0, "mrt_scene_update_mesh_device: buffers must be 4-byte aligned");
+    const mrt::HostMesh &m = scene->meshes[(size_t)mesh_id];
+    REQUIRE(m.source < 0, "mrt_scene_update_mesh_device: an instance has no vertices of its own (update its source mesh)");
+    REQUIRE(nverts * 3 == m.positions.size(), "mrt_scene_update_mesh_device: the vertex count must stay the same (the topology is kept)");
+    if (int rc = mrt::device_refit_prepare(scene->meshes, scene->opt, scene->dev)) return rc;          // (the first call after a build allocates the workspace; later ones find it)
+    return mrt::device_update_mesh(scene->dev, (size_t)mesh_id, d_positions, pos_stride, d_normals, nrm_stride, nverts, (hipStream_t)hip_stream);
+    MRT_CATCH
+}
+int mrt_scene_refit_device(MRTScene scene, void *hip_stream) {
+    MRT_TRY
+    if (int rc = device_refit_prologue("mrt_scene_refit_device", scene)) return rc;
+    if (int rc = mrt::device_refit_prepare(scene->meshes, scene->opt, scene->dev)) return rc;
+    return mrt::device_refit(scene->dev, (hipStream_t)hip_stream);
+    MRT_CATCH
+}
+int mrt_scene_device_updates_rejected(MRTScene scene, uint64_t *count) {
+    MRT_TRY
+    REQUIRE(scene && count, "mrt_scene_device_updates_rejected: bad argument");
+    int rc = bind_device(scene->ctx); if (rc) return rc;
+    return mrt::device_updates_rejected(scene->dev, count);
     MRT_CATCH
 }
 

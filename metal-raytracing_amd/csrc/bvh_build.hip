@@ -1097,21 +1097,62 @@ __global__ void k_wide_histogram(const float4 *__restrict__ wnodes, uint32_t n, 
     atomicAdd(&out[inner + leaves], 1u); atomicAdd(&out[9], inner); atomicAdd(&out[10], leaves); atomicAdd(&out[11], tris);
 }
 
+// ------------------------------------------------------------------ vertices from device memory (mrt_scene_update_mesh_device)
+// What mrt_scene_update_mesh checks on the host — no NaN, no infinity in a position or a normal — cannot be known here before the whole input is read, and a call whose input
+// fails it must change nothing.  So a call is TWO launches on the caller's stream: k_ingest_check reads everything and notes the call's sequence number in words[0] when it
+// finds such a value; k_ingest_write, behind it in stream order (the kernel boundary is the grid-wide decision: every store of the first launch is visible to the second),
+// writes only when the word does not name this call.  One launch with a grid barrier would save the second read of the input (it comes from L2 for all but the largest
+// meshes) at the price of a co-resident grid and a spin; the sequence number instead of a flag means the word is never cleared, so calls queue up without a memset between them.
+__device__ __forceinline__ uint32_t not_finite(uint32_t bits) { return ((bits & 0x7F800000u) + 0x00800000u) >> 31; }      // exponent all ones (all_finite, api.cpp)
+__global__ void k_ingest_check(const uint8_t *__restrict__ pos, size_t pos_stride, const uint8_t *__restrict__ nrm, size_t nrm_stride, uint32_t nv, uint32_t seq, uint32_t *__restrict__ words) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t bad = 0;
+    if (v < nv) {
+        const uint32_t *p = reinterpret_cast<const uint32_t *>(pos + (size_t)v * pos_stride), *n = reinterpret_cast<const uint32_t *>(nrm + (size_t)v * nrm_stride);
+        for (int k = 0; k < 3; k++) bad |= not_finite(p[k]) | not_finite(n[k]);
+    }
+    if (__ballot(bad != 0u) != 0ull && (threadIdx.x & 63u) == 0u) atomicExch(&words[0], seq);      // (every wave that finds one writes the same value)
+}
+// Every flattened instance of the mesh has its own vertex range in g_pos / normals (build_flat): all of them take the new vertices and are marked dirty.
+__global__ void k_ingest_write(const uint8_t *__restrict__ pos, size_t pos_stride, const uint8_t *__restrict__ nrm, size_t nrm_stride, uint32_t nv, uint32_t seq, const uint32_t *words,
+                               unsigned long long *__restrict__ rejected, const uint2 *__restrict__ refs, uint32_t nrefs, float *__restrict__ g_pos, float4 *__restrict__ normals, uint8_t *__restrict__ inst_dirty) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (words[0] == seq) { if (v == 0u) atomicAdd(rejected, 1ull); return; }      // the scene keeps what it had; the caller learns of it from mrt_scene_device_updates_rejected
+    if (v >= nv) return;
+    const float *p = reinterpret_cast<const float *>(pos + (size_t)v * pos_stride), *n = reinterpret_cast<const float *>(nrm + (size_t)v * nrm_stride);
+    const float px = p[0], py = p[1], pz = p[2];
+    const float4 n4 = make_float4(n[0], n[1], n[2], 0.0f);
+    for (uint32_t r = 0; r < nrefs; r++) {
+        const uint2 e = refs[r];
+        const size_t d = (size_t)e.y + v;
+        g_pos[3 * d] = px; g_pos[3 * d + 1] = py; g_pos[3 * d + 2] = pz;
+        normals[d] = n4;
+        if (v == 0u) inst_dirty[e.x] = 1;
+    }
+}
+// end of a stream-ordered refit: this refit's growth sums into the chained leaf_growth (build_flat's host arithmetic, the same operations in the same precision), sums cleared
+__global__ void k_refit_fold(double *__restrict__ growth, float *__restrict__ leaf_growth) {
+    if (blockIdx.x != 0u || threadIdx.x != 0u) return;
+    const double g0 = growth[0], g1 = growth[1];
+    *leaf_growth = *leaf_growth * (g0 > 0.0 ? (float)(g1 / g0) : 1.0f);
+    growth[0] = 0.0; growth[1] = 0.0;
+}
+
 }  // namespace
 
 // cost of the subtree of 8-wide nodes [first, first + count) rooted at `root`, per unit of the root's area: (c_node x area(root) + k_wide_cost's sum) / area(root).  Blocks.
-int wide_tree_cost(const float4 *wnodes, uint32_t first, uint32_t count, uint32_t root, float c_node, float c_tri, hipStream_t stream, float *out) {
+int wide_tree_cost(const float4 *wnodes, uint32_t first, uint32_t count, uint32_t root, float c_node, float c_tri, hipStream_t stream, void *scratch32, float *out) {
     *out = 0.0f;
     if (count == 0) return MRT_OK;
-    DevBuf<double> d_sum; DevBuf<uint32_t> d_box;
-    MRT_HIP(d_sum.alloc(1)); MRT_HIP(d_box.alloc(6));
+    // (its 8 + 24 bytes are the caller's — a piece of the build's arena or of the scene's refit workspace: a hipMalloc / hipFree pair of its own cost more than the kernel, and hipFree waits for the device)
+    double *const d_sum = static_cast<double *>(scratch32); uint32_t *const d_box = reinterpret_cast<uint32_t *>(d_sum + 1);
     const uint32_t init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
-    MRT_HIP(hipMemsetAsync(d_sum.p, 0, 8, stream));
-    MRT_HIP(hipMemcpyAsync(d_box.p, init, sizeof init, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_wide_cost, dim3(cdiv(count, 256)), dim3(256), 0, stream, wnodes, first, count, root, c_node, c_tri, d_sum.p, d_box.p);
+    MRT_HIP(hipMemsetAsync(d_sum, 0, 8, stream));
+    MRT_HIP(hipMemcpyAsync(d_box, init, sizeof init, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_wide_cost, dim3(cdiv(count, 256)), dim3(256), 0, stream, wnodes, first, count, root, c_node, c_tri, d_sum, d_box);
     double h_sum = 0.0; uint32_t h_box[6];
-    MRT_HIP(hipMemcpyAsync(&h_sum, d_sum.p, 8, hipMemcpyDeviceToHost, stream));
-    MRT_HIP(hipMemcpyAsync(h_box, d_box.p, sizeof h_box, hipMemcpyDeviceToHost, stream));
+    MRT_HIP(hipMemcpyAsync(&h_sum, d_sum, 8, hipMemcpyDeviceToHost, stream));
+    MRT_HIP(hipMemcpyAsync(h_box, d_box, sizeof h_box, hipMemcpyDeviceToHost, stream));
     MRT_HIP(hipStreamSynchronize(stream));
     MRT_HIP(hipGetLastError());
     float b[6];
@@ -1255,9 +1296,17 @@ void pack_material(const MRTMaterial &m, float4 *out3) {
     out3[2] = make_float4(m.emission.x, m.emission.y, m.emission.z, m.refractionIndex);
 }
 
+// which of the resident layouts a refit works on: the one predicate of build_flat's refit branch and of the stream-ordered refit (which keeps the answer in its workspace)
+RefitLayouts refit_layouts(const DeviceScene &sc, const BuildOptions &opt) {
+    RefitLayouts l;
+    l.wide = opt.wide && sc.num_wnodes != 0 && sc.wnodes.p && sc.wpackets.p && !sc.wide_levels.empty();
+    l.rope = sc.nodes.p != nullptr && sc.rope_nodes != 0;
+    return l;
+}
+
 int build_scene(const std::vector<HostMesh> &meshes_in, const BuildOptions &opt, hipStream_t stream, DeviceScene &out, bool only_transforms_changed, bool only_vertices_changed) {
     out.validate = opt.validate != 0;
-    if (opt.instancing) return build_two_level(meshes_in, opt, stream, out);
+    if (opt.instancing) { drop_refit_workspace(out); return build_two_level(meshes_in, opt, stream, out); }
     out.num_inst = 0; out.inst.release(); out.tlas_index.release(); out.wtlas_index.release(); out.tri_packet.release(); out.inst_box.release(); out.tlas_wcap = 0; out.blas_wdepth = 0; out.bnodes.release(); out.h_inst.clear();
     // an instance (mrt_scene_add_instance) takes its geometry from its source mesh; flattening gives every instance its own world-space copy
     std::vector<MeshRef> refs;
@@ -1365,10 +1414,11 @@ int build_flat(const std::vector<MeshRef> &refs, const BuildOptions &opt_in, hip
     run_tasks(tasks, task_bytes);
     // a refit keeps the tree (and what the statistics say about it): same triangle count as the build that made the layouts — the 8-wide one, the rope one (scene option rope = 1, or a
     // scene built without the 8-wide layout), or both: whatever is resident is refitted
-    const bool wide_there = opt.wide && out.num_wnodes != 0 && out.wnodes.p && out.wpackets.p && !out.wide_levels.empty(), rope_there = out.nodes.p != nullptr && out.rope_nodes != 0;
+    const RefitLayouts there = refit_layouts(out, opt);
+    const bool wide_there = there.wide, rope_there = there.rope;
     const bool do_refit = refit && out.refit_triangles == T && T != 0 && (wide_there || rope_there) && (wide_there || !opt.wide);
     const MRTSceneStats stats_before = out.stats;
-    if (!do_refit) { out.wide_levels.clear(); out.refit_triangles = 0; out.refits = 0; }
+    if (!do_refit) { out.wide_levels.clear(); out.refit_triangles = 0; out.refits = 0; drop_refit_workspace(out); }
     out.stats = MRTSceneStats{};
     out.stats.triangles = T; out.stats.vertices = V; out.stats.instances = (int32_t)I; out.stats.max_submeshes = max_sub;
     out.stats.max_leaf_tris = opt.max_leaf;
@@ -1418,6 +1468,7 @@ int build_flat(const std::vector<MeshRef> &refs, const BuildOptions &opt_in, hip
     static_assert(sizeof(SubRec) == 24, "SubRec is six 32-bit words");
     MRT_HIP(tri_world.alloc_in(arena, 3 * (size_t)T32)); MRT_HIP(tri_lo.alloc_in(arena, T32)); MRT_HIP(tri_hi.alloc_in(arena, T32));
     MRT_HIP(cbounds.alloc_in(arena, 6)); MRT_HIP(stat.alloc_in(arena, 4));
+    DevBuf<double> cost_words; MRT_HIP(cost_words.alloc_in(arena, 4));          // wide_tree_cost's sum and root box
 
     struct EventPair {           // destroyed on every return path
         hipEvent_t a = nullptr, b = nullptr;
@@ -1479,7 +1530,7 @@ int build_flat(const std::vector<MeshRef> &refs, const BuildOptions &opt_in, hip
         out.stats = stats_before;          // the tree's shape, and what was measured on it
         out.stats.build_ms = ms;
         // what the refit did to the tree: the 8-wide tree's cost as it lies now against the build's (MRTSceneStats.wide_cost / wide_cost_built); sah_cost — the build's binary-tree figure — scaled alike
-        if (wide_there) { if (int rc = wide_tree_cost(out.wnodes.p, 0, out.num_wnodes, 0, opt.wide_cost_node, opt.wide_cost_tri, stream, &out.stats.wide_cost)) return rc; }
+        if (wide_there) { if (int rc = wide_tree_cost(out.wnodes.p, 0, out.num_wnodes, 0, opt.wide_cost_node, opt.wide_cost_tri, stream, cost_words.p, &out.stats.wide_cost)) return rc; }
         if (out.stats.wide_cost_built > 0.0f) out.stats.sah_cost = out.sah_cost_built * (out.stats.wide_cost / out.stats.wide_cost_built);
         out.stats.refits = out.refits + 1;
         // the moved meshes' leaf boxes against what they were before this refit, chained over the refits since the build: the view-independent cost above hardly moves when a small,
@@ -1698,7 +1749,7 @@ int build_flat(const std::vector<MeshRef> &refs, const BuildOptions &opt_in, hip
         out.wide_depth = depth;
         out.wide_levels.assign(h_lv.begin(), h_lv.begin() + depth); out.refit_triangles = T;
         if (depth <= WIDE_STACK_MAX && total < (1u << 24)) out.num_wnodes = total;
-        if (int rc = wide_tree_cost(out.wnodes.p, 0, total, 0, opt.wide_cost_node, opt.wide_cost_tri, stream, &out.stats.wide_cost)) return rc;
+        if (int rc = wide_tree_cost(out.wnodes.p, 0, total, 0, opt.wide_cost_node, opt.wide_cost_tri, stream, cost_words.p, &out.stats.wide_cost)) return rc;
         out.stats.wide_cost_built = out.stats.wide_cost; out.sah_cost_built = out.stats.sah_cost; out.stats.leaf_growth = 1.0f;       // deeper than any LDS stack the kernels are launched with (or child_base beyond its 24 stack bits): the rope backend, reported by MRTSceneStats::wide_layout = 0
         out.stats.scene_bytes += (uint64_t)total * 16 * WNODE_STRIDE + (uint64_t)n * 48;
         out.stats.bvh_nodes = out.num_wnodes ? total : h_size;
@@ -1727,6 +1778,180 @@ int build_flat(const std::vector<MeshRef> &refs, const BuildOptions &opt_in, hip
         out.stats.scene_bytes += (uint64_t)h_size * 64 + (uint64_t)n * 48;
     }
     out.commit_ms[4] = since(tw4);
+    return MRT_OK;
+}
+
+// ------------------------------------------------------------------ the stream-ordered refit (mrt_scene_update_mesh_device / mrt_scene_refit_device)
+// build_flat's refit branch with nothing of the host in it: the vertices are already in g_pos / normals (k_ingest_write), the dirty bytes already on the device, the scratch the
+// scene's own (RefitWorkspace), the launch parameters of every level from the host's wide_levels.  What the blocking path reads back at once — the growth sums, the root box,
+// the event pair, the tree's cost — stays on the device until somebody asks (resolve_device_refits).
+int device_refit_supported(const DeviceScene &sc, const BuildOptions &opt, const char *who) {
+    const uint64_t T = sc.stats.triangles;
+    const RefitLayouts there = refit_layouts(sc, opt);
+    const bool wide_there = there.wide, rope_there = there.rope;
+    const char *why = nullptr;
+    if (opt.instancing || sc.num_inst) why = "two-level scenes (instancing = 1) are not refitted from device buffers: their instance boxes are computed on the host";
+    else if (!opt.refit) why = "scene option refit = 0: every change builds the tree again (mrt_scene_update_mesh + mrt_scene_commit)";
+    else if (T == 0 || sc.refit_triangles != T || !(wide_there || rope_there) || !(wide_there || !opt.wide) || !sc.g_pos.p || !sc.g_idx.p || !sc.g_recs.p || !sc.normals.p || !sc.tri_shade.p)
+        why = "the resident tree cannot be refitted (an empty scene, or one that lost its 8-wide layout): mrt_scene_update_mesh + mrt_scene_commit builds it";
+    if (!why) return MRT_OK;
+    set_error(std::string(who) + ": " + why);
+    return MRT_ERR_UNSUPPORTED;
+}
+
+void drop_refit_workspace(DeviceScene &sc) {
+    if (!sc.refit_ws) return;
+    uint64_t n = 0;
+    if (device_updates_rejected(sc, &n) == MRT_OK) sc.rejected_before = n; else (void)hipGetLastError();
+    sc.refit_ws.reset();
+}
+
+int device_updates_rejected(DeviceScene &sc, uint64_t *count) {
+    *count = sc.rejected_before;
+    if (!sc.refit_ws) return MRT_OK;
+    RefitWorkspace &ws = *sc.refit_ws;
+    unsigned long long h = 0;
+    MRT_HIP(hipEventSynchronize(ws.ev_last));
+    MRT_HIP(hipMemcpy(&h, ws.rejected.p, 8, hipMemcpyDeviceToHost));
+    *count = sc.rejected_before + h;
+    return MRT_OK;
+}
+
+int device_refit_prepare(const std::vector<HostMesh> &meshes, const BuildOptions &opt, DeviceScene &sc) {
+    if (sc.refit_ws) return MRT_OK;
+    const size_t I = meshes.size(), T = sc.stats.triangles;
+    // where build_flat put every flattened instance's vertices: in mesh order, an instance with its source's count
+    std::vector<uint32_t> vbase(I, 0u); size_t V = 0;
+    for (size_t mi = 0; mi < I; mi++) { const HostMesh &g = meshes[mi].source >= 0 ? meshes[(size_t)meshes[mi].source] : meshes[mi]; vbase[mi] = (uint32_t)V; V += g.positions.size() / 3; }
+    if (sc.g_pos.n != std::max<size_t>(V * 3, 3) || sc.normals.n != std::max<size_t>(V, 1) || sc.stats.instances != (int32_t)I) { set_error("mrt_scene_update_mesh_device: the resident geometry is not this scene's"); return MRT_ERR_STATE; }
+    std::unique_ptr<RefitWorkspace> w(new RefitWorkspace());
+    w->instances = (uint32_t)I; w->mesh_vbase = vbase; w->layouts = refit_layouts(sc, opt);          // (device_refit_supported has accepted them; the tree stays until the workspace goes)
+    w->ref_first.assign(I, 0u); w->ref_count.assign(I, 0u); w->host_stale.assign(I, 0); w->pending.assign(I, 0);
+    std::vector<uint2> table; table.reserve(I);
+    for (size_t mi = 0; mi < I; mi++) {
+        if (meshes[mi].source >= 0) continue;
+        w->ref_first[mi] = (uint32_t)table.size();
+        for (size_t r = 0; r < I; r++) if (r == mi || meshes[r].source == (int)mi) table.push_back(make_uint2((uint32_t)r, vbase[r]));
+        w->ref_count[mi] = (uint32_t)table.size() - w->ref_first[mi];
+    }
+    w->level_first.assign(sc.wide_levels.size(), 0u);
+    for (size_t L = 1; L < sc.wide_levels.size(); L++) w->level_first[L] = w->level_first[L - 1] + sc.wide_levels[L - 1];
+    const size_t nw = std::max<uint32_t>(sc.num_wnodes, 1u), nr = std::max<uint32_t>(sc.rope_nodes, 1u);
+    // one allocation: 80 B per triangle + 32 B per 8-wide node + 16 B per rope node, every piece below rounded up as the arena hands it out (a piece added below and forgotten
+    // here costs a second chunk, nothing else)
+    const auto piece = [](size_t bytes) { return (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; };
+    const size_t nref = std::max<size_t>(table.size(), 1), ninst = std::max<size_t>(I, 1);
+    w->arena.chunk_bytes = piece(48 * T) + 2 * piece(16 * T) + piece(32 * nw) + 2 * piece(4 * nr) + piece(8 * nr) + piece(sizeof(uint2) * nref) + piece(ninst)
+                         + piece(6 * 4) + piece(4 * 4) + piece(6 * 8) + piece(8) + piece(4);
+    MRT_HIP(w->tri_world.alloc_in(w->arena, 3 * T)); MRT_HIP(w->tri_lo.alloc_in(w->arena, T)); MRT_HIP(w->tri_hi.alloc_in(w->arena, T)); MRT_HIP(w->nbox.alloc_in(w->arena, 2 * nw));
+    MRT_HIP(w->parent.alloc_in(w->arena, nr)); MRT_HIP(w->arrived.alloc_in(w->arena, nr)); MRT_HIP(w->ab.alloc_in(w->arena, nr));
+    MRT_HIP(w->ref_table.alloc_in(w->arena, nref)); MRT_HIP(w->inst_dirty.alloc_in(w->arena, ninst));
+    MRT_HIP(w->cbounds.alloc_in(w->arena, 6)); MRT_HIP(w->words.alloc_in(w->arena, 4)); MRT_HIP(w->growth.alloc_in(w->arena, 6)); MRT_HIP(w->rejected.alloc_in(w->arena, 1)); MRT_HIP(w->leaf_growth.alloc_in(w->arena, 1));
+    MRT_HIP(hipEventCreate(&w->ev_begin)); MRT_HIP(hipEventCreate(&w->ev_end)); MRT_HIP(hipEventCreateWithFlags(&w->ev_last, hipEventDisableTiming));
+    if (!table.empty()) MRT_HIP(hipMemcpy(w->ref_table.p, table.data(), table.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    MRT_HIP(hipMemset(w->inst_dirty.p, 0, w->inst_dirty.bytes())); MRT_HIP(hipMemset(w->words.p, 0, w->words.bytes())); MRT_HIP(hipMemset(w->growth.p, 0, w->growth.bytes())); MRT_HIP(hipMemset(w->rejected.p, 0, 8));
+    MRT_HIP(hipMemcpy(w->leaf_growth.p, &sc.stats.leaf_growth, 4, hipMemcpyHostToDevice));
+    MRT_HIP(hipDeviceSynchronize());          // (the first call after a build may block: from here on the caller's stream finds the workspace as the lines above left it)
+    MRT_HIP(hipEventRecord(w->ev_last, nullptr));
+    sc.refit_ws = std::move(w);
+    return MRT_OK;
+}
+
+int device_update_mesh(DeviceScene &sc, size_t mesh, const void *d_pos, size_t pos_stride, const void *d_nrm, size_t nrm_stride, size_t nverts, hipStream_t stream) {
+    RefitWorkspace &ws = *sc.refit_ws;
+    if (++ws.seq == 0u) ws.seq = 1u;          // (0 is what words[0] starts as)
+    if (nverts != 0 && ws.ref_count[mesh] != 0) {
+        const uint32_t nv = (uint32_t)nverts;
+        const dim3 grid(cdiv(nv, 256)), block(256);
+        hipLaunchKernelGGL(k_ingest_check, grid, block, 0, stream, static_cast<const uint8_t *>(d_pos), pos_stride, static_cast<const uint8_t *>(d_nrm), nrm_stride, nv, ws.seq, ws.words.p);
+        hipLaunchKernelGGL(k_ingest_write, grid, block, 0, stream, static_cast<const uint8_t *>(d_pos), pos_stride, static_cast<const uint8_t *>(d_nrm), nrm_stride, nv, ws.seq, (const uint32_t *)ws.words.p,
+                           ws.rejected.p, (const uint2 *)(ws.ref_table.p + ws.ref_first[mesh]), ws.ref_count[mesh], sc.g_pos.p, sc.normals.p, ws.inst_dirty.p);
+        MRT_HIP(hipGetLastError());
+        MRT_HIP(hipEventRecord(ws.ev_last, stream));
+    }
+    // (set for a call the device refuses too: the host cannot know without a read-back.  The bits on the device are then the old ones, so all it costs is a download of
+    // vertices the host already has and a refit of an unchanged mesh at the next commit)
+    ws.host_stale[mesh] = 1; ws.pending[mesh] = 1;
+    return MRT_OK;
+}
+
+int device_refit(DeviceScene &sc, hipStream_t stream) {
+    RefitWorkspace &ws = *sc.refit_ws;
+    const bool wide_there = ws.layouts.wide, rope_there = ws.layouts.rope;
+    const uint32_t T32 = (uint32_t)sc.stats.triangles;
+    const int B = 256, nrec = (int)(sc.g_recs.n / 6);
+    MRT_HIP(hipMemsetAsync(ws.cbounds.p, 0, 24, stream));          // (k_flatten's centroid bounds: written, never read here)
+    if (rope_there) MRT_HIP(hipMemsetAsync(ws.arrived.p, 0, (size_t)sc.rope_nodes * 4, stream));
+    MRT_HIP(hipEventRecord(ws.ev_begin, stream));
+    hipLaunchKernelGGL(k_flatten, dim3(cdiv(T32, 1024)), dim3(1024), 0, stream, reinterpret_cast<const SubRec *>(sc.g_recs.p), nrec, (const float *)sc.g_pos.p, (const uint32_t *)sc.g_idx.p, (const float4 *)sc.inst_cols.p, T32,
+                       ws.tri_world.p, sc.tri_shade.p, ws.tri_lo.p, ws.tri_hi.p, ws.cbounds.p);
+    if (wide_there) {
+        hipLaunchKernelGGL(k_refit_wide_packets, dim3(cdiv(sc.num_packets, B)), dim3(B), 0, stream, (const float4 *)ws.tri_world.p, sc.wpackets.p, sc.num_packets);
+        for (size_t L = sc.wide_levels.size(); L-- > 0;)
+            hipLaunchKernelGGL(k_refit_wide_level, dim3(cdiv(sc.wide_levels[L], 64)), dim3(64), 0, stream, sc.wnodes.p, (const float4 *)sc.wpackets.p, (const float4 *)ws.tri_lo.p, (const float4 *)ws.tri_hi.p, (const uint4 *)sc.tri_shade.p,
+                               (const uint8_t *)ws.inst_dirty.p, ws.nbox.p, ws.level_first[L], sc.wide_levels[L], ws.growth.p);
+    }
+    if (rope_there) {
+        float4 *const rp = sc.nodes.p + sc.packets_offset;
+        hipLaunchKernelGGL(k_refit_wide_packets, dim3(cdiv(sc.num_packets, B)), dim3(B), 0, stream, (const float4 *)ws.tri_world.p, rp, sc.num_packets);
+        hipLaunchKernelGGL(k_rope_prepare, dim3(cdiv(sc.rope_nodes, B)), dim3(B), 0, stream, (const float4 *)sc.nodes.p, sc.rope_nodes, ws.parent.p, ws.ab.p);
+        hipLaunchKernelGGL(k_rope_refit, dim3(cdiv(sc.rope_nodes, B)), dim3(B), 0, stream, sc.nodes.p, sc.rope_nodes, (const float4 *)rp, (const float4 *)ws.tri_lo.p, (const float4 *)ws.tri_hi.p, (const uint32_t *)ws.parent.p, (const uint2 *)ws.ab.p, ws.arrived.p,
+                           (const uint4 *)sc.tri_shade.p, (const uint8_t *)ws.inst_dirty.p);
+    }
+    hipLaunchKernelGGL(k_refit_fold, dim3(1), dim3(64), 0, stream, ws.growth.p, ws.leaf_growth.p);
+    MRT_HIP(hipMemsetAsync(ws.inst_dirty.p, 0, ws.inst_dirty.bytes(), stream));          // the marks are spent
+    MRT_HIP(hipEventRecord(ws.ev_end, stream));
+    MRT_HIP(hipEventRecord(ws.ev_last, stream));
+    MRT_HIP(hipGetLastError());
+    std::fill(ws.pending.begin(), ws.pending.end(), 0);
+    sc.refits++; ws.unresolved = true;
+    return MRT_OK;
+}
+
+// What build_flat's refit branch leaves in the statistics, for the refits enqueued since they were last read: blocks on the last one's end.
+int resolve_device_refits(DeviceScene &sc, const BuildOptions &opt, hipStream_t stream) {
+    if (!sc.refit_ws || !sc.refit_ws->unresolved) return MRT_OK;
+    RefitWorkspace &ws = *sc.refit_ws;
+    const bool wide_there = ws.layouts.wide;
+    MRT_HIP(hipEventSynchronize(ws.ev_end));
+    float ms = 0; MRT_HIP(hipEventElapsedTime(&ms, ws.ev_begin, ws.ev_end));
+    float4 h_box[2]; float h_growth = 1.0f;
+    MRT_HIP(hipMemcpy(h_box, wide_there ? ws.nbox.p : sc.nodes.p, sizeof h_box, hipMemcpyDeviceToHost));
+    MRT_HIP(hipMemcpy(&h_growth, ws.leaf_growth.p, 4, hipMemcpyDeviceToHost));
+    sc.stats.build_ms = ms;
+    if (wide_there) { if (int rc = wide_tree_cost(sc.wnodes.p, 0, sc.num_wnodes, 0, opt.wide_cost_node, opt.wide_cost_tri, stream, ws.growth.p + 2, &sc.stats.wide_cost)) return rc; }
+    if (sc.stats.wide_cost_built > 0.0f) sc.stats.sah_cost = sc.sah_cost_built * (sc.stats.wide_cost / sc.stats.wide_cost_built);
+    sc.stats.refits = sc.refits; sc.stats.leaf_growth = h_growth;
+    sc.root_lo[0] = h_box[0].x; sc.root_lo[1] = h_box[0].y; sc.root_lo[2] = h_box[0].z; sc.root_hi[0] = h_box[1].x; sc.root_hi[1] = h_box[1].y; sc.root_hi[2] = h_box[1].z;
+    ws.unresolved = false;
+    return MRT_OK;
+}
+
+// The scene's host copy of a mesh is stale once its vertices were replaced on the device: whoever reads HostMesh::positions / normals (a commit, the replication of a scene
+// for a device group) calls this first.  A mesh updated and not yet refitted counts as changed for the commit that follows.
+int download_stale_meshes(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *pending_found) {
+    if (pending_found) *pending_found = false;
+    if (!sc.refit_ws) return MRT_OK;
+    RefitWorkspace &ws = *sc.refit_ws;
+    // meshes are only ever appended (mrt_scene_add_mesh / _add_instance / _add_obj), and the resident arrays keep their layout until the next build: the meshes the workspace
+    // knows are the first host_stale.size() of the scene, whatever was added behind them since
+    const size_t known = std::min(ws.host_stale.size(), meshes.size());
+    bool waited = false;
+    std::vector<float4> n4;
+    for (size_t mi = 0; mi < known; mi++) {
+        if (ws.pending[mi]) { meshes[mi].dirty = true; ws.pending[mi] = 0; if (pending_found) *pending_found = true; }
+        if (!ws.host_stale[mi]) continue;
+        if (!waited) { MRT_HIP(hipEventSynchronize(ws.ev_last)); waited = true; }
+        HostMesh &m = meshes[mi];
+        const size_t nv = m.positions.size() / 3;
+        if (nv) {
+            n4.resize(nv);
+            MRT_HIP(hipMemcpy(m.positions.data(), sc.g_pos.p + 3 * (size_t)ws.mesh_vbase[mi], nv * 12, hipMemcpyDeviceToHost));
+            MRT_HIP(hipMemcpy(n4.data(), sc.normals.p + ws.mesh_vbase[mi], nv * 16, hipMemcpyDeviceToHost));
+            for (size_t v = 0; v < nv; v++) { m.normals[3 * v] = n4[v].x; m.normals[3 * v + 1] = n4[v].y; m.normals[3 * v + 2] = n4[v].z; }
+        }
+        ws.host_stale[mi] = 0;
+    }
     return MRT_OK;
 }
 

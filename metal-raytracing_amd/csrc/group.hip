@@ -236,6 +236,7 @@ int mrt_group_renderer_create(MRTGroup g, MRTScene scene, int32_t width, int32_t
     gr->g = g; gr->width = width; gr->height = height; g->renderers++;          // (from here on every way out goes through mrt_group_renderer_destroy, which counts it off)
     const int n = (int)g->ctx.size();
     MRTGroupRenderer_ *raw = gr.release();        // from here on the Undo guard owns it
+    { int rc = mrt_scene_sync_host_meshes(scene); if (rc) return rc; }          // (the template's meshes are copied below: vertices replaced on its device come back first)
     raw->scenes.assign((size_t)n, nullptr); raw->r.assign((size_t)n, nullptr); raw->done.assign((size_t)n, nullptr);
     // every rank on its own host thread: eight BVH builds (and the eight uploads in front of them) run side by side instead of one after the other
     int rc_all = g->pool.run(n, [&](int rank) -> int {

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <memory>
 #include <string>
 #include <vector>
 #include "../../include/mrt_abi.h"
@@ -224,6 +225,35 @@ struct BlasRange {
     float wide_cost = 0.0f, leaf_growth = 1.0f;              // leaf_growth: its leaf boxes' area against the build's, chained over its refits
 };
 
+// What the stream-ordered refit (mrt_scene_update_mesh_device / mrt_scene_refit_device) keeps on the device between calls, so that a call allocates nothing,
+// copies nothing from the host and waits for nothing: k_flatten's outputs (tri_world 48 B, tri_lo / tri_hi 32 B per triangle), the refit's node boxes (32 B per 8-wide node),
+// the rope refit's parent / arrived / ab (16 B per rope node), the dirty byte per flattened instance and a handful of words.  Made by the first device update after a build
+// (which may allocate), dropped by the next build and by mrt_scene_destroy.
+struct RefitLayouts { bool wide = false, rope = false; };          // which resident layouts a refit works on (refit_layouts)
+struct RefitWorkspace {
+    ScratchArena arena;                                    // before the buffers that borrow from it
+    DevBuf<float4> tri_world, tri_lo, tri_hi, nbox;
+    DevBuf<uint32_t> cbounds, parent, arrived;
+    DevBuf<uint32_t> words;                                // [0]: sequence number of the last update call whose input held a NaN or an infinity (k_ingest_check)
+    DevBuf<uint2> ab, ref_table;                           // ref_table: {flattened instance, its first vertex in g_pos / normals}, grouped by source mesh
+    DevBuf<double> growth;                                 // [0 .. 1]: k_refit_wide_level's sums of one refit (folded and cleared by k_refit_fold); [2 .. 5]: wide_tree_cost's 8 + 24 bytes
+    DevBuf<unsigned long long> rejected;                   // update calls refused on the device since the workspace was made (sticky)
+    DevBuf<float> leaf_growth;                             // MRTSceneStats.leaf_growth, chained on the device over the refits
+    DevBuf<uint8_t> inst_dirty;                            // per flattened instance: its vertices were replaced since the last refit
+    std::vector<uint32_t> ref_first, ref_count, mesh_vbase;   // per mesh of the scene: its range of ref_table (instances: empty), its first vertex
+    std::vector<uint32_t> level_first;                     // first node of every level of the 8-wide tree
+    std::vector<uint8_t> host_stale, pending;              // per mesh: the HostMesh copy is older than the device's vertices; updated on the device and not yet refitted
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;       // around the last refit (MRTSceneStats.build_ms)
+    hipEvent_t ev_last = nullptr;                          // behind the last update or refit enqueued: what a blocking reader waits for
+    uint32_t seq = 0;                                      // update calls so far
+    uint32_t instances = 0;
+    RefitLayouts layouts;                                  // refit_layouts() of the tree the workspace was made for
+    bool unresolved = false;                               // refits enqueued whose statistics the host has not read yet (resolve_device_refits)
+    RefitWorkspace() = default;
+    RefitWorkspace(const RefitWorkspace &) = delete; RefitWorkspace &operator=(const RefitWorkspace &) = delete;
+    ~RefitWorkspace() { if (ev_last) (void)hipEventSynchronize(ev_last); for (hipEvent_t e : {ev_begin, ev_end, ev_last}) if (e) (void)hipEventDestroy(e); }
+};
+
 struct DeviceScene {
     DevBuf<float4> nodes, packets, normals, base_color, materials, inst_cols, wnodes, wpackets;
     uint32_t num_wnodes = 0; int wide_depth = 0;
@@ -253,13 +283,16 @@ struct DeviceScene {
     DevBuf<float> g_pos; DevBuf<uint32_t> g_idx, g_recs;       // flattened build: packed object-space positions, indices and submesh records as uploaded (kept: a commit that only changes transforms does not upload them again)
     PinnedBuf stage;                                           // upload staging of build_flat (grow-only, reused by every commit of this scene)
     double commit_ms[6] = {0, 0, 0, 0, 0, 0};                    // host wall time of the last flat build, by phase: staging (reserve + fill), device allocations + upload enqueue, topology (sort .. refit, incl. its read-backs), 8-wide emit, rope emit, validation (mrt_debug_commit_times)
+    std::unique_ptr<RefitWorkspace> refit_ws;                    // the stream-ordered refit's resident scratch (null until the first mrt_scene_update_mesh_device after a build)
+    DevBuf<double> cost_words;                                   // wide_tree_cost's 8 + 24 bytes for refit_two_level (made once, kept: no hipMalloc / hipFree pair per commit)
+    uint64_t rejected_before = 0;                                // device updates refused in the lifetimes of earlier workspaces of this scene
     SceneView view() const;
 };
 
 // bvh_build.hip
 void pack_material(const MRTMaterial &m, float4 *out3);
 int wide_histogram(const DeviceScene &sc, hipStream_t stream, uint32_t out12[12]);      // diagnostics: children per 8-wide node
-int wide_tree_cost(const float4 *wnodes, uint32_t first, uint32_t count, uint32_t root, float c_node, float c_tri, hipStream_t stream, float *out);      // SAH cost of the 8-wide subtree [first, first + count) rooted at `root`, as it lies in memory, per unit of root area
+int wide_tree_cost(const float4 *wnodes, uint32_t first, uint32_t count, uint32_t root, float c_node, float c_tri, hipStream_t stream, void *scratch32, float *out);      // SAH cost of the 8-wide subtree [first, first + count) rooted at `root`, as it lies in memory, per unit of root area; scratch32: 32 bytes of device memory, 8-byte aligned (the caller's arena or workspace)
 int layout_limits(uint64_t triangles, uint64_t nodes);    // MRT_OK, or MRT_ERR_UNSUPPORTED when the traversal layouts cannot address such a scene
 int build_scene(const std::vector<HostMesh> &meshes, const BuildOptions &opt, hipStream_t stream, DeviceScene &out, bool only_transforms_changed = false, bool only_vertices_changed = false);      // only_transforms_changed: same meshes, submeshes and options as the commit before (flattened scenes keep their geometry on the device)
 // bvh_host_sah.cpp (builder = 2): binned-SAH topology over n reference boxes, built on the host
@@ -273,6 +306,16 @@ int refit_blas(const HostMesh &g, const BlasRange &br, hipStream_t stream, Devic
 int update_tlas(const std::vector<HostMesh> &meshes, hipStream_t stream, DeviceScene &out);      // after transform changes: instance rows + TLAS, BLASes untouched
 int validate_layout(const DeviceScene &sc, hipStream_t stream, bool tlas_only, const float4 *wnodes_override = nullptr);      // wnodes_override: a device copy of the 8-wide nodes to check in place of the scene's (mrt_debug_validate_patched)
          // every index of the 8-wide layout / instance rows inside its array; MRT_ERR_STATE + message otherwise
+// the stream-ordered refit (bvh_build.hip)
+RefitLayouts refit_layouts(const DeviceScene &sc, const BuildOptions &opt);
+int device_refit_supported(const DeviceScene &sc, const BuildOptions &opt, const char *who);      // MRT_OK, or MRT_ERR_UNSUPPORTED + message: what build_flat's refit branch would not take
+int device_refit_prepare(const std::vector<HostMesh> &meshes, const BuildOptions &opt, DeviceScene &sc);      // makes sc.refit_ws if it is not there (allocates, uploads its tables, blocks)
+int device_update_mesh(DeviceScene &sc, size_t mesh, const void *d_pos, size_t pos_stride, const void *d_nrm, size_t nrm_stride, size_t nverts, hipStream_t stream);
+int device_refit(DeviceScene &sc, hipStream_t stream);
+int resolve_device_refits(DeviceScene &sc, const BuildOptions &opt, hipStream_t stream);      // blocks on the last refit and brings sc.stats up to date (no-op when nothing is pending)
+int download_stale_meshes(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *pending_found = nullptr);      // blocks; the HostMesh copies of meshes updated on the device, read back from g_pos / normals; pending_found: a mesh was updated on the device and not refitted since (it is marked dirty)
+int device_updates_rejected(DeviceScene &sc, uint64_t *count);      // blocks
+void drop_refit_workspace(DeviceScene &sc);      // (a build: the tree the workspace was made for is gone)
 int upload_lights(const MRTLight *lights, int count, hipStream_t stream, DeviceScene &out);
 
 }  // namespace mrt

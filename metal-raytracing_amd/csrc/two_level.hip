@@ -596,13 +596,14 @@ int refit_two_level(const std::vector<HostMesh> &meshes, const BuildOptions &opt
     if (!out.blas_all_wide || out.num_inst != meshes.size() || out.blas_ranges.empty() || out.h_inst.size() != meshes.size()) return MRT_ERR_UNSUPPORTED;
     for (const BlasRange &r : out.blas_ranges) if (r.src_mesh >= meshes.size() || (meshes[r.src_mesh].dirty && (r.wnodes == 0 || r.wide_levels.empty() || meshes[r.src_mesh].positions.size() / 3 == 0))) return MRT_ERR_UNSUPPORTED;
     float ms_total = 0, growth_max = 1.0f; double sah = 0, wcost = 0;
+    MRT_HIP(out.cost_words.alloc(4));          // wide_tree_cost's sum and root box: the scene's, allocated by its first refit and found by every later one
     for (size_t b = 0; b < out.blas_ranges.size(); b++) {
         BlasRange &r = out.blas_ranges[b];
         if (meshes[r.src_mesh].dirty && r.ntri != 0) {
             float ms = 0, gr = 1.0f;
             if (int rc = refit_blas(meshes[r.src_mesh], r, stream, out, &out.blas_lo[3 * b], &out.blas_hi[3 * b], &ms, &gr)) return rc;
             r.leaf_growth *= gr;
-            if (int rc = wide_tree_cost(out.wnodes.p, r.wnode_base, r.wnodes, r.wnode_base, opt.wide_cost_node, opt.wide_cost_tri, stream, &r.wide_cost)) return rc;
+            if (int rc = wide_tree_cost(out.wnodes.p, r.wnode_base, r.wnodes, r.wnode_base, opt.wide_cost_node, opt.wide_cost_tri, stream, out.cost_words.p, &r.wide_cost)) return rc;
             ms_total += ms;
         }
         growth_max = std::max(growth_max, r.leaf_growth); wcost += r.wide_cost; sah += r.wide_cost_built > 0.0f ? r.sah_cost_built * (r.wide_cost / r.wide_cost_built) : r.sah_cost_built;

@@ -134,12 +134,8 @@ class DeviceScene:
             out = torch.empty(shape, dtype=torch.int32, device=dev)
         elif not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous torch.int32 tensor of shape {shape} on {dev}")
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        elif isinstance(stream, torch.cuda.Stream):
-            stream = stream.cuda_stream
         n = rays.shape[0]
-        check(fn(self.handle, C.c_void_p(rays.data_ptr() if n else None), n, C.c_void_p(out.data_ptr() if n else None), C.c_void_p(int(stream))))
+        check(fn(self.handle, C.c_void_p(rays.data_ptr() if n else None), n, C.c_void_p(out.data_ptr() if n else None), C.c_void_p(self._stream_handle(stream))))
         return out
 
     def intersect_closest_device(self, rays, out=None, stream=None):
@@ -152,6 +148,46 @@ class DeviceScene:
     def intersect_any_device(self, rays, out=None, stream=None):
         """Any-hit form of intersect_closest_device: torch.int32 (n,), 1 = occluded."""
         return self._device_query(lib.mrt_scene_intersect_any_device, rays, out, stream, ())
+
+    def _stream_handle(self, stream):
+        """the stream argument of every *_device method as an integer handle: None = torch's current stream of the context's device, a torch.cuda.Stream, or the handle itself"""
+        import torch
+        if stream is None:
+            return int(torch.cuda.current_stream(torch.device("cuda", self.ctx.device)).cuda_stream)
+        return int(stream.cuda_stream if isinstance(stream, torch.cuda.Stream) else stream)
+
+    def _vertex_rows(self, t, what):
+        """a torch.float32 (n, 3) tensor on the context's device whose rows are contiguous and a multiple of 4 bytes apart -> (pointer, row stride in bytes): no copy"""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        if not isinstance(t, torch.Tensor) or t.device != dev:
+            raise ValueError(f"{what} must be a torch tensor on {dev}")
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < 3):
+            raise ValueError(f"{what} must be a torch.float32 tensor of shape (n, 3) with contiguous rows (a slice of a wider tensor is fine)")
+        return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else 3) * 4
+
+    def update_mesh_device(self, mesh_id, positions, normals, stream=None):
+        """Deforming geometry that lives on the GPU, ordered on a stream: positions and normals are torch.float32 (n, 3) tensors on the context's device, n the mesh's
+        vertex count; rows may be any multiple of 4 bytes apart (x[:, :3] of an (n, 4) tensor, two halves of one interleaved (n, 8) tensor), nothing is copied.  Call
+        refit_device() afterwards (several updates may share one).  stream: None = torch's current stream of that device, an integer handle (0 = the null stream) or a
+        torch.cuda.Stream.  A NaN or an infinity in the input leaves the scene as it was and is counted in device_updates_rejected.  Keep the tensors alive until the
+        stream has passed the call.  A tensor that is not what the first sentence says raises ValueError; normals of another length than positions raise
+        MRTError(MRT_ERR_INVALID_ARGUMENT), as update_mesh does for the same mistake."""
+        p, ps = self._vertex_rows(positions, "positions"); n, ns = self._vertex_rows(normals, "normals")
+        if normals.shape[0] != positions.shape[0]:          # the device reads vertex_count normals: a shorter tensor would be read past its end
+            raise MRTError(1, f"update_mesh_device: {normals.shape[0]} normals for {positions.shape[0]} positions (one normal per vertex)")
+        check(lib.mrt_scene_update_mesh_device(self.handle, int(mesh_id), C.c_void_p(p), ps, C.c_void_p(n), ns, positions.shape[0], C.c_void_p(self._stream_handle(stream))))
+
+    def refit_device(self, stream=None):
+        """The refit of the resident tree after update_mesh_device, enqueued on the stream (as a commit after update_mesh computes it, without the commit's copies and waits)."""
+        check(lib.mrt_scene_refit_device(self.handle, C.c_void_p(self._stream_handle(stream))))
+
+    @property
+    def device_updates_rejected(self):
+        """update_mesh_device calls refused on the device for a NaN or an infinity since the scene was created (blocks until the calls enqueued so far have run)."""
+        v = C.c_uint64()
+        check(lib.mrt_scene_device_updates_rejected(self.handle, C.byref(v)))
+        return v.value
 
     def traversal_stats(self, rays, any_hit=False, alu_dup=0, mem_dup=0):
         """Diagnostics: (n, 8) uint32 {node visits, leaf visits, triangle tests, hit gid, t0, t1, 0, 0} per ray."""

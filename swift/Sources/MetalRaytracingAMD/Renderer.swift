@@ -60,6 +60,12 @@ public final class Renderer {
         try check(mrt_scene_update_mesh(scene, meshId, positions, 12, normals, 12, positions.count / 3))
     }
     public func commit() throws { try check(mrt_scene_commit(scene)) }
+    /// deforming geometry from device buffers, ordered on a HIP stream (mrt_scene_update_mesh_device / mrt_scene_refit_device): strided float3 rows in device memory
+    public func updateMeshDevice(meshId: Int32, positions: UnsafeRawPointer, positionStride: Int, normals: UnsafeRawPointer, normalStride: Int, vertexCount: Int, stream: UnsafeMutableRawPointer?) throws {
+        try check(mrt_scene_update_mesh_device(scene, meshId, positions, positionStride, normals, normalStride, vertexCount, stream))
+    }
+    public func refitDevice(stream: UnsafeMutableRawPointer?) throws { try check(mrt_scene_refit_device(scene, stream)) }
+    public func deviceUpdatesRejected() throws -> UInt64 { var n: UInt64 = 0; try check(mrt_scene_device_updates_rejected(scene, &n)); return n }
     /// implementation knobs of include/mrt_abi.h: "frames_in_flight", "frame_batch", "materials", "megakernel", ...
     public func setOption(_ key: String, _ value: Double) throws { try check(mrt_renderer_set_option(renderer, key, value)) }
     public func drawableSizeWillChange(width: Int, height: Int) throws {
