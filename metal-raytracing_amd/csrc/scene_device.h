@@ -1,4 +1,4 @@
-// scene_device.h — HBM data layout of a committed scene, shared by the BVH builder (bvh_build.hip)
+// scene_device.h — HBM data layout of a committed scene, shared by the BVH builder (bvh_build.hip, bvh_refit.hip)
 // and the render kernels (renderer.hip, traverse.h, traverse_wide.h).  DESIGN.md §4 documents every array.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -230,6 +230,19 @@ struct BlasRange {
 // the rope refit's parent / arrived / ab (16 B per rope node), the dirty byte per flattened instance and a handful of words.  Made by the first device update after a build
 // (which may allocate), dropped by the next build and by mrt_scene_destroy.
 struct RefitLayouts { bool wide = false, rope = false; };          // which resident layouts a refit works on (refit_layouts)
+// One refit enqueue (enqueue_refit, bvh_refit.hip) for the commit of a flattened scene, a BLAS of a two-level scene and the stream-ordered refit: what is refitted ...
+struct RefitTarget {
+    float4 *wnodes = nullptr, *wpackets = nullptr;         // the 8-wide arrays as its nodes index them (null wnodes: no 8-wide layout to refit)
+    uint32_t wpacket_first = 0;                            // the tree's first packet in wpackets (a BLAS in the shared array)
+    const uint32_t *level_first = nullptr, *level_count = nullptr; size_t levels = 0;      // per level of the 8-wide tree: its first node and its node count
+    float4 *rope_nodes = nullptr, *rope_packets = nullptr; // the tree's own first rope node and first rope packet (null rope_packets: no rope layout to refit)
+    uint32_t rope_nodes_n = 0;                             // 0: only the rope packets are rewritten
+    uint32_t packets = 0;                                  // triangle packets per layout
+    const uint4 *tri_shade = nullptr; const uint8_t *dirty = nullptr;      // a leaf none of whose triangles' instances (tri_shade[gid].w >> 16) is dirty keeps its box
+    bool rope_every_leaf = false;                          // k_rope_refit recomputes every leaf (it gets neither tri_shade nor dirty)
+};
+// ... and the scratch it works in: k_flatten's outputs, a box per 8-wide node, the two growth sums, and per rope node its parent, arrival counter (zeroed) and {a, b} words
+struct RefitScratch { const float4 *tri_world, *tri_lo, *tri_hi; float4 *nbox; double *growth; uint32_t *parent, *arrived; uint2 *ab; };
 struct RefitWorkspace {
     ScratchArena arena;                                    // before the buffers that borrow from it
     DevBuf<float4> tri_world, tri_lo, tri_hi, nbox;
@@ -257,7 +270,7 @@ struct RefitWorkspace {
 struct DeviceScene {
     DevBuf<float4> nodes, packets, normals, base_color, materials, inst_cols, wnodes, wpackets;
     uint32_t num_wnodes = 0; int wide_depth = 0;
-    std::vector<uint32_t> wide_levels;           // flattened scenes: nodes per level of the 8-wide tree (BFS numbering) — what a refit walks bottom-up (build_flat, refit)
+    std::vector<uint32_t> wide_levels;           // flattened scenes: nodes per level of the 8-wide tree (BFS numbering) — what a refit walks bottom-up
     uint32_t refits = 0;                         // commits served by a refit since the last build
     float sah_cost_built = 0.0f;                 // stats.sah_cost as the last build left it (a refit scales it by the 8-wide tree's cost ratio)
     uint64_t refit_triangles = 0;                // triangles of the build that made the 8-wide layout (a refit needs the same count)
@@ -291,8 +304,6 @@ struct DeviceScene {
 
 // bvh_build.hip
 void pack_material(const MRTMaterial &m, float4 *out3);
-int wide_histogram(const DeviceScene &sc, hipStream_t stream, uint32_t out12[12]);      // diagnostics: children per 8-wide node
-int wide_tree_cost(const float4 *wnodes, uint32_t first, uint32_t count, uint32_t root, float c_node, float c_tri, hipStream_t stream, void *scratch32, float *out);      // SAH cost of the 8-wide subtree [first, first + count) rooted at `root`, as it lies in memory, per unit of root area; scratch32: 32 bytes of device memory, 8-byte aligned (the caller's arena or workspace)
 int layout_limits(uint64_t triangles, uint64_t nodes);    // MRT_OK, or MRT_ERR_UNSUPPORTED when the traversal layouts cannot address such a scene
 int build_scene(const std::vector<HostMesh> &meshes, const BuildOptions &opt, hipStream_t stream, DeviceScene &out, bool only_transforms_changed = false, bool only_vertices_changed = false);      // only_transforms_changed: same meshes, submeshes and options as the commit before (flattened scenes keep their geometry on the device)
 // bvh_host_sah.cpp (builder = 2): binned-SAH topology over n reference boxes, built on the host
@@ -302,13 +313,18 @@ int build_flat(const std::vector<MeshRef> &refs, const BuildOptions &opt, hipStr
 // two_level.hip
 int build_two_level(const std::vector<HostMesh> &meshes, const BuildOptions &opt, hipStream_t stream, DeviceScene &out);
 int refit_two_level(const std::vector<HostMesh> &meshes, const BuildOptions &opt, hipStream_t stream, DeviceScene &out);      // after mrt_scene_update_mesh alone: the BLASes of the updated meshes refitted in place (both layouts) + the TLAS; MRT_ERR_UNSUPPORTED (no message): the scene cannot be refitted, build it
-int refit_blas(const HostMesh &g, const BlasRange &br, hipStream_t stream, DeviceScene &out, float root_lo[3], float root_hi[3], float *ms_out, float *growth_out);      // bvh_build.hip
+int refit_blas(const HostMesh &g, const BlasRange &br, hipStream_t stream, DeviceScene &out, float root_lo[3], float root_hi[3], float *ms_out, float *growth_out);      // bvh_refit.hip
 int update_tlas(const std::vector<HostMesh> &meshes, hipStream_t stream, DeviceScene &out);      // after transform changes: instance rows + TLAS, BLASes untouched
 int validate_layout(const DeviceScene &sc, hipStream_t stream, bool tlas_only, const float4 *wnodes_override = nullptr);      // wnodes_override: a device copy of the 8-wide nodes to check in place of the scene's (mrt_debug_validate_patched)
          // every index of the 8-wide layout / instance rows inside its array; MRT_ERR_STATE + message otherwise
-// the stream-ordered refit (bvh_build.hip)
+// bvh_refit.hip: the refit of resident layouts
+int wide_histogram(const DeviceScene &sc, hipStream_t stream, uint32_t out12[12]);      // diagnostics: children per 8-wide node
+int wide_tree_cost(const float4 *wnodes, uint32_t first, uint32_t count, uint32_t root, float c_node, float c_tri, hipStream_t stream, void *scratch32, float *out);      // SAH cost of the 8-wide subtree [first, first + count) rooted at `root`, as it lies in memory, per unit of root area; scratch32: 32 bytes of device memory, 8-byte aligned (the caller's arena or workspace)
 RefitLayouts refit_layouts(const DeviceScene &sc, const BuildOptions &opt);
-int device_refit_supported(const DeviceScene &sc, const BuildOptions &opt, const char *who);      // MRT_OK, or MRT_ERR_UNSUPPORTED + message: what build_flat's refit branch would not take
+void enqueue_refit(const RefitTarget &tg, const RefitScratch &s, hipStream_t stream);      // the five refit kernels on the stream, nothing else
+int apply_refit_result(DeviceScene &sc, const BuildOptions &opt, bool wide, float ms, const float4 box[2], float leaf_growth, void *scratch32, hipStream_t stream);      // what a refit of a flattened scene leaves in sc.stats and the root box; blocks (wide_tree_cost)
+// the stream-ordered refit (bvh_refit.hip)
+int device_refit_supported(const DeviceScene &sc, const BuildOptions &opt, const char *who);      // MRT_OK, or MRT_ERR_UNSUPPORTED + message: what a refitting commit (build_flat) would not take
 int device_refit_prepare(const std::vector<HostMesh> &meshes, const BuildOptions &opt, DeviceScene &sc);      // makes sc.refit_ws if it is not there (allocates, uploads its tables, blocks)
 int device_update_mesh(DeviceScene &sc, size_t mesh, const void *d_pos, size_t pos_stride, const void *d_nrm, size_t nrm_stride, size_t nverts, hipStream_t stream);
 int device_refit(DeviceScene &sc, hipStream_t stream);

@@ -23,13 +23,9 @@ def _scene(mrt, n, seed):
     return S((64, 64))
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("builder", [0, 1])
-@pytest.mark.parametrize("n", [1, 2, 3, 63, 65, 1023, 1024, 1025, 1026, 2047, 2049, 4097, 16385, 70001])
-def test_build_at_phase_boundaries(mrt, orc, gpu_ctx, n, builder):
-    sc = _scene(mrt, n, 7 * n + builder)
+def _check_build(mrt, orc, gpu_ctx, n, opts, seed):
+    sc = _scene(mrt, n, seed)
     osc = orc.OracleScene(mrt.flatten_scene(sc), sc.lights)
-    opts = {"builder": builder, "presplit": 0}
     d = mrt.DeviceScene(gpu_ctx, sc, opts)
     st = d.stats
     assert st.triangles == n and st.bvh_leaves >= 1
@@ -37,13 +33,28 @@ def test_build_at_phase_boundaries(mrt, orc, gpu_ctx, n, builder):
     o = osc.intersect_closest(rays)
     for g in (d.intersect_closest(rays), d.intersect_stream(rays)):
         for f in ("type", "distance", "primitive_id", "u", "v"):
-            assert np.array_equal(g[f], o[f]), (f, n, builder)
+            assert np.array_equal(g[f], o[f]), (f, n, opts)
     rays[:, 7] = 3.0
     assert np.array_equal(d.intersect_any(rays), osc.intersect_any(rays))
     d2 = mrt.DeviceScene(gpu_ctx, sc, opts)                  # node ids inside the build are handed out in arrival order: the emitted tree must not depend on it
     s2 = d2.stats
     assert (s2.bvh_nodes, s2.bvh_leaves, s2.max_depth, s2.sah_cost) == (st.bvh_nodes, st.bvh_leaves, st.max_depth, st.sah_cost)
     d.close(); d2.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("builder", [0, 1])
+@pytest.mark.parametrize("n", [1, 2, 3, 63, 65, 1023, 1024, 1025, 1026, 2047, 2049, 4097, 16385, 70001])
+def test_build_at_phase_boundaries(mrt, orc, gpu_ctx, n, builder):
+    _check_build(mrt, orc, gpu_ctx, n, {"builder": builder, "presplit": 0}, 7 * n + builder)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("opts", [{"builder": 2, "presplit": 0}, {"builder": 1, "wide_collapse": 0, "presplit": 0}], ids=["host_sah", "greedy_collapse"])
+@pytest.mark.parametrize("n", [3, 1025])
+def test_build_driver_branches(mrt, orc, gpu_ctx, n, opts):
+    """the host-SAH topology (builder 2) and the greedy 8-wide collapse (wide_collapse 0): two branches of the build driver that only a full-size render test walked"""
+    _check_build(mrt, orc, gpu_ctx, n, opts, 7 * n + 2)
 
 
 @pytest.mark.gpu

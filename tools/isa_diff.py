@@ -1,4 +1,4 @@
-"""Per-kernel comparison of two `hipcc --cuda-device-only -S` listings of one translation unit: is the instruction sequence identical, and the
+"""Per-kernel comparison of two `hipcc --cuda-device-only -S` listings of one translation unit (or of the units it was split into, concatenated): is the instruction sequence identical, and the
 instruction count, VGPR, AGPR, scratch bytes, LDS bytes and occupancy of both sides (A | B).  Comments and the __hip_cuid_* lines are dropped first.
 Usage: hipcc $(CXXFLAGS) --offload-arch=gfx950 --cuda-device-only -S -o a.s x.hip   (at both commits);  python tools/isa_diff.py a.s b.s [--only-different]
 Exit status 1 when a kernel exists on one side only or its resources differ; a different sequence with equal resources is reported, not an error."""
@@ -14,7 +14,7 @@ def kernels(path):
         m = re.match(r"; (NumVgprs|NumAgprs|ScratchSize|LDSByteSize|Occupancy): (\d+)", ln)
         if m: out[name][m.group(1)] = m.group(2); continue
         if ln.startswith(".Lfunc_end"): out[name]["done"] = True
-        code = ln.split(";")[0].strip()
+        code = re.sub(r"\.L(BB|JTI)\d+_", r".L\1_", ln.split(";")[0].strip())       # labels carry the function's index in its translation unit: a kernel that moved to another file keeps its code, not that index
         if code and not out[name].get("done"): body.append(code)
     return out
 
