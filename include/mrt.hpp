@@ -120,6 +120,12 @@ struct Scene {                                                       // Scene.sw
     }
     static void refitDevice(MRTScene committed, void *hipStream) { check(mrt_scene_refit_device(committed, hipStream)); }
     static uint64_t deviceUpdatesRejected(MRTScene scene) { uint64_t n = 0; check(mrt_scene_device_updates_rejected(scene, &n)); return n; }
+    // Stream-ordered instance moves of a committed two-level MRTScene (mrt_scene_set_instance_transforms_device / mrt_scene_refit_instances_device): column-major float 4x4
+    // matrices in device memory for the mesh ids firstMeshId .. + count - 1, then the TLAS boxes refitted (topology kept), all on hipStream
+    static void setInstanceTransformsDevice(MRTScene committed, int32_t firstMeshId, size_t count, const void *deviceTransforms, size_t strideBytes, void *hipStream) {
+        check(mrt_scene_set_instance_transforms_device(committed, firstMeshId, count, deviceTransforms, strideBytes, hipStream));
+    }
+    static void refitInstancesDevice(MRTScene committed, void *hipStream) { check(mrt_scene_refit_instances_device(committed, hipStream)); }
     void updateUniforms(int width, int height) { camera = setupCamera(width, height); }   // Scene.swift:36-38
     static Camera setupCamera(int width, int height) { Camera c; check(mrt_default_camera(width, height, &c)); return c; }   // :40-57
     static Light setupLight() {                                      // :59-67

@@ -275,6 +275,29 @@ int mrt_scene_update_mesh_device(MRTScene scene, int32_t mesh_id, const void *d_
                                  const void *d_normals, size_t nrm_stride_bytes, size_t vertex_count, void *hip_stream);
 int mrt_scene_refit_device(MRTScene scene, void *hip_stream);
 int mrt_scene_device_updates_rejected(MRTScene scene, uint64_t *count);
+/* Moving the instances of a TWO-LEVEL scene (scene option instancing = 1) from DEVICE buffers, ordered on a stream of the caller's: the loop "new poses -> refit -> query
+ * or draw" on one stream.  mrt_scene_set_instance_transforms_device reads `count` column-major float32 4x4 matrices (stride_bytes >= 64, a multiple of
+ * 4; a 4-byte aligned pointer) for the mesh ids first_mesh_id .. first_mesh_id + count - 1, as mrt_scene_set_instance_transform takes them (the last row is forced to
+ * 0 0 0 1), and rewrites in place each instance's columns, its world->object rows and its padded world box — the bits a commit computes on the host for the same matrix.
+ * mrt_scene_refit_instances_device then refits the boxes of the TLAS (the rope form, and the 8-wide form when it is resident) bottom-up.  Several set calls may precede
+ * one refit; a refit with nothing moved changes no answer.  Both calls enqueue kernels on hip_stream (taken literally: 0 is HIP's null stream) and return.  The FIRST of
+ * them after a commit creates a small workspace (it allocates and may block) that stays until the next commit or mrt_scene_destroy; every later call allocates nothing,
+ * copies nothing from host memory and synchronises neither the stream nor the device.
+ *   The topology is kept: both TLAS forms keep the shape the last commit gave them, so the tree loosens as instances travel far from where it was built (the answers stay
+ *   the same, the queries get slower); mrt_scene_commit builds the TLAS again from the poses the device holds.
+ *   Every id must name an instance that is in the TLAS of the last commit (it has triangles and its matrix was invertible then); a commit brings the others in.
+ *   Validation happens on the device: a call in which ANY matrix holds a NaN or an infinity, or has a determinant that is zero or not finite, writes NOTHING — the whole
+ *   call, not the one matrix: a half-applied pose set is worse than none, and an instance cannot leave the tree without a rebuild — and is counted in the count
+ *   mrt_scene_device_updates_rejected returns.
+ *   The caller owes what mrt_scene_update_mesh_device asks for: live buffers on the scene's device, no use of the scene on another stream that is not ordered behind the refit.
+ *   The host side stays truthful: a later mrt_scene_commit (and the replication of the scene for a device group) reads the moved instances' matrices back first, so
+ *   mrt_scene_set_instance_transform on another instance + commit builds the TLAS from the poses the device holds plus the new one; mrt_scene_stats keeps working
+ *   (bvh_nodes and max_depth do not change).
+ * MRT_ERR_STATE: the scene is not committed, or host-side changes wait for a commit.  MRT_ERR_INVALID_ARGUMENT: NULL scene, NULL or misaligned pointer, bad stride, an id
+ * out of range.  MRT_ERR_UNSUPPORTED: a flattened scene (its transforms are baked into world-space triangles), a scene without an instance, an id that names an instance
+ * outside the TLAS.  count == 0: MRT_OK, nothing is launched.                                                                                                          */
+int mrt_scene_set_instance_transforms_device(MRTScene scene, int32_t first_mesh_id, size_t count, const void *d_transforms_colmajor_4x4, size_t stride_bytes, void *hip_stream);
+int mrt_scene_refit_instances_device(MRTScene scene, void *hip_stream);
 
 /* ---------------------------------------------------------------- host-side geometry helpers
  * (no GPU needed) — the library's OBJ/MTL reader standing in for ModelIO (Model.swift:16-21,

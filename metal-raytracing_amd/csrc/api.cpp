@@ -29,13 +29,21 @@ static int sync_host_meshes(MRTScene scene) {
     bool pending = false;
     int rc = mrt::download_stale_meshes(scene->meshes, scene->dev, &pending);
     if (!rc && pending && scene->committed) scene->only_vertices_changed = true;
+    // instances moved on the device (mrt_scene_set_instance_transforms_device): their HostMesh::xf read back — a transform change like mrt_scene_set_instance_transform's
+    bool moved = false;
+    if (!rc) rc = mrt::download_moved_transforms(scene->meshes, scene->dev, &moved);
+    if (!rc && moved) {
+        if (scene->committed) scene->only_transforms_changed = true;
+        else if (scene->only_vertices_changed) { scene->only_vertices_changed = false; scene->only_transforms_changed = false; }      // vertices AND transforms changed: a full build
+    }
     return rc;
 }
 
-// The meshes' host copies as the device has them now (a scene whose vertices were replaced by mrt_scene_update_mesh_device): for readers of MRTScene_::meshes outside this file.
+// The meshes' host copies as the device has them now (a scene whose vertices were replaced by mrt_scene_update_mesh_device, or whose instances were moved by
+// mrt_scene_set_instance_transforms_device): for readers of MRTScene_::meshes outside this file.
 // Leaves the calling thread's current device as it found it.
 int mrt_scene_sync_host_meshes(MRTScene scene) {
-    if (!scene->dev.refit_ws) return MRT_OK;
+    if (!scene->dev.refit_ws && !scene->dev.inst_ws) return MRT_OK;
     int before = 0; MRT_HIP(hipGetDevice(&before));
     int rc = bind_device(scene->ctx);
     if (!rc) rc = sync_host_meshes(scene);
@@ -301,6 +309,7 @@ int mrt_scene_set_instance_transform(MRTScene scene, int32_t mesh_id, const floa
     REQUIRE(all_finite(xf, 64, 1, 16), "mrt_scene_set_instance_transform: the transform holds a NaN or an infinity (the instance keeps what it had)");
     float *m = scene->meshes[mesh_id].xf;
     memcpy(m, xf, 64);
+    if (scene->dev.inst_ws && (size_t)mesh_id < scene->dev.inst_ws->moved.size()) scene->dev.inst_ws->moved[(size_t)mesh_id] = 0;      // (moved on the device before: this matrix is the newer one now)
     m[3] = m[7] = m[11] = 0.0f; m[15] = 1.0f;
     // flattened scene: the world-space BVH is rebuilt by the next mrt_scene_commit (22 ms for 885 K triangles);
     // two-level scene: the next commit rewrites the instance rows and rebuilds the TLAS only
@@ -394,6 +403,42 @@ int mrt_scene_refit_device(MRTScene scene, void *hip_stream) {
     if (int rc = device_refit_prologue("mrt_scene_refit_device", scene)) return rc;
     if (int rc = mrt::device_refit_prepare(scene->meshes, scene->opt, scene->dev)) return rc;
     return mrt::device_refit(scene->dev, (hipStream_t)hip_stream);
+    MRT_CATCH
+}
+
+// Instances of a two-level scene moved from device buffers (tlas_refit.hip)
+static int device_instances_prologue(const char *who, MRTScene scene) {
+    if (!scene) { mrt::set_error(std::string(who) + ": scene is NULL"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (!scene->committed) {
+        mrt::set_error(std::string(who) + (scene->only_vertices_changed || scene->only_transforms_changed ? ": host-side changes are pending (mrt_scene_commit first)" : ": scene not committed"));
+        return MRT_ERR_STATE;
+    }
+    if (int rc = mrt::instances_device_supported(scene->dev, scene->opt, who)) return rc;
+    return bind_device(scene->ctx);
+}
+int mrt_scene_set_instance_transforms_device(MRTScene scene, int32_t first_mesh_id, size_t count, const void *d_transforms, size_t stride_bytes, void *hip_stream) {
+    MRT_TRY
+    const char *who = "mrt_scene_set_instance_transforms_device";
+    if (int rc = device_instances_prologue(who, scene)) return rc;
+    REQUIRE(first_mesh_id >= 0 && (size_t)first_mesh_id <= scene->dev.in_tlas.size() && count <= scene->dev.in_tlas.size() - (size_t)first_mesh_id, "mrt_scene_set_instance_transforms_device: mesh ids out of range");
+    if (count == 0) return MRT_OK;
+    REQUIRE(d_transforms, "mrt_scene_set_instance_transforms_device: NULL buffer");
+    REQUIRE(stride_bytes >= 64 && stride_bytes % 4 == 0, "mrt_scene_set_instance_transforms_device: the stride must be a multiple of 4 and >= 64");
+    REQUIRE((uintptr_t)d_transforms % 4 == 0, "mrt_scene_set_instance_transforms_device: the buffer must be 4-byte aligned");
+    for (size_t i = (size_t)first_mesh_id; i < (size_t)first_mesh_id + count; i++)
+        if (!scene->dev.in_tlas[i]) {
+            mrt::set_error(std::string(who) + ": instance " + std::to_string(i) + " is not in the TLAS of the last commit (no triangles, or a singular matrix then): mrt_scene_set_instance_transform + mrt_scene_commit brings it in");
+            return MRT_ERR_UNSUPPORTED;
+        }
+    if (int rc = mrt::instances_device_prepare(scene->dev)) return rc;          // (the first call after a commit allocates the workspace; later ones find it)
+    return mrt::device_set_instance_transforms(scene->dev, (uint32_t)first_mesh_id, (uint32_t)count, d_transforms, stride_bytes, (hipStream_t)hip_stream);
+    MRT_CATCH
+}
+int mrt_scene_refit_instances_device(MRTScene scene, void *hip_stream) {
+    MRT_TRY
+    if (int rc = device_instances_prologue("mrt_scene_refit_instances_device", scene)) return rc;
+    if (int rc = mrt::instances_device_prepare(scene->dev)) return rc;
+    return mrt::device_refit_instances(scene->dev, (hipStream_t)hip_stream);
     MRT_CATCH
 }
 int mrt_scene_device_updates_rejected(MRTScene scene, uint64_t *count) {

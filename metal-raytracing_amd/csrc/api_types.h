@@ -27,7 +27,7 @@ struct MRTRenderer_ {
     mrt::Renderer r;
 };
 struct MRTMeshData_ { mrt::MeshData m; };
-int mrt_scene_sync_host_meshes(MRTScene scene);      // api.cpp: HostMesh copies brought up to date after mrt_scene_update_mesh_device (blocks; no-op otherwise)
+int mrt_scene_sync_host_meshes(MRTScene scene);      // api.cpp: HostMesh copies brought up to date after mrt_scene_update_mesh_device (vertices) or mrt_scene_set_instance_transforms_device (matrices); blocks; no-op otherwise
 
 
 #define MRT_TRY try {

@@ -1351,6 +1351,7 @@ struct FlatBuild {
 
 int build_scene(const std::vector<HostMesh> &meshes_in, const BuildOptions &opt, hipStream_t stream, DeviceScene &out, bool only_transforms_changed, bool only_vertices_changed) {
     out.validate = opt.validate != 0;
+    drop_instance_workspace(out);          // (a build: the TLAS the workspace was made for is gone)
     if (opt.instancing) { drop_refit_workspace(out); return build_two_level(meshes_in, opt, stream, out); }
     out.num_inst = 0; out.inst.release(); out.tlas_index.release(); out.wtlas_index.release(); out.tri_packet.release(); out.inst_box.release(); out.tlas_wcap = 0; out.blas_wdepth = 0; out.bnodes.release(); out.h_inst.clear();
     // an instance (mrt_scene_add_instance) takes its geometry from its source mesh; flattening gives every instance its own world-space copy

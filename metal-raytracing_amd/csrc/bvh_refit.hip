@@ -419,6 +419,12 @@ void drop_refit_workspace(DeviceScene &sc) {
 
 int device_updates_rejected(DeviceScene &sc, uint64_t *count) {
     *count = sc.rejected_before;
+    if (sc.inst_ws) {          // a two-level scene: set calls refused by k_inst_check (tlas_refit.hip); it has no refit workspace
+        unsigned long long h = 0;
+        MRT_HIP(hipEventSynchronize(sc.inst_ws->ev_last));
+        MRT_HIP(hipMemcpy(&h, sc.inst_ws->rejected.p, 8, hipMemcpyDeviceToHost));
+        *count += h;
+    }
     if (!sc.refit_ws) return MRT_OK;
     RefitWorkspace &ws = *sc.refit_ws;
     unsigned long long h = 0;

@@ -267,6 +267,23 @@ struct RefitWorkspace {
     ~RefitWorkspace() { if (ev_last) (void)hipEventSynchronize(ev_last); for (hipEvent_t e : {ev_begin, ev_end, ev_last}) if (e) (void)hipEventDestroy(e); }
 };
 
+// What the stream-ordered instance moves (mrt_scene_set_instance_transforms_device / mrt_scene_refit_instances_device, tlas_refit.hip) keep between calls.
+// Made by the first such call after a commit (which may allocate and block), dropped by the next commit's update_tlas and by mrt_scene_destroy.
+struct InstanceWorkspace {
+    DevBuf<uint32_t> words;                                // [0]: sequence number of the last set call the device refused (k_inst_check)
+    DevBuf<unsigned long long> rejected;                   // set calls refused on the device since the workspace was made (sticky)
+    DevBuf<uint32_t> rope_order;                           // the rope TLAS's nodes grouped by depth (DeviceScene::tlas_rope_order)
+    DevBuf<float4> nbox;                                   // the 8-wide TLAS refit's box per node (lo, hi)
+    std::vector<uint32_t> rope_first;                      // first entry of every depth in rope_order
+    std::vector<uint32_t> wide_first;                      // first node of every level of the 8-wide TLAS
+    std::vector<uint8_t> moved;                            // per instance: the HostMesh::xf copy is older than the device's inst_cols
+    hipEvent_t ev_last = nullptr;                          // behind the last set or refit enqueued: what a blocking reader waits for
+    uint32_t seq = 0;                                      // set calls so far
+    InstanceWorkspace() = default;
+    InstanceWorkspace(const InstanceWorkspace &) = delete; InstanceWorkspace &operator=(const InstanceWorkspace &) = delete;
+    ~InstanceWorkspace() { if (ev_last) { (void)hipEventSynchronize(ev_last); (void)hipEventDestroy(ev_last); } }
+};
+
 struct DeviceScene {
     DevBuf<float4> nodes, packets, normals, base_color, materials, inst_cols, wnodes, wpackets;
     uint32_t num_wnodes = 0; int wide_depth = 0;
@@ -292,6 +309,10 @@ struct DeviceScene {
     bool blas_all_wide = false;                                // every BLAS has the 8-wide layout (the shared wnodes / wpackets exist)
     std::vector<float> blas_lo, blas_hi;                       // per BLAS root box (object space), 3 floats each
     float tlas_ms = 0;                                         // host + upload time of the last TLAS build
+    std::vector<uint8_t> in_tlas;                              // per instance: it is a leaf of the last TLAS build (ntri > 0, invertible then)
+    std::vector<uint32_t> tlas_rope_order, tlas_rope_levels;   // rope TLAS: node indices grouped by depth (root first), nodes per depth — what refit_instances walks bottom-up
+    std::vector<uint32_t> tlas_wide_levels;                    // 8-wide TLAS, when resident: nodes per level (BFS numbering from node 0)
+    std::unique_ptr<InstanceWorkspace> inst_ws;                // null until the first mrt_scene_set_instance_transforms_device / _refit_instances_device after a commit
     bool validate = true, validated_blas = false;              // commit-time index validation (two_level.hip validate_layout); BLAS part already checked
     DevBuf<float> g_pos; DevBuf<uint32_t> g_idx, g_recs;       // flattened build: packed object-space positions, indices and submesh records as uploaded (kept: a commit that only changes transforms does not upload them again)
     PinnedBuf stage;                                           // upload staging of build_flat (grow-only, reused by every commit of this scene)
@@ -332,6 +353,13 @@ int resolve_device_refits(DeviceScene &sc, const BuildOptions &opt, hipStream_t 
 int download_stale_meshes(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *pending_found = nullptr);      // blocks; the HostMesh copies of meshes updated on the device, read back from g_pos / normals; pending_found: a mesh was updated on the device and not refitted since (it is marked dirty)
 int device_updates_rejected(DeviceScene &sc, uint64_t *count);      // blocks
 void drop_refit_workspace(DeviceScene &sc);      // (a build: the tree the workspace was made for is gone)
+// tlas_refit.hip: instance moves from device buffers, ordered on the caller's stream
+int instances_device_supported(const DeviceScene &sc, const BuildOptions &opt, const char *who);      // MRT_OK, or MRT_ERR_UNSUPPORTED + message: a flattened scene, a scene without an instance
+int instances_device_prepare(DeviceScene &sc);      // makes sc.inst_ws if it is not there (allocates, uploads the level tables, blocks)
+int device_set_instance_transforms(DeviceScene &sc, uint32_t first, uint32_t count, const void *d_xf, size_t stride, hipStream_t stream);
+int device_refit_instances(DeviceScene &sc, hipStream_t stream);
+int download_moved_transforms(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *moved_found = nullptr);      // blocks; HostMesh::xf of the instances moved on the device, read back from inst_cols
+void drop_instance_workspace(DeviceScene &sc);      // (update_tlas: the TLAS the workspace was made for is gone; the rejected count is kept)
 int upload_lights(const MRTLight *lights, int count, hipStream_t stream, DeviceScene &out);
 
 }  // namespace mrt

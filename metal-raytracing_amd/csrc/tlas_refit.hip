@@ -1,0 +1,308 @@
+// tlas_refit.hip — instances of a two-level scene moved from device buffers, ordered on the caller's stream, for gfx950.
+//
+//   mrt_scene_set_instance_transforms_device   k_inst_check + k_inst_write: new object->world matrices from device memory; per instance its columns (inst_cols), its
+//                                              world->object rows (InstanceDev::w2o) and its padded world box (inst_box) rewritten in place — the device restatement of
+//                                              invert_affine and instance_box of two_level.hip, in double, in their operation order: the host's bits.
+//   mrt_scene_refit_instances_device           k_tlas_rope_level per depth, k_tlas_wide_level per level, bottom-up: the boxes of both TLAS forms follow the instances'
+//                                              world boxes.  The topology is the last commit's (update_tlas); a commit builds the tree again.
+// The launch boundary is the only grid-wide ordering used here: one launch per depth / level, each over at most a few thousand nodes.
+#include "scene_device.h"
+#include <algorithm>
+
+namespace mrt {
+namespace {
+
+inline uint32_t blocks_of(size_t n, size_t per) { return (uint32_t)((n + per - 1) / per); }
+
+// std::min / std::max as two_level.hip's host code evaluates them (the second argument only where it compares strictly beyond the first)
+template <class T> __device__ __forceinline__ T h_min(T a, T b) { return b < a ? b : a; }
+template <class T> __device__ __forceinline__ T h_max(T a, T b) { return a < b ? b : a; }
+
+struct DBox { float lo[3], hi[3]; };
+
+__device__ __forceinline__ uint32_t not_finite(uint32_t bits) { return ((bits & 0x7F800000u) + 0x00800000u) >> 31; }      // exponent all ones
+
+// invert_affine (two_level.hip): the determinant first — what decides whether the matrix is taken at all —, then the rows
+struct Cofactors { double c[3][3], det; };
+__device__ __forceinline__ Cofactors cofactors_of(const float *xf) {
+    const double a00 = xf[0], a10 = xf[1], a20 = xf[2], a01 = xf[4], a11 = xf[5], a21 = xf[6], a02 = xf[8], a12 = xf[9], a22 = xf[10];
+    Cofactors k;
+    k.c[0][0] = a11 * a22 - a12 * a21; k.c[0][1] = a02 * a21 - a01 * a22; k.c[0][2] = a01 * a12 - a02 * a11;
+    k.c[1][0] = a12 * a20 - a10 * a22; k.c[1][1] = a00 * a22 - a02 * a20; k.c[1][2] = a02 * a10 - a00 * a12;
+    k.c[2][0] = a10 * a21 - a11 * a20; k.c[2][1] = a01 * a20 - a00 * a21; k.c[2][2] = a00 * a11 - a01 * a10;
+    k.det = a00 * k.c[0][0] + a01 * k.c[1][0] + a02 * k.c[2][0];
+    return k;
+}
+__device__ __forceinline__ bool invertible(double det) { return fabs(det) > 0.0 && isfinite(det); }
+__device__ __forceinline__ void rows_of(const float *xf, const Cofactors &k, float rows[3][4]) {
+    const double tx = xf[12], ty = xf[13], tz = xf[14];
+    for (int r = 0; r < 3; r++) {
+        const double i0 = k.c[r][0] / k.det, i1 = k.c[r][1] / k.det, i2 = k.c[r][2] / k.det;
+        rows[r][0] = (float)i0; rows[r][1] = (float)i1; rows[r][2] = (float)i2;
+        rows[r][3] = (float)(-(i0 * tx + i1 * ty + i2 * tz));
+    }
+}
+
+// The corner loop and the float padding at the end of instance_box: the box [lo, hi] through the object->world matrix and, with `mi`, through the exact inverse of the float32 rows too.
+__device__ DBox corners_box(const float *xf, const double lo[3], const double hi[3], const double (*mi)[4]) {
+    DBox b;
+    for (int k = 0; k < 3; k++) { b.lo[k] = 3.0e38f; b.hi[k] = -3.0e38f; }
+    for (int c = 0; c < 8; c++) {
+        const double p[3] = {(c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2]};
+        for (int k = 0; k < 3; k++) {
+            const double w = (double)xf[k] * p[0] + (double)xf[4 + k] * p[1] + (double)xf[8 + k] * p[2] + (double)xf[12 + k];
+            b.lo[k] = h_min(b.lo[k], (float)w); b.hi[k] = h_max(b.hi[k], (float)w);
+            if (mi) {
+                const double v = mi[k][0] * p[0] + mi[k][1] * p[1] + mi[k][2] * p[2] + mi[k][3];
+                b.lo[k] = h_min(b.lo[k], nextafterf((float)v, -3.0e38f)); b.hi[k] = h_max(b.hi[k], nextafterf((float)v, 3.0e38f));
+            }
+        }
+    }
+    for (int k = 0; k < 3; k++) {
+        const float m = h_max(fabsf(b.lo[k]), fabsf(b.hi[k])), e = 4e-5f * m + 4e-6f;
+        b.lo[k] -= e; b.hi[k] += e;
+    }
+    return b;
+}
+
+// instance_box (two_level.hip) with the rows: the eight-round fixed point of the growth delta, then the corners through both maps
+__device__ DBox instance_box_dev(const float *xf, const float lo_in[3], const float hi_in[3], const float rows[3][4]) {
+    double lo[3] = {lo_in[0], lo_in[1], lo_in[2]}, hi[3] = {hi_in[0], hi_in[1], hi_in[2]};
+    const double g4 = 4.0 * 0x1p-24 / (1.0 - 4.0 * 0x1p-24);
+    DBox cur = corners_box(xf, lo, hi, nullptr);
+    for (int it = 0; it < 8; it++) {
+        double X[3];
+        for (int j = 0; j < 3; j++) X[j] = 1.1 * h_max(fabs((double)cur.lo[j]), fabs((double)cur.hi[j]));
+        double glo[3], ghi[3];
+        for (int k = 0; k < 3; k++) {
+            const double dk = 1.1 * g4 * (fabs((double)rows[k][0]) * X[0] + fabs((double)rows[k][1]) * X[1] + fabs((double)rows[k][2]) * X[2] + fabs((double)rows[k][3]));
+            lo[k] = (double)lo_in[k] - dk; hi[k] = (double)hi_in[k] + dk;
+            glo[k] = (double)nextafterf((float)lo[k], -3.0e38f); ghi[k] = (double)nextafterf((float)hi[k], 3.0e38f);
+        }
+        const DBox next = corners_box(xf, glo, ghi, nullptr);
+        bool grew = false;
+        for (int k = 0; k < 3; k++) grew = grew || next.lo[k] < cur.lo[k] || next.hi[k] > cur.hi[k];
+        cur = next;
+        if (!grew && it > 0) break;
+    }
+    double mi[3][4];
+    {
+        const double a[3][3] = {{rows[0][0], rows[0][1], rows[0][2]}, {rows[1][0], rows[1][1], rows[1][2]}, {rows[2][0], rows[2][1], rows[2][2]}};
+        const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) + a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++)
+            mi[r][c] = (a[(c + 1) % 3][(r + 1) % 3] * a[(c + 2) % 3][(r + 2) % 3] - a[(c + 1) % 3][(r + 2) % 3] * a[(c + 2) % 3][(r + 1) % 3]) / det;
+        for (int r = 0; r < 3; r++) mi[r][3] = -(mi[r][0] * rows[0][3] + mi[r][1] * rows[1][3] + mi[r][2] * rows[2][3]);
+    }
+    return corners_box(xf, lo, hi, mi);
+}
+
+// ------------------------------------------------------------------ matrices from device memory
+// What mrt_scene_set_instance_transform and update_tlas refuse on the host — a NaN or an infinity anywhere in the 16 floats, a matrix invert_affine does not take — is known here
+// only after every matrix was read, and a call that holds one must change nothing: a half-applied pose set is worse than none, and an instance cannot leave the tree without a
+// rebuild.  So a call is two launches, as §10d's ingest: k_inst_check notes the call's sequence number in words[0], k_inst_write behind it writes only when the word names another call.
+__global__ void k_inst_check(const uint8_t *__restrict__ src, size_t stride, uint32_t count, uint32_t seq, uint32_t *__restrict__ words) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t bad = 0;
+    if (j < count) {
+        const uint32_t *u = reinterpret_cast<const uint32_t *>(src + (size_t)j * stride);
+        float xf[16];
+        for (int k = 0; k < 16; k++) { bad |= not_finite(u[k]); xf[k] = __uint_as_float(u[k]); }
+        if (!bad && !invertible(cofactors_of(xf).det)) bad = 1u;
+    }
+    if (__ballot(bad != 0u) != 0ull && (threadIdx.x & 63u) == 0u) atomicExch(&words[0], seq);      // (every wave that finds one writes the same value)
+}
+__global__ void k_inst_write(const uint8_t *__restrict__ src, size_t stride, uint32_t first, uint32_t count, uint32_t seq, const uint32_t *words, unsigned long long *__restrict__ rejected,
+                             float4 *__restrict__ inst_cols, InstanceDev *__restrict__ inst, float4 *__restrict__ inst_box) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (words[0] == seq) { if (j == 0u) atomicAdd(rejected, 1ull); return; }      // the scene keeps what it had; the caller learns of it from mrt_scene_device_updates_rejected
+    if (j >= count) return;
+    const size_t i = (size_t)first + j;
+    const float *s = reinterpret_cast<const float *>(src + (size_t)j * stride);
+    float xf[16];
+    for (int k = 0; k < 16; k++) xf[k] = s[k];
+    xf[3] = xf[7] = xf[11] = 0.0f; xf[15] = 1.0f;          // (mrt_scene_set_instance_transform forces the last row)
+    float rows[3][4];
+    rows_of(xf, cofactors_of(xf), rows);
+    const float4 blo = inst_box[4 * i], bhi = inst_box[4 * i + 1];          // the root box of its BLAS, object space: resident since the commit
+    const float lo_in[3] = {blo.x, blo.y, blo.z}, hi_in[3] = {bhi.x, bhi.y, bhi.z};
+    const DBox b = instance_box_dev(xf, lo_in, hi_in, rows);
+    for (int c = 0; c < 4; c++) inst_cols[4 * i + c] = make_float4(xf[c * 4 + 0], xf[c * 4 + 1], xf[c * 4 + 2], 0.0f);
+    for (int r = 0; r < 3; r++) inst[i].w2o[r] = make_float4(rows[r][0], rows[r][1], rows[r][2], rows[r][3]);
+    inst_box[4 * i + 2] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.0f); inst_box[4 * i + 3] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.0f);
+}
+
+// ------------------------------------------------------------------ the rope TLAS (nodes, tlas_index): one launch per depth, deepest first
+// order[0 .. count): the nodes of one depth.  A leaf takes the union of the world boxes of its one or two instances, an internal node the union of its children's boxes, which
+// the launch before this one wrote.  The words a and b, and the escape links, are the build's.
+__global__ void k_tlas_rope_level(float4 *__restrict__ nodes, const uint32_t *__restrict__ order, uint32_t count, const uint32_t *__restrict__ tlas_index, const float4 *__restrict__ inst_box) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    const size_t n = order[j];
+    float4 lo = nodes[4 * n], hi = nodes[4 * n + 1];
+    const uint32_t a = __float_as_uint(lo.w), b = __float_as_uint(hi.w);
+    const float BIG = 3.0e38f;
+    float l[3] = {BIG, BIG, BIG}, h[3] = {-BIG, -BIG, -BIG};
+    if (a & NODE_LEAF) {
+        const uint32_t first = a & 0x7FFFFFFFu;
+        for (uint32_t r = 0; r < b; r++) {
+            const size_t i = tlas_index[first + r];
+            const float4 ql = inst_box[4 * i + 2], qh = inst_box[4 * i + 3];
+            l[0] = fminf(l[0], ql.x); l[1] = fminf(l[1], ql.y); l[2] = fminf(l[2], ql.z); h[0] = fmaxf(h[0], qh.x); h[1] = fmaxf(h[1], qh.y); h[2] = fmaxf(h[2], qh.z);
+        }
+    } else {
+        const size_t c[2] = {a, b & NODE_INDEX_MASK};
+        for (int s = 0; s < 2; s++) {
+            const float4 ql = nodes[4 * c[s]], qh = nodes[4 * c[s] + 1];
+            l[0] = fminf(l[0], ql.x); l[1] = fminf(l[1], ql.y); l[2] = fminf(l[2], ql.z); h[0] = fmaxf(h[0], qh.x); h[1] = fmaxf(h[1], qh.y); h[2] = fmaxf(h[2], qh.z);
+        }
+    }
+    lo.x = l[0]; lo.y = l[1]; lo.z = l[2]; hi.x = h[0]; hi.y = h[1]; hi.z = h[2];
+    nodes[4 * n] = lo; nodes[4 * n + 1] = hi;
+}
+
+// ------------------------------------------------------------------ the 8-wide TLAS (wnodes[0, tlas_wcap), wtlas_index): one launch per level, deepest first
+// One thread per node: the box of a leaf child is its instance's world box, that of an internal child the box the level below left in nbox; the node's origin, its power-of-two
+// grid and the children's planes by WideTlasBuilder's rules.  Slot assignment, imask, meta, child_base and tri_base stay.
+__global__ void k_tlas_wide_level(float4 *__restrict__ wnodes, const uint32_t *__restrict__ wtlas_index, const float4 *__restrict__ inst_box, float4 *__restrict__ nbox, uint32_t first, uint32_t count) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    const size_t node = (size_t)first + j, w = WNODE_STRIDE * node;
+    const float4 n0 = wnodes[w], n1 = wnodes[w + 1];
+    const uint32_t imask = __float_as_uint(n0.w) >> 24, cbase = __float_as_uint(n1.x), tbase = __float_as_uint(n1.y), meta[2] = {__float_as_uint(n1.z), __float_as_uint(n1.w)};
+    const float BIG = 3.0e38f;
+    float clo[8][3], chi[8][3]; bool occ[8];
+    float nl[3] = {BIG, BIG, BIG}, nh[3] = {-BIG, -BIG, -BIG};
+    uint32_t rank = 0; bool any = false;
+    for (int sl = 0; sl < 8; sl++) {
+        float4 a = make_float4(0, 0, 0, 0), b = a;
+        occ[sl] = false;
+        if ((imask >> sl) & 1u) {
+            const size_t c = (size_t)cbase + rank++;
+            a = nbox[2 * c]; b = nbox[2 * c + 1]; occ[sl] = true;
+        } else {
+            const uint32_t m = (meta[sl >> 2] >> (8 * (sl & 3))) & 0xFFu;
+            if (m >> 5) {          // a leaf child of the TLAS is one instance
+                const size_t i = wtlas_index[tbase + (m & 31u)];
+                a = inst_box[4 * i + 2]; b = inst_box[4 * i + 3]; occ[sl] = true;
+            }
+        }
+        clo[sl][0] = a.x; clo[sl][1] = a.y; clo[sl][2] = a.z; chi[sl][0] = b.x; chi[sl][1] = b.y; chi[sl][2] = b.z;
+        if (occ[sl]) for (int k = 0; k < 3; k++) { nl[k] = fminf(nl[k], clo[sl][k]); nh[k] = fmaxf(nh[k], chi[sl][k]); }
+        any = any || occ[sl];
+    }
+    if (!any) { nbox[2 * node] = make_float4(n0.x, n0.y, n0.z, 0.0f); nbox[2 * node + 1] = make_float4(n0.x, n0.y, n0.z, 0.0f); return; }      // (a node without children: nothing to move)
+    uint32_t eb[3]; float inv_step[3], step[3];
+    for (int k = 0; k < 3; k++) {
+        const float sdiv = (nh[k] - nl[k]) / 255.0f;
+        const uint32_t bits = __float_as_uint(sdiv);
+        uint32_t e = (bits >> 23) + ((bits & 0x7FFFFFu) ? 1u : 0u);
+        if (e < 1u) e = 1u;
+        if (e > 254u) e = 254u;
+        eb[k] = e; step[k] = __uint_as_float(e << 23); inv_step[k] = __uint_as_float((254u - e) << 23);
+    }
+    uint32_t q[6][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}};
+    for (int sl = 0; sl < 8; sl++) {
+        uint32_t ql[3] = {255, 255, 255}, qh[3] = {0, 0, 0};
+        if (occ[sl]) for (int k = 0; k < 3; k++) {
+            float fl = floorf((clo[sl][k] - nl[k]) * inv_step[k]), fh = ceilf((chi[sl][k] - nl[k]) * inv_step[k]);
+            fl = fminf(fmaxf(fl, 0.0f), 255.0f); fh = fminf(fmaxf(fh, 0.0f), 255.0f);
+            if (nl[k] + fl * step[k] > clo[sl][k] && fl > 0.0f) fl -= 1.0f;
+            if (nl[k] + fh * step[k] < chi[sl][k] && fh < 255.0f) fh += 1.0f;
+            ql[k] = (uint32_t)fl; qh[k] = (uint32_t)fh;
+        }
+        for (int k = 0; k < 3; k++) { q[k][sl >> 2] |= ql[k] << (8 * (sl & 3)); q[3 + k][sl >> 2] |= qh[k] << (8 * (sl & 3)); }
+    }
+    wnodes[w + 0] = make_float4(nl[0], nl[1], nl[2], __uint_as_float(((eb[0] - 127u) & 0xFFu) | (((eb[1] - 127u) & 0xFFu) << 8) | (((eb[2] - 127u) & 0xFFu) << 16) | (imask << 24)));
+    wnodes[w + 2] = make_float4(__uint_as_float(q[0][0]), __uint_as_float(q[0][1]), __uint_as_float(q[1][0]), __uint_as_float(q[1][1]));
+    wnodes[w + 3] = make_float4(__uint_as_float(q[2][0]), __uint_as_float(q[2][1]), __uint_as_float(q[3][0]), __uint_as_float(q[3][1]));
+    wnodes[w + 4] = make_float4(__uint_as_float(q[4][0]), __uint_as_float(q[4][1]), __uint_as_float(q[5][0]), __uint_as_float(q[5][1]));
+    nbox[2 * node] = make_float4(nl[0], nl[1], nl[2], 0.0f); nbox[2 * node + 1] = make_float4(nh[0], nh[1], nh[2], 0.0f);
+}
+
+}  // namespace
+
+int instances_device_supported(const DeviceScene &sc, const BuildOptions &opt, const char *who) {
+    const char *why = nullptr;
+    if (!opt.instancing)
+        why = "flattened scenes (instancing = 0) bake their transforms into world-space triangles: mrt_scene_set_instance_transform + mrt_scene_commit builds them again";
+    else if (sc.num_inst == 0 || sc.h_inst.size() != sc.num_inst || sc.in_tlas.size() != sc.num_inst || sc.tlas_rope_order.empty())
+        why = "the scene has no instance in its TLAS";
+    if (!why) return MRT_OK;
+    set_error(std::string(who) + ": " + why);
+    return MRT_ERR_UNSUPPORTED;
+}
+
+void drop_instance_workspace(DeviceScene &sc) {
+    if (!sc.inst_ws) return;
+    unsigned long long h = 0;
+    if (hipEventSynchronize(sc.inst_ws->ev_last) == hipSuccess && hipMemcpy(&h, sc.inst_ws->rejected.p, 8, hipMemcpyDeviceToHost) == hipSuccess) sc.rejected_before += h; else (void)hipGetLastError();
+    sc.inst_ws.reset();
+}
+
+int instances_device_prepare(DeviceScene &sc) {
+    if (sc.inst_ws) return MRT_OK;
+    std::unique_ptr<InstanceWorkspace> w(new InstanceWorkspace());
+    w->moved.assign(sc.num_inst, 0);
+    uint32_t at = 0;
+    for (uint32_t n : sc.tlas_rope_levels) { w->rope_first.push_back(at); at += n; }
+    at = 0;
+    for (uint32_t n : sc.tlas_wide_levels) { w->wide_first.push_back(at); at += n; }
+    MRT_HIP(w->words.alloc(4)); MRT_HIP(w->rejected.alloc(1));
+    MRT_HIP(w->rope_order.alloc(sc.tlas_rope_order.size())); MRT_HIP(w->nbox.alloc(2 * std::max<size_t>(at, 1)));
+    MRT_HIP(hipMemset(w->words.p, 0, w->words.bytes())); MRT_HIP(hipMemset(w->rejected.p, 0, 8));
+    if (!sc.tlas_rope_order.empty()) MRT_HIP(hipMemcpy(w->rope_order.p, sc.tlas_rope_order.data(), sc.tlas_rope_order.size() * 4, hipMemcpyHostToDevice));
+    MRT_HIP(hipEventCreateWithFlags(&w->ev_last, hipEventDisableTiming));
+    MRT_HIP(hipDeviceSynchronize());          // (the first call after a commit may block: from here on the caller's stream finds the workspace as the lines above left it)
+    MRT_HIP(hipEventRecord(w->ev_last, nullptr));
+    sc.inst_ws = std::move(w);
+    return MRT_OK;
+}
+
+int device_set_instance_transforms(DeviceScene &sc, uint32_t first, uint32_t count, const void *d_xf, size_t stride, hipStream_t stream) {
+    InstanceWorkspace &ws = *sc.inst_ws;
+    if (++ws.seq == 0u) ws.seq = 1u;          // (0 is what words[0] starts as)
+    const dim3 grid(blocks_of(count, 64)), block(64);
+    hipLaunchKernelGGL(k_inst_check, grid, block, 0, stream, static_cast<const uint8_t *>(d_xf), stride, count, ws.seq, ws.words.p);
+    hipLaunchKernelGGL(k_inst_write, grid, block, 0, stream, static_cast<const uint8_t *>(d_xf), stride, first, count, ws.seq, (const uint32_t *)ws.words.p, ws.rejected.p, sc.inst_cols.p, sc.inst.p, sc.inst_box.p);
+    MRT_HIP(hipGetLastError());
+    MRT_HIP(hipEventRecord(ws.ev_last, stream));
+    // (marked for a call the device refuses too: the host cannot know without a read-back, and the columns it then reads back are the ones it has)
+    std::fill(ws.moved.begin() + first, ws.moved.begin() + first + count, (uint8_t)1);
+    return MRT_OK;
+}
+
+int device_refit_instances(DeviceScene &sc, hipStream_t stream) {
+    InstanceWorkspace &ws = *sc.inst_ws;
+    for (size_t d = sc.tlas_rope_levels.size(); d-- > 0;)
+        hipLaunchKernelGGL(k_tlas_rope_level, dim3(blocks_of(sc.tlas_rope_levels[d], 64)), dim3(64), 0, stream, sc.nodes.p, (const uint32_t *)(ws.rope_order.p + ws.rope_first[d]), sc.tlas_rope_levels[d],
+                           (const uint32_t *)sc.tlas_index.p, (const float4 *)sc.inst_box.p);
+    if (sc.num_wnodes)          // the 8-wide TLAS is resident (update_tlas)
+        for (size_t L = sc.tlas_wide_levels.size(); L-- > 0;)
+            hipLaunchKernelGGL(k_tlas_wide_level, dim3(blocks_of(sc.tlas_wide_levels[L], 64)), dim3(64), 0, stream, sc.wnodes.p, (const uint32_t *)sc.wtlas_index.p, (const float4 *)sc.inst_box.p, ws.nbox.p,
+                               ws.wide_first[L], sc.tlas_wide_levels[L]);
+    MRT_HIP(hipGetLastError());
+    MRT_HIP(hipEventRecord(ws.ev_last, stream));
+    return MRT_OK;
+}
+
+// HostMesh::xf of an instance moved on the device is stale: whoever reads it (a commit in all its branches, the replication of a scene for a device group) calls this first.
+int download_moved_transforms(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *moved_found) {
+    if (moved_found) *moved_found = false;
+    if (!sc.inst_ws) return MRT_OK;
+    InstanceWorkspace &ws = *sc.inst_ws;
+    const size_t known = std::min(ws.moved.size(), meshes.size());          // (meshes are only ever appended)
+    if (std::find(ws.moved.begin(), ws.moved.begin() + known, (uint8_t)1) == ws.moved.begin() + known) return MRT_OK;
+    MRT_HIP(hipEventSynchronize(ws.ev_last));
+    std::vector<float4> cols(4 * known);
+    MRT_HIP(hipMemcpy(cols.data(), sc.inst_cols.p, cols.size() * 16, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < known; i++) {
+        if (!ws.moved[i]) continue;
+        float *xf = meshes[i].xf;
+        for (int c = 0; c < 4; c++) { xf[c * 4 + 0] = cols[4 * i + c].x; xf[c * 4 + 1] = cols[4 * i + c].y; xf[c * 4 + 2] = cols[4 * i + c].z; xf[c * 4 + 3] = c == 3 ? 1.0f : 0.0f; }
+        ws.moved[i] = 0;
+    }
+    if (moved_found) *moved_found = true;
+    return MRT_OK;
+}
+
+}  // namespace mrt

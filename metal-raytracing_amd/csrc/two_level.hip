@@ -108,6 +108,7 @@ struct TlasBuilder {
     const std::vector<Box> &boxes;
     std::vector<uint32_t> order;          // instance ids, leaf order
     std::vector<float4> nodes;            // 4 per node
+    std::vector<uint32_t> node_depth;     // per node, the root's = 1: what a refit of the boxes walks bottom-up (tlas_refit.hip)
     int depth = 0;
     explicit TlasBuilder(const std::vector<Box> &b) : boxes(b) {}
     static float4 f4(float x, float y, float z, uint32_t w) { float f; memcpy(&f, &w, 4); return make_float4(x, y, z, f); }
@@ -124,7 +125,7 @@ struct TlasBuilder {
             }
         }
         const uint32_t me = (uint32_t)(nodes.size() / 4);
-        nodes.resize(nodes.size() + 4);
+        nodes.resize(nodes.size() + 4); node_depth.push_back((uint32_t)d);
         uint32_t a, bb;
         if (count <= 2) { a = NODE_LEAF | first; bb = count; }
         else {
@@ -169,6 +170,7 @@ struct WideTlasBuilder {
     std::vector<BNode> bn;
     std::vector<uint32_t> order;          // instance ids, leaf-child order
     std::vector<float4> nodes;            // 5 per wide node
+    std::vector<uint32_t> levels;         // nodes per level (BFS numbering): what a refit of the boxes walks bottom-up (tlas_refit.hip)
     int depth = 0;
     explicit WideTlasBuilder(const std::vector<Box> &b) : boxes(b) {}
     static float area(const Box &q) { const float x = q.hi[0] - q.lo[0], y = q.hi[1] - q.lo[1], z = q.hi[2] - q.lo[2]; return x * y + y * z + z * x; }
@@ -201,7 +203,7 @@ struct WideTlasBuilder {
         std::vector<int> level{root};                 // binary nodes that become the wide nodes of this level
         uint32_t base = 0;
         while (!level.empty()) {
-            depth++;
+            depth++; levels.push_back((uint32_t)level.size());
             std::vector<int> next;
             const uint32_t next_base = base + (uint32_t)level.size();
             nodes.resize(nodes.size() + 5 * level.size());
@@ -414,6 +416,7 @@ int update_tlas(const std::vector<HostMesh> &meshes, hipStream_t stream, DeviceS
     const auto t0 = std::chrono::steady_clock::now();
     const size_t I = meshes.size();
     if (out.h_inst.size() != I) { set_error("update_tlas: the scene's instance list changed; commit rebuilds it"); return MRT_ERR_STATE; }
+    drop_instance_workspace(out);          // (made for the tree this call replaces)
     std::vector<Box> boxes(I);
     std::vector<uint32_t> live;
     std::vector<float4> h_cols(std::max<size_t>(I * 4, 4));
@@ -435,6 +438,15 @@ int update_tlas(const std::vector<HostMesh> &meshes, hipStream_t stream, DeviceS
     TlasBuilder tb(boxes);
     tb.order = live;
     if (!live.empty()) tb.build(0, (uint32_t)live.size(), NODE_TERM, 1);
+    // what mrt_scene_refit_instances_device needs of this tree: which instances are its leaves, its nodes by depth
+    out.in_tlas.assign(I, 0); for (uint32_t i : live) out.in_tlas[i] = 1;
+    out.tlas_rope_levels.assign((size_t)tb.depth, 0u); out.tlas_rope_order.resize(tb.node_depth.size()); out.tlas_wide_levels.clear();
+    {
+        for (uint32_t d : tb.node_depth) out.tlas_rope_levels[d - 1]++;
+        std::vector<uint32_t> at(out.tlas_rope_levels.size(), 0u);
+        for (size_t d = 1; d < at.size(); d++) at[d] = at[d - 1] + out.tlas_rope_levels[d - 1];
+        for (size_t n = 0; n < tb.node_depth.size(); n++) out.tlas_rope_order[at[tb.node_depth[n] - 1]++] = (uint32_t)n;
+    }
     MRT_HIP(out.inst_box.alloc(h_box.size()));
     MRT_HIP(hipMemcpyAsync(out.inst_box.p, h_box.data(), h_box.size() * 16, hipMemcpyHostToDevice, stream));
     MRT_HIP(out.inst.alloc(std::max<size_t>(I, 1)));
@@ -455,8 +467,12 @@ int update_tlas(const std::vector<HostMesh> &meshes, hipStream_t stream, DeviceS
             MRT_HIP(out.wtlas_index.alloc(std::max<size_t>(wb.order.size(), 1)));
             MRT_HIP(hipMemcpyAsync(out.wtlas_index.p, wb.order.data(), wb.order.size() * 4, hipMemcpyHostToDevice, stream));
             MRT_HIP(hipMemcpyAsync(out.wnodes.p, wb.nodes.data(), wb.nodes.size() * 16, hipMemcpyHostToDevice, stream));
+            // the slots this tree does not use are empty nodes, as build_two_level left them: a TLAS that lost an instance (a matrix gone singular) must not leave nodes of the
+            // larger tree behind, whose instance slots validate_layout would find outside the shorter wtlas_index
+            if (wn < out.tlas_wcap) MRT_HIP(hipMemsetAsync(out.wnodes.p + wb.nodes.size(), 0, (out.tlas_wcap - wn) * WNODE_STRIDE * 16, stream));
             out.num_wnodes = (uint32_t)(out.wnodes.n / WNODE_STRIDE);
             out.wide_depth = wb.depth + 1 + out.blas_wdepth;
+            out.tlas_wide_levels = wb.levels;
         }
     }
     MRT_HIP(hipStreamSynchronize(stream));

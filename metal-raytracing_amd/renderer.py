@@ -182,9 +182,30 @@ class DeviceScene:
         """The refit of the resident tree after update_mesh_device, enqueued on the stream (as a commit after update_mesh computes it, without the commit's copies and waits)."""
         check(lib.mrt_scene_refit_device(self.handle, C.c_void_p(self._stream_handle(stream))))
 
+    def set_instance_transforms_device(self, first_mesh_id, transforms, stream=None):
+        """Instances of a two-level scene (option instancing = 1) moved from the GPU, ordered on a stream: transforms is a torch.float32 (n, 16) tensor on the context's
+        device, column-major like set_instance_transform, for the mesh ids first_mesh_id .. first_mesh_id + n - 1; rows are contiguous and any multiple of 4 bytes apart
+        (x[:, :16] of an (n, 20) tensor is fine), nothing is copied.  Call refit_instances_device() afterwards (several set calls may share one).  A NaN, an infinity or
+        a singular matrix anywhere in the call leaves the scene as it was and is counted in device_updates_rejected.  The TLAS keeps the shape of the last commit;
+        commit() builds it again from the poses the device holds.  stream: as update_mesh_device takes it.  Anything else than such a tensor raises ValueError."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        t = transforms
+        if not isinstance(t, torch.Tensor) or t.device != dev:
+            raise ValueError(f"transforms must be a torch tensor on {dev}")
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 16 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < 16):
+            raise ValueError("transforms must be a torch.float32 tensor of shape (n, 16) with contiguous rows (a slice of a wider tensor is fine)")
+        n = t.shape[0]
+        check(lib.mrt_scene_set_instance_transforms_device(self.handle, int(first_mesh_id), n, C.c_void_p(t.data_ptr() if n else None), (t.stride(0) if n > 1 else 16) * 4,
+                                                           C.c_void_p(self._stream_handle(stream))))
+
+    def refit_instances_device(self, stream=None):
+        """The refit of both TLAS forms after set_instance_transforms_device, enqueued on the stream: boxes bottom-up, topology kept."""
+        check(lib.mrt_scene_refit_instances_device(self.handle, C.c_void_p(self._stream_handle(stream))))
+
     @property
     def device_updates_rejected(self):
-        """update_mesh_device calls refused on the device for a NaN or an infinity since the scene was created (blocks until the calls enqueued so far have run)."""
+        """update_mesh_device / set_instance_transforms_device calls refused on the device since the scene was created (blocks until the calls enqueued so far have run)."""
         v = C.c_uint64()
         check(lib.mrt_scene_device_updates_rejected(self.handle, C.byref(v)))
         return v.value
