@@ -126,6 +126,13 @@ struct Scene {                                                       // Scene.sw
         check(mrt_scene_set_instance_transforms_device(committed, firstMeshId, count, deviceTransforms, strideBytes, hipStream));
     }
     static void refitInstancesDevice(MRTScene committed, void *hipStream) { check(mrt_scene_refit_instances_device(committed, hipStream)); }
+    // Stream-ordered deformation of a mesh inside a committed two-level MRTScene (mrt_scene_update_blas_device / mrt_scene_refit_blas_device): object-space vertices of a
+    // source mesh from device memory, then its BLAS, its instances' boxes and the TLAS refitted on the stream.
+    static void updateBlasDevice(MRTScene committed, int32_t meshId, const void *devicePositions, size_t positionStrideBytes, const void *deviceNormals, size_t normalStrideBytes,
+                                 size_t vertexCount, void *hipStream) {
+        check(mrt_scene_update_blas_device(committed, meshId, devicePositions, positionStrideBytes, deviceNormals, normalStrideBytes, vertexCount, hipStream));
+    }
+    static void refitBlasDevice(MRTScene committed, void *hipStream) { check(mrt_scene_refit_blas_device(committed, hipStream)); }
     void updateUniforms(int width, int height) { camera = setupCamera(width, height); }   // Scene.swift:36-38
     static Camera setupCamera(int width, int height) { Camera c; check(mrt_default_camera(width, height, &c)); return c; }   // :40-57
     static Light setupLight() {                                      // :59-67

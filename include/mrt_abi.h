@@ -269,7 +269,7 @@ int mrt_scene_intersect_any_device(MRTScene scene, const void *d_rays, size_t n,
  *   would; a later mrt_scene_commit builds or refits from the vertices the device holds (it reads them back first; an update that no mrt_scene_refit_device followed
  *   counts as a vertex change, so a commit with nothing else changed refits); mrt_scene_update_mesh on such a mesh simply replaces them.  Scene option "refit_max_cost_ratio" is NOT acted on here — that would take a read-back; the statistics carry the signal and the next mrt_scene_commit may act.
  * MRT_ERR_STATE: the scene is not committed, or host-side changes wait for a commit.  MRT_ERR_INVALID_ARGUMENT: NULL scene, NULL or misaligned buffers, bad strides,
- * mesh_id out of range or an instance (update its source), vertex_count other than the mesh's.  MRT_ERR_UNSUPPORTED: a two-level scene (instancing = 1), scene option
+ * mesh_id out of range or an instance (update its source), vertex_count other than the mesh's.  MRT_ERR_UNSUPPORTED: a two-level scene (instancing = 1: mrt_scene_update_blas_device below), scene option
  * refit = 0, or a resident tree the refit cannot take (an empty scene).                                                                                              */
 int mrt_scene_update_mesh_device(MRTScene scene, int32_t mesh_id, const void *d_positions, size_t pos_stride_bytes,
                                  const void *d_normals, size_t nrm_stride_bytes, size_t vertex_count, void *hip_stream);
@@ -298,6 +298,32 @@ int mrt_scene_device_updates_rejected(MRTScene scene, uint64_t *count);
  * outside the TLAS.  count == 0: MRT_OK, nothing is launched.                                                                                                          */
 int mrt_scene_set_instance_transforms_device(MRTScene scene, int32_t first_mesh_id, size_t count, const void *d_transforms_colmajor_4x4, size_t stride_bytes, void *hip_stream);
 int mrt_scene_refit_instances_device(MRTScene scene, void *hip_stream);
+/* Deforming a mesh INSIDE a two-level scene (scene option instancing = 1) from DEVICE buffers, ordered on a stream of the caller's: a skinned character or
+ * cloth among rigid instances, one deforming BLAS shared by many instances.  mrt_scene_update_blas_device replaces the OBJECT-space vertices of one source mesh of a
+ * COMMITTED two-level scene with vertex_count strided float3 positions and normals read from device memory (strides >= 12, multiples of 4; 4-byte aligned pointers): the
+ * vertices exist once, in the mesh's BLAS, and every instance of it shares them.  mrt_scene_refit_blas_device then, for every mesh updated since the last refit, refits that
+ * BLAS in place in both layouts exactly as the commit after mrt_scene_update_mesh does (same kernels, same bits), gives each of its instances in the TLAS the BLAS's new
+ * root box and a padded world box recomputed from it under the instance's CURRENT matrix — poses set by mrt_scene_set_instance_transforms_device are honoured, so a caller
+ * who moves poses and vertices in one step needs only this refit —, and refits both TLAS forms with their topology kept.  Several updates may precede one refit; a refit
+ * with nothing updated changes no answer.  Both calls enqueue kernels on hip_stream (taken literally: 0 is HIP's null stream) and return.  The FIRST of them after a commit
+ * creates the BLAS workspace (the meshes' positions and indices, about 24 B per vertex and triangle, + scratch of about 100 B per triangle of the largest BLAS + 32 B per
+ * 8-wide node; it allocates and may block), and the instance workspace of the entries above if it is absent; every later call allocates nothing, copies nothing from host
+ * memory and synchronises neither the stream nor the device.  The workspace stays over a commit that only changes transforms and goes with every other commit.
+ *   Validation happens on the device, as for mrt_scene_update_mesh_device: a call whose positions or normals hold a NaN or an infinity writes NOTHING and is counted in
+ *   the count mrt_scene_device_updates_rejected returns (the sum over all the device entries of this scene).
+ *   The caller owes what mrt_scene_update_mesh_device asks for: live buffers on the scene's device, no use of the scene on another stream that is not ordered behind the refit.
+ *   The host side stays truthful: mrt_scene_stats (which then blocks on the last refit) reports refits, wide_cost, sah_cost, leaf_growth and build_ms as the host path would;
+ *   a later mrt_scene_commit (and the replication of the scene for a device group) reads the vertices and the BLASes' root boxes back first; an update that no refit followed
+ *   counts as a vertex change, so a commit with nothing else changed refits; mrt_scene_update_mesh on such a mesh simply replaces them.  Scene option
+ *   "refit_max_cost_ratio" is NOT acted on here; the statistics carry the signal.
+ * MRT_ERR_STATE: the scene is not committed, or host-side changes wait for a commit.  MRT_ERR_INVALID_ARGUMENT: NULL scene, NULL or misaligned buffers, bad strides,
+ * mesh_id out of range or an instance (update its source mesh), vertex_count other than the mesh's.  MRT_ERR_UNSUPPORTED: a flattened scene (mrt_scene_update_mesh_device
+ * is for those), scene option refit = 0, a scene whose BLASes do not all have the 8-wide layout (wide = 0), a mesh whose BLAS has no 8-wide nodes or no triangles;
+ * mrt_scene_refit_blas_device also for a scene with no instance in the TLAS of the last commit (as mrt_scene_refit_instances_device: nothing of it can be hit, and nothing
+ * is refitted — updates made before stay pending and the next mrt_scene_commit applies them).                                                                          */
+int mrt_scene_update_blas_device(MRTScene scene, int32_t mesh_id, const void *d_positions, size_t pos_stride_bytes,
+                                 const void *d_normals, size_t nrm_stride_bytes, size_t vertex_count, void *hip_stream);
+int mrt_scene_refit_blas_device(MRTScene scene, void *hip_stream);
 
 /* ---------------------------------------------------------------- host-side geometry helpers
  * (no GPU needed) — the library's OBJ/MTL reader standing in for ModelIO (Model.swift:16-21,

@@ -158,6 +158,8 @@ SIGNATURES = {
     "mrt_scene_device_updates_rejected": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "mrt_scene_set_instance_transforms_device": (C.c_int, [_P, _I32, _SZ, _P, _SZ, _P]),
     "mrt_scene_refit_instances_device": (C.c_int, [_P, _P]),
+    "mrt_scene_update_blas_device": (C.c_int, [_P, _I32, _P, _SZ, _P, _SZ, _SZ, _P]),
+    "mrt_scene_refit_blas_device": (C.c_int, [_P, _P]),
     "mrt_obj_load": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "mrt_dragon_proxy": (C.c_int, [C.POINTER(_P)]),
     "mrt_dragon_proxy_irregular": (C.c_int, [C.POINTER(_P)]),

@@ -29,12 +29,23 @@ static int sync_host_meshes(MRTScene scene) {
     bool pending = false;
     int rc = mrt::download_stale_meshes(scene->meshes, scene->dev, &pending);
     if (!rc && pending && scene->committed) scene->only_vertices_changed = true;
+    // a two-level scene whose BLASes were refitted on the device (mrt_scene_refit_blas_device): their root boxes — update_tlas builds the TLAS from them — and statistics first,
+    // then the vertices of the meshes updated there
+    if (!rc) rc = mrt::resolve_blas_refits(scene->dev, scene->opt, scene->ctx->stream);
+    bool blas_pending = false;
+    if (!rc) rc = mrt::download_stale_blas_meshes(scene->meshes, scene->dev, &blas_pending);
+    if (!rc && blas_pending) {          // a mesh updated by mrt_scene_update_blas_device that no refit followed: a vertex change, whatever else waits for the commit
+        if (scene->committed) scene->only_vertices_changed = true;
+        else if (scene->only_transforms_changed) { scene->only_vertices_changed = false; scene->only_transforms_changed = false; }      // mrt_scene_set_instance_transform since: vertices AND transforms, a full build
+    }
     // instances moved on the device (mrt_scene_set_instance_transforms_device): their HostMesh::xf read back — a transform change like mrt_scene_set_instance_transform's
     bool moved = false;
     if (!rc) rc = mrt::download_moved_transforms(scene->meshes, scene->dev, &moved);
     if (!rc && moved) {
-        if (scene->committed) scene->only_transforms_changed = true;
-        else if (scene->only_vertices_changed) { scene->only_vertices_changed = false; scene->only_transforms_changed = false; }      // vertices AND transforms changed: a full build
+        // vertices AND transforms changed: a full build.  A scene still `committed` can be here too — its vertex change was found two lines up (poses and an unrefitted
+        // update, both on the device) —, and neither flag set with `committed` set is a full build for mrt_scene_commit
+        if (scene->only_vertices_changed) { scene->only_vertices_changed = false; scene->only_transforms_changed = false; }
+        else if (scene->committed) scene->only_transforms_changed = true;
     }
     return rc;
 }
@@ -43,7 +54,7 @@ static int sync_host_meshes(MRTScene scene) {
 // mrt_scene_set_instance_transforms_device): for readers of MRTScene_::meshes outside this file.
 // Leaves the calling thread's current device as it found it.
 int mrt_scene_sync_host_meshes(MRTScene scene) {
-    if (!scene->dev.refit_ws && !scene->dev.inst_ws) return MRT_OK;
+    if (!scene->dev.refit_ws && !scene->dev.inst_ws && !scene->dev.blas_ws) return MRT_OK;
     int before = 0; MRT_HIP(hipGetDevice(&before));
     int rc = bind_device(scene->ctx);
     if (!rc) rc = sync_host_meshes(scene);
@@ -294,6 +305,7 @@ int mrt_scene_update_mesh(MRTScene scene, int32_t mesh_id, const float *position
         for (int k = 0; k < 3; k++) { m.positions[i * 3 + k] = p[k]; m.normals[i * 3 + k] = n[k]; }
     }
     if (scene->dev.refit_ws && (size_t)mesh_id < scene->dev.refit_ws->host_stale.size()) scene->dev.refit_ws->host_stale[(size_t)mesh_id] = 0;      // (replaced on the device before: this copy is the newer one now)
+    if (scene->dev.blas_ws && (size_t)mesh_id < scene->dev.blas_ws->blas_of_mesh.size() && scene->dev.blas_ws->blas_of_mesh[(size_t)mesh_id] >= 0) scene->dev.blas_ws->host_stale[(size_t)scene->dev.blas_ws->blas_of_mesh[(size_t)mesh_id]] = 0;
     // a committed scene in which nothing else changes until the next commit keeps its tree: that commit refits (flattened scenes with the 8-wide layout; others build again)
     m.dirty = true;
     if (scene->committed) scene->only_vertices_changed = true;                         // the first change since the commit
@@ -325,6 +337,10 @@ int mrt_scene_stats(MRTScene scene, MRTSceneStats *out) {
     if (scene->dev.refit_ws && scene->dev.refit_ws->unresolved) {          // refits enqueued by mrt_scene_refit_device: wait for the last one and read what it left (the only place this blocks)
         int rc = bind_device(scene->ctx); if (rc) return rc;
         rc = mrt::resolve_device_refits(scene->dev, scene->opt, scene->ctx->stream); if (rc) return rc;
+    }
+    if (scene->dev.blas_ws && scene->dev.blas_ws->unresolved) {          // ... or by mrt_scene_refit_blas_device
+        int rc = bind_device(scene->ctx); if (rc) return rc;
+        rc = mrt::resolve_blas_refits(scene->dev, scene->opt, scene->ctx->stream); if (rc) return rc;
     }
     *out = scene->dev.stats;
     out->wide_layout = scene->dev.num_wnodes > 0 ? 1 : 0; out->wide_depth = scene->dev.wide_depth;
@@ -439,6 +455,48 @@ int mrt_scene_refit_instances_device(MRTScene scene, void *hip_stream) {
     if (int rc = device_instances_prologue("mrt_scene_refit_instances_device", scene)) return rc;
     if (int rc = mrt::instances_device_prepare(scene->dev)) return rc;
     return mrt::device_refit_instances(scene->dev, (hipStream_t)hip_stream);
+    MRT_CATCH
+}
+
+// Meshes of a two-level scene deformed from device buffers (bvh_refit.hip, tlas_refit.hip)
+static int device_blas_prologue(const char *who, MRTScene scene) {
+    if (!scene) { mrt::set_error(std::string(who) + ": scene is NULL"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (!scene->committed) {
+        mrt::set_error(std::string(who) + (scene->only_vertices_changed || scene->only_transforms_changed ? ": host-side changes are pending (mrt_scene_commit first)" : ": scene not committed"));
+        return MRT_ERR_STATE;
+    }
+    if (int rc = mrt::blas_device_supported(scene->dev, scene->opt, scene->meshes.size(), who)) return rc;
+    return bind_device(scene->ctx);
+}
+int mrt_scene_update_blas_device(MRTScene scene, int32_t mesh_id, const void *d_positions, size_t pos_stride, const void *d_normals, size_t nrm_stride, size_t nverts, void *hip_stream) {
+    MRT_TRY
+    const char *who = "mrt_scene_update_blas_device";
+    if (int rc = device_blas_prologue(who, scene)) return rc;
+    REQUIRE(d_positions && d_normals, "mrt_scene_update_blas_device: NULL buffers");
+    REQUIRE(mesh_id >= 0 && (size_t)mesh_id < scene->meshes.size(), "mrt_scene_update_blas_device: mesh_id out of range");
+    REQUIRE(pos_stride >= 12 && nrm_stride >= 12 && pos_stride % 4 == 0 && nrm_stride % 4 == 0, "mrt_scene_update_blas_device: strides must be multiples of 4 and >= 12");
+    REQUIRE((uintptr_t)d_positions % 4 == 0 && (uintptr_t)d_normals % 4 == 0, "mrt_scene_update_blas_device: buffers must be 4-byte aligned");
+    const mrt::HostMesh &m = scene->meshes[(size_t)mesh_id];
+    REQUIRE(m.source < 0, "mrt_scene_update_blas_device: an instance has no vertices of its own (update its source mesh)");
+    REQUIRE(nverts * 3 == m.positions.size(), "mrt_scene_update_blas_device: the vertex count must stay the same (the topology is kept)");
+    size_t b = 0;
+    while (b < scene->dev.blas_ranges.size() && scene->dev.blas_ranges[b].src_mesh != (uint32_t)mesh_id) b++;
+    if (b == scene->dev.blas_ranges.size() || !mrt::blas_refittable(scene->dev.blas_ranges[b], nverts) || scene->dev.blas_ranges[b].ntri == 0) {
+        mrt::set_error(std::string(who) + ": the BLAS of mesh " + std::to_string(mesh_id) + " has no 8-wide nodes or no triangles: there is nothing to refit");
+        return MRT_ERR_UNSUPPORTED;
+    }
+    if (int rc = mrt::blas_device_prepare(scene->meshes, scene->dev)) return rc;          // (the first call after a commit allocates the workspace; later ones find it)
+    return mrt::device_update_blas(scene->dev, b, d_positions, pos_stride, d_normals, nrm_stride, nverts, (hipStream_t)hip_stream);
+    MRT_CATCH
+}
+int mrt_scene_refit_blas_device(MRTScene scene, void *hip_stream) {
+    MRT_TRY
+    const char *who = "mrt_scene_refit_blas_device";
+    if (int rc = device_blas_prologue(who, scene)) return rc;
+    if (int rc = mrt::instances_device_supported(scene->dev, scene->opt, who)) return rc;          // (its last step is the TLAS refit of §10e)
+    if (int rc = mrt::blas_device_prepare(scene->meshes, scene->dev)) return rc;
+    if (int rc = mrt::instances_device_prepare(scene->dev)) return rc;
+    return mrt::device_refit_blas(scene->dev, (hipStream_t)hip_stream);
     MRT_CATCH
 }
 int mrt_scene_device_updates_rejected(MRTScene scene, uint64_t *count) {

@@ -312,6 +312,20 @@ int apply_refit_result(DeviceScene &sc, const BuildOptions &opt, bool wide, floa
     return MRT_OK;
 }
 
+// The index list and the submesh records of a BLAS's mesh in the BLAS's own numbering (one "instance", vertices from 0), appended to `recs` / `idx` with index offsets
+// relative to where this mesh's indices start: what k_flatten reads in refit_blas and in the stream-ordered BLAS refit.  Returns the triangle count.
+static size_t blas_geometry(const HostMesh &g, std::vector<SubRec> &recs, std::vector<uint32_t> &idx) {
+    const size_t idx0 = idx.size();
+    size_t tb = 0;
+    for (size_t s = 0; s < g.sub_indices.size(); s++) {
+        const auto &ix = g.sub_indices[s];
+        if (ix.empty()) continue;
+        recs.push_back(SubRec{(uint32_t)tb, (uint32_t)(ix.size() / 3), (uint32_t)(idx.size() - idx0), 0u, 0u, (uint32_t)s});
+        idx.insert(idx.end(), ix.begin(), ix.end()); tb += ix.size() / 3;
+    }
+    return tb;
+}
+
 // Refit of ONE BLAS of a two-level scene in the scene's shared arrays (two_level.hip refit_two_level): the mesh's new object-space triangles (k_flatten under the identity),
 // the BLAS's packets of both layouts rewritten by the id each carries, its 8-wide nodes [wnode_base, + wnodes) bottom-up level by level (k_refit_wide_level: child and packet
 // indices in there are absolute, the triangle arrays are the BLAS's own), its rope nodes by k_rope_refit, its normals.  Leaves the BLAS's root box (object space) in root_lo / root_hi.
@@ -320,14 +334,7 @@ int refit_blas(const HostMesh &g, const BlasRange &br, hipStream_t stream, Devic
     if (T == 0 || br.wnodes == 0 || g.normals.size() != g.positions.size()) { set_error("refit_blas: nothing to refit"); return MRT_ERR_STATE; }
     static_assert(WPK == 3, "k_refit_wide_packets serves both packet arrays at a stride of three float4");
     std::vector<SubRec> recs; std::vector<uint32_t> idx; idx.reserve(3 * T);
-    size_t tb = 0;
-    for (size_t s = 0; s < g.sub_indices.size(); s++) {
-        const auto &ix = g.sub_indices[s];
-        if (ix.empty()) continue;
-        recs.push_back(SubRec{(uint32_t)tb, (uint32_t)(ix.size() / 3), (uint32_t)idx.size(), 0u, 0u, (uint32_t)s});
-        idx.insert(idx.end(), ix.begin(), ix.end()); tb += ix.size() / 3;
-    }
-    if (tb != T) { set_error("refit_blas: the mesh's triangle count changed"); return MRT_ERR_STATE; }
+    if (blas_geometry(g, recs, idx) != T) { set_error("refit_blas: the mesh's triangle count changed"); return MRT_ERR_STATE; }
     std::vector<float4> h_nrm(nv);
     for (size_t v = 0; v < nv; v++) h_nrm[v] = make_float4(g.normals[3 * v], g.normals[3 * v + 1], g.normals[3 * v + 2], 0.0f);
     const float4 ident[4] = {make_float4(1, 0, 0, 0), make_float4(0, 1, 0, 0), make_float4(0, 0, 1, 0), make_float4(0, 0, 0, 0)};
@@ -401,7 +408,7 @@ int device_refit_supported(const DeviceScene &sc, const BuildOptions &opt, const
     const RefitLayouts there = refit_layouts(sc, opt);
     const bool wide_there = there.wide, rope_there = there.rope;
     const char *why = nullptr;
-    if (opt.instancing || sc.num_inst) why = "two-level scenes (instancing = 1) are not refitted from device buffers: their instance boxes are computed on the host";
+    if (opt.instancing || sc.num_inst) why = "two-level scenes (instancing = 1) are not refitted by this entry: mrt_scene_update_blas_device + mrt_scene_refit_blas_device deform their meshes";
     else if (!opt.refit) why = "scene option refit = 0: every change builds the tree again (mrt_scene_update_mesh + mrt_scene_commit)";
     else if (T == 0 || sc.refit_triangles != T || !(wide_there || rope_there) || !(wide_there || !opt.wide) || !sc.g_pos.p || !sc.g_idx.p || !sc.g_recs.p || !sc.normals.p || !sc.tri_shade.p)
         why = "the resident tree cannot be refitted (an empty scene, or one that lost its 8-wide layout): mrt_scene_update_mesh + mrt_scene_commit builds it";
@@ -412,25 +419,25 @@ int device_refit_supported(const DeviceScene &sc, const BuildOptions &opt, const
 
 void drop_refit_workspace(DeviceScene &sc) {
     if (!sc.refit_ws) return;
-    uint64_t n = 0;
-    if (device_updates_rejected(sc, &n) == MRT_OK) sc.rejected_before = n; else (void)hipGetLastError();
+    unsigned long long h = 0;
+    if (hipEventSynchronize(sc.refit_ws->ev_last) == hipSuccess && hipMemcpy(&h, sc.refit_ws->rejected.p, 8, hipMemcpyDeviceToHost) == hipSuccess) sc.rejected_before += h; else (void)hipGetLastError();
     sc.refit_ws.reset();
 }
 
 int device_updates_rejected(DeviceScene &sc, uint64_t *count) {
     *count = sc.rejected_before;
-    if (sc.inst_ws) {          // a two-level scene: set calls refused by k_inst_check (tlas_refit.hip); it has no refit workspace
+    // every workspace that exists has a counter of its own: set calls refused by k_inst_check (tlas_refit.hip), update calls refused by k_ingest_check for a flattened scene
+    // (refit_ws) or for the BLASes of a two-level one (blas_ws)
+    const auto add = [count](hipEvent_t ev_last, const unsigned long long *d) {
         unsigned long long h = 0;
-        MRT_HIP(hipEventSynchronize(sc.inst_ws->ev_last));
-        MRT_HIP(hipMemcpy(&h, sc.inst_ws->rejected.p, 8, hipMemcpyDeviceToHost));
+        MRT_HIP(hipEventSynchronize(ev_last));
+        MRT_HIP(hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost));
         *count += h;
-    }
-    if (!sc.refit_ws) return MRT_OK;
-    RefitWorkspace &ws = *sc.refit_ws;
-    unsigned long long h = 0;
-    MRT_HIP(hipEventSynchronize(ws.ev_last));
-    MRT_HIP(hipMemcpy(&h, ws.rejected.p, 8, hipMemcpyDeviceToHost));
-    *count = sc.rejected_before + h;
+        return (int)MRT_OK;
+    };
+    if (sc.inst_ws) { if (int rc = add(sc.inst_ws->ev_last, sc.inst_ws->rejected.p)) return rc; }
+    if (sc.blas_ws) { if (int rc = add(sc.blas_ws->ev_last, sc.blas_ws->rejected.p)) return rc; }
+    if (sc.refit_ws) { if (int rc = add(sc.refit_ws->ev_last, sc.refit_ws->rejected.p)) return rc; }
     return MRT_OK;
 }
 
@@ -555,6 +562,183 @@ int download_stale_meshes(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *
             for (size_t v = 0; v < nv; v++) { m.normals[3 * v] = n4[v].x; m.normals[3 * v + 1] = n4[v].y; m.normals[3 * v + 2] = n4[v].z; }
         }
         ws.host_stale[mi] = 0;
+    }
+    return MRT_OK;
+}
+
+// ------------------------------------------------------------------ meshes of two-level scenes deformed on the stream (mrt_scene_update_blas_device / mrt_scene_refit_blas_device)
+// refit_two_level with nothing of the host in it.  The vertices of a mesh exist once, in its BLAS: k_ingest_write puts them into the workspace's resident positions and the
+// scene's normals (a one-row reference table per BLAS).  The refit then runs refit_blas's kernel sequence per updated BLAS with refit_blas's arguments — so nodes and packets
+// come out as a refitting commit leaves them —, hands the new root box to the BLAS's instances (tlas_refit.hip k_blas_instance_boxes) and refits both TLAS forms with their
+// topology kept (device_refit_instances).  What the host path reads back at once — root boxes, growth sums, the trees' costs — waits on the device for resolve_blas_refits.
+int blas_device_supported(const DeviceScene &sc, const BuildOptions &opt, size_t meshes, const char *who) {
+    const char *why = nullptr;
+    if (!opt.instancing || sc.num_inst == 0)
+        why = "flattened scenes (instancing = 0) have no BLAS: mrt_scene_update_mesh_device + mrt_scene_refit_device refit them";
+    else if (!opt.refit) why = "scene option refit = 0: every change builds the scene again (mrt_scene_update_mesh + mrt_scene_commit)";
+    else if (!two_level_refittable(sc, meshes) || !sc.normals.p || !sc.bnodes.p || !sc.inst_box.p)
+        why = "the scene's BLASes cannot be refitted (not every one has the 8-wide layout, e.g. wide = 0): mrt_scene_update_mesh + mrt_scene_commit builds them";
+    if (!why) return MRT_OK;
+    set_error(std::string(who) + ": " + why);
+    return MRT_ERR_UNSUPPORTED;
+}
+
+void drop_blas_workspace(DeviceScene &sc) {
+    if (!sc.blas_ws) return;
+    unsigned long long h = 0;
+    if (hipEventSynchronize(sc.blas_ws->ev_last) == hipSuccess && hipMemcpy(&h, sc.blas_ws->rejected.p, 8, hipMemcpyDeviceToHost) == hipSuccess) sc.rejected_before += h; else (void)hipGetLastError();
+    sc.blas_ws.reset();
+}
+
+int blas_device_prepare(const std::vector<HostMesh> &meshes, DeviceScene &sc) {
+    if (sc.blas_ws) return MRT_OK;
+    const size_t B = sc.blas_ranges.size(), I = sc.h_inst.size();
+    std::unique_ptr<BlasWorkspace> w(new BlasWorkspace());
+    w->blas_of_mesh.assign(meshes.size(), -1);
+    w->idx_first.assign(B, 0u); w->rec_first.assign(B, 0u); w->rec_count.assign(B, 0u); w->inst_first.assign(B, 0u); w->inst_count.assign(B, 0u); w->level_first.resize(B);
+    w->host_stale.assign(B, 0); w->pending.assign(B, 0); w->refitted.assign(B, 0);
+    // the host copies are truthful here (a commit is behind us and nothing changed since): every BLAS's geometry as refit_blas would upload it
+    std::vector<SubRec> recs; std::vector<uint32_t> idx; std::vector<uint2> table(std::max<size_t>(B, 1), make_uint2(0u, 0u)); std::vector<float> lg(std::max<size_t>(B, 1), 1.0f);
+    size_t V = 0, maxT = 1, maxR = 1;
+    for (size_t b = 0; b < B; b++) {
+        const BlasRange &r = sc.blas_ranges[b];
+        const HostMesh &g = meshes[r.src_mesh];
+        const size_t nv = g.positions.size() / 3;
+        w->blas_of_mesh[r.src_mesh] = (int)b;
+        w->idx_first[b] = (uint32_t)idx.size(); w->rec_first[b] = (uint32_t)recs.size();
+        if (blas_geometry(g, recs, idx) != r.ntri || g.normals.size() != g.positions.size()) { set_error("mrt_scene_update_blas_device: the resident BLASes are not this scene's"); return MRT_ERR_STATE; }
+        w->rec_count[b] = (uint32_t)recs.size() - w->rec_first[b];
+        w->level_first[b] = level_first(r.wide_levels, r.wnode_base);
+        table[b] = make_uint2(0u, r.vbase); lg[b] = r.leaf_growth;
+        V = std::max(V, (size_t)r.vbase + nv); maxT = std::max<size_t>(maxT, r.ntri); maxR = std::max<size_t>(maxR, r.rope_nodes);
+    }
+    if (V > sc.normals.n) { set_error("mrt_scene_update_blas_device: the resident normals are not this scene's"); return MRT_ERR_STATE; }
+    std::vector<float> h_pos(std::max<size_t>(3 * V, 3), 0.0f);
+    for (size_t b = 0; b < B; b++) { const HostMesh &g = meshes[sc.blas_ranges[b].src_mesh]; if (!g.positions.empty()) memcpy(&h_pos[3 * (size_t)sc.blas_ranges[b].vbase], g.positions.data(), g.positions.size() * 4); }
+    std::vector<uint32_t> list(std::max<size_t>(I, 1), 0u);          // the instances grouped by BLAS (InstanceDev::blas is the build's: it stays until the next build)
+    for (size_t i = 0; i < I; i++) if (sc.h_inst[i].blas < B) w->inst_count[sc.h_inst[i].blas]++;
+    for (size_t b = 1; b < B; b++) w->inst_first[b] = w->inst_first[b - 1] + w->inst_count[b - 1];
+    { std::vector<uint32_t> at = w->inst_first; for (size_t i = 0; i < I; i++) if (sc.h_inst[i].blas < B) list[at[sc.h_inst[i].blas]++] = (uint32_t)i; }
+    const size_t nw = std::max<size_t>(sc.wnodes.n / WNODE_STRIDE, 1), nrec = std::max<size_t>(recs.size(), 1), nidx = std::max<size_t>(idx.size(), 3);
+    const auto piece = [](size_t bytes) { return (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; };
+    w->arena.chunk_bytes = piece(4 * h_pos.size()) + piece(4 * nidx) + piece(sizeof(SubRec) * nrec) + piece(64) + piece(48 * maxT) + 3 * piece(16 * maxT) + piece(32 * nw) + 2 * piece(4 * maxR) + piece(8 * maxR)
+                         + piece(8 * table.size()) + piece(4 * list.size()) + piece(6 * 4) + piece(4 * 4) + piece(8 * (2 * B + 4)) + piece(8) + piece(4 * lg.size()) + piece(4);
+    MRT_HIP(w->pos.alloc_in(w->arena, h_pos.size())); MRT_HIP(w->idx.alloc_in(w->arena, nidx)); MRT_HIP(w->recs.alloc_in(w->arena, 6 * nrec)); MRT_HIP(w->cols.alloc_in(w->arena, 4));
+    MRT_HIP(w->tri_world.alloc_in(w->arena, 3 * maxT)); MRT_HIP(w->tri_lo.alloc_in(w->arena, maxT)); MRT_HIP(w->tri_hi.alloc_in(w->arena, maxT)); MRT_HIP(w->tri_shade.alloc_in(w->arena, maxT));
+    MRT_HIP(w->nbox.alloc_in(w->arena, 2 * nw)); MRT_HIP(w->parent.alloc_in(w->arena, maxR)); MRT_HIP(w->arrived.alloc_in(w->arena, maxR)); MRT_HIP(w->ab.alloc_in(w->arena, maxR));
+    MRT_HIP(w->ref_table.alloc_in(w->arena, table.size())); MRT_HIP(w->inst_list.alloc_in(w->arena, list.size()));
+    MRT_HIP(w->cbounds.alloc_in(w->arena, 6)); MRT_HIP(w->words.alloc_in(w->arena, 4)); MRT_HIP(w->growth.alloc_in(w->arena, 2 * B + 4)); MRT_HIP(w->rejected.alloc_in(w->arena, 1));
+    MRT_HIP(w->leaf_growth.alloc_in(w->arena, lg.size())); MRT_HIP(w->dirty.alloc_in(w->arena, 4));
+    MRT_HIP(hipEventCreate(&w->ev_begin)); MRT_HIP(hipEventCreate(&w->ev_end)); MRT_HIP(hipEventCreateWithFlags(&w->ev_last, hipEventDisableTiming));
+    const float4 ident[4] = {make_float4(1, 0, 0, 0), make_float4(0, 1, 0, 0), make_float4(0, 0, 1, 0), make_float4(0, 0, 0, 0)};
+    MRT_HIP(hipMemcpy(w->pos.p, h_pos.data(), h_pos.size() * 4, hipMemcpyHostToDevice));
+    if (!idx.empty()) MRT_HIP(hipMemcpy(w->idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
+    if (!recs.empty()) MRT_HIP(hipMemcpy(w->recs.p, recs.data(), recs.size() * sizeof(SubRec), hipMemcpyHostToDevice));
+    MRT_HIP(hipMemcpy(w->cols.p, ident, sizeof ident, hipMemcpyHostToDevice));
+    MRT_HIP(hipMemcpy(w->ref_table.p, table.data(), table.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    MRT_HIP(hipMemcpy(w->inst_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice));
+    MRT_HIP(hipMemcpy(w->leaf_growth.p, lg.data(), lg.size() * 4, hipMemcpyHostToDevice));
+    MRT_HIP(hipMemset(w->dirty.p, 1, 4)); MRT_HIP(hipMemset(w->words.p, 0, w->words.bytes())); MRT_HIP(hipMemset(w->growth.p, 0, w->growth.bytes())); MRT_HIP(hipMemset(w->rejected.p, 0, 8));
+    MRT_HIP(hipDeviceSynchronize());          // (the first call after a commit may block: from here on the caller's stream finds the workspace as the lines above left it)
+    MRT_HIP(hipEventRecord(w->ev_last, nullptr));
+    sc.blas_ws = std::move(w);
+    return MRT_OK;
+}
+
+int device_update_blas(DeviceScene &sc, size_t blas, const void *d_pos, size_t pos_stride, const void *d_nrm, size_t nrm_stride, size_t nverts, hipStream_t stream) {
+    BlasWorkspace &ws = *sc.blas_ws;
+    if (++ws.seq == 0u) ws.seq = 1u;          // (0 is what words[0] starts as)
+    const uint32_t nv = (uint32_t)nverts;
+    const dim3 grid(cdiv(nv, 256)), block(256);
+    hipLaunchKernelGGL(k_ingest_check, grid, block, 0, stream, static_cast<const uint8_t *>(d_pos), pos_stride, static_cast<const uint8_t *>(d_nrm), nrm_stride, nv, ws.seq, ws.words.p);
+    hipLaunchKernelGGL(k_ingest_write, grid, block, 0, stream, static_cast<const uint8_t *>(d_pos), pos_stride, static_cast<const uint8_t *>(d_nrm), nrm_stride, nv, ws.seq, (const uint32_t *)ws.words.p,
+                       ws.rejected.p, (const uint2 *)(ws.ref_table.p + blas), 1u, ws.pos.p, sc.normals.p, ws.dirty.p);
+    MRT_HIP(hipGetLastError());
+    MRT_HIP(hipEventRecord(ws.ev_last, stream));
+    ws.host_stale[blas] = 1; ws.pending[blas] = 1;          // (for a call the device refuses too, as device_update_mesh)
+    return MRT_OK;
+}
+
+int device_refit_blas(DeviceScene &sc, hipStream_t stream) {
+    BlasWorkspace &ws = *sc.blas_ws;
+    MRT_HIP(hipEventRecord(ws.ev_begin, stream));
+    for (size_t b = 0; b < sc.blas_ranges.size(); b++) {
+        if (!ws.pending[b]) continue;
+        const BlasRange &br = sc.blas_ranges[b];
+        const uint32_t T32 = br.ntri;
+        MRT_HIP(hipMemsetAsync(ws.cbounds.p, 0, 24, stream));          // (k_flatten's centroid bounds: written, never read here)
+        if (br.rope_nodes) MRT_HIP(hipMemsetAsync(ws.arrived.p, 0, (size_t)br.rope_nodes * 4, stream));
+        hipLaunchKernelGGL(k_flatten, dim3(cdiv(T32, 1024)), dim3(1024), 0, stream, reinterpret_cast<const SubRec *>(ws.recs.p) + ws.rec_first[b], (int)ws.rec_count[b], (const float *)(ws.pos.p + 3 * (size_t)br.vbase),
+                           (const uint32_t *)(ws.idx.p + ws.idx_first[b]), (const float4 *)ws.cols.p, T32, ws.tri_world.p, ws.tri_shade.p, ws.tri_lo.p, ws.tri_hi.p, ws.cbounds.p);
+        RefitTarget tg;          // refit_blas's, field for field
+        tg.wnodes = sc.wnodes.p; tg.wpackets = sc.wpackets.p; tg.wpacket_first = br.packet_base; tg.level_first = ws.level_first[b].data(); tg.level_count = br.wide_levels.data(); tg.levels = br.wide_levels.size();
+        tg.rope_nodes = sc.bnodes.p + 4 * (size_t)br.node_base; tg.rope_packets = sc.bnodes.p + sc.bpackets_offset + 3 * (size_t)br.packet_base; tg.rope_nodes_n = br.rope_nodes;
+        tg.packets = T32; tg.tri_shade = ws.tri_shade.p; tg.dirty = ws.dirty.p; tg.rope_every_leaf = true;
+        enqueue_refit(tg, RefitScratch{ws.tri_world.p, ws.tri_lo.p, ws.tri_hi.p, ws.nbox.p, ws.growth.p + 2 * b, ws.parent.p, ws.arrived.p, ws.ab.p}, stream);
+        hipLaunchKernelGGL(k_refit_fold, dim3(1), dim3(64), 0, stream, ws.growth.p + 2 * b, ws.leaf_growth.p + b);
+        enqueue_blas_instance_boxes(sc, ws.nbox.p, br.wnode_base, ws.inst_list.p + ws.inst_first[b], ws.inst_count[b], stream);
+        MRT_HIP(hipGetLastError());
+        ws.pending[b] = 0; ws.refitted[b] = 1;
+    }
+    if (int rc = device_refit_instances(sc, stream)) return rc;          // both TLAS forms follow the instances' world boxes (and whatever poses were set since the last refit)
+    MRT_HIP(hipEventRecord(ws.ev_end, stream));
+    MRT_HIP(hipEventRecord(ws.ev_last, stream));
+    sc.refits++; ws.unresolved = true;
+    return MRT_OK;
+}
+
+// What refit_two_level reads back at once, read when somebody asks: per refitted BLAS its root box (update_tlas builds the next TLAS from blas_lo / blas_hi), its chained
+// leaf_growth and its tree's cost as it lies now; then the scene's figures by refit_two_level's arithmetic in its order.  Blocks on the last refit's end.
+// wide_tree_cost runs on the context's stream, ordered behind the caller's stream only by the host's wait for ev_end: that rests on no refit being enqueued between the wait
+// and the cost kernel (the caller owes it: one thread drives a scene), and on update calls touching neither wnodes nor the cost words — they write pos and normals only.
+int resolve_blas_refits(DeviceScene &sc, const BuildOptions &opt, hipStream_t stream) {
+    if (!sc.blas_ws || !sc.blas_ws->unresolved) return MRT_OK;
+    BlasWorkspace &ws = *sc.blas_ws;
+    const size_t B = sc.blas_ranges.size();
+    MRT_HIP(hipEventSynchronize(ws.ev_end));
+    float ms = 0; MRT_HIP(hipEventElapsedTime(&ms, ws.ev_begin, ws.ev_end));
+    float growth_max = 1.0f; double sah = 0, wcost = 0;
+    for (size_t b = 0; b < B; b++) {
+        BlasRange &r = sc.blas_ranges[b];
+        if (ws.refitted[b]) {
+            float4 h_box[2];
+            MRT_HIP(hipMemcpy(h_box, ws.nbox.p + 2 * (size_t)r.wnode_base, sizeof h_box, hipMemcpyDeviceToHost));
+            MRT_HIP(hipMemcpy(&r.leaf_growth, ws.leaf_growth.p + b, 4, hipMemcpyDeviceToHost));
+            set_root_box(&sc.blas_lo[3 * b], &sc.blas_hi[3 * b], h_box[0], h_box[1]);
+            if (int rc = wide_tree_cost(sc.wnodes.p, r.wnode_base, r.wnodes, r.wnode_base, opt.wide_cost_node, opt.wide_cost_tri, stream, ws.growth.p + 2 * B, &r.wide_cost)) return rc;
+            ws.refitted[b] = 0;
+        }
+        growth_max = std::max(growth_max, r.leaf_growth); wcost += r.wide_cost; sah += r.wide_cost_built > 0.0f ? r.sah_cost_built * (r.wide_cost / r.wide_cost_built) : r.sah_cost_built;
+    }
+    sc.stats.build_ms = ms; sc.stats.wide_cost = (float)(wcost / (double)B); sc.stats.sah_cost = (float)(sah / (double)B);
+    sc.stats.refits = sc.refits; sc.stats.leaf_growth = growth_max;
+    ws.unresolved = false;
+    return MRT_OK;
+}
+
+// download_stale_meshes for a two-level scene: the HostMesh copies of meshes updated on the device, from the workspace's positions and the scene's normals.  A mesh updated
+// and not refitted since counts as changed for the commit that follows (refit_two_level then refits it from the host copy this call brings up to date).
+int download_stale_blas_meshes(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *pending_found) {
+    if (pending_found) *pending_found = false;
+    if (!sc.blas_ws) return MRT_OK;
+    BlasWorkspace &ws = *sc.blas_ws;
+    bool waited = false;
+    std::vector<float4> n4;
+    for (size_t b = 0; b < sc.blas_ranges.size() && b < ws.host_stale.size(); b++) {
+        const BlasRange &r = sc.blas_ranges[b];
+        if (r.src_mesh >= meshes.size()) continue;
+        HostMesh &m = meshes[r.src_mesh];
+        if (ws.pending[b]) { m.dirty = true; ws.pending[b] = 0; if (pending_found) *pending_found = true; }
+        if (!ws.host_stale[b]) continue;
+        if (!waited) { MRT_HIP(hipEventSynchronize(ws.ev_last)); waited = true; }
+        const size_t nv = m.positions.size() / 3;
+        if (nv) {
+            n4.resize(nv);
+            MRT_HIP(hipMemcpy(m.positions.data(), ws.pos.p + 3 * (size_t)r.vbase, nv * 12, hipMemcpyDeviceToHost));
+            MRT_HIP(hipMemcpy(n4.data(), sc.normals.p + r.vbase, nv * 16, hipMemcpyDeviceToHost));
+            for (size_t v = 0; v < nv; v++) { m.normals[3 * v] = n4[v].x; m.normals[3 * v + 1] = n4[v].y; m.normals[3 * v + 2] = n4[v].z; }
+        }
+        ws.host_stale[b] = 0;
     }
     return MRT_OK;
 }

@@ -284,6 +284,39 @@ struct InstanceWorkspace {
     ~InstanceWorkspace() { if (ev_last) { (void)hipEventSynchronize(ev_last); (void)hipEventDestroy(ev_last); } }
 };
 
+// What the stream-ordered BLAS refit of a two-level scene (mrt_scene_update_blas_device / mrt_scene_refit_blas_device) keeps between calls: the object-space
+// geometry build_two_level's scratch scenes took with them (packed positions, indices and submesh records per BLAS, as refit_blas assembles them), ONE set of refit scratch sized
+// for the largest BLAS (the BLASes are refitted in sequence on the stream), a box per 8-wide node of the whole shared array (refit indices are absolute) and a few words per
+// BLAS.  Made by the first such call after a commit from the HostMesh copies (which may allocate and block), kept by a transforms-only commit (update_tlas), dropped by
+// build_two_level, by refit_two_level (whose uploads would leave `pos` stale) and by mrt_scene_destroy.
+struct BlasWorkspace {
+    ScratchArena arena;                                    // before the buffers that borrow from it
+    DevBuf<float> pos;                                     // packed positions of every BLAS's mesh, at 3 * BlasRange::vbase
+    DevBuf<uint32_t> idx, recs;                            // per BLAS: its index list (at idx_first) and its SubRecs (at rec_first), BLAS-local as refit_blas uploads them
+    DevBuf<float4> cols;                                   // the identity, for k_flatten
+    DevBuf<float4> tri_world, tri_lo, tri_hi, nbox;        // scratch of the largest BLAS; nbox: 2 per 8-wide node of the shared array
+    DevBuf<uint4> tri_shade;                               // k_flatten's shading records of the BLAS's own numbering (scratch: the scene's are the build's)
+    DevBuf<uint32_t> cbounds, parent, arrived;
+    DevBuf<uint32_t> words;                                // [0]: sequence number of the last update call whose input held a NaN or an infinity (k_ingest_check)
+    DevBuf<uint2> ab, ref_table;                           // ref_table[b] = {0, vbase of BLAS b}: k_ingest_write's one-row table
+    DevBuf<uint32_t> inst_list;                            // instance ids grouped by BLAS (inst_first / inst_count)
+    DevBuf<double> growth;                                 // [2b, 2b + 1]: k_refit_wide_level's sums of BLAS b (folded and cleared by k_refit_fold); [2B .. 2B + 3]: wide_tree_cost's 8 + 24 bytes
+    DevBuf<unsigned long long> rejected;                   // update calls refused on the device since the workspace was made (sticky)
+    DevBuf<float> leaf_growth;                             // per BLAS: BlasRange::leaf_growth, chained on the device over the refits
+    DevBuf<uint8_t> dirty;                                 // 4 bytes of 1: the one "instance" of a BLAS's own triangle arrays moved
+    std::vector<int> blas_of_mesh;                         // per mesh known at the commit: its BLAS, -1 for an instance
+    std::vector<uint32_t> idx_first, rec_first, rec_count, inst_first, inst_count;      // per BLAS
+    std::vector<std::vector<uint32_t>> level_first;        // per BLAS: first node of every level of its 8-wide tree (absolute)
+    std::vector<uint8_t> host_stale, pending, refitted;    // per BLAS: the HostMesh copy is older than the device's vertices; updated and not yet refitted; refitted since the host last read its root box and statistics
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;       // around the last refit (MRTSceneStats.build_ms)
+    hipEvent_t ev_last = nullptr;                          // behind the last update or refit enqueued: what a blocking reader waits for
+    uint32_t seq = 0;                                      // update calls so far
+    bool unresolved = false;                               // refits enqueued whose results the host has not read yet (resolve_blas_refits)
+    BlasWorkspace() = default;
+    BlasWorkspace(const BlasWorkspace &) = delete; BlasWorkspace &operator=(const BlasWorkspace &) = delete;
+    ~BlasWorkspace() { if (ev_last) (void)hipEventSynchronize(ev_last); for (hipEvent_t e : {ev_begin, ev_end, ev_last}) if (e) (void)hipEventDestroy(e); }
+};
+
 struct DeviceScene {
     DevBuf<float4> nodes, packets, normals, base_color, materials, inst_cols, wnodes, wpackets;
     uint32_t num_wnodes = 0; int wide_depth = 0;
@@ -318,6 +351,7 @@ struct DeviceScene {
     PinnedBuf stage;                                           // upload staging of build_flat (grow-only, reused by every commit of this scene)
     double commit_ms[6] = {0, 0, 0, 0, 0, 0};                    // host wall time of the last flat build, by phase: staging (reserve + fill), device allocations + upload enqueue, topology (sort .. refit, incl. its read-backs), 8-wide emit, rope emit, validation (mrt_debug_commit_times)
     std::unique_ptr<RefitWorkspace> refit_ws;                    // the stream-ordered refit's resident scratch (null until the first mrt_scene_update_mesh_device after a build)
+    std::unique_ptr<BlasWorkspace> blas_ws;                      // two-level scenes: the stream-ordered BLAS refit's resident geometry and scratch (null until the first mrt_scene_update_blas_device / _refit_blas_device after a commit)
     DevBuf<double> cost_words;                                   // wide_tree_cost's 8 + 24 bytes for refit_two_level (made once, kept: no hipMalloc / hipFree pair per commit)
     uint64_t rejected_before = 0;                                // device updates refused in the lifetimes of earlier workspaces of this scene
     SceneView view() const;
@@ -334,6 +368,10 @@ int build_flat(const std::vector<MeshRef> &refs, const BuildOptions &opt, hipStr
 // two_level.hip
 int build_two_level(const std::vector<HostMesh> &meshes, const BuildOptions &opt, hipStream_t stream, DeviceScene &out);
 int refit_two_level(const std::vector<HostMesh> &meshes, const BuildOptions &opt, hipStream_t stream, DeviceScene &out);      // after mrt_scene_update_mesh alone: the BLASes of the updated meshes refitted in place (both layouts) + the TLAS; MRT_ERR_UNSUPPORTED (no message): the scene cannot be refitted, build it
+// what refit_two_level takes, for the commit and for the stream-ordered BLAS refit alike: the scene (every BLAS with the 8-wide layout, the mesh list of the build) ...
+inline bool two_level_refittable(const DeviceScene &sc, size_t meshes) { return sc.blas_all_wide && sc.num_inst == meshes && !sc.blas_ranges.empty() && sc.h_inst.size() == meshes; }
+// ... and one BLAS of it whose mesh (of nverts vertices) changed
+inline bool blas_refittable(const BlasRange &r, size_t nverts) { return r.wnodes != 0 && !r.wide_levels.empty() && nverts != 0; }
 int refit_blas(const HostMesh &g, const BlasRange &br, hipStream_t stream, DeviceScene &out, float root_lo[3], float root_hi[3], float *ms_out, float *growth_out);      // bvh_refit.hip
 int update_tlas(const std::vector<HostMesh> &meshes, hipStream_t stream, DeviceScene &out);      // after transform changes: instance rows + TLAS, BLASes untouched
 int validate_layout(const DeviceScene &sc, hipStream_t stream, bool tlas_only, const float4 *wnodes_override = nullptr);      // wnodes_override: a device copy of the 8-wide nodes to check in place of the scene's (mrt_debug_validate_patched)
@@ -359,7 +397,16 @@ int instances_device_prepare(DeviceScene &sc);      // makes sc.inst_ws if it is
 int device_set_instance_transforms(DeviceScene &sc, uint32_t first, uint32_t count, const void *d_xf, size_t stride, hipStream_t stream);
 int device_refit_instances(DeviceScene &sc, hipStream_t stream);
 int download_moved_transforms(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *moved_found = nullptr);      // blocks; HostMesh::xf of the instances moved on the device, read back from inst_cols
+void enqueue_blas_instance_boxes(DeviceScene &sc, const float4 *nbox, uint32_t root, const uint32_t *inst_list, uint32_t count, hipStream_t stream);      // the instances inst_list[0 .. count) of one BLAS take nbox[2 * root] as their object box and a world box recomputed from it (k_blas_instance_boxes)
 void drop_instance_workspace(DeviceScene &sc);      // (update_tlas: the TLAS the workspace was made for is gone; the rejected count is kept)
+// bvh_refit.hip: meshes of two-level scenes deformed from device buffers, ordered on the caller's stream
+int blas_device_supported(const DeviceScene &sc, const BuildOptions &opt, size_t meshes, const char *who);      // MRT_OK, or MRT_ERR_UNSUPPORTED + message: a flattened scene, refit = 0, a scene refit_two_level would not take
+int blas_device_prepare(const std::vector<HostMesh> &meshes, DeviceScene &sc);      // makes sc.blas_ws if it is not there (allocates, uploads the meshes' geometry, blocks)
+int device_update_blas(DeviceScene &sc, size_t blas, const void *d_pos, size_t pos_stride, const void *d_nrm, size_t nrm_stride, size_t nverts, hipStream_t stream);
+int device_refit_blas(DeviceScene &sc, hipStream_t stream);      // needs sc.inst_ws too (instances_device_prepare)
+int resolve_blas_refits(DeviceScene &sc, const BuildOptions &opt, hipStream_t stream);      // blocks on the last refit; blas_lo / blas_hi, the BlasRanges' and the scene's statistics brought up to date (no-op when nothing is pending)
+int download_stale_blas_meshes(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *pending_found = nullptr);      // blocks; as download_stale_meshes, from the BLAS workspace
+void drop_blas_workspace(DeviceScene &sc);      // (the rejected count is kept)
 int upload_lights(const MRTLight *lights, int count, hipStream_t stream, DeviceScene &out);
 
 }  // namespace mrt

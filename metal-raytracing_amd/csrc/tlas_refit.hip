@@ -5,6 +5,7 @@
 //                                              invert_affine and instance_box of two_level.hip, in double, in their operation order: the host's bits.
 //   mrt_scene_refit_instances_device           k_tlas_rope_level per depth, k_tlas_wide_level per level, bottom-up: the boxes of both TLAS forms follow the instances'
 //                                              world boxes.  The topology is the last commit's (update_tlas); a commit builds the tree again.
+//   mrt_scene_refit_blas_device (bvh_refit.hip)  k_blas_instance_boxes between its BLAS refits and the TLAS refit above: the instances of a refitted BLAS take its new root box.
 // The launch boundary is the only grid-wide ordering used here: one launch per depth / level, each over at most a few thousand nodes.
 #include "scene_device.h"
 #include <algorithm>
@@ -131,6 +132,26 @@ __global__ void k_inst_write(const uint8_t *__restrict__ src, size_t stride, uin
     inst_box[4 * i + 2] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.0f); inst_box[4 * i + 3] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.0f);
 }
 
+// ------------------------------------------------------------------ a BLAS refitted on the stream (mrt_scene_refit_blas_device)
+// Its root box changed, so what update_tlas would compute on the host for each of its instances changes with it: the object box is the BLAS's new root box (the refit's
+// nbox[2 * root], as refit_blas reads it back), the padded world box is instance_box_dev of it under the instance's CURRENT columns and world->object rows — a pose set by
+// k_inst_write is honoured.  An instance outside the TLAS of the last commit (no triangles, a singular matrix then) has the empty box update_tlas gave it, lo > hi, and keeps it.
+__global__ void k_blas_instance_boxes(const float4 *__restrict__ nbox, uint32_t root, const uint32_t *__restrict__ inst_list, uint32_t count, const float4 *__restrict__ inst_cols,
+                                      const InstanceDev *__restrict__ inst, float4 *__restrict__ inst_box) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    const size_t i = inst_list[j];
+    if (inst_box[4 * i].x > inst_box[4 * i + 1].x) return;
+    const float4 blo = nbox[2 * (size_t)root], bhi = nbox[2 * (size_t)root + 1];
+    float xf[16], rows[3][4];
+    for (int c = 0; c < 4; c++) { const float4 q = inst_cols[4 * i + c]; xf[c * 4 + 0] = q.x; xf[c * 4 + 1] = q.y; xf[c * 4 + 2] = q.z; xf[c * 4 + 3] = c == 3 ? 1.0f : 0.0f; }
+    for (int r = 0; r < 3; r++) { const float4 q = inst[i].w2o[r]; rows[r][0] = q.x; rows[r][1] = q.y; rows[r][2] = q.z; rows[r][3] = q.w; }
+    const float lo_in[3] = {blo.x, blo.y, blo.z}, hi_in[3] = {bhi.x, bhi.y, bhi.z};
+    const DBox b = instance_box_dev(xf, lo_in, hi_in, rows);
+    inst_box[4 * i] = make_float4(blo.x, blo.y, blo.z, 0.0f); inst_box[4 * i + 1] = make_float4(bhi.x, bhi.y, bhi.z, 0.0f);
+    inst_box[4 * i + 2] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.0f); inst_box[4 * i + 3] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.0f);
+}
+
 // ------------------------------------------------------------------ the rope TLAS (nodes, tlas_index): one launch per depth, deepest first
 // order[0 .. count): the nodes of one depth.  A leaf takes the union of the world boxes of its one or two instances, an internal node the union of its children's boxes, which
 // the launch before this one wrote.  The words a and b, and the escape links, are the build's.
@@ -230,6 +251,11 @@ int instances_device_supported(const DeviceScene &sc, const BuildOptions &opt, c
     if (!why) return MRT_OK;
     set_error(std::string(who) + ": " + why);
     return MRT_ERR_UNSUPPORTED;
+}
+
+void enqueue_blas_instance_boxes(DeviceScene &sc, const float4 *nbox, uint32_t root, const uint32_t *inst_list, uint32_t count, hipStream_t stream) {
+    if (count == 0) return;
+    hipLaunchKernelGGL(k_blas_instance_boxes, dim3(blocks_of(count, 64)), dim3(64), 0, stream, nbox, root, inst_list, count, (const float4 *)sc.inst_cols.p, (const InstanceDev *)sc.inst.p, sc.inst_box.p);
 }
 
 void drop_instance_workspace(DeviceScene &sc) {

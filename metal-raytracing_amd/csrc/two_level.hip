@@ -487,6 +487,7 @@ int update_tlas(const std::vector<HostMesh> &meshes, hipStream_t stream, DeviceS
 
 int build_two_level(const std::vector<HostMesh> &meshes, const BuildOptions &opt_in, hipStream_t stream, DeviceScene &out) {
     const size_t I = meshes.size();
+    drop_blas_workspace(out);          // (made for the BLASes this call replaces)
     BuildOptions opt = opt_in; opt.instancing = 0; opt.rope = 1;      // the BLASes keep both layouts: the stackless two-level walk serves the query API and is the fallback of the render kernels
     opt.presplit = 0.0f;                                                // one packet per triangle in a BLAS: the instance rows address packets by triangle count (ntri)                      // a BLAS is a flat scene of one mesh: rope layout (queries, A/B path) + 8-wide layout (render kernels)
     // distinct geometries, in order of first use
@@ -609,8 +610,9 @@ int build_two_level(const std::vector<HostMesh> &meshes, const BuildOptions &opt
 // walk, the rope one the query API and the in-place fallbacks walk (bvh_build.hip refit_blas) — its instances share the result; then the TLAS is rebuilt from the new BLAS boxes
 // (update_tlas).  MRT_ERR_UNSUPPORTED without a message: this scene cannot be refitted (no 8-wide layout, another mesh list) — the caller builds it.
 int refit_two_level(const std::vector<HostMesh> &meshes, const BuildOptions &opt, hipStream_t stream, DeviceScene &out) {
-    if (!out.blas_all_wide || out.num_inst != meshes.size() || out.blas_ranges.empty() || out.h_inst.size() != meshes.size()) return MRT_ERR_UNSUPPORTED;
-    for (const BlasRange &r : out.blas_ranges) if (r.src_mesh >= meshes.size() || (meshes[r.src_mesh].dirty && (r.wnodes == 0 || r.wide_levels.empty() || meshes[r.src_mesh].positions.size() / 3 == 0))) return MRT_ERR_UNSUPPORTED;
+    if (!two_level_refittable(out, meshes.size())) return MRT_ERR_UNSUPPORTED;
+    for (const BlasRange &r : out.blas_ranges) if (r.src_mesh >= meshes.size() || (meshes[r.src_mesh].dirty && !blas_refittable(r, meshes[r.src_mesh].positions.size() / 3))) return MRT_ERR_UNSUPPORTED;
+    drop_blas_workspace(out);          // (refit_blas uploads the changed meshes' vertices into scratch of its own: the workspace's resident copies would be stale.  The next mrt_scene_update_blas_device makes it again)
     float ms_total = 0, growth_max = 1.0f; double sah = 0, wcost = 0;
     MRT_HIP(out.cost_words.alloc(4));          // wide_tree_cost's sum and root box: the scene's, allocated by its first refit and found by every later one
     for (size_t b = 0; b < out.blas_ranges.size(); b++) {

@@ -203,9 +203,25 @@ class DeviceScene:
         """The refit of both TLAS forms after set_instance_transforms_device, enqueued on the stream: boxes bottom-up, topology kept."""
         check(lib.mrt_scene_refit_instances_device(self.handle, C.c_void_p(self._stream_handle(stream))))
 
+    def update_blas_device(self, mesh_id, positions, normals, stream=None):
+        """A mesh deforming inside a two-level scene (option instancing = 1), from the GPU and ordered on a stream: positions and normals are torch.float32 (n, 3)
+        tensors on the context's device in OBJECT space, n the vertex count of source mesh mesh_id, rows as update_mesh_device takes them; every instance of the mesh
+        shares the result.  Call refit_blas_device() afterwards (several updates may share one).  A NaN or an infinity in the input leaves the scene as it was and is
+        counted in device_updates_rejected.  A tensor that is not what the first sentence says raises ValueError; normals of another length than positions raise
+        MRTError(MRT_ERR_INVALID_ARGUMENT)."""
+        p, ps = self._vertex_rows(positions, "positions"); n, ns = self._vertex_rows(normals, "normals")
+        if normals.shape[0] != positions.shape[0]:          # the device reads vertex_count normals: a shorter tensor would be read past its end
+            raise MRTError(1, f"update_blas_device: {normals.shape[0]} normals for {positions.shape[0]} positions (one normal per vertex)")
+        check(lib.mrt_scene_update_blas_device(self.handle, int(mesh_id), C.c_void_p(p), ps, C.c_void_p(n), ns, positions.shape[0], C.c_void_p(self._stream_handle(stream))))
+
+    def refit_blas_device(self, stream=None):
+        """The refit after update_blas_device, enqueued on the stream: the updated meshes' BLASes in place (as a commit after update_mesh computes them), their instances'
+        boxes under the poses the device holds, both TLAS forms with the topology kept.  Poses set by set_instance_transforms_device need no refit of their own before it."""
+        check(lib.mrt_scene_refit_blas_device(self.handle, C.c_void_p(self._stream_handle(stream))))
+
     @property
     def device_updates_rejected(self):
-        """update_mesh_device / set_instance_transforms_device calls refused on the device since the scene was created (blocks until the calls enqueued so far have run)."""
+        """update_mesh_device / update_blas_device / set_instance_transforms_device calls refused on the device since the scene was created (blocks until the calls enqueued so far have run)."""
         v = C.c_uint64()
         check(lib.mrt_scene_device_updates_rejected(self.handle, C.byref(v)))
         return v.value
