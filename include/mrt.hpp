@@ -126,6 +126,8 @@ struct Scene {                                                       // Scene.sw
         check(mrt_scene_set_instance_transforms_device(committed, firstMeshId, count, deviceTransforms, strideBytes, hipStream));
     }
     static void refitInstancesDevice(MRTScene committed, void *hipStream) { check(mrt_scene_refit_instances_device(committed, hipStream)); }
+    // ... or, when instances have migrated, the topology of both TLAS forms rebuilt on hipStream and then refitted (mrt_scene_rebuild_tlas_device): instead of the refit above
+    static void rebuildTlasDevice(MRTScene committed, void *hipStream) { check(mrt_scene_rebuild_tlas_device(committed, hipStream)); }
     // Stream-ordered deformation of a mesh inside a committed two-level MRTScene (mrt_scene_update_blas_device / mrt_scene_refit_blas_device): object-space vertices of a
     // source mesh from device memory, then its BLAS, its instances' boxes and the TLAS refitted on the stream.
     static void updateBlasDevice(MRTScene committed, int32_t meshId, const void *devicePositions, size_t positionStrideBytes, const void *deviceNormals, size_t normalStrideBytes,

@@ -298,6 +298,21 @@ int mrt_scene_device_updates_rejected(MRTScene scene, uint64_t *count);
  * outside the TLAS.  count == 0: MRT_OK, nothing is launched.                                                                                                          */
 int mrt_scene_set_instance_transforms_device(MRTScene scene, int32_t first_mesh_id, size_t count, const void *d_transforms_colmajor_4x4, size_t stride_bytes, void *hip_stream);
 int mrt_scene_refit_instances_device(MRTScene scene, void *hip_stream);
+/* The TOPOLOGY of both TLAS forms of a committed two-level scene rebuilt on a stream of the caller's, from the world boxes the device holds — as
+ * mrt_scene_set_instance_transforms_device and mrt_scene_refit_blas_device leave them —, followed by the refit of both forms' boxes.  It contains the
+ * refit: a caller who moved poses calls EITHER mrt_scene_refit_instances_device (the tree keeps its shape and loosens as instances migrate) OR this entry (instances that
+ * traded places trade leaves).  The host builders split every range of instances at half its count, so the shape of the tree depends on the instance count alone; the
+ * rebuild re-sorts the instance ids under that shape by the builders' own strict order (centre sum on the widest axis, then id) and refits.  The rope form then holds the
+ * nodes mrt_scene_commit would build from the same poses, bit for bit; the 8-wide form keeps the last commit's collapse (which subtrees became children of which node,
+ * their slots) and gets fresh instance sets under it.  The work is enqueued on hip_stream (taken literally: 0 is HIP's null stream).  The FIRST call after a commit may
+ * create or extend the instance workspace (4 bytes per instance, 12 above 1024 instances; it allocates and may block); every later call allocates nothing, copies nothing
+ * from host memory and synchronises neither the stream nor the device.  Up to 1024 instances the re-sort is one launch; the limit is 65 536 instances in the TLAS.
+ *   A rebuild with nothing moved changes no answer, and because the order is strict a second rebuild leaves every word of both forms as the first left it.
+ *   The caller owes what mrt_scene_refit_instances_device asks for.
+ *   The host side stays truthful with no new work: the next mrt_scene_commit builds both forms from the matrices it reads back; mrt_scene_stats is untouched.
+ * MRT_ERR_STATE: the scene is not committed, or host-side changes wait for a commit.  MRT_ERR_UNSUPPORTED: a flattened scene, a scene with no instance in the TLAS of the
+ * last commit, more than 65 536 instances in it.  MRT_ERR_INVALID_ARGUMENT: NULL scene.                                                                                  */
+int mrt_scene_rebuild_tlas_device(MRTScene scene, void *hip_stream);
 /* Deforming a mesh INSIDE a two-level scene (scene option instancing = 1) from DEVICE buffers, ordered on a stream of the caller's: a skinned character or
  * cloth among rigid instances, one deforming BLAS shared by many instances.  mrt_scene_update_blas_device replaces the OBJECT-space vertices of one source mesh of a
  * COMMITTED two-level scene with vertex_count strided float3 positions and normals read from device memory (strides >= 12, multiples of 4; 4-byte aligned pointers): the

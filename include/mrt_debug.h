@@ -40,7 +40,8 @@ int mrt_debug_read_wnodes(MRTScene scene, void *out, size_t nbytes, uint64_t *nu
  * nodes (80 B each), 1 = wpackets as the triangle test reads them (v0 | id word, e1, e2: 48 B each), 2 = the instance rows (InstanceDev, 80 B: w2o rows,
  * node / packet / gid / shading bases, ntri, blas, wroot), 3 = inst_box (64 B per instance: object-space BLAS box lo, hi, padded world box lo, hi),
  * 4 = wtlas_index (uint32), 5 = a header of 8 uint32 {num_wnodes, tlas_wcap, num_inst, wide_depth, packets, deepest BLAS, wtlas entries, packet stride in
- * float4}.  *count = elements of the part; out == NULL: only the count; otherwise nbytes must be count x the element size.                            */
+ * float4}, 6 = the rope TLAS nodes of a two-level scene (64 B each: lo | a, hi | b, eight escape links), 7 = tlas_index (uint32: instance ids in the rope TLAS's
+ * leaf order).  *count = elements of the part; out == NULL: only the count; otherwise nbytes must be count x the element size.                            */
 int mrt_debug_read_layout(MRTScene scene, int32_t part, void *out, size_t nbytes, uint64_t *count);
 /* Diagnostics: commits of this scene served by a refit (mrt_scene_update_mesh) since its last build.   */
 int mrt_debug_scene_refits(MRTScene scene, uint32_t *out);
@@ -60,6 +61,11 @@ int mrt_debug_poke_wnode(MRTScene scene, uint32_t node, uint32_t word, uint32_t 
 /* Scene option "builder" = 2's host part on caller boxes (n x float4 lo, n x float4 hi): a top-down binned-SAH binary tree — leaf order[n], left /
  * right of the n - 1 internal nodes (ids 0 .. n-2; leaf at position j = id n-1+j), parent of all 2n - 1 nodes (0xFFFFFFFF = root).  No device needed. */
 int mrt_debug_host_sah(const float *lo4, const float *hi4, uint32_t n, uint32_t *order, uint32_t *left, uint32_t *right, uint32_t *parent);
+/* The two host TLAS builders of a two-level scene on n caller boxes (n x float4 lo, n x float4 hi; 1 <= n <= 65536), instance ids 0 .. n-1.  No device needed.
+ * rope_order[n]: the rope TLAS's leaf order; rope_links: per rope node (at most 2n - 1) four words {a, b, escape link, depth (root = 1)}; wide_order[n]: the 8-wide
+ * TLAS's leaf-child order; wide_pos[n]: per entry of wide_order, its position in the binary median order; counts68 = {rope nodes, rope depths, 8-wide nodes, 8-wide
+ * levels, rope nodes per depth [32], 8-wide nodes per level [32]}.  What mrt_scene_rebuild_tlas_device rests on — the links depend on n alone — is checked with it. */
+int mrt_debug_tlas_host_build(const float *lo4, const float *hi4, uint32_t n, uint32_t *rope_order, uint32_t *rope_links, uint32_t *wide_order, uint32_t *wide_pos, uint32_t *counts68);
 /* The size check mrt_scene_commit applies (host only, no device needed): MRT_OK, or MRT_ERR_UNSUPPORTED when a scene of
  * `triangles` triangles whose BVH keeps `nodes` nodes (0 = unknown) cannot be addressed by the traversal layouts.      */
 int mrt_debug_layout_limits(uint64_t triangles, uint64_t nodes);

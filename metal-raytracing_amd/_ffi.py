@@ -158,6 +158,7 @@ SIGNATURES = {
     "mrt_scene_device_updates_rejected": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "mrt_scene_set_instance_transforms_device": (C.c_int, [_P, _I32, _SZ, _P, _SZ, _P]),
     "mrt_scene_refit_instances_device": (C.c_int, [_P, _P]),
+    "mrt_scene_rebuild_tlas_device": (C.c_int, [_P, _P]),
     "mrt_scene_update_blas_device": (C.c_int, [_P, _I32, _P, _SZ, _P, _SZ, _SZ, _P]),
     "mrt_scene_refit_blas_device": (C.c_int, [_P, _P]),
     "mrt_obj_load": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
@@ -234,6 +235,7 @@ SIGNATURES = {
     "mrt_debug_read_layout": (C.c_int, [_P, _I32, _P, _SZ, C.POINTER(C.c_uint64)]),
     "mrt_debug_layout_limits": (C.c_int, [C.c_uint64, C.c_uint64]),
     "mrt_debug_host_sah": (C.c_int, [_P, _P, _U32, _P, _P, _P, _P]),
+    "mrt_debug_tlas_host_build": (C.c_int, [_P, _P, _U32, _P, _P, _P, _P, _P]),
     "mrt_debug_validate": (C.c_int, [_P]),
     "mrt_debug_validate_patched": (C.c_int, [_P, _U32, _U32, _U32]),
 }

@@ -457,6 +457,15 @@ int mrt_scene_refit_instances_device(MRTScene scene, void *hip_stream) {
     return mrt::device_refit_instances(scene->dev, (hipStream_t)hip_stream);
     MRT_CATCH
 }
+int mrt_scene_rebuild_tlas_device(MRTScene scene, void *hip_stream) {
+    MRT_TRY
+    const char *who = "mrt_scene_rebuild_tlas_device";
+    if (int rc = device_instances_prologue(who, scene)) return rc;
+    if (int rc = mrt::tlas_rebuild_supported(scene->dev, who)) return rc;
+    if (int rc = mrt::instances_device_prepare(scene->dev)) return rc;          // (the first call after a commit allocates the workspace; later ones find it)
+    return mrt::device_rebuild_tlas(scene->dev, (hipStream_t)hip_stream);
+    MRT_CATCH
+}
 
 // Meshes of a two-level scene deformed from device buffers (bvh_refit.hip, tlas_refit.hip)
 static int device_blas_prologue(const char *who, MRTScene scene) {
@@ -986,14 +995,15 @@ int mrt_debug_read_wnodes(MRTScene scene, void *out, size_t nbytes, uint64_t *nu
 int mrt_debug_read_layout(MRTScene scene, int32_t part, void *out, size_t nbytes, uint64_t *count) {
     MRT_TRY
     REQUIRE(scene && count, "mrt_debug_read_layout: bad argument");
-    REQUIRE(part >= 0 && part <= 5, "mrt_debug_read_layout: part must be 0 .. 5");
+    REQUIRE(part >= 0 && part <= 7, "mrt_debug_read_layout: part must be 0 .. 7");
     if (!scene->committed) { mrt::set_error("mrt_debug_read_layout: scene not committed"); return MRT_ERR_STATE; }
     const mrt::DeviceScene &d = scene->dev;
     const size_t npk = d.wpackets.p ? d.wpackets.n / mrt::WPK : 0, ninst = d.num_inst, nwt = (d.num_inst && d.wtlas_index.p) ? d.wtlas_index.n : 0;
     uint32_t header[8] = {d.num_wnodes, d.num_inst ? d.tlas_wcap : 0u, d.num_inst, (uint32_t)d.wide_depth, (uint32_t)npk, (uint32_t)d.blas_wdepth, (uint32_t)nwt, mrt::WPK};
-    const size_t elem[6] = {16 * (size_t)mrt::WNODE_STRIDE, 16 * (size_t)mrt::WPK, sizeof(mrt::InstanceDev), 64, 4, 4};
-    const size_t n[6] = {d.num_wnodes, npk, ninst, ninst, nwt, 8};
-    const void *src[6] = {d.wnodes.p, d.wpackets.p, d.inst.p, d.inst_box.p, d.wtlas_index.p, header};
+    const size_t nrope = d.num_inst ? d.rope_nodes : 0, ntl = d.num_inst ? d.tlas_instances : 0;          // the rope TLAS of a two-level scene: its nodes and its index array
+    const size_t elem[8] = {16 * (size_t)mrt::WNODE_STRIDE, 16 * (size_t)mrt::WPK, sizeof(mrt::InstanceDev), 64, 4, 4, 64, 4};
+    const size_t n[8] = {d.num_wnodes, npk, ninst, ninst, nwt, 8, nrope, ntl};
+    const void *src[8] = {d.wnodes.p, d.wpackets.p, d.inst.p, d.inst_box.p, d.wtlas_index.p, header, d.nodes.p, d.tlas_index.p};
     *count = n[part];
     if (out == nullptr) return MRT_OK;
     REQUIRE(nbytes == n[part] * elem[part], "mrt_debug_read_layout: nbytes must be count x the element size of the part");
@@ -1055,6 +1065,13 @@ int mrt_debug_host_sah(const float *lo4, const float *hi4, uint32_t n, uint32_t 
     memcpy(order, o.data(), (size_t)n * 4); memcpy(parent, p.data(), (2 * (size_t)n - 1) * 4);
     if (n > 1) { memcpy(left, l.data(), (size_t)(n - 1) * 4); memcpy(right, r.data(), (size_t)(n - 1) * 4); }
     return MRT_OK;
+    MRT_CATCH
+}
+// TlasBuilder and WideTlasBuilder on caller boxes (no device needed): what mrt_scene_rebuild_tlas_device rests on is checked against them (tests/test_tlas_rebuild_device_cpu.py)
+int mrt_debug_tlas_host_build(const float *lo4, const float *hi4, uint32_t n, uint32_t *rope_order, uint32_t *rope_links, uint32_t *wide_order, uint32_t *wide_pos, uint32_t *counts68) {
+    MRT_TRY
+    REQUIRE(lo4 && hi4 && n >= 1 && n <= 65536 && rope_order && rope_links && wide_order && wide_pos && counts68, "mrt_debug_tlas_host_build: bad argument");
+    return mrt::tlas_host_build(lo4, hi4, n, rope_order, rope_links, wide_order, wide_pos, counts68);
     MRT_CATCH
 }
 int mrt_debug_layout_limits(uint64_t triangles, uint64_t nodes) {

@@ -277,6 +277,8 @@ struct InstanceWorkspace {
     std::vector<uint32_t> rope_first;                      // first entry of every depth in rope_order
     std::vector<uint32_t> wide_first;                      // first node of every level of the 8-wide TLAS
     std::vector<uint8_t> moved;                            // per instance: the HostMesh::xf copy is older than the device's inst_cols
+    DevBuf<uint32_t> wide_of_pos;                          // mrt_scene_rebuild_tlas_device (tlas_rebuild.hip): per leaf position of the binary median order, the entry of wtlas_index that names it (the inverse of DeviceScene::tlas_wide_pos)
+    DevBuf<uint32_t> ids[2], seg_axis;                     // ... and, above TLAS_RESORT_LDS_LIMIT instances only, the ping-pong id buffers of its one-level-per-step part and the split axis per range of a level
     hipEvent_t ev_last = nullptr;                          // behind the last set or refit enqueued: what a blocking reader waits for
     uint32_t seq = 0;                                      // set calls so far
     InstanceWorkspace() = default;
@@ -345,6 +347,8 @@ struct DeviceScene {
     std::vector<uint8_t> in_tlas;                              // per instance: it is a leaf of the last TLAS build (ntri > 0, invertible then)
     std::vector<uint32_t> tlas_rope_order, tlas_rope_levels;   // rope TLAS: node indices grouped by depth (root first), nodes per depth — what refit_instances walks bottom-up
     std::vector<uint32_t> tlas_wide_levels;                    // 8-wide TLAS, when resident: nodes per level (BFS numbering from node 0)
+    std::vector<uint32_t> tlas_wide_pos;                       // 8-wide TLAS, when resident: per entry of wtlas_index, the leaf position of its instance in the binary median order (WideTlasBuilder::pos)
+    uint32_t tlas_instances = 0;                               // instances in the TLAS of the last commit: the live entries of tlas_index (and of wtlas_index)
     std::unique_ptr<InstanceWorkspace> inst_ws;                // null until the first mrt_scene_set_instance_transforms_device / _refit_instances_device after a commit
     bool validate = true, validated_blas = false;              // commit-time index validation (two_level.hip validate_layout); BLAS part already checked
     DevBuf<float> g_pos; DevBuf<uint32_t> g_idx, g_recs;       // flattened build: packed object-space positions, indices and submesh records as uploaded (kept: a commit that only changes transforms does not upload them again)
@@ -398,6 +402,12 @@ int device_set_instance_transforms(DeviceScene &sc, uint32_t first, uint32_t cou
 int device_refit_instances(DeviceScene &sc, hipStream_t stream);
 int download_moved_transforms(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *moved_found = nullptr);      // blocks; HostMesh::xf of the instances moved on the device, read back from inst_cols
 void enqueue_blas_instance_boxes(DeviceScene &sc, const float4 *nbox, uint32_t root, const uint32_t *inst_list, uint32_t count, hipStream_t stream);      // the instances inst_list[0 .. count) of one BLAS take nbox[2 * root] as their object box and a world box recomputed from it (k_blas_instance_boxes)
+// tlas_rebuild.hip: the topology of both TLAS forms rebuilt on the caller's stream
+constexpr uint32_t TLAS_RESORT_LDS_LIMIT = 1024;      // instances one workgroup re-sorts in LDS, all levels in one launch: 16 bytes each (the three centre sums and the id)
+constexpr uint32_t TLAS_RESORT_MAX = 65536;           // instances mrt_scene_rebuild_tlas_device takes: above the LDS limit a level ranks its ranges by counting, quadratic in the range
+int tlas_rebuild_supported(const DeviceScene &sc, const char *who);      // MRT_OK, or MRT_ERR_UNSUPPORTED + message: more than TLAS_RESORT_MAX instances in the TLAS
+int device_rebuild_tlas(DeviceScene &sc, hipStream_t stream);      // needs sc.inst_ws (instances_device_prepare); ends with device_refit_instances
+int tlas_host_build(const float *lo4, const float *hi4, uint32_t n, uint32_t *rope_order, uint32_t *rope_links, uint32_t *wide_order, uint32_t *wide_pos, uint32_t *counts);      // two_level.hip: mrt_debug_tlas_host_build
 void drop_instance_workspace(DeviceScene &sc);      // (update_tlas: the TLAS the workspace was made for is gone; the rejected count is kept)
 // bvh_refit.hip: meshes of two-level scenes deformed from device buffers, ordered on the caller's stream
 int blas_device_supported(const DeviceScene &sc, const BuildOptions &opt, size_t meshes, const char *who);      // MRT_OK, or MRT_ERR_UNSUPPORTED + message: a flattened scene, refit = 0, a scene refit_two_level would not take

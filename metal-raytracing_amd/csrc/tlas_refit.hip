@@ -277,6 +277,18 @@ int instances_device_prepare(DeviceScene &sc) {
     MRT_HIP(w->rope_order.alloc(sc.tlas_rope_order.size())); MRT_HIP(w->nbox.alloc(2 * std::max<size_t>(at, 1)));
     MRT_HIP(hipMemset(w->words.p, 0, w->words.bytes())); MRT_HIP(hipMemset(w->rejected.p, 0, 8));
     if (!sc.tlas_rope_order.empty()) MRT_HIP(hipMemcpy(w->rope_order.p, sc.tlas_rope_order.data(), sc.tlas_rope_order.size() * 4, hipMemcpyHostToDevice));
+    // what mrt_scene_rebuild_tlas_device adds (tlas_rebuild.hip): 4 bytes per instance, and 8 more above the LDS limit
+    const uint32_t live = sc.tlas_instances;
+    if (!sc.tlas_wide_pos.empty()) {
+        std::vector<uint32_t> inv(sc.tlas_wide_pos.size());
+        for (size_t i = 0; i < inv.size(); i++) inv[sc.tlas_wide_pos[i]] = (uint32_t)i;
+        MRT_HIP(w->wide_of_pos.alloc(inv.size()));
+        MRT_HIP(hipMemcpy(w->wide_of_pos.p, inv.data(), inv.size() * 4, hipMemcpyHostToDevice));
+    }
+    if (live > TLAS_RESORT_LDS_LIMIT && live <= TLAS_RESORT_MAX) {
+        MRT_HIP(w->ids[0].alloc(live)); MRT_HIP(w->ids[1].alloc(live));
+        MRT_HIP(w->seg_axis.alloc((live + TLAS_RESORT_LDS_LIMIT - 1) / TLAS_RESORT_LDS_LIMIT));          // (a level handled one step at a time has fewer ranges than that)
+    }
     MRT_HIP(hipEventCreateWithFlags(&w->ev_last, hipEventDisableTiming));
     MRT_HIP(hipDeviceSynchronize());          // (the first call after a commit may block: from here on the caller's stream finds the workspace as the lines above left it)
     MRT_HIP(hipEventRecord(w->ev_last, nullptr));

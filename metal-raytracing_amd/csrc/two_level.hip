@@ -166,9 +166,10 @@ struct TlasBuilder {
 // k_wide_level.  A leaf child's "packet" tri_base + offset is an entry of `order` (instance ids).
 struct WideTlasBuilder {
     const std::vector<Box> &boxes;
-    struct BNode { Box b; int left = -1, right = -1, inst = -1; };
+    struct BNode { Box b; int left = -1, right = -1, inst = -1; uint32_t first = 0; };      // first: where its range of the median order begins (a leaf: its position there)
     std::vector<BNode> bn;
     std::vector<uint32_t> order;          // instance ids, leaf-child order
+    std::vector<uint32_t> pos;            // beside order: the leaf's position in the binary median order (what a re-sort of the instances under this tree needs, tlas_rebuild.hip)
     std::vector<float4> nodes;            // 5 per wide node
     std::vector<uint32_t> levels;         // nodes per level (BFS numbering): what a refit of the boxes walks bottom-up (tlas_refit.hip)
     int depth = 0;
@@ -184,6 +185,7 @@ struct WideTlasBuilder {
                 const float c = 0.5f * (q.lo[k] + q.hi[k]); clo[k] = std::min(clo[k], c); chi[k] = std::max(chi[k], c);
             }
         }
+        n.first = first;
         const int me = (int)bn.size(); bn.push_back(n);
         if (count == 1) { bn[me].inst = (int)ids[first]; return me; }
         int ax = 0; if (chi[1] - clo[1] > chi[ax] - clo[ax]) ax = 1; if (chi[2] - clo[2] > chi[ax] - clo[ax]) ax = 2;
@@ -253,7 +255,7 @@ struct WideTlasBuilder {
                             if (f.b.lo[a] + fh * step[a] < c.b.hi[a] && fh < 255.0f) fh += 1.0f;
                             ql[a] = (uint32_t)fl; qh[a] = (uint32_t)fh;
                         }
-                        if (c.inst >= 0) { meta[sl >> 2] |= ((1u << 5) | off_t) << (8 * (sl & 3)); order.push_back((uint32_t)c.inst); off_t++; }
+                        if (c.inst >= 0) { meta[sl >> 2] |= ((1u << 5) | off_t) << (8 * (sl & 3)); order.push_back((uint32_t)c.inst); pos.push_back(c.first); off_t++; }
                         else { imask |= 1u << sl; next.push_back(ch[k]); }
                     }
                     for (int a = 0; a < 3; a++) { q[a][sl >> 2] |= ql[a] << (8 * (sl & 3)); q[3 + a][sl >> 2] |= qh[a] << (8 * (sl & 3)); }
@@ -440,7 +442,8 @@ int update_tlas(const std::vector<HostMesh> &meshes, hipStream_t stream, DeviceS
     if (!live.empty()) tb.build(0, (uint32_t)live.size(), NODE_TERM, 1);
     // what mrt_scene_refit_instances_device needs of this tree: which instances are its leaves, its nodes by depth
     out.in_tlas.assign(I, 0); for (uint32_t i : live) out.in_tlas[i] = 1;
-    out.tlas_rope_levels.assign((size_t)tb.depth, 0u); out.tlas_rope_order.resize(tb.node_depth.size()); out.tlas_wide_levels.clear();
+    out.tlas_rope_levels.assign((size_t)tb.depth, 0u); out.tlas_rope_order.resize(tb.node_depth.size()); out.tlas_wide_levels.clear(); out.tlas_wide_pos.clear();
+    out.tlas_instances = (uint32_t)live.size();
     {
         for (uint32_t d : tb.node_depth) out.tlas_rope_levels[d - 1]++;
         std::vector<uint32_t> at(out.tlas_rope_levels.size(), 0u);
@@ -472,7 +475,7 @@ int update_tlas(const std::vector<HostMesh> &meshes, hipStream_t stream, DeviceS
             if (wn < out.tlas_wcap) MRT_HIP(hipMemsetAsync(out.wnodes.p + wb.nodes.size(), 0, (out.tlas_wcap - wn) * WNODE_STRIDE * 16, stream));
             out.num_wnodes = (uint32_t)(out.wnodes.n / WNODE_STRIDE);
             out.wide_depth = wb.depth + 1 + out.blas_wdepth;
-            out.tlas_wide_levels = wb.levels;
+            out.tlas_wide_levels = wb.levels; out.tlas_wide_pos = wb.pos;
         }
     }
     MRT_HIP(hipStreamSynchronize(stream));
@@ -482,6 +485,30 @@ int update_tlas(const std::vector<HostMesh> &meshes, hipStream_t stream, DeviceS
     out.stats.max_depth = tb.depth;
     out.tlas_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (out.validate) { if (int rc = validate_layout(out, stream, out.validated_blas)) return rc; out.validated_blas = true; }
+    return MRT_OK;
+}
+
+// mrt_debug_tlas_host_build: both host builders on n caller boxes, no device needed.  rope_order[n]; rope_links: {a, b, escape, depth} per rope node (at most 2n - 1);
+// wide_order[n], wide_pos[n]; counts[68] = {rope nodes, rope depths, 8-wide nodes, 8-wide levels, rope nodes per depth [32], 8-wide nodes per level [32]}
+int tlas_host_build(const float *lo4, const float *hi4, uint32_t n, uint32_t *rope_order, uint32_t *rope_links, uint32_t *wide_order, uint32_t *wide_pos, uint32_t *counts) {
+    std::vector<Box> boxes(n);
+    std::vector<uint32_t> live(n);
+    for (uint32_t i = 0; i < n; i++) { live[i] = i; for (int k = 0; k < 3; k++) { boxes[i].lo[k] = lo4[4 * (size_t)i + k]; boxes[i].hi[k] = hi4[4 * (size_t)i + k]; } }
+    TlasBuilder tb(boxes);
+    tb.order = live;
+    tb.build(0, n, NODE_TERM, 1);
+    WideTlasBuilder wb(boxes);
+    wb.build(live);
+    if (tb.depth > 32 || wb.levels.size() > 32) { set_error("mrt_debug_tlas_host_build: more than 32 levels"); return MRT_ERR_UNSUPPORTED; }
+    memcpy(rope_order, tb.order.data(), (size_t)n * 4); memcpy(wide_order, wb.order.data(), (size_t)n * 4); memcpy(wide_pos, wb.pos.data(), (size_t)n * 4);
+    const size_t rn = tb.nodes.size() / 4;
+    memset(counts, 0, 68 * 4);
+    counts[0] = (uint32_t)rn; counts[1] = (uint32_t)tb.depth; counts[2] = (uint32_t)(wb.nodes.size() / 5); counts[3] = (uint32_t)wb.levels.size();
+    for (size_t k = 0; k < rn; k++) {
+        memcpy(&rope_links[4 * k + 0], &tb.nodes[4 * k].w, 4); memcpy(&rope_links[4 * k + 1], &tb.nodes[4 * k + 1].w, 4); memcpy(&rope_links[4 * k + 2], &tb.nodes[4 * k + 2].x, 4);
+        rope_links[4 * k + 3] = tb.node_depth[k]; counts[4 + tb.node_depth[k] - 1]++;
+    }
+    for (size_t L = 0; L < wb.levels.size(); L++) counts[36 + L] = wb.levels[L];
     return MRT_OK;
 }
 

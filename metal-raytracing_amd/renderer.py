@@ -203,6 +203,12 @@ class DeviceScene:
         """The refit of both TLAS forms after set_instance_transforms_device, enqueued on the stream: boxes bottom-up, topology kept."""
         check(lib.mrt_scene_refit_instances_device(self.handle, C.c_void_p(self._stream_handle(stream))))
 
+    def rebuild_tlas_device(self, stream=None):
+        """The topology of both TLAS forms rebuilt on the stream from the poses the device holds, then their boxes refitted: call it INSTEAD of refit_instances_device()
+        when instances have migrated.  The rope TLAS gets the nodes a commit would build, bit for bit; the 8-wide TLAS keeps the last commit's collapse and gets fresh
+        instance sets under it.  Nothing is allocated, copied from the host or waited for after the first call."""
+        check(lib.mrt_scene_rebuild_tlas_device(self.handle, C.c_void_p(self._stream_handle(stream))))
+
     def update_blas_device(self, mesh_id, positions, normals, stream=None):
         """A mesh deforming inside a two-level scene (option instancing = 1), from the GPU and ordered on a stream: positions and normals are torch.float32 (n, 3)
         tensors on the context's device in OBJECT space, n the vertex count of source mesh mesh_id, rows as update_mesh_device takes them; every instance of the mesh
@@ -241,20 +247,21 @@ class DeviceScene:
         check(lib.mrt_debug_stream_stats(self.handle, ptr(rays), rays.shape[0], 1 if any_hit else 0, per_wave, ptr(out), nw))
         return out
 
-    _LAYOUT_PARTS = {"wnodes": 0, "wpackets": 1, "instances": 2, "inst_box": 3, "wtlas_index": 4, "header": 5}
+    _LAYOUT_PARTS = {"wnodes": 0, "wpackets": 1, "instances": 2, "inst_box": 3, "wtlas_index": 4, "header": 5, "tlas_nodes": 6, "tlas_index": 7}
 
     def read_layout(self, part):
         """Diagnostics: one array of the committed 8-wide layout (mrt_debug_read_layout) as numpy — "wnodes" (n, 20) uint32, "wpackets" (n, 4 x stride)
-        uint32, "instances" (n, 20) uint32 (InstanceDev), "inst_box" (n, 16) float32, "wtlas_index" (n,) uint32, "header" (8,) uint32."""
+        uint32, "instances" (n, 20) uint32 (InstanceDev), "inst_box" (n, 16) float32, "wtlas_index" (n,) uint32, "header" (8,) uint32,
+        "tlas_nodes" (n, 16) uint32 (the rope TLAS of a two-level scene), "tlas_index" (n,) uint32."""
         k = self._LAYOUT_PARTS[part] if isinstance(part, str) else int(part)
         n = C.c_uint64()
         check(lib.mrt_debug_read_layout(self.handle, k, None, 0, C.byref(n)))
         if k == 5:
             out = np.zeros(8, np.uint32)
-        elif k == 4:
+        elif k in (4, 7):
             out = np.zeros(n.value, np.uint32)
         else:
-            words = {0: 20, 2: 20, 3: 16}.get(k)
+            words = {0: 20, 2: 20, 3: 16, 6: 16}.get(k)
             if words is None:
                 hdr = self.read_layout(5)
                 words = 4 * int(hdr[7])

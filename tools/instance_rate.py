@@ -4,8 +4,9 @@
   (b) the path there was before: the same torch expression, .cpu(), DeviceScene.set_instance_transform per instance + commit, then the same device query; wall time,
       the stream drained at both ends.
 Both in this process on this device, alternating; 3 warm + 20 timed steps each, median.  (b) on the same box is the yardstick: there is no bar.
-Then the price of the kept topology: the movers trade places end for end (the first with the last, ...), (a) refits the tree it has, (b) commits, and the same queries are
-timed on both trees.
+  (c) as (a) with DeviceScene.rebuild_tlas_device in place of the refit: the topology of both TLAS forms rebuilt on the stream at every step.
+Then the price of the kept topology: the movers trade places end for end (the first with the last, ...), (a) refits the tree it has, (b) commits, (c) rebuilds on the
+device, and the same queries are timed on the three trees.
 Scenes: dragon4 (DragonScene with the dragon four times: 1 BLAS x 4 instances beside the scene's other meshes) and a plane under 64 and under 1 024 small spheres.
 Usage: python tools/instance_rate.py [--rays 1048576] [--reps 20] [--scenes dragon4,64,1024]      (prints one JSON line)"""
 import argparse
@@ -49,7 +50,7 @@ def run(m, ctx, name, a):
     else:
         movers = list(range(1, I))
     dev = torch.device("cuda", ctx.device)
-    dsa, dsb = m.DeviceScene(ctx, sc, {"instancing": 1}), m.DeviceScene(ctx, sc, {"instancing": 1})          # (a) and (b) each move a scene of their own
+    dsa, dsb, dsc = (m.DeviceScene(ctx, sc, {"instancing": 1}) for _ in range(3))          # (a), (b) and (c) each move a scene of their own
     base = torch.from_numpy(np.stack([np.asarray(e[2], np.float32).reshape(16) for e in meshes])).to(dev)
     mask = torch.zeros((I, 1), device=dev); mask[movers] = 1.0
     phase = torch.arange(I, device=dev, dtype=torch.float32).reshape(I, 1)
@@ -69,7 +70,7 @@ def run(m, ctx, name, a):
         for k in movers: ds.set_instance_transform(k, h[k])
         ds.commit()
 
-    ta, tb, parts = [], [], []
+    ta, tb, parts, tc, tcommit = [], [], [], [], []
     e0, e1, e2, e3 = (torch.cuda.Event(enable_timing=True) for _ in range(4))
     hits = 0
     with torch.cuda.stream(stream):
@@ -87,25 +88,40 @@ def run(m, ctx, name, a):
             hits_a = int((out[:, 0] == 1).sum())
             if step >= a.warm:
                 ta.append(e0.elapsed_time(e3)); parts.append((e0.elapsed_time(e1), e1.elapsed_time(e2), e2.elapsed_time(e3)))
+            # (c): as (a), the TLAS rebuilt instead of refitted
+            e0.record(stream)
+            x = poses(step)
+            e1.record(stream)
+            dsc.set_instance_transforms_device(0, x)
+            dsc.rebuild_tlas_device()
+            e2.record(stream)
+            dsc.intersect_closest_device(d_rays, out=out)
+            e3.record(stream)
+            stream.synchronize()
+            hits_c = int((out[:, 0] == 1).sum())
+            if step >= a.warm: tc.append((e1.elapsed_time(e2), e2.elapsed_time(e3)))
             # (b): through the host
             stream.synchronize()
             t0 = time.perf_counter()
             host_move(dsb, poses(step))
+            stream.synchronize()
+            t1 = time.perf_counter()
             dsb.intersect_closest_device(d_rays, out=out)
             stream.synchronize()
             if step >= a.warm:
-                tb.append((time.perf_counter() - t0) * 1e3)
+                tb.append((time.perf_counter() - t0) * 1e3); tcommit.append((t1 - t0) * 1e3)
             hits = int((out[:, 0] == 1).sum())
-            assert hits_a == hits, (hits_a, hits)
+            assert hits_a == hits and hits_c == hits, (hits_a, hits_c, hits)
         # the kept topology at its worst: the movers trade places end for end; (a) refits the tree it has, (b) builds one for the new places
         x = poses(0)
         idx = torch.tensor(movers, device=dev)
         x[idx, 12:15] = x[idx.flip(0), 12:15]
         dsa.set_instance_transforms_device(0, x); dsa.refit_instances_device()
+        dsc.set_instance_transforms_device(0, x); dsc.rebuild_tlas_device()
         host_move(dsb, x)
-        q = {"refit": [], "rebuild": []}
+        q = {"refit": [], "rebuild": [], "rebuild_device": []}
         for rep in range(a.warm + a.reps):
-            for which, ds in (("refit", dsa), ("rebuild", dsb)):
+            for which, ds in (("refit", dsa), ("rebuild", dsb), ("rebuild_device", dsc)):
                 e0.record(stream)
                 ds.intersect_closest_device(d_rays, out=out)
                 e1.record(stream)
@@ -116,8 +132,10 @@ def run(m, ctx, name, a):
            "a_stream_ms": med(ta), "b_host_ms": med(tb), "b_over_a": med(tb) / med(ta), "a_min_ms": min(ta), "b_min_ms": min(tb),
            "a_parts_ms": {"poses": med([p[0] for p in parts]), "set_and_refit": med([p[1] for p in parts]), "query": med([p[2] for p in parts])},
            "hits": hits, "rejected": dsa.device_updates_rejected,
-           "swapped_query_ms": {k: med(v) for k, v in q.items()}, "refit_over_rebuild_rate": med(q["rebuild"]) / med(q["refit"])}
-    dsa.close(); dsb.close()
+           "c_set_and_rebuild_ms": med([p[0] for p in tc]), "c_query_ms": med([p[1] for p in tc]), "b_commit_step_ms": med(tcommit),
+           "swapped_query_ms": {k: med(v) for k, v in q.items()}, "refit_over_rebuild_rate": med(q["rebuild"]) / med(q["refit"]),
+           "device_rebuild_over_rebuild_rate": med(q["rebuild"]) / med(q["rebuild_device"])}
+    dsa.close(); dsb.close(); dsc.close()
     return res
 
 
