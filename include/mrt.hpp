@@ -135,6 +135,21 @@ struct Scene {                                                       // Scene.sw
         check(mrt_scene_update_blas_device(committed, meshId, devicePositions, positionStrideBytes, deviceNormals, normalStrideBytes, vertexCount, hipStream));
     }
     static void refitBlasDevice(MRTScene committed, void *hipStream) { check(mrt_scene_refit_blas_device(committed, hipStream)); }
+    // The step after the query, on device buffers and a stream (mrt_scene_resolve_hits_device / mrt_scene_interpolate_device): n x MRTRay and the n x MRTIntersection the
+    // query wrote for them -> n x MRTSurface (position | distance, shading normal | type, base colour | resource slot, ids), read from what the device holds now; and any
+    // per-vertex float data of the caller's (channels floats per vertex, numbered as vertexOffsets describes) interpolated at the hits.  The first call after a commit makes
+    // a small table; later ones allocate, copy and wait for nothing.
+    static void resolveHitsDevice(MRTScene committed, const void *deviceRays, const void *deviceHits, size_t n, void *deviceSurfaces, void *hipStream) {
+        check(mrt_scene_resolve_hits_device(committed, deviceRays, deviceHits, n, deviceSurfaces, hipStream));
+    }
+    static void interpolateDevice(MRTScene committed, const void *deviceHits, size_t n, const void *deviceAttributes, size_t attributeStrideBytes, int32_t channels,
+                                  void *deviceOut, size_t outStrideBytes, void *hipStream) {
+        check(mrt_scene_interpolate_device(committed, deviceHits, n, deviceAttributes, attributeStrideBytes, channels, deviceOut, outStrideBytes, hipStream));
+    }
+    // each mesh's first attribute row (an instance reports its source's) and, last, the number of rows: meshCount + 1 entries
+    static std::vector<uint64_t> vertexOffsets(MRTScene scene, size_t meshCount) {
+        std::vector<uint64_t> o(meshCount + 1); check(mrt_scene_vertex_offsets(scene, o.data(), o.size())); return o;
+    }
     void updateUniforms(int width, int height) { camera = setupCamera(width, height); }   // Scene.swift:36-38
     static Camera setupCamera(int width, int height) { Camera c; check(mrt_default_camera(width, height, &c)); return c; }   // :40-57
     static Light setupLight() {                                      // :59-67
@@ -214,6 +229,12 @@ class Renderer {                                                     // Renderer
     void *stream() const { void *s = nullptr; check(mrt_context_get_stream(ctx_, &s)); return s; }
     void intersectClosestDevice(const void *deviceRays, size_t n, void *deviceOut, void *hipStream) { Scene::intersectClosestDevice(scene_, deviceRays, n, deviceOut, hipStream); }
     void intersectAnyDevice(const void *deviceRays, size_t n, void *deviceOccluded, void *hipStream) { Scene::intersectAnyDevice(scene_, deviceRays, n, deviceOccluded, hipStream); }
+    // hit records resolved to surface data, and the caller's per-vertex data interpolated at the hits (Scene::resolveHitsDevice / interpolateDevice / vertexOffsets)
+    void resolveHitsDevice(const void *deviceRays, const void *deviceHits, size_t n, void *deviceSurfaces, void *hipStream) { Scene::resolveHitsDevice(scene_, deviceRays, deviceHits, n, deviceSurfaces, hipStream); }
+    void interpolateDevice(const void *deviceHits, size_t n, const void *deviceAttributes, size_t attributeStrideBytes, int32_t channels, void *deviceOut, size_t outStrideBytes, void *hipStream) {
+        Scene::interpolateDevice(scene_, deviceHits, n, deviceAttributes, attributeStrideBytes, channels, deviceOut, outStrideBytes, hipStream);
+    }
+    std::vector<uint64_t> vertexOffsets() const { MRTSceneStats st; check(mrt_scene_stats(scene_, &st)); return Scene::vertexOffsets(scene_, (size_t)st.instances); }
     // deformation from device buffers on a stream (Scene::updateMeshDevice): packed or strided float3 rows; refitDevice() after one or more updates
     void updateMeshDevice(int32_t meshId, const void *devicePositions, size_t positionStrideBytes, const void *deviceNormals, size_t normalStrideBytes, size_t vertexCount, void *hipStream) {
         Scene::updateMeshDevice(scene_, meshId, devicePositions, positionStrideBytes, deviceNormals, normalStrideBytes, vertexCount, hipStream);

@@ -340,6 +340,43 @@ int mrt_scene_update_blas_device(MRTScene scene, int32_t mesh_id, const void *d_
                                  const void *d_normals, size_t nrm_stride_bytes, size_t vertex_count, void *hip_stream);
 int mrt_scene_refit_blas_device(MRTScene scene, void *hip_stream);
 
+/* The step after the query, on DEVICE buffers and ordered on a stream of the caller's: what the reference's kernel does right after its intersector call —
+ * interpolateVertexAttribute, the instance transform of the normal and the resource-table lookup (Raytracing.metal:63-72, :261-269) — for a caller's own rays and the
+ * MRTIntersection records the query entries wrote for them.  Vertex indices, normals, instance matrices and the material table live inside the library, and after
+ * mrt_scene_update_mesh_device / mrt_scene_update_blas_device / mrt_scene_set_instance_transforms_device only the device holds their current values: these entries read
+ * exactly those.
+ *   mrt_scene_resolve_hits_device: d_rays is n x MRTRay, d_hits n x MRTIntersection, d_surfaces n x MRTSurface (64 B each); EVERY surface record is written.
+ *     position   origin + direction * distance per component, a product and a sum (two roundings), the renderer's own P; `distance` is the record's
+ *     normal     the renderer's shading normal: (u * n1 + v * n2) + ((1 - u) - v) * n0 of the triangle's object-space vertex normals, through columns 0..2 of
+ *                the instance's matrix ((c0.k * x + c1.k * y) + c2.k * z), times 1 / sqrt of its own dot product — float32, no contraction, bit for bit what the render
+ *                kernels and MRT_GUIDE_NORMAL_DEPTH hold for the same hit
+ *     base_color baseColor of the material at resource_slot = instance_id * MRTSceneStats.max_submeshes + geometry_id (Renderer.swift:139), the key to the other fields
+ *     A record with type == 0, and a record whose ids name nothing in the scene (instance_id, geometry_id or primitive_id negative or past the end), gives the miss record
+ *     {0, 0, 0, -1.0f | 0, 0, 0, 0 | 0, 0, 0, -1 | -1, -1, -1, 0}: every id is checked against the scene's tables before anything is indexed with it.
+ *   mrt_scene_interpolate_device: the general form of interpolateVertexAttribute — any per-vertex float32 data of the caller's at the hits.  d_attributes holds `channels`
+ *     (1 .. 64) float32 per vertex, rows attr_stride_bytes apart (>= 4 * channels, a multiple of 4; 4-byte aligned), numbered as the caller knows the vertices: the source
+ *     meshes concatenated in mesh-id order, an instance sharing its source's rows (mrt_scene_vertex_offsets: each mesh's first row — an instance reports its source's — and,
+ *     last, the total).  For a hit on the triangle (i0, i1, i2): out[c] = (u * a[i1][c] + v * a[i2][c]) + ((1.0f - u) - v) * a[i0][c], float32, no contraction; a miss or
+ *     an invalid id writes 0 in every channel.  d_out: n rows of `channels` float32, out_stride_bytes apart (same rules); bytes between the rows are left alone.
+ * Both scene forms and every layout (8-wide, 8-wide + rope, rope only): the tree is not read.
+ * The contract of the _device query entries: buffers in device memory of the scene's device that stay alive until the stream has passed the call; hip_stream taken literally
+ * (0 is HIP's null stream); no mrt_scene_commit while a call is in flight, and device updates of the scene on ANOTHER stream ordered by the caller.  The FIRST call after a
+ * commit creates a table of 16 bytes per resource slot (it allocates and may block); every later call enqueues one kernel and returns: it allocates nothing, copies nothing
+ * from host memory and synchronises neither the stream nor the device.  Nothing here writes the scene, so the stale-host rules of mrt_scene_update_mesh_device do not apply.
+ * n == 0: MRT_OK, nothing is launched.  MRT_ERR_STATE: the scene is not committed.  MRT_ERR_INVALID_ARGUMENT: NULL scene, NULL buffers with n > 0, d_rays / d_hits /
+ * d_surfaces not 16-byte aligned, attributes / output not 4-byte aligned, channels outside 1 .. 64, a bad stride, n >= 2^31; mrt_scene_vertex_offsets: count other than
+ * the number of meshes + 1.                                                                                                                                             */
+typedef struct {
+    float   position[3];   float   distance;       /* origin + direction * distance | the record's distance (-1 for a miss)                   */
+    float   normal[3];     int32_t type;           /* shading normal, world space, normalised | 1 = triangle, 0 = none                        */
+    float   base_color[3]; int32_t resource_slot;  /* base_color[instance * max_submeshes + geometry] | that slot (-1 for a miss)             */
+    int32_t instance_id, geometry_id, primitive_id, _pad;
+} MRTSurface;                                                         /* 64 B                   */
+int mrt_scene_resolve_hits_device(MRTScene scene, const void *d_rays, const void *d_hits, size_t n, void *d_surfaces, void *hip_stream);
+int mrt_scene_interpolate_device(MRTScene scene, const void *d_hits, size_t n, const void *d_attributes, size_t attr_stride_bytes, int32_t channels,
+                                 void *d_out, size_t out_stride_bytes, void *hip_stream);
+int mrt_scene_vertex_offsets(MRTScene scene, uint64_t *offsets /* meshes + 1 entries */, size_t count);
+
 /* ---------------------------------------------------------------- host-side geometry helpers
  * (no GPU needed) — the library's OBJ/MTL reader standing in for ModelIO (Model.swift:16-21,
  * SubMesh.swift:37-54) and the procedural dragon proxy (dragon.obj is absent upstream).        */

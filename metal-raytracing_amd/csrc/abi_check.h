@@ -28,6 +28,10 @@ MRT_AT(MRTMaterial, specularExponent, 48); MRT_AT(MRTMaterial, refractionIndex, 
 // query records
 static_assert(sizeof(MRTRay) == 32 && sizeof(MRTIntersection) == 32, "ray / intersection records are 32 bytes");
 MRT_AT(MRTRay, min_distance, 12); MRT_AT(MRTRay, direction, 16); MRT_AT(MRTRay, max_distance, 28);
+// surface records (mrt_scene_resolve_hits_device; no counterpart in ShaderTypes.h): four 16-byte groups
+static_assert(sizeof(MRTSurface) == 64, "MRTSurface is 64 bytes");
+MRT_AT(MRTSurface, position, 0); MRT_AT(MRTSurface, distance, 12); MRT_AT(MRTSurface, normal, 16); MRT_AT(MRTSurface, type, 28);
+MRT_AT(MRTSurface, base_color, 32); MRT_AT(MRTSurface, resource_slot, 44); MRT_AT(MRTSurface, instance_id, 48); MRT_AT(MRTSurface, _pad, 60);
 // denoiser parameters (no counterpart in ShaderTypes.h)
 static_assert(sizeof(MRTDenoiseParams) == 32, "MRTDenoiseParams is 32 bytes");
 MRT_AT(MRTDenoiseParams, iterations, 0); MRT_AT(MRTDenoiseParams, sigma_color, 4); MRT_AT(MRTDenoiseParams, sigma_normal, 8);

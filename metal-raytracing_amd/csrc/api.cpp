@@ -270,6 +270,7 @@ int mrt_scene_commit(MRTScene scene) {
     MRT_TRY
     REQUIRE(scene, "mrt_scene_commit: scene is NULL");
     int rc = bind_device(scene->ctx); if (rc) return rc;
+    mrt::drop_surface_workspace(scene->dev);          // (the surface entries' slot table restates the mesh list of the commit before; the next such call makes it again)
     // vertices replaced on the device since the last commit (mrt_scene_update_mesh_device): the statistics of those refits are read first (a refit below chains on them), then the
     // meshes' host copies, which everything below reads, are brought up to date
     rc = mrt::resolve_device_refits(scene->dev, scene->opt, scene->ctx->stream); if (rc) return rc;
@@ -513,6 +514,52 @@ int mrt_scene_device_updates_rejected(MRTScene scene, uint64_t *count) {
     REQUIRE(scene && count, "mrt_scene_device_updates_rejected: bad argument");
     int rc = bind_device(scene->ctx); if (rc) return rc;
     return mrt::device_updates_rejected(scene->dev, count);
+    MRT_CATCH
+}
+
+// Hit records resolved to surface data on the caller's stream (surface.hip).  The plain arguments are checked before the scene is looked at: a refusal
+// of theirs needs no device.
+static int surface_prologue(const char *who, MRTScene scene, size_t n) {
+    if (n >= (size_t(1) << 31)) { mrt::set_error(std::string(who) + ": too many hits (n must be below 2^31)"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (!scene) { mrt::set_error(std::string(who) + ": scene is NULL"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (!scene->committed) { mrt::set_error(std::string(who) + ": scene not committed"); return MRT_ERR_STATE; }
+    return MRT_OK;
+}
+int mrt_scene_resolve_hits_device(MRTScene scene, const void *d_rays, const void *d_hits, size_t n, void *d_surfaces, void *hip_stream) {
+    MRT_TRY
+    const char *who = "mrt_scene_resolve_hits_device";
+    REQUIRE(n == 0 || (d_rays && d_hits && d_surfaces), "mrt_scene_resolve_hits_device: NULL buffers");
+    REQUIRE((uintptr_t)d_rays % 16 == 0 && (uintptr_t)d_hits % 16 == 0 && (uintptr_t)d_surfaces % 16 == 0, "mrt_scene_resolve_hits_device: buffers must be 16-byte aligned");
+    if (int rc = surface_prologue(who, scene, n)) return rc;
+    if (n == 0) return MRT_OK;
+    if (int rc = bind_device(scene->ctx)) return rc;
+    if (int rc = mrt::surface_prepare(scene->meshes, scene->dev)) return rc;          // (the first call after a commit makes the slot table; later ones find it)
+    return mrt::resolve_hits_device(scene->dev, (hipStream_t)hip_stream, d_rays, d_hits, n, d_surfaces);
+    MRT_CATCH
+}
+int mrt_scene_interpolate_device(MRTScene scene, const void *d_hits, size_t n, const void *d_attributes, size_t attr_stride, int32_t channels, void *d_out, size_t out_stride, void *hip_stream) {
+    MRT_TRY
+    const char *who = "mrt_scene_interpolate_device";
+    REQUIRE(channels >= 1 && channels <= 64, "mrt_scene_interpolate_device: channels must be 1 .. 64");
+    REQUIRE(attr_stride >= 4 * (size_t)channels && out_stride >= 4 * (size_t)channels, "mrt_scene_interpolate_device: a row stride is below 4 x channels bytes");
+    REQUIRE(attr_stride % 4 == 0 && out_stride % 4 == 0, "mrt_scene_interpolate_device: row strides must be multiples of 4");
+    REQUIRE(n == 0 || (d_hits && d_attributes && d_out), "mrt_scene_interpolate_device: NULL buffers");
+    REQUIRE((uintptr_t)d_hits % 16 == 0, "mrt_scene_interpolate_device: the hit records must be 16-byte aligned");
+    REQUIRE((uintptr_t)d_attributes % 4 == 0 && (uintptr_t)d_out % 4 == 0, "mrt_scene_interpolate_device: attributes and output must be 4-byte aligned");
+    if (int rc = surface_prologue(who, scene, n)) return rc;
+    if (n == 0) return MRT_OK;
+    if (int rc = bind_device(scene->ctx)) return rc;
+    if (int rc = mrt::surface_prepare(scene->meshes, scene->dev)) return rc;
+    return mrt::interpolate_device(scene->dev, (hipStream_t)hip_stream, d_hits, n, d_attributes, attr_stride, (uint32_t)channels, d_out, out_stride);
+    MRT_CATCH
+}
+int mrt_scene_vertex_offsets(MRTScene scene, uint64_t *offsets, size_t count) {
+    MRT_TRY
+    REQUIRE(scene && offsets, "mrt_scene_vertex_offsets: bad argument");
+    REQUIRE(count == scene->meshes.size() + 1, "mrt_scene_vertex_offsets: count must be the number of meshes + 1");
+    std::vector<uint64_t> o; mrt::surface_vertex_offsets(scene->meshes, o);
+    std::copy(o.begin(), o.end(), offsets);
+    return MRT_OK;
     MRT_CATCH
 }
 

@@ -319,6 +319,16 @@ struct BlasWorkspace {
     ~BlasWorkspace() { if (ev_last) (void)hipEventSynchronize(ev_last); for (hipEvent_t e : {ev_begin, ev_end, ev_last}) if (e) (void)hipEventDestroy(e); }
 };
 
+// What the surface entries (mrt_scene_resolve_hits_device / mrt_scene_interpolate_device, surface.hip) keep between calls: one row per resource slot —
+// {first shading record, triangle count, vertex base in `normals`, caller's vertex row minus the library's vertex id} — restated from the host's mesh list, so that a record's
+// ids are checked against sizes before anything is indexed with them and both scene forms resolve alike.  Made by the first such call after a commit (it allocates, uploads
+// and blocks), dropped by the next mrt_scene_commit and by mrt_scene_destroy.
+struct SurfaceWorkspace {
+    DevBuf<uint4> slots;
+    uint32_t instances = 0, max_sub = 1;
+    uint64_t vertices = 0;                                 // rows of the caller's numbering (mrt_scene_vertex_offsets' last entry)
+};
+
 struct DeviceScene {
     DevBuf<float4> nodes, packets, normals, base_color, materials, inst_cols, wnodes, wpackets;
     uint32_t num_wnodes = 0; int wide_depth = 0;
@@ -357,6 +367,7 @@ struct DeviceScene {
     std::unique_ptr<RefitWorkspace> refit_ws;                    // the stream-ordered refit's resident scratch (null until the first mrt_scene_update_mesh_device after a build)
     std::unique_ptr<BlasWorkspace> blas_ws;                      // two-level scenes: the stream-ordered BLAS refit's resident geometry and scratch (null until the first mrt_scene_update_blas_device / _refit_blas_device after a commit)
     DevBuf<double> cost_words;                                   // wide_tree_cost's 8 + 24 bytes for refit_two_level (made once, kept: no hipMalloc / hipFree pair per commit)
+    std::unique_ptr<SurfaceWorkspace> surface_ws;                // the surface entries' slot table (null until the first mrt_scene_resolve_hits_device / _interpolate_device after a commit)
     uint64_t rejected_before = 0;                                // device updates refused in the lifetimes of earlier workspaces of this scene
     SceneView view() const;
 };
@@ -417,6 +428,12 @@ int device_refit_blas(DeviceScene &sc, hipStream_t stream);      // needs sc.ins
 int resolve_blas_refits(DeviceScene &sc, const BuildOptions &opt, hipStream_t stream);      // blocks on the last refit; blas_lo / blas_hi, the BlasRanges' and the scene's statistics brought up to date (no-op when nothing is pending)
 int download_stale_blas_meshes(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *pending_found = nullptr);      // blocks; as download_stale_meshes, from the BLAS workspace
 void drop_blas_workspace(DeviceScene &sc);      // (the rejected count is kept)
+// surface.hip: hit records resolved to surface data on the caller's stream
+void surface_vertex_offsets(const std::vector<HostMesh> &meshes, std::vector<uint64_t> &offsets);      // the caller's vertex numbering: meshes + 1 entries
+int surface_prepare(const std::vector<HostMesh> &meshes, DeviceScene &sc);      // makes sc.surface_ws if it is not there (allocates, uploads the slot table, blocks)
+int resolve_hits_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, const void *d_hits, size_t n, void *d_surfaces);      // one launch, nothing else; needs sc.surface_ws
+int interpolate_device(const DeviceScene &sc, hipStream_t stream, const void *d_hits, size_t n, const void *d_attr, size_t attr_stride, uint32_t channels, void *d_out, size_t out_stride);
+void drop_surface_workspace(DeviceScene &sc);      // (a commit: the table restates the mesh list of the commit before)
 int upload_lights(const MRTLight *lights, int count, hipStream_t stream, DeviceScene &out);
 
 }  // namespace mrt

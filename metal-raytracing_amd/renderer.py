@@ -149,6 +149,74 @@ class DeviceScene:
         """Any-hit form of intersect_closest_device: torch.int32 (n,), 1 = occluded."""
         return self._device_query(lib.mrt_scene_intersect_any_device, rays, out, stream, ())
 
+    def _hit_records(self, hits, what="hits"):
+        """the (n, 8) torch.int32 tensor of MRTIntersection records intersect_closest_device returns, checked"""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        if not isinstance(hits, torch.Tensor) or hits.device != dev:
+            raise ValueError(f"{what} must be a torch tensor on {dev}")
+        if hits.dtype != torch.int32 or hits.dim() != 2 or hits.shape[1] != 8 or not hits.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous torch.int32 tensor of shape (n, 8): the records of intersect_closest_device")
+        return dev
+
+    def resolve_hits_device(self, rays, hits, out=None, stream=None):
+        """The step after intersect_closest_device, on the GPU and ordered on a stream: rays (n, 8) float32 and hits (n, 8) int32 as that method takes and returns them ->
+        torch.float32 (n, 16), one MRTSurface per row: position | distance, shading normal | type, base colour | resource slot, instance / geometry / primitive ids
+        (unpack_surfaces gives the fields).  The values are the ones the device holds now: vertices written by update_mesh_device / update_blas_device, poses written by
+        set_instance_transforms_device.  A miss, and a record whose ids name nothing in the scene, gives the miss record.  After the first call (which makes a small
+        table) nothing is allocated (but `out` when it is None), copied or synchronised.  stream: as intersect_closest_device takes it."""
+        import torch
+        dev = self._hit_records(hits)
+        if not isinstance(rays, torch.Tensor) or rays.device != dev:
+            raise ValueError(f"rays must be a torch tensor on {dev}")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.shape[0] != hits.shape[0]:
+            raise ValueError("rays must be a contiguous torch.float32 tensor of shape (n, 8), one row per hit record")
+        n = rays.shape[0]
+        if out is None:
+            out = torch.empty((n, 16), dtype=torch.float32, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != (n, 16) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous torch.float32 tensor of shape {(n, 16)} on {dev}")
+        check(lib.mrt_scene_resolve_hits_device(self.handle, C.c_void_p(rays.data_ptr() if n else None), C.c_void_p(hits.data_ptr() if n else None), n,
+                                                C.c_void_p(out.data_ptr() if n else None), C.c_void_p(self._stream_handle(stream))))
+        return out
+
+    def interpolate_device(self, hits, attributes, out=None, stream=None):
+        """Per-vertex data of the caller's interpolated at the hits, on the GPU and ordered on a stream: attributes is a torch.float32 (V, C) tensor on the context's
+        device, 1 <= C <= 64, rows contiguous and any multiple of 4 bytes apart (a slice of a wider tensor is fine; nothing is copied), one row per vertex in the
+        numbering vertex_offsets() describes -> torch.float32 (n, C): (u * a1 + v * a2) + ((1 - u) - v) * a0 over the hit triangle's vertices, zeros for a miss.
+        out: an (n, C) float32 tensor with the same freedom of row stride; the elements between its rows are left alone.  stream: as intersect_closest_device takes it."""
+        import torch
+        dev = self._hit_records(hits)
+        a = attributes
+        if not isinstance(a, torch.Tensor) or a.device != dev:
+            raise ValueError(f"attributes must be a torch tensor on {dev}")
+        if a.dtype != torch.float32 or a.dim() != 2 or not 1 <= a.shape[1] <= 64 or a.stride(1) != 1 or (a.shape[0] > 1 and a.stride(0) < a.shape[1]):
+            raise ValueError("attributes must be a torch.float32 tensor of shape (V, C), 1 <= C <= 64, with contiguous rows (a slice of a wider tensor is fine)")
+        total = int(self.vertex_offsets()[-1])
+        if a.shape[0] != total:          # the device reads a row per vertex of the scene: a shorter tensor would be read past its end
+            raise MRTError(1, f"interpolate_device: {a.shape[0]} attribute rows for the scene's {total} vertices (vertex_offsets()[-1])")
+        n, ch = hits.shape[0], a.shape[1]
+        if out is None:
+            out = torch.empty((n, ch), dtype=torch.float32, device=dev)
+        elif (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != (n, ch) or out.stride(1) != 1
+              or (n > 1 and out.stride(0) < ch)):
+            raise ValueError(f"out must be a torch.float32 tensor of shape {(n, ch)} on {dev} with contiguous rows")
+        check(lib.mrt_scene_interpolate_device(self.handle, C.c_void_p(hits.data_ptr() if n else None), n, C.c_void_p(a.data_ptr() if n else None),
+                                               (a.stride(0) if a.shape[0] > 1 else ch) * 4, ch, C.c_void_p(out.data_ptr() if n else None), (out.stride(0) if n > 1 else ch) * 4,
+                                               C.c_void_p(self._stream_handle(stream))))
+        return out
+
+    def vertex_offsets(self):
+        """The vertex numbering interpolate_device reads attributes in: (meshes + 1,) uint64 — each mesh's first row, the source meshes concatenated in mesh-id order and
+        an instance reporting its source's; the last entry is the number of rows."""
+        cached = getattr(self, "_vertex_offsets", None)          # (the mesh list of a DeviceScene is fixed at construction; asked once — stats may wait for a refit in flight)
+        if cached is None:
+            count = int(self.stats.instances) + 1
+            cached = np.zeros(count, np.uint64)
+            check(lib.mrt_scene_vertex_offsets(self.handle, cached.ctypes.data_as(C.POINTER(C.c_uint64)), count))
+            self._vertex_offsets = cached
+        return cached.copy()
+
     def _stream_handle(self, stream):
         """the stream argument of every *_device method as an integer handle: None = torch's current stream of the context's device, a torch.cuda.Stream, or the handle itself"""
         import torch
@@ -284,6 +352,20 @@ def unpack_intersections(t):
     import torch
     return {"type": t[:, 0], "distance": t[:, 1].view(torch.float32), "instance_id": t[:, 2], "geometry_id": t[:, 3], "primitive_id": t[:, 4],
             "u": t[:, 5].view(torch.float32), "v": t[:, 6].view(torch.float32)}
+
+
+SURFACE_DTYPE = np.dtype([("position", np.float32, 3), ("distance", np.float32), ("normal", np.float32, 3), ("type", np.int32),
+                          ("base_color", np.float32, 3), ("resource_slot", np.int32),
+                          ("instance_id", np.int32), ("geometry_id", np.int32), ("primitive_id", np.int32), ("_pad", np.int32)])
+
+
+def unpack_surfaces(t):
+    """The MRTSurface records of DeviceScene.resolve_hits_device as a structured numpy array (SURFACE_DTYPE), one per row of the (n, 16) float32 tensor: a view of a numpy
+    array, of a CPU tensor's memory, or of the host copy of a GPU tensor (which waits for the tensor's stream)."""
+    if not isinstance(t, np.ndarray):
+        t = t.detach().cpu().numpy()
+    t = np.ascontiguousarray(t, np.float32).reshape(-1, 16)
+    return t.view(SURFACE_DTYPE).reshape(-1)
 
 
 class Renderer:
