@@ -243,6 +243,7 @@ SIGNATURES = {
     "mrt_debug_read_wnodes": (C.c_int, [_P, _P, _SZ, C.POINTER(C.c_uint64)]),
     "mrt_debug_read_layout": (C.c_int, [_P, _I32, _P, _SZ, C.POINTER(C.c_uint64)]),
     "mrt_debug_layout_limits": (C.c_int, [C.c_uint64, C.c_uint64]),
+    "mrt_debug_segment_sizing": (C.c_int, [C.c_uint32, C.c_int32, C.POINTER(C.c_uint64)]),
     "mrt_debug_host_sah": (C.c_int, [_P, _P, _U32, _P, _P, _P, _P]),
     "mrt_debug_tlas_host_build": (C.c_int, [_P, _P, _U32, _P, _P, _P, _P, _P]),
     "mrt_debug_validate": (C.c_int, [_P]),

@@ -797,6 +797,7 @@ int mrt_debug_renderer_set_option(MRTRenderer r, const char *key, double value) 
     std::string k(key);
     if (k == "persistent") { REQUIRE(value == 0 || value == 1 || value == 2, "persistent must be 0 (never), 1 (always) or 2 (by launch size)"); r->r.persistent = (int)value; }
     else if (k == "xcd_counters") { REQUIRE(value == 0 || value == 1, "xcd_counters must be 0 or 1"); r->r.xcd_counters = (int)value; }
+    else if (k == "queue_segments") { REQUIRE(value == 1 || value == 8, "queue_segments must be 1 or 8"); r->r.queue_segments = r->r.segments_used = (int)value; }
     else if (k == "tile_groups") { REQUIRE(value >= 0 && value <= mrt::MAX_TILE_GROUPS && value == (int)value, "tile_groups must be 0 (by the draw), 1 (never) or 2..4"); r->r.tile_groups = (int)value; }
     else if (k == "shade_pack") { REQUIRE(value == 0 || value == 1, "shade_pack must be 0 or 1"); r->r.shade_pack = (int)value; }
     else if (k == "hit_lds") { REQUIRE(value == 0 || value == 1, "hit_lds must be 0 or 1"); r->r.hit_lds = (int)value; }
@@ -831,6 +832,7 @@ int mrt_debug_renderer_get_option(MRTRenderer r, const char *key, double *value)
     else if (k == "tile_groups") *value = r->r.tile_groups;
     else if (k == "groups_used") *value = r->r.groups_used;
     else if (k == "xcd_counters") *value = r->r.xcd_counters;
+    else if (k == "queue_segments") *value = r->r.segments_used;
     else if (k == "wave_slots") *value = r->r.wave_slots;
     else if (k == "stream_stride") *value = r->r.stream_stride;
     else if (k == "halton_table") *value = r->r.halton_table;
@@ -1124,6 +1126,14 @@ int mrt_debug_tlas_host_build(const float *lo4, const float *hi4, uint32_t n, ui
 int mrt_debug_layout_limits(uint64_t triangles, uint64_t nodes) {
     MRT_TRY
     return mrt::layout_limits(triangles, nodes);
+    MRT_CATCH
+}
+int mrt_debug_segment_sizing(uint32_t capacity, int32_t batch, uint64_t *out4) {
+    MRT_TRY
+    if (!out4 || batch < 1 || batch > mrt::MAX_FRAME_BATCH) { mrt::set_error("mrt_debug_segment_sizing: NULL output or batch outside 1 .. MAX_FRAME_BATCH"); return MRT_ERR_INVALID_ARGUMENT; }
+    const mrt::SegmentSizing z = mrt::segment_sizing(capacity, batch);
+    out4[0] = z.blocks; out4[1] = z.per_block; out4[2] = z.seg_cap; out4[3] = mrt::queue_entries(capacity, batch);
+    return MRT_OK;
     MRT_CATCH
 }
 int mrt_debug_calibrate(MRTContext ctx, size_t table_bytes, double *out3) {

@@ -71,10 +71,18 @@ struct PassPlan {
     PullGrid pg;                         // pairs, pull_x, pull
     uint32_t even = 0, static_grid = 0;  // static_x, static_split
     uint32_t mega_waves = 0;             // DrawPlan::mega
+    int segs = 1; uint32_t seg_cap = 0;  // segmented queues (shade.h FrameParams::segs): 8 segments of seg_cap entries, or the one queue
 };
+// shade(0) of a bundled pass and the capacity of one of its eight queue segments (renderer.hip segment_sizing: host arithmetic)
+struct SegmentSizing { uint32_t bundle_groups = 1, bundle_w = 1, bundle_per_wave = 64, per_block = 0; uint64_t blocks = 0, seg_cap = 0; };
+SegmentSizing segment_sizing(uint32_t capacity, int B);
+size_t queue_entries(uint32_t capacity, int alloc_batch);          // entries of each of a lane's ray queues and of its hit records, the segments' rounding included
 struct SlotCache { size_t lds_bytes = ~(size_t)0; int per_cu = 0; };      // resident 64-thread workgroups of a kernel per compute unit at this LDS size (renderer.hip wave_slots_for)
 struct DrawCtx;                          // renderer.hip: what the enqueue steps of one draw share
 
+#ifndef MRT_QUEUE_SEGMENTS_DEFAULT
+#define MRT_QUEUE_SEGMENTS_DEFAULT 8      // (a variant build with 1 runs the whole suite on the one-queue form: tools/build_variant.sh oneq "-DMRT_QUEUE_SEGMENTS_DEFAULT=1")
+#endif
 struct Renderer {
     hipStream_t stream = nullptr;
     const DeviceScene *scene = nullptr;
@@ -118,12 +126,14 @@ struct Renderer {
     int primary_wide = 2;                // primary rays of a flattened scene: 2 = one ray per lane on the 8-wide layout (inside shade(0) or in their own launch; default), 1 = the 8-wide stream kernel with lane refill (own launch), 0 = the rope walk (scene option rope = 1)
     int persistent = 2;                  // bounce / shadow traversal as persistent waves pulling chunks of rays from a shared counter: 0 never, 1 always, 2 by launch size
     int xcd_counters = 1;                  // pulling traversal launches: 1 = one work counter and one eighth of every sub-frame's rays per XCD (traverse_wide.h XcdRegions), 0 = one counter for all
+    int queue_segments = MRT_QUEUE_SEGMENTS_DEFAULT;      // the default pass's queues as eight segments with a tail word each, one per XCD (shade.h FrameParams::segs; plan_pass decides per pass): 8, or 1 = one queue and one word everywhere
+    int segments_used = MRT_QUEUE_SEGMENTS_DEFAULT;      // what the option reads back: the value in force as of the last draw (its first pass), or the value just set until the next draw decides
     int hit_lds = 1;                     // pulling traversal launches of flattened scenes: a lane's closest hit keeps U, V, |det| and id in LDS; a finished ray is reported without re-testing its triangle (traverse_wide.h StreamExt)
     int shade_pack = 1;                  // k_shade of bounces >= 1 compacts the hits of its queue in LDS and shades them on full waves (k_shade_pack)
     int persist_chunk = 256;             // rays per pull (upper bound; small queues pull less, see pull_grid())
     int wave_slots = 7168;               // resident waves the persistent launch is sized for (occupancy query at the first draw)
     bool wave_slots_user = false;        // set through the option: keep it
-    mutable SlotCache mega_cache, persist_cache, persist_x_cache;      // k_megakernel, k_trace_mixed_wide_persist, k_trace_mixed_wide_persist_x
+    mutable SlotCache mega_cache, persist_cache, persist_x_cache, persist_xs_cache;      // k_megakernel, k_trace_mixed_wide_persist, k_trace_mixed_wide_persist_x<false>, <true> (segmented passes)
     mutable int cu_count = 0;            // compute units of the device (looked up once)
     int alloc_planes(FrameLane &L);
     bool tail_accumulate = true;         // the last passes of a draw (one per lane) are accumulated in one launch after the join instead of one after the other

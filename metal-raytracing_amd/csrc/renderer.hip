@@ -241,15 +241,18 @@ __global__ void __launch_bounds__(64, TWO_LEVEL ? MRT_TWO_LEVEL_WAVES : MRT_WIDE
 
 // The pulling launch of flattened scenes with the hit words in LDS (traverse_wide.h StreamExt; renderer option hit_lds, default): every wave has its own hit
 // words (1 KB + the root's hit bits of the prefetched batch) in front of its stack.  Shadow planes only (`lit`): the default path of the pipeline.
+// SEG: a segmented pass (SegRegions) — `counts` is segment 0's tail word, `subframes` the segments' capacity, and a ray's index is physical with SEG_SHADOW_BIT for a shadow ray.
+template <bool SEG>
 __global__ void __launch_bounds__(64, MRT_WIDE_STREAM_WAVES) k_trace_mixed_wide_persist_x(SceneView s, const float4 *__restrict__ rayA, const float4 *__restrict__ rayB, float4 *__restrict__ hits,
                                                                 const float4 *__restrict__ srayA, const float4 *__restrict__ srayB, const unsigned long long *__restrict__ counts,
                                                                 uint32_t *__restrict__ work, uint32_t chunk, uint8_t *__restrict__ lit, uint32_t subframes) {
     extern __shared__ uint32_t lds_dyn[];
-    const unsigned long long c = *counts;
+    unsigned long long c = *counts;
+    if (SEG) for (uint32_t x = 1; x < QUEUE_SEGMENTS; x++) c += counts[(size_t)x * SEG_TAIL_STRIDE];          // (neither half carries: a pass queues fewer than 2^31 rays of a kind)
     const uint32_t n_next = (uint32_t)c, n_shadow = (uint32_t)(c >> 32), n = n_next + n_shadow;
-    if (blockIdx.x * chunk >= n) return;            // more waves than chunks (small queue): the surplus leaves at once
+    if ((unsigned long long)blockIdx.x * chunk >= (unsigned long long)n + (SEG ? 2ull * QUEUE_SEGMENTS * chunk : 0ull)) return;            // more waves than chunks (small queue; SEG: every segment rounds its two parts up): the surplus leaves at once
     auto fetch = [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) {
-            const bool sh = i >= n_next; tag = sh ? i - n_next : i; is_any = sh ? 1u : 0u;
+            const bool sh = SEG ? (i & SEG_SHADOW_BIT) != 0u : i >= n_next; tag = SEG ? i & ~SEG_SHADOW_BIT : sh ? i - n_next : i; is_any = sh ? 1u : 0u;
             A = qload(sh ? &srayA[tag] : &rayA[tag]); B = qload(sh ? &srayB[tag] : &rayB[tag]);
             if (!sh) A.w = __builtin_inff();          // a bounce ray's tmax word may carry the throughput chain
             else tag = __float_as_uint(B.w);          // shadow planes: the ray reports to its pixel's byte
@@ -259,7 +262,8 @@ __global__ void __launch_bounds__(64, MRT_WIDE_STREAM_WAVES) k_trace_mixed_wide_
             else qstore(&hits[j], hit ? make_float4(h.t, h.U / h.ad, h.V / h.ad, __uint_as_float(h.gid)) : make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)));
         };
     StreamExt<true> ext{reinterpret_cast<float *>(lds_dyn), lds_dyn + 256u};
-    traverse_wide_stream<false, false, false, NoPairs, StreamExt<true>>(s, XcdRegions{work, n_next, n, chunk, subframes, blockIdx.x & 7u}, lds_dyn + HIT_LDS_WORDS, fetch, emit, nullptr, NoPairs{}, ext);
+    if constexpr (SEG) traverse_wide_stream<false, false, false, NoPairs, StreamExt<true>>(s, SegRegions{work, counts, subframes, chunk, blockIdx.x & 7u}, lds_dyn + HIT_LDS_WORDS, fetch, emit, nullptr, NoPairs{}, ext);
+    else traverse_wide_stream<false, false, false, NoPairs, StreamExt<true>>(s, XcdRegions{work, n_next, n, chunk, subframes, blockIdx.x & 7u}, lds_dyn + HIT_LDS_WORDS, fetch, emit, nullptr, NoPairs{}, ext);
 }
 
 // The static split of small launches (k_trace_mixed_wide_stream) with the hit words in LDS (renderer option hit_lds): flattened scenes, shadow planes.
@@ -367,18 +371,31 @@ __global__ void __launch_bounds__(64, 5) k_trace_primary_wide_stream(SceneView s
 // Also the frame's bookkeeping (block 0, thread 0): per-bounce queue counters {next rays, shadow rays} are
 // folded into the running totals and zeroed for the next frame.
 constexpr size_t WORK_COUNTERS = 128, WORK_COUNTERS_PER_BOUNCE = 8 * XCD_COUNTER_STRIDE / 2;      // in 64-bit words of FrameLane::bounce_counts
+constexpr size_t SEG_TAILS = WORK_COUNTERS + 32 * WORK_COUNTERS_PER_BOUNCE, SEG_TAILS_PER_BOUNCE = QUEUE_SEGMENTS * SEG_TAIL_STRIDE;      // a segmented pass's tail words {next, shadow}: per bounce, one per segment on its own 128-byte line
+// The pass's bookkeeping of bounce b (one thread): {next rays, shadow rays} queued — on the one word or on the segments' — and every counter of the bounce back to zero.
+MRT_DEV unsigned long long fold_bounce_counters(unsigned long long *__restrict__ bounce_counts, int b) {
+    unsigned long long c = bounce_counts[b];
+    unsigned long long *const tails = bounce_counts + SEG_TAILS + (size_t)b * SEG_TAILS_PER_BOUNCE;
+    for (uint32_t x = 0; x < QUEUE_SEGMENTS; x++) { c += tails[x * SEG_TAIL_STRIDE]; tails[x * SEG_TAIL_STRIDE] = 0; }      // (a pass uses the one word or the eight; neither half carries)
+    bounce_counts[b] = 0;
+    bounce_counts[32 + b] = 0;               // work counter of the TLAS pass of this bounce (two-level scenes, binned)
+    for (int x = 0; x < 8; x++) reinterpret_cast<uint32_t *>(bounce_counts + WORK_COUNTERS + (size_t)b * WORK_COUNTERS_PER_BOUNCE)[x * XCD_COUNTER_STRIDE] = 0;      // work counters of the persistent trace launch of this bounce (one per XCD region)
+    bounce_counts[65 + b] = 0;               // two-level scenes, binned: {pairs queued (lo), work counter of the BLAS pass (hi)}
+    return c;
+}
+#ifdef MRT_PROBE_SHADE_TAILS
+constexpr size_t PROBE_TAIL_WORDS = 32 * 8 * 16;      // the probe build's eight reservation words per bounce, 128 bytes apart, behind the work counters (probe_tails_mask below)
+#else
+constexpr size_t PROBE_TAIL_WORDS = 0;
+#endif
 __global__ void __launch_bounds__(64) k_accumulate(FrameParams fp, const float4 *__restrict__ sample, const float4 *__restrict__ prev, float4 *__restrict__ dst,
                                                    unsigned long long *__restrict__ bounce_counts, unsigned long long *__restrict__ totals, uint32_t primary) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         unsigned long long closest = primary, shadow = 0;
         for (int b = 0; b < fp.max_bounces; b++) {
-            unsigned long long c = bounce_counts[b];
+            const unsigned long long c = fold_bounce_counters(bounce_counts, b);
             if (b + 1 < fp.max_bounces) closest += (uint32_t)c;
             shadow += c >> 32;
-            bounce_counts[b] = 0;
-            bounce_counts[32 + b] = 0;               // work counter of the TLAS pass of this bounce (two-level scenes, binned)
-            for (int x = 0; x < 8; x++) reinterpret_cast<uint32_t *>(bounce_counts + WORK_COUNTERS + (size_t)b * WORK_COUNTERS_PER_BOUNCE)[x * XCD_COUNTER_STRIDE] = 0;      // work counters of the persistent trace launch of this bounce (one per XCD region)
-            bounce_counts[65 + b] = 0;               // two-level scenes, binned: {pairs queued (lo), work counter of the BLAS pass (hi)}
         }
         atomicAdd(&totals[0], closest); atomicAdd(&totals[1], shadow); atomicAdd(&totals[2], (unsigned long long)primary);      // (the tile groups of a pass accumulate side by side)
     }
@@ -417,13 +434,9 @@ __global__ void __launch_bounds__(64) k_accumulate_planes(FrameParams fp, const 
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         unsigned long long closest = primary, shadow = 0;
         for (int b = 0; b < fp.max_bounces; b++) {
-            unsigned long long c = bounce_counts[b];
+            const unsigned long long c = fold_bounce_counters(bounce_counts, b);
             if (b + 1 < fp.max_bounces) closest += (uint32_t)c;
             shadow += c >> 32;
-            bounce_counts[b] = 0;
-            bounce_counts[32 + b] = 0;               // work counter of the TLAS pass of this bounce (two-level scenes, binned)
-            for (int x = 0; x < 8; x++) reinterpret_cast<uint32_t *>(bounce_counts + WORK_COUNTERS + (size_t)b * WORK_COUNTERS_PER_BOUNCE)[x * XCD_COUNTER_STRIDE] = 0;      // work counters of the persistent trace launch of this bounce (one per XCD region)
-            bounce_counts[65 + b] = 0;               // two-level scenes, binned: {pairs queued (lo), work counter of the BLAS pass (hi)}
         }
         atomicAdd(&totals[0], closest); atomicAdd(&totals[1], shadow); atomicAdd(&totals[2], (unsigned long long)primary);
     }
@@ -457,11 +470,9 @@ __global__ void __launch_bounds__(64) k_accumulate_planes_group(FrameParams fp, 
             if (p >= g.n) break;
             closest += g.p[p].primary; primary += g.p[p].primary;
             for (int b = 0; b < fp.max_bounces; b++) {
-                const unsigned long long c = g.p[p].counts[b];
+                const unsigned long long c = fold_bounce_counters(g.p[p].counts, b);
                 if (b + 1 < fp.max_bounces) closest += (uint32_t)c;
                 shadow += c >> 32;
-                g.p[p].counts[b] = 0; g.p[p].counts[32 + b] = 0; g.p[p].counts[65 + b] = 0;
-                for (int x = 0; x < 8; x++) reinterpret_cast<uint32_t *>(g.p[p].counts + WORK_COUNTERS + (size_t)b * WORK_COUNTERS_PER_BOUNCE)[x * XCD_COUNTER_STRIDE] = 0;
             }
         }
         totals[0] += closest; totals[1] += shadow; totals[2] += primary;
@@ -741,8 +752,8 @@ int Renderer::init(hipStream_t st, const DeviceScene *sc, int w, int h, uint32_t
         MRT_HIP(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
         MRT_HIP(hipEventCreateWithFlags(&L.accumulated, hipEventDisableTiming));
         // per bounce b: [b] queue counts {next rays (lo 32), shadow rays (hi 32)}; [32 + b] work counter of the TLAS pass and [65 + b] {pairs queued, work counter of the BLAS pass} (two-level scenes, binned);
-        // from WORK_COUNTERS on: the eight work counters of the pulling traversal launch, 128 bytes apart (XcdRegions)
-        MRT_HIP(L.bounce_counts.alloc(WORK_COUNTERS + 32 * WORK_COUNTERS_PER_BOUNCE));
+        // from WORK_COUNTERS on: the eight work counters of the pulling traversal launch, 128 bytes apart (XcdRegions); from SEG_TAILS on: the eight tail words of a segmented pass
+        MRT_HIP(L.bounce_counts.alloc(SEG_TAILS + 32 * SEG_TAILS_PER_BOUNCE + PROBE_TAIL_WORDS));
         MRT_HIP(hipMemsetAsync(L.bounce_counts.p, 0, L.bounce_counts.bytes(), stream));
     }
     MRT_HIP(totals.alloc(4));
@@ -855,8 +866,30 @@ int Renderer::alloc_queues() {
 
 constexpr int PLANES_MAX_BOUNCES = 3;        // shadow planes: sample + two more contribution planes, three flag bytes of the pixel's word
 
+// Segments of a bundled pass of B frames over `capacity` slots (PassPlan::segs): what its shade(0) launch looks like and what a segment can receive.
+// INVARIANT: segment x receives the entries of shade(0)'s blocks j = x (mod 8) — `blocks_per_seg` of them at most, each emitting at most `per_block` entries per queue (its
+// active lanes) — so seg_cap = blocks_per_seg x per_block holds bounce 0; a packing block of a later bounce reads one segment and writes the same one, one entry per queue at
+// most for each entry read, so no later bounce can hold more.  When bundle_groups x bundle_w == B (passes of 7, 8, 16, 32 frames), 8 x seg_cap exceeds capacity x B by less
+// than QUEUE_SEGMENTS x SHADE_THREADS entries: the slack alloc_lane adds.  plan_pass checks 8 x seg_cap against the allocation and keeps one queue otherwise.
+SegmentSizing segment_sizing(uint32_t capacity, int B) {
+    SegmentSizing z;
+    z.bundle_groups = ((uint32_t)B + 7u) / 8u; z.bundle_w = ((uint32_t)B + z.bundle_groups - 1u) / z.bundle_groups; z.bundle_per_wave = 64u / z.bundle_w;
+    const uint64_t waves = cdiv((uint64_t)capacity * z.bundle_groups, (uint64_t)z.bundle_per_wave);
+    z.blocks = cdiv(waves * 64u, (uint64_t)SHADE_THREADS);
+    z.per_block = (uint32_t)SHADE_WAVES * z.bundle_per_wave * z.bundle_w;
+    z.seg_cap = cdiv(z.blocks, (uint64_t)QUEUE_SEGMENTS) * z.per_block;
+    return z;
+}
+size_t queue_entries(uint32_t capacity, int alloc_batch) {
+    size_t qcap = (size_t)capacity * (size_t)std::max(1, alloc_batch);      // a batch of frames shares one set of queues
+    qcap += (size_t)QUEUE_SEGMENTS * SHADE_THREADS;      // segmented passes: the rounding of eight segments' capacities (segment_sizing)
+#ifdef MRT_PROBE_SHADE_TAILS
+    qcap += 8 * (size_t)SHADE_PACK_RANGE;      // the probe's disjoint segments: eight times the rounding of a segment's capacity (enqueue_shade)
+#endif
+    return qcap;
+}
 size_t Renderer::lane_bytes() const {
-    const size_t qcap = (size_t)capacity * (size_t)std::max(1, alloc_batch);
+    const size_t qcap = queue_entries(capacity, alloc_batch);
     const bool need_thr = !(throughput_chain && !materials && max_bounces <= 3);
     const size_t spix = (size_t)std::max<uint32_t>(capacity, 1u) * (size_t)std::max(1, alloc_batch);      // sample indices of a pass: sub-frame * capacity + slot
     const size_t planes_bytes = shadow_planes ? 2 * spix * sizeof(float4) + spix * 4 : 0;
@@ -875,7 +908,7 @@ int Renderer::alloc_planes(FrameLane &L) {
     return MRT_OK;
 }
 int Renderer::alloc_lane(FrameLane &L) {
-    const size_t qcap = (size_t)capacity * (size_t)std::max(1, alloc_batch);      // a batch of frames shares one set of queues
+    const size_t qcap = queue_entries(capacity, alloc_batch);
     const bool need_thr = !(throughput_chain && !materials && max_bounces <= 3);      // else on demand (prepare_lane)
     for (int k = 0; k < 2; k++) { MRT_HIP(L.rayA[k].alloc(qcap)); MRT_HIP(L.rayB[k].alloc(qcap)); if (need_thr) MRT_HIP(L.thr[k].alloc(qcap)); }
     MRT_HIP(L.hits.alloc(qcap)); MRT_HIP(L.srayA.alloc(qcap)); MRT_HIP(L.srayB.alloc(qcap));
@@ -1012,6 +1045,17 @@ int Renderer::read_denoised_tonemapped(uint8_t *rgba, size_t nbytes) {
 static inline int ablate_mask() { static const int mask = getenv("MRT_ABLATE") ? atoi(getenv("MRT_ABLATE")) : 0; return mask; }
 #else
 static constexpr int ablate_mask() { return 0; }
+#endif
+#ifdef MRT_PROBE_SHADE_TAILS
+// timing probe of the shade kernels' queue reservation (tools/build_variant.sh tails "-DMRT_PROBE_SHADE_TAILS"; tools/shade_tail_probe.py): MRT_PROBE_TAILS is a mask of bounces whose
+// shade launch reserves on eight words, 128 bytes apart, behind the lane's counters (block j on word j & 7) instead of on bounce_counts[b].  The eight words are zeroed ahead of the
+// launch, so no ticket exceeds what the one word would have handed out and every store stays inside the queues; bounce_counts[b] stays 0, so the stages behind the probed launch
+// find empty queues.  Images are garbage; only the probed launch's time is read (MRT_PROBE_LOG=1: wait() prints every timed launch of the draw, in enqueue order).
+static inline int probe_disjoint() { static const int v = getenv("MRT_PROBE_DISJOINT") ? atoi(getenv("MRT_PROBE_DISJOINT")) : 0; return v; }
+__global__ void k_probe_tails_init(unsigned long long *__restrict__ words, uint32_t seg_cap) {
+    if (threadIdx.x < 8u) { const unsigned long long v = (unsigned long long)seg_cap * threadIdx.x; words[threadIdx.x * 16u] = v | (v << 32); }
+}
+static inline int probe_tails_mask() { static const int mask = getenv("MRT_PROBE_TAILS") ? atoi(getenv("MRT_PROBE_TAILS")) : 0; return mask; }
 #endif
 // MRT_WAVE_TIMES builds: a traversal launch carries its bounce in the top byte of its chunk / rays-per-wave argument
 static inline uint32_t tag_bounce(uint32_t arg, int b) {
@@ -1153,13 +1197,26 @@ int Renderer::plan_pass(const DrawPlan &dp, const SceneView &sv, const TileGroup
     const bool takes_x = !two_level && pp.planes && hit_lds;          // the kernels with the hit words in LDS; k_trace_mixed_wide_stream_x is also the one kernel that deals batches round-robin (BatchStride)
     pp.trace = pp.pairs ? TraceForm::pairs : !pp.on_wide ? TraceForm::rope : pp.pull ? (takes_x ? TraceForm::pull_x : TraceForm::pull) : (takes_x ? TraceForm::static_x : TraceForm::static_split);
     pp.trace_lds = pp.trace == TraceForm::rope ? 0 : pp.stack_bytes + (takes_x ? (size_t)HIT_LDS_WORDS * 4 : 0);
+    // segmented queues: the default pass only — shade(0) as one row of bundled k_shade_primary<2> blocks, packed shades, the pulling launch with hit words in LDS and per-XCD
+    // counters (flattened scene, planes, chain) — and only when eight segments fit the lane's queues (segment_sizing); every other pass keeps one queue and one word
+    pp.segs = 1; pp.seg_cap = 0;
+    if (queue_segments == (int)QUEUE_SEGMENTS && pp.trace == TraceForm::pull_x && pp.trace0_wide && !two_level && pp.bundle && shade_pack && pp.chain && xcd_counters && max_bounces <= 3) {
+        const SegmentSizing z = segment_sizing(TG.capacity, B);
+        const uint64_t all = (uint64_t)QUEUE_SEGMENTS * z.seg_cap;
+        if (all <= (uint64_t)queue_entries(capacity, alloc_batch) && all < (uint64_t)SEG_SHADOW_BIT) { pp.segs = (int)QUEUE_SEGMENTS; pp.seg_cap = (uint32_t)z.seg_cap; }
+    }
+#ifdef MRT_PROBE_SHADE_TAILS
+    if (probe_tails_mask()) { pp.segs = 1; pp.seg_cap = 0; }          // the probe times the one-queue form
+#endif
     if (pp.trace == TraceForm::pairs) pp.pg = pull_grid(slots, (size_t)pp.wave_slots, 64, dp.long_call);
     else if (pp.trace == TraceForm::pull) pp.pg = pull_grid(slots, (size_t)pp.wave_slots, 128, dp.long_call);
     else if (pp.trace == TraceForm::pull_x) {
         // the variant with the hit words in LDS: its own LDS size, hence its own count of wave slots
-        if (int rc = wave_slots_for(k_trace_mixed_wide_persist_x, pp.trace_lds, persist_x_cache, cu_count)) return rc;
-        if (persist_x_cache.per_cu < 1) { set_error("hit_lds: the traversal kernel does not fit a compute unit with " + std::to_string(pp.trace_lds) + " bytes of LDS"); return MRT_ERR_UNSUPPORTED; }
-        pp.pg = pull_grid(slots, wave_slots_user ? (size_t)pp.wave_slots : (size_t)(persist_x_cache.per_cu * cu_count), 128, dp.long_call);
+        // (the instantiation this pass launches: pp.segs is decided above)
+        SlotCache &xc = pp.segs > 1 ? persist_xs_cache : persist_x_cache;
+        if (int rc = pp.segs > 1 ? wave_slots_for(k_trace_mixed_wide_persist_x<true>, pp.trace_lds, xc, cu_count) : wave_slots_for(k_trace_mixed_wide_persist_x<false>, pp.trace_lds, xc, cu_count)) return rc;
+        if (xc.per_cu < 1) { set_error("hit_lds: the traversal kernel does not fit a compute unit with " + std::to_string(pp.trace_lds) + " bytes of LDS"); return MRT_ERR_UNSUPPORTED; }
+        pp.pg = pull_grid(slots, wave_slots_user ? (size_t)pp.wave_slots : (size_t)(xc.per_cu * cu_count), 128, dp.long_call);
     }
     else if (pp.trace != TraceForm::rope) {
         // a shard's launches (a rank of eight over the driver's 20 frames: three passes of its 1/8 of the tiles in flight) do better with ONE round of waves that take the queue's
@@ -1317,6 +1374,8 @@ void Renderer::enqueue_shade(DrawCtx &d, FrameLane &L, const TileGroup &TG, cons
     // bounce 0: one grid row per sub-frame of the batch over the primary slots; later bounces: the compact queue of the whole batch
     const bool pack = shade_pack && b > 0;          // bounces >= 1 read a queue half of whose rays missed: its hits are compacted in LDS and shaded on full waves (k_shade_pack)
     fp.pack_range = pp.pack_range;
+    const bool seg = pp.segs > 1;
+    fp.segs = (uint32_t)pp.segs; fp.seg_cap = pp.seg_cap;
     fp.frame_bundle = (pp.bundle && b == 0) ? 1 : 0;
     if (fp.frame_bundle) {
         fp.bundle_groups = ((uint32_t)B + 7u) / 8u; fp.bundle_w = ((uint32_t)B + fp.bundle_groups - 1u) / fp.bundle_groups;
@@ -1326,12 +1385,25 @@ void Renderer::enqueue_shade(DrawCtx &d, FrameLane &L, const TileGroup &TG, cons
     if (fp.frame_bundle && fp.bundle_w >= 4u && halton_table && halton_tab.p) {          // a wave reads bundle_w consecutive values per load: the table pays from four on (indices outside its window: the recurrence)
         fp.halton_tab = halton_tab.p; fp.halton_w0 = halton_w0; fp.halton_n = HALTON_TAB_SPAN;
     }
-    const dim3 gs = b == 0 ? (fp.frame_bundle ? dim3(cdiv(cdiv((size_t)TG.capacity * fp.bundle_groups, fp.bundle_per_wave) * 64, SHADE_THREADS), 1) : dim3(pp.grid_shade, B)) : dim3(cdiv((size_t)TG.capacity * B, pack ? fp.pack_range : (uint32_t)SHADE_THREADS));
+    const dim3 gs = b == 0 ? (fp.frame_bundle ? dim3(cdiv(cdiv((size_t)TG.capacity * fp.bundle_groups, fp.bundle_per_wave) * 64, SHADE_THREADS), 1) : dim3(pp.grid_shade, B)) : (seg && pack) ? dim3(QUEUE_SEGMENTS * cdiv(pp.seg_cap, fp.pack_range)) : dim3(cdiv((size_t)TG.capacity * B, pack ? fp.pack_range : (uint32_t)SHADE_THREADS));
     float4 *const con_b = !pp.planes ? L.scon.p : b == 0 ? L.sample.p : L.f_con[b - 1].p;         // PLANES: this bounce's contribution plane in place of the queue
     const size_t shade_lds = (pp.trace0_wide && b == 0) ? (size_t)SHADE_WAVES * (scene->wide_depth * WIDE_STACK_LEVEL_BYTES + (MRT_LANE_HIT_LDS ? 1024 : 0)) : 0;
+    // (segmented pass: segment 0's tail word of the bounce read and of the bounce written; pp.segs > 1 implies packed shades)
+    unsigned long long *count_out = seg ? bc + SEG_TAILS + (size_t)b * SEG_TAILS_PER_BOUNCE : bc + b;
+    const unsigned long long *const count_in = b == 0 ? nullptr : seg ? bc + SEG_TAILS + (size_t)(b - 1) * SEG_TAILS_PER_BOUNCE : bc + (b - 1);
+#ifdef MRT_PROBE_SHADE_TAILS
+    fp.probe_tails = (probe_tails_mask() >> b) & 1;
+    if (fp.probe_tails) {
+        count_out = bc + SEG_TAILS + 32 * SEG_TAILS_PER_BOUNCE + (size_t)b * 8 * 16;
+        // MRT_PROBE_DISJOINT=1: word x starts at x * seg_cap in both halves, seg_cap = what the blocks of one word can emit together — eight disjoint segments, the full write
+        // footprint of the real queues (overlapping segments write one eighth of it); alloc_lane's probe slack holds the rounding
+        const uint32_t per_block = pack ? fp.pack_range : (uint32_t)SHADE_THREADS, seg_cap = (probe_disjoint() && pp.planes && pp.chain && gs.y == 1u) ? cdiv(gs.x, 8u) * per_block : 0u;
+        hipLaunchKernelGGL(k_probe_tails_init, dim3(1), dim3(64), 0, L.stream, count_out, seg_cap);
+    }
+#endif
     // (two-level, binned, b > 0: L.hits holds the 64-bit keys of the TLAS / BLAS passes)
     launch_timed(timed(MRT_KERNEL_SHADE), shade_kernel_for(pp, materials, pack, b), gs, dim3(SHADE_THREADS), shade_lds, L.stream, d.sv, fp, TG.seeds, L.rayA[1 - q].p, L.rayB[1 - q].p, L.thr[1 - q].p, L.hits.p,
-                 b == 0 ? nullptr : bc + (b - 1), TG.capacity, L.rayA[q].p, L.rayB[q].p, L.thr[q].p, L.srayA.p, L.srayB.p, con_b, bc + b, b == 0 ? L.sample.p : nullptr, L.sample.p,
+                 count_in, TG.capacity, L.rayA[q].p, L.rayB[q].p, L.thr[q].p, L.srayA.p, L.srayB.p, con_b, count_out, b == 0 ? L.sample.p : nullptr, L.sample.p,
                  (b == 0 && pp.trace0_pass && pp.trace0_hint) ? hint.p : nullptr);
 }
 
@@ -1362,7 +1434,9 @@ void Renderer::enqueue_trace(DrawCtx &d, FrameLane &L, const TileGroup &TG, cons
         break;
     }
     case TraceForm::pull_x:
-        launch_timed(timed(MRT_KERNEL_TRACE), k_trace_mixed_wide_persist_x, dim3(pp.pg.waves), dim3(64), pp.trace_lds, st, d.sv, rayA, rayB, L.hits.p, srayA, srayB, counts, work, pp.pg.chunk, lit_b, xcd_frames);
+        if (pp.segs > 1) launch_timed(timed(MRT_KERNEL_TRACE), k_trace_mixed_wide_persist_x<true>, dim3(pp.pg.waves), dim3(64), pp.trace_lds, st, d.sv, rayA, rayB, L.hits.p, srayA, srayB,
+                                      (const unsigned long long *)(bc + SEG_TAILS + (size_t)b * SEG_TAILS_PER_BOUNCE), work, pp.pg.chunk, lit_b, pp.seg_cap);
+        else launch_timed(timed(MRT_KERNEL_TRACE), k_trace_mixed_wide_persist_x<false>, dim3(pp.pg.waves), dim3(64), pp.trace_lds, st, d.sv, rayA, rayB, L.hits.p, srayA, srayB, counts, work, pp.pg.chunk, lit_b, xcd_frames);
         break;
     case TraceForm::pull:
         launch_timed(timed(MRT_KERNEL_TRACE), pp.two_level ? k_trace_mixed_wide_persist<true> : k_trace_mixed_wide_persist<false>, dim3(pp.pg.waves), dim3(64), pp.trace_lds, st, d.sv, rayA, rayB, L.hits.p, srayA, srayB, L.scon.p,
@@ -1458,6 +1532,7 @@ int Renderer::render(int n_frames) {
     for (int k = 0; k < 2; k++)
         for (int g = 0; g < dp.G; g++) { if (int rc = plan_pass(dp, d.sv, dp.G > 1 ? tgroups[g] : self_group, dp.pass_size(k == 0 ? 0 : dp.n_passes - 1), plans[k][g])) return rc; }
     wave_slots = plans[0][0].wave_slots;          // (the option reads back what the grids were sized for)
+    segments_used = plans[0][0].segs;
     begin_draw(d);
     ext_used = 0;
     if (halton_table && frame_bundle && !megakernel && n_frames > 1) { if (int rc = ensure_halton_table(frame_index + sample_offset, (uint32_t)n_frames)) return rc; }      // (ahead of the fork: see there)
@@ -1527,6 +1602,9 @@ int Renderer::wait() {
             float e = 0; MRT_HIP(hipEventElapsedTime(&e, ev_ext[k].a, ev_ext[k].b));
             const int kind = ev_ext[k].kind;
             kernel_times.ms[kind] += e; kernel_times.launches[kind]++;
+#ifdef MRT_PROBE_SHADE_TAILS
+            if (getenv("MRT_PROBE_LOG")) fprintf(stderr, "probe_launch %d kind %d ms %.5f\n", k, kind, e);
+#endif
             if (kind == MRT_KERNEL_PRIMARY || kind == MRT_KERNEL_TRACE) { ext += e; next++; }
         }
         ms_extend_last = ext; extend_launches_last = next;

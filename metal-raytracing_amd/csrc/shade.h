@@ -55,6 +55,15 @@ struct FrameParams {            // Uniforms (ShaderTypes.h:89-97) + shard + boun
     // from one or two cache lines instead.  nullptr (passes of one frame, narrow bundles, an index outside the window):
     // the recurrence.
     const float *halton_tab; uint32_t halton_w0, halton_n;
+    // segmented queues (renderer option queue_segments, PassPlan::segs): the pass's bounce-ray queue, hit records and shadow-ray queue are `segs` = QUEUE_SEGMENTS regions
+    // [x * seg_cap, x * seg_cap + count_x) of the same arrays, each with its own tail word {next, shadow} on its own 128-byte line (count_in / count_out then point at
+    // segment 0's word); a shade block j reserves on, and writes, segment j % segs — one word per XCD instead of one for the chip.  0 or 1: one queue from 0, one word
+    uint32_t segs, seg_cap;
+#ifdef MRT_PROBE_SHADE_TAILS
+    // timing probe, never in the release library (profiles/r07_shade_tail_probe.txt): this launch's block j reserves on word j & 7 of eight words 128 bytes apart instead
+    // of on the one word — the queues overlap and the image is garbage; only the launch's time is read
+    uint32_t probe_tails;
+#endif
 };
 #ifndef MRT_HALTON_INTERLEAVED
 #define MRT_HALTON_INTERLEAVED 1      // the six dimensions of an index side by side (24 B): the eight sub-frames of a pixel read 192 contiguous bytes — three or four 64-byte requests — instead of one request in each of six planes (profiles/r06_shade_primary_bytes.txt: the table was 0.83 GB of k_shade_primary's fetches per launch)
@@ -106,6 +115,8 @@ MRT_DEV void primary_ray(const FrameParams &fp, const uint32_t *__restrict__ see
 #endif
 constexpr int SHADE_THREADS = MRT_SHADE_THREADS;
 constexpr int SHADE_WAVES = SHADE_THREADS / 64;
+constexpr uint32_t QUEUE_SEGMENTS = 8;                // segments of a segmented pass (FrameParams::segs): one per XCD — workgroups are dealt to the XCDs round-robin
+constexpr uint32_t SEG_TAIL_STRIDE = 16;              // 64-bit words between two segments' tail words: 128 bytes
 #ifndef MRT_SHADE_PACK_RANGE
 #define MRT_SHADE_PACK_RANGE 4096
 #endif
@@ -318,7 +329,14 @@ MRT_DEV void shade_entry(const SceneView &s, const FrameParams &fp, const ShadeI
         uint32_t tn = 0, ts = 0, tp = 0;
         for (int k = 0; k < SHADE_WAVES; k++) { uint32_t a = sh.w_next[k], b = sh.w_shadow[k]; sh.w_next[k] = tn; sh.w_shadow[k] = ts; tn += a; ts += b; }
         if (MATERIALS) for (int k = 0; k < SHADE_WAVES; k++) { uint32_t a = sh.w_spec[k]; sh.w_spec[k] = tn + tp; tp += a; }
-        sh.blk_base = (tn | ts | tp) ? atomicAdd(io.count_out, ((unsigned long long)ts << 32) | (tn + tp)) : 0ull;
+        const uint32_t seg = fp.segs > 1u ? blockIdx.x & (QUEUE_SEGMENTS - 1u) : 0u;          // (segmented launches are one grid row)
+#ifdef MRT_PROBE_SHADE_TAILS
+        unsigned long long *const tail = io.count_out + (fp.probe_tails ? (size_t)(blockIdx.x & 7u) * 16u : (size_t)seg * SEG_TAIL_STRIDE);
+#else
+        unsigned long long *const tail = io.count_out + (size_t)seg * SEG_TAIL_STRIDE;
+#endif
+        const unsigned long long first = (unsigned long long)seg * fp.seg_cap;          // the segment's first entry, in both queues
+        sh.blk_base = (tn | ts | tp) ? atomicAdd(tail, ((unsigned long long)ts << 32) | (tn + tp)) + ((first << 32) | first) : 0ull;
     }
     __syncthreads();
     const unsigned long long base = sh.blk_base;
@@ -443,9 +461,11 @@ __global__ void __launch_bounds__(SHADE_THREADS, MRT_SHADE_WAVES) k_shade_pack(S
     __shared__ ShadeShared sh;
     __shared__ uint32_t p_idx[2 * SHADE_THREADS], p_w[SHADE_WAVES];
     __shared__ float4 p_hit[2 * SHADE_THREADS];
-    const uint32_t n = io.count_in ? (uint32_t)*io.count_in : io.capacity;
+    // segmented queues: block j is range j / segs of segment j % segs — it reads that segment and (shade_entry) writes the same one; a range at or beyond its segment's count is empty
+    const uint32_t seg = fp.segs > 1u ? blockIdx.x & (QUEUE_SEGMENTS - 1u) : 0u, range = fp.segs > 1u ? blockIdx.x / QUEUE_SEGMENTS : blockIdx.x, first = seg * fp.seg_cap;
+    const uint32_t n = io.count_in ? (uint32_t)io.count_in[(size_t)seg * SEG_TAIL_STRIDE] : io.capacity;
     const float4 miss = make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)), noB = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
-    const uint32_t begin = blockIdx.x * fp.pack_range, end = min(n, begin + fp.pack_range);
+    const uint32_t begin = first + min(n, range * fp.pack_range), end = first + min(n, (range + 1u) * fp.pack_range);
     const uint32_t lane_ = threadIdx.x & 63, wv_ = threadIdx.x >> 6;
     uint32_t head = 0, tail = 0, cur = begin;                  // the ring's positions only ever grow; entry k lives in slot k & (2 * SHADE_THREADS - 1); all three are workgroup-uniform
     for (;;) {

@@ -537,6 +537,32 @@ struct XcdRegions {
     }
 };
 
+// The dynamic split over a SEGMENTED pass (FrameParams::segs; renderer option queue_segments): region x is segment x of the pass's queues — the chunks of its bounce rays
+// [x * seg_cap, x * seg_cap + next_x), then those of its shadow rays [x * seg_cap, x * seg_cap + shadow_x), counted by the segment's tail word — so an XCD walks the rays its own
+// shade blocks queued.  The stealing rule is XcdRegions': a wave whose home region is used up goes on with the next one, and every counter only grows (a wave asks at most
+// chunks + 8 times; an empty segment costs no atomic).  Indices stay physical: a chunk of shadow rays carries SEG_SHADOW_BIT in both ends (queues hold fewer than 2^31 entries).
+constexpr uint32_t SEG_SHADOW_BIT = 0x80000000u;
+struct SegRegions {
+    uint32_t *counters; const unsigned long long *tails; uint32_t seg_cap, chunk; uint32_t home; uint32_t tries = 0;
+    MRT_DEV bool operator()(uint32_t &ob, uint32_t &oe) {
+        while (tries < 8u) {
+            const uint32_t x = (home + tries) & 7u;
+            const unsigned long long c = tails[(size_t)x * 16u];
+            const uint32_t n1 = (uint32_t)c, n2 = (uint32_t)(c >> 32), C1 = (n1 + chunk - 1u) / chunk, C = C1 + (n2 + chunk - 1u) / chunk;
+            if (C == 0u) { tries++; continue; }
+            uint32_t k = 0;
+            if ((threadIdx.x & 63) == 0) k = atomicAdd(&counters[x * XCD_COUNTER_STRIDE], 1u);
+            k = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
+            if (k >= C) { tries++; continue; }
+            const bool p2 = k >= C1;
+            const uint32_t kk = p2 ? k - C1 : k, lim = p2 ? n2 : n1, first = x * seg_cap, flag = p2 ? SEG_SHADOW_BIT : 0u;
+            ob = (first + kk * chunk) | flag; oe = (first + min(lim, (kk + 1u) * chunk)) | flag;
+            return true;
+        }
+        return false;
+    }
+};
+
 // Two-level scenes, binned form (renderer option tl_pairs).  The TLAS pass — this loop with a PairQueue — tests instances of at most eight triangles in place and,
 // instead of entering a larger one, appends {ray, instance} to a queue; a second launch walks every pair in object space with the FLATTENED loop (TWO_LEVEL = false, per-ray root:
 // ROOTS), its lanes never changing level, and folds the hits into the rays' results with atomics.  When the queue is full a lane enters the instance in place, as without a queue.
