@@ -146,6 +146,13 @@ struct Scene {                                                       // Scene.sw
                                   void *deviceOut, size_t outStrideBytes, void *hipStream) {
         check(mrt_scene_interpolate_device(committed, deviceHits, n, deviceAttributes, attributeStrideBytes, channels, deviceOut, outStrideBytes, hipStream));
     }
+    // What follows a surface in the reference's kernel, its diffuse path (mrt_scene_scatter_device; the materials extension stays inside Renderer::draw): n x MRTSurface
+    // and the n x int32 Halton indices of Renderer::primaryRaysDevice -> n x MRTRay shadow rays, n x 4 float light rows {colour | 1.0f where the shadow ray is wanted},
+    // n x MRTRay bounce rays (deviceNextRays may be nullptr: the last bounce).  Row i in, row i out; zeros for a row that is no surface.  bounce 0 .. 18; lightCount 0 = all.
+    static void scatterDevice(MRTScene committed, const void *deviceSurfaces, const void *deviceHaltonIndex, size_t n, int32_t bounce, int32_t lightCount, void *deviceShadowRays,
+                              void *deviceLight, void *deviceNextRays, void *hipStream) {
+        check(mrt_scene_scatter_device(committed, deviceSurfaces, deviceHaltonIndex, n, bounce, lightCount, deviceShadowRays, deviceLight, deviceNextRays, hipStream));
+    }
     // each mesh's first attribute row (an instance reports its source's) and, last, the number of rows: meshCount + 1 entries
     static std::vector<uint64_t> vertexOffsets(MRTScene scene, size_t meshCount) {
         std::vector<uint64_t> o(meshCount + 1); check(mrt_scene_vertex_offsets(scene, o.data(), o.size())); return o;
@@ -233,6 +240,12 @@ class Renderer {                                                     // Renderer
     void resolveHitsDevice(const void *deviceRays, const void *deviceHits, size_t n, void *deviceSurfaces, void *hipStream) { Scene::resolveHitsDevice(scene_, deviceRays, deviceHits, n, deviceSurfaces, hipStream); }
     void interpolateDevice(const void *deviceHits, size_t n, const void *deviceAttributes, size_t attributeStrideBytes, int32_t channels, void *deviceOut, size_t outStrideBytes, void *hipStream) {
         Scene::interpolateDevice(scene_, deviceHits, n, deviceAttributes, attributeStrideBytes, channels, deviceOut, outStrideBytes, hipStream);
+    }
+    // the path-tracing stages around them (mrt_renderer_primary_rays_device / Scene::scatterDevice): width x height primary rays and Halton indices of this renderer's image at
+    // a sample index (pixel y * width + x, row 0 at the bottom; nothing of the renderer's is written), and light, shadow ray and bounce ray of resolved surfaces
+    void primaryRaysDevice(uint32_t sampleIndex, void *deviceRays, void *deviceHaltonIndex, void *hipStream) { check(mrt_renderer_primary_rays_device(r_, sampleIndex, deviceRays, deviceHaltonIndex, hipStream)); }
+    void scatterDevice(const void *deviceSurfaces, const void *deviceHaltonIndex, size_t n, int32_t bounce, int32_t lightCount, void *deviceShadowRays, void *deviceLight, void *deviceNextRays, void *hipStream) {
+        Scene::scatterDevice(scene_, deviceSurfaces, deviceHaltonIndex, n, bounce, lightCount, deviceShadowRays, deviceLight, deviceNextRays, hipStream);
     }
     std::vector<uint64_t> vertexOffsets() const { MRTSceneStats st; check(mrt_scene_stats(scene_, &st)); return Scene::vertexOffsets(scene_, (size_t)st.instances); }
     // deformation from device buffers on a stream (Scene::updateMeshDevice): packed or strided float3 rows; refitDevice() after one or more updates

@@ -377,6 +377,41 @@ int mrt_scene_interpolate_device(MRTScene scene, const void *d_hits, size_t n, c
                                  void *d_out, size_t out_stride_bytes, void *hip_stream);
 int mrt_scene_vertex_offsets(MRTScene scene, uint64_t *offsets /* meshes + 1 entries */, size_t count);
 
+/* The two steps of the reference's kernel that frame the query and the surface lookup, on DEVICE buffers and ordered on a stream of the caller's: where the
+ * rays come from (Raytracing.metal:171-221) and what follows a surface (:272-391) — the light pick and its evaluation, the next-event shadow ray, the cosine-hemisphere
+ * bounce.  With them the reference's integrator, or a variant of it, is five stream-ordered calls — generate, mrt_scene_intersect_closest_device,
+ * mrt_scene_resolve_hits_device, scatter, mrt_scene_intersect_any_device — and element-wise arithmetic of the caller's (throughput = throughput * base_color; radiance +=
+ * light * throughput where the shadow ray got through); composed so, the image is the renderer's own, bit for bit.  Materials extension OFF: these are the expressions of
+ * the reference's diffuse path; the semantics of renderer option materials = 1 stay reachable through mrt_renderer_render alone.
+ *   mrt_renderer_primary_rays_device: for every pixel p = y * width + x of the renderer's image (row 0 at the bottom, as mrt_renderer_read_accum; the WHOLE image whatever
+ *     the renderer's shard) d_halton_index[p] = (int32)(hash(seed, p) + sample_index), the renderer's own per-pixel seed plus the caller's sample index with wrap-around,
+ *     and d_rays[p] = {camera position | 0, normalize((uvx * right + uvy * up) + forward) | +inf} with uv = ((x, y) + halton(index, 0 and 1)) / (width, height) * 2 - 1:
+ *     the primary ray mrt_renderer_render traces for that pixel at Uniforms.frameIndex == sample_index (renderer option sample_offset is not added: pass it in).  Reads the
+ *     camera as mrt_renderer_set_camera left it and the renderer's width and height; writes nothing of the renderer's and does not advance the frame index.
+ *   mrt_scene_scatter_device: row i in, row i out, no compaction.  d_surfaces is n x MRTSurface as mrt_scene_resolve_hits_device wrote them (position, normal and type are
+ *     read), d_halton_index n x int32 as above, `bounce` the path depth of these surfaces (0 for primary hits; at most 18: five Halton dimensions per bounce from dimension
+ *     2 on, and the prime table holds 100), light_count Uniforms.lightCount (0 = every light of the scene; more than the scene holds is refused).  For a surface with
+ *     type == 1:
+ *       the light    li = min((int)(halton(index, 2 + 5 * bounce) * light_count), light_count - 1); its direction, distance and colour by the light's type (an area light
+ *                    takes dimensions + 1 and + 2), * saturate(dot(normal, direction)) * light_count               -> d_light[i] = {colour | wanted ? 1.0f : 0.0f}
+ *       wanted       length(colour) > 0.0001f: the reference traces a shadow ray only then
+ *       shadow ray   {position + normal * 1e-3f | 0, direction to the light | its distance - 1e-3f (+inf for a sun)}  -> d_shadow_rays[i], when wanted
+ *       bounce ray   {position + normal * 1e-3f | 0, the cosine-weighted direction about the normal from dimensions + 3 and + 4 | +inf}      -> d_next_rays[i]
+ *     A row whose type is not 1 gives zeros in all three outputs, and a shadow ray that is not wanted is 32 zero bytes (the light row then still holds the colour that
+ *     fell below the threshold, with 0 in its fourth component).  A zero ray — zero direction, max_distance 0 — is inside the query entries' domain, but what they answer
+ *     for it is unspecified: go by the light row's fourth component and by the surface's type, never by the answer to such a row.  d_light is n x 4 float32;
+ *     d_next_rays may be NULL (the last bounce): nothing is computed for it.  The entry reads the scene's light table only — no tree and no geometry — so both scene forms
+ *     and every layout take one path.
+ * float32, no contraction, IEEE divide and square root: the bits the render kernels hold for the same pixel.  The contract of the _device query entries: buffers in device
+ * memory of the renderer's / scene's device, alive until the stream has passed the call; hip_stream taken literally (0 is HIP's null stream); each call enqueues one kernel
+ * and returns — no allocation, no copy from host memory, no wait; no mrt_scene_set_lights or mrt_scene_commit while a call is in flight.
+ * Plain arguments are checked first and a NULL handle last.  MRT_ERR_INVALID_ARGUMENT: NULL buffers (scatter: with n > 0), rays / surfaces / light rows not 16-byte
+ * aligned, the index not 4-byte aligned, n >= 2^31, bounce < 0 or > 18, light_count < 0 or above the scene's, a NULL handle.  MRT_ERR_STATE: the scene is not committed or
+ * has no light (as mrt_renderer_render).  n == 0: MRT_OK, nothing is launched.                                                                                          */
+int mrt_renderer_primary_rays_device(MRTRenderer r, uint32_t sample_index, void *d_rays /* w*h x MRTRay */, void *d_halton_index /* w*h x int32 */, void *hip_stream);
+int mrt_scene_scatter_device(MRTScene scene, const void *d_surfaces /* n x MRTSurface */, const void *d_halton_index /* n x int32 */, size_t n, int32_t bounce, int32_t light_count,
+                             void *d_shadow_rays /* n x MRTRay */, void *d_light /* n x 4 float32 */, void *d_next_rays /* n x MRTRay, may be NULL */, void *hip_stream);
+
 /* ---------------------------------------------------------------- host-side geometry helpers
  * (no GPU needed) — the library's OBJ/MTL reader standing in for ModelIO (Model.swift:16-21,
  * SubMesh.swift:37-54) and the procedural dragon proxy (dragon.obj is absent upstream).        */

@@ -170,6 +170,7 @@ SIGNATURES = {
     "mrt_scene_resolve_hits_device": (C.c_int, [_P, _P, _P, _SZ, _P, _P]),
     "mrt_scene_interpolate_device": (C.c_int, [_P, _P, _SZ, _P, _SZ, _I32, _P, _SZ, _P]),
     "mrt_scene_vertex_offsets": (C.c_int, [_P, C.POINTER(C.c_uint64), _SZ]),
+    "mrt_scene_scatter_device": (C.c_int, [_P, _P, _P, _SZ, _I32, _I32, _P, _P, _P, _P]),
     "mrt_obj_load": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "mrt_dragon_proxy": (C.c_int, [C.POINTER(_P)]),
     "mrt_dragon_proxy_irregular": (C.c_int, [C.POINTER(_P)]),
@@ -195,6 +196,7 @@ SIGNATURES = {
     "mrt_renderer_set_shard": (C.c_int, [_P, _I32, _I32]),
     "mrt_renderer_set_frame_index": (C.c_int, [_P, _U32]),
     "mrt_renderer_frame_index": (C.c_int, [_P, _PU32]),
+    "mrt_renderer_primary_rays_device": (C.c_int, [_P, _U32, _P, _P, _P]),
     "mrt_renderer_render": (C.c_int, [_P, _I32]),
     "mrt_renderer_wait": (C.c_int, [_P]),
     "mrt_renderer_read_accum": (C.c_int, [_P, _P, _SZ]),

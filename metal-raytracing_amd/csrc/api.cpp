@@ -563,6 +563,26 @@ int mrt_scene_vertex_offsets(MRTScene scene, uint64_t *offsets, size_t count) {
     MRT_CATCH
 }
 
+// What follows a surface, on the caller's stream (stages.hip).  Plain arguments first, as the surface entries: a refusal of theirs needs no device.
+int mrt_scene_scatter_device(MRTScene scene, const void *d_surfaces, const void *d_halton_index, size_t n, int32_t bounce, int32_t light_count, void *d_shadow_rays, void *d_light,
+                             void *d_next_rays, void *hip_stream) {
+    MRT_TRY
+    const char *who = "mrt_scene_scatter_device";
+    REQUIRE(n == 0 || (d_surfaces && d_halton_index && d_shadow_rays && d_light), "mrt_scene_scatter_device: NULL buffers (d_surfaces, d_halton_index, d_shadow_rays and d_light are required; only d_next_rays may be NULL)");
+    REQUIRE((uintptr_t)d_surfaces % 16 == 0 && (uintptr_t)d_shadow_rays % 16 == 0 && (uintptr_t)d_light % 16 == 0 && (uintptr_t)d_next_rays % 16 == 0,
+            "mrt_scene_scatter_device: d_surfaces, d_shadow_rays, d_light and d_next_rays must be 16-byte aligned");
+    REQUIRE((uintptr_t)d_halton_index % 4 == 0, "mrt_scene_scatter_device: d_halton_index must be 4-byte aligned");
+    REQUIRE(bounce >= 0 && bounce <= 18, "mrt_scene_scatter_device: bounce must be in [0, 18] (Halton dimensions 2 + 5 * bounce .. + 4 of a table of 100 primes)");
+    REQUIRE(light_count >= 0, "mrt_scene_scatter_device: light_count must be >= 0 (0 = every light of the scene)");
+    if (int rc = surface_prologue(who, scene, n)) return rc;
+    REQUIRE(light_count <= scene->dev.light_count, "mrt_scene_scatter_device: light_count is above the number of lights of the scene");
+    if (scene->dev.light_count < 1) { mrt::set_error("mrt_scene_scatter_device: scene has no lights (lightCount must be >= 1, Raytracing.metal:273)"); return MRT_ERR_STATE; }
+    if (n == 0) return MRT_OK;
+    if (int rc = bind_device(scene->ctx)) return rc;
+    return mrt::scatter_device(scene->dev, (hipStream_t)hip_stream, d_surfaces, d_halton_index, n, bounce, light_count > 0 ? light_count : scene->dev.light_count, d_shadow_rays, d_light, d_next_rays);
+    MRT_CATCH
+}
+
 int mrt_debug_traversal_stats(MRTScene scene, const MRTRay *rays, size_t n, int32_t any_hit, uint32_t *out4) {
     MRT_TRY
     REQUIRE(scene && (n == 0 || (rays && out4)), "mrt_debug_traversal_stats: bad argument");
@@ -855,6 +875,17 @@ int mrt_renderer_set_shard(MRTRenderer r, int32_t rank, int32_t world) {
     MRT_TRY
     RENDERER_PROLOGUE("mrt_renderer_set_shard")
     return r->r.set_shard(rank, world);
+    MRT_CATCH
+}
+// Where the rays come from, on the caller's stream (stages.hip): reads the renderer's size, seed and camera, writes nothing of its own
+int mrt_renderer_primary_rays_device(MRTRenderer r, uint32_t sample_index, void *d_rays, void *d_halton_index, void *hip_stream) {
+    MRT_TRY
+    REQUIRE(d_rays && d_halton_index, "mrt_renderer_primary_rays_device: NULL buffers (d_rays, d_halton_index)");
+    REQUIRE((uintptr_t)d_rays % 16 == 0, "mrt_renderer_primary_rays_device: d_rays must be 16-byte aligned");
+    REQUIRE((uintptr_t)d_halton_index % 4 == 0, "mrt_renderer_primary_rays_device: d_halton_index must be 4-byte aligned");
+    REQUIRE(r, "mrt_renderer_primary_rays_device: renderer is NULL");
+    if (int rc = bind_device(r->ctx)) return rc;
+    return mrt::primary_rays_device(r->r, (hipStream_t)hip_stream, sample_index, d_rays, d_halton_index);
     MRT_CATCH
 }
 int mrt_renderer_set_frame_index(MRTRenderer r, uint32_t fi) { REQUIRE(r, "mrt_renderer_set_frame_index: NULL"); r->r.frame_index = fi; return MRT_OK; }

@@ -232,6 +232,8 @@ int query_any(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, siz
 // the stream-ordered forms on caller device buffers: two launches on `stream`, no allocation, copy or synchronisation (renderer.hip)
 int query_closest_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_out);
 int query_any_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_occluded);
+// stages.hip: the primary rays of a renderer's image and their Halton indices on caller device buffers: one launch on `stream`, nothing of the renderer's is written
+int primary_rays_device(const Renderer &r, hipStream_t stream, uint32_t sample_index, void *d_rays, void *d_halton_index);
 int query_stats(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, int any, uint32_t *out4);
 int query_stream(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, int any, MRTIntersection *out);
 int query_stream_stats(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, int any, uint32_t per_wave, uint32_t *out8, size_t nwaves);

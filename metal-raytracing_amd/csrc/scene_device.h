@@ -435,5 +435,8 @@ int resolve_hits_device(const DeviceScene &sc, hipStream_t stream, const void *d
 int interpolate_device(const DeviceScene &sc, hipStream_t stream, const void *d_hits, size_t n, const void *d_attr, size_t attr_stride, uint32_t channels, void *d_out, size_t out_stride);
 void drop_surface_workspace(DeviceScene &sc);      // (a commit: the table restates the mesh list of the commit before)
 int upload_lights(const MRTLight *lights, int count, hipStream_t stream, DeviceScene &out);
+// stages.hip: what follows a surface in the reference's kernel, on the caller's stream
+int scatter_device(const DeviceScene &sc, hipStream_t stream, const void *d_surfaces, const void *d_halton_index, size_t n, int bounce, int light_count, void *d_shadow_rays, void *d_light,
+                   void *d_next_rays);      // one launch, nothing else; light_count in [1, sc.light_count], bounce in [0, 18]
 
 }  // namespace mrt

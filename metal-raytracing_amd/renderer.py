@@ -206,6 +206,34 @@ class DeviceScene:
                                                C.c_void_p(self._stream_handle(stream))))
         return out
 
+    def scatter_device(self, surfaces, halton_index, bounce, light_count=0, next_rays=True, out=None, stream=None):
+        """What follows a surface in the reference's kernel (its diffuse path; the materials extension stays inside Renderer), on the GPU and ordered on a stream: surfaces
+        (n, 16) float32 as resolve_hits_device returns them, halton_index (n,) int32 as Renderer.primary_rays_device returns it, bounce the path depth of these surfaces
+        (0 .. 18), light_count Uniforms.lightCount (0 = every light of the scene) -> (shadow_rays (n, 8) float32, light (n, 4) float32, next_rays (n, 8) float32 or
+        None).  Row i in gives row i out: light[i] = the picked light's colour at the surface | 1.0 where the reference traces a shadow ray (else 0.0),
+        shadow_rays[i] that ray (zeros where it is not wanted), next_rays[i] the cosine-weighted bounce ray; a row that is no surface (type != 1) gives zeros
+        everywhere — go by light[:, 3] and the surface's type, never by what a query answers for a zero ray.  next_rays=False (the last bounce) computes and writes
+        no third buffer.  out: the tuple of tensors to write, (shadow_rays, light, next_rays) or (shadow_rays, light).  Nothing is allocated (but the outputs when
+        out is None), copied or synchronised.  stream: as intersect_closest_device takes it."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        if not isinstance(surfaces, torch.Tensor) or surfaces.device != dev or surfaces.dtype != torch.float32 or surfaces.dim() != 2 or surfaces.shape[1] != 16 or not surfaces.is_contiguous():
+            raise ValueError(f"surfaces must be a contiguous torch.float32 tensor of shape (n, 16) on {dev}: the records of resolve_hits_device")
+        n = surfaces.shape[0]
+        h = halton_index
+        if not isinstance(h, torch.Tensor) or h.device != dev or h.dtype != torch.int32 or tuple(h.shape) != (n,) or not h.is_contiguous():
+            raise ValueError(f"halton_index must be a contiguous torch.int32 tensor of shape {(n,)} on {dev}")
+        shapes = [(n, 8), (n, 4)] + ([(n, 8)] if next_rays else [])
+        if out is None:
+            out = tuple(torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes)
+        else:
+            out = tuple(out)
+            if len(out) != len(shapes) or any(not isinstance(o, torch.Tensor) or o.device != dev or o.dtype != torch.float32 or tuple(o.shape) != sh or not o.is_contiguous() for o, sh in zip(out, shapes)):
+                raise ValueError(f"out must be {len(shapes)} contiguous torch.float32 tensors of shapes {shapes} on {dev}")
+        p = [C.c_void_p(t.data_ptr() if n else None) for t in (surfaces, h) + out]
+        check(lib.mrt_scene_scatter_device(self.handle, p[0], p[1], n, int(bounce), int(light_count), p[2], p[3], p[4] if next_rays else None, C.c_void_p(self._stream_handle(stream))))
+        return (out[0], out[1], out[2] if next_rays else None)
+
     def vertex_offsets(self):
         """The vertex numbering interpolate_device reads attributes in: (meshes + 1,) uint64 — each mesh's first row, the source meshes concatenated in mesh-id order and
         an instance reporting its source's; the last entry is the number of rows."""
@@ -401,6 +429,26 @@ class Renderer:
 
     def set_camera(self, camera: Camera):
         check(lib.mrt_renderer_set_camera(self.handle, C.byref(camera)))
+
+    def primary_rays_device(self, sample_index=None, out=None, stream=None):
+        """Where the rays come from (Raytracing.metal:171-221), on the GPU and ordered on a stream -> (rays (n, 8) float32, halton_index (n,) int32), n = width x height,
+        pixel p = y * width + x with row 0 at the bottom as accumulation(): the primary ray draw() traces for that pixel at frame index sample_index (None = the
+        renderer's current frameIndex) and the pixel's Halton index, hash(seed, p) + sample_index as int32 — what DeviceScene.scatter_device takes.  The whole image
+        whatever the shard; the camera as set_camera left it.  Nothing of the renderer's is written and the frame index does not advance.  out: the tuple (rays,
+        halton_index) to write.  Nothing is allocated (but the outputs when out is None), copied or synchronised.  stream: as intersect_closest_device takes it."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        n = self.size[0] * self.size[1]
+        if out is None:
+            out = (torch.empty((n, 8), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev))
+        else:
+            out = tuple(out)
+            if (len(out) != 2 or any(not isinstance(o, torch.Tensor) or o.device != dev or not o.is_contiguous() for o in out) or out[0].dtype != torch.float32 or tuple(out[0].shape) != (n, 8)
+                    or out[1].dtype != torch.int32 or tuple(out[1].shape) != (n,)):
+                raise ValueError(f"out must be (rays, halton_index): contiguous tensors on {dev}, torch.float32 {(n, 8)} and torch.int32 {(n,)}")
+        si = self.frameIndex if sample_index is None else int(sample_index) & 0xFFFFFFFF
+        check(lib.mrt_renderer_primary_rays_device(self.handle, si, C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(self.device_scene._stream_handle(stream))))
+        return out
 
     # -- Renderer.uniforms / updateUniforms (Renderer.swift:216-229): size, frameIndex, lightCount and camera in one 96-byte block
     @property

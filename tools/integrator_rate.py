@@ -1,0 +1,128 @@
+"""Rate of the path-tracing stages on device buffers (Renderer.primary_rays_device / DeviceScene.scatter_device) and of a frame composed from the five public stages beside
+Renderer drawing the same frame — DESIGN.md §10i.  Per scene (DragonScene flattened; dragon4 two-level):
+  (a) each new stage alone at 2^22 rows — primary_rays_device of a 2048 x 2048 image; scatter_device at bounce 0 on the surfaces its rays hit and at bounce 1 on the surfaces
+      the bounce rays hit (dense rows, the misses among them) — against its byte floor at this box's device copy bandwidth (a 256 MiB torch copy, read + write counted, timed
+      the same way, as tools/surface_rate.py defines it): 36 B per pixel written; 68 B read + 80 B written per row;
+  (b) one composed frame at 1920 x 1080 — generate, closest, resolve, scatter, any; three bounces; throughput and radiance as torch mul / add / where — against Renderer
+      drawing one frame alone (frame index 0 both).  Host wall time from the first enqueue to the end of a device synchronize for both legs; the composed leg's HIP-event time
+      and the renderer's own device time (stats.ms_gpu_last) beside them.  No bar: the composed frame has dense rows, no compaction, more launches and torch ops in between.
+3 warm + 20 timed repetitions, the legs alternating, medians.
+Usage: python tools/integrator_rate.py [--scenes dragon,dragon4] [--reps 20]      (prints one JSON line)"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def compose(torch, r, ds, sample_index, dev, miss, bounces=3):
+    """one frame of the reference's integrator from the public stages on torch's current stream -> (n, 3) radiance sample"""
+    rays, hidx = r.primary_rays_device(sample_index=sample_index)
+    n = rays.shape[0]
+    thr = torch.ones((n, 3), device=dev); acc = torch.zeros((n, 3), device=dev); alive = torch.ones(n, dtype=torch.bool, device=dev)
+    for b in range(bounces):
+        hits = ds.intersect_closest_device(rays)
+        surf = ds.resolve_hits_device(rays, hits)
+        alive = alive & (surf[:, 7].view(torch.int32) == 1)
+        surf = torch.where(alive[:, None], surf, miss)
+        shadow, light, nxt = ds.scatter_device(surf, hidx, b, next_rays=b + 1 < bounces)
+        occluded = ds.intersect_any_device(shadow)
+        thr = torch.mul(thr, surf[:, 8:11])
+        lit = alive & (light[:, 3] == 1.0) & (occluded == 0)
+        acc = torch.where(lit[:, None], torch.add(acc, torch.mul(light[:, 0:3], thr)), acc)
+        rays = nxt
+    return acc
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", default="dragon,dragon4")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--side", type=int, default=2048, help="(a): the image is side x side pixels")
+    a = ap.parse_args()
+    import torch
+    import metal_raytracing_amd as m
+    ctx = m.Context(0)
+    dev = torch.device("cuda", 0)
+    ts = torch.cuda.Stream(dev)
+    rows = a.side * a.side
+    res = {"device": ctx.device_name, "rows": rows, "reps": a.reps, "scenes": {}}
+
+    def timed(fns):
+        """the callables in turn on the side stream, reps times over; median device ms of each"""
+        ms = [[] for _ in fns]
+        with torch.cuda.stream(ts):
+            for rep in range(3 + a.reps):
+                for k, fn in enumerate(fns):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(ts); fn(); e1.record(ts); ts.synchronize()
+                    if rep >= 3: ms[k].append(e0.elapsed_time(e1))
+        return [statistics.median(x) for x in ms]
+
+    src = torch.empty(256 << 20, dtype=torch.uint8, device=dev); dst = torch.empty_like(src)
+    copy_ms = timed([lambda: dst.copy_(src)])[0]
+    copy_gbs = 2 * src.numel() / copy_ms / 1e6                     # read + write
+    res["copy_256MiB_ms"] = copy_ms; res["copy_GBps"] = copy_gbs
+    del src, dst
+    miss = torch.tensor([[0.0, 0.0, 0.0, -1.0] + [0.0] * 12], device=dev)
+    miss.view(torch.int32)[0, 11] = -1; miss.view(torch.int32)[0, 12:15] = -1          # the miss record of resolve_hits_device
+    for name in a.scenes.split(","):
+        two_level = name == "dragon4"
+        opts = {"instancing": 1} if two_level else None
+        row = {"instancing": int(two_level)}
+        # (a) the stages alone
+        sc = m.SCENES[name]((a.side, a.side))
+        r = m.Renderer((a.side, a.side), sc, ctx=ctx, scene_options=opts)
+        ds = r.device_scene
+        row["triangles"] = int(ds.stats.triangles)
+        prim = (torch.empty((rows, 8), device=dev), torch.empty((rows,), dtype=torch.int32, device=dev))
+        outs = (torch.empty((rows, 8), device=dev), torch.empty((rows, 4), device=dev), torch.empty((rows, 8), device=dev))
+        s = ts.cuda_stream
+        r.primary_rays_device(sample_index=0, out=prim, stream=0)
+        surf0 = ds.resolve_hits_device(prim[0], ds.intersect_closest_device(prim[0], stream=0), stream=0)
+        ds.scatter_device(surf0, prim[1], 0, out=outs, stream=0)
+        surf1 = ds.resolve_hits_device(outs[2], ds.intersect_closest_device(outs[2], stream=0), stream=0)
+        torch.cuda.synchronize()
+        t = timed([lambda: r.primary_rays_device(sample_index=0, out=prim, stream=s), lambda: ds.scatter_device(surf0, prim[1], 0, out=outs, stream=s),
+                   lambda: ds.scatter_device(surf1, prim[1], 1, out=outs, stream=s)])
+        floor_p = 36.0 * rows / copy_gbs / 1e6; floor_s = 148.0 * rows / copy_gbs / 1e6
+        row["a"] = {"primary_ms": t[0], "primary_floor_ms": floor_p, "primary_over_floor": t[0] / floor_p,
+                    "scatter_b0_ms": t[1], "scatter_b1_ms": t[2], "scatter_floor_ms": floor_s, "scatter_b0_over_floor": t[1] / floor_s, "scatter_b1_over_floor": t[2] / floor_s,
+                    "surface_share_b0": float((surf0[:, 7].view(torch.int32) == 1).float().mean()), "surface_share_b1": float((surf1[:, 7].view(torch.int32) == 1).float().mean())}
+        del prim, outs, surf0, surf1
+        r.close()
+        # (b) the composed frame beside the renderer's
+        sc = m.SCENES[name]((1920, 1080))
+        r = m.Renderer((1920, 1080), sc, ctx=ctx, scene_options=opts)
+        ds = r.device_scene
+        wall = {"composed": [], "renderer": []}; ev = []; own = []
+        for rep in range(3 + a.reps):
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0 = time.perf_counter()
+                e0.record(ts); acc = compose(torch, r, ds, 0, dev, miss); e1.record(ts); ts.synchronize()
+                t1 = time.perf_counter()
+            r.frameIndex = 0
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            r.draw(1, wait=True)
+            t3 = time.perf_counter()
+            if rep >= 3:
+                wall["composed"].append((t1 - t0) * 1e3); wall["renderer"].append((t3 - t2) * 1e3); ev.append(e0.elapsed_time(e1)); own.append(float(r.stats.ms_gpu_last))
+        img = torch.from_numpy(r.accumulation()).to(dev).reshape(-1, 4)[:, 0:3]
+        row["b"] = {"composed_wall_ms": statistics.median(wall["composed"]), "renderer_wall_ms": statistics.median(wall["renderer"]), "composed_event_ms": statistics.median(ev),
+                    "renderer_device_ms": statistics.median(own), "composed_over_renderer_wall": statistics.median(wall["composed"]) / statistics.median(wall["renderer"]),
+                    "same_bits": bool(torch.equal(acc.view(torch.int32), img.contiguous().view(torch.int32)))}
+        r.close()
+        res["scenes"][name] = row
+    ctx.close()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
