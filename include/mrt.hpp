@@ -146,12 +146,20 @@ struct Scene {                                                       // Scene.sw
                                   void *deviceOut, size_t outStrideBytes, void *hipStream) {
         check(mrt_scene_interpolate_device(committed, deviceHits, n, deviceAttributes, attributeStrideBytes, channels, deviceOut, outStrideBytes, hipStream));
     }
-    // What follows a surface in the reference's kernel, its diffuse path (mrt_scene_scatter_device; the materials extension stays inside Renderer::draw): n x MRTSurface
+    // What follows a surface in the reference's kernel, its diffuse path (mrt_scene_scatter_device; the materials extension is scatterMaterialsDevice): n x MRTSurface
     // and the n x int32 Halton indices of Renderer::primaryRaysDevice -> n x MRTRay shadow rays, n x 4 float light rows {colour | 1.0f where the shadow ray is wanted},
     // n x MRTRay bounce rays (deviceNextRays may be nullptr: the last bounce).  Row i in, row i out; zeros for a row that is no surface.  bounce 0 .. 18; lightCount 0 = all.
     static void scatterDevice(MRTScene committed, const void *deviceSurfaces, const void *deviceHaltonIndex, size_t n, int32_t bounce, int32_t lightCount, void *deviceShadowRays,
                               void *deviceLight, void *deviceNextRays, void *hipStream) {
         check(mrt_scene_scatter_device(committed, deviceSurfaces, deviceHaltonIndex, n, bounce, lightCount, deviceShadowRays, deviceLight, deviceNextRays, hipStream));
+    }
+    // The same step with the materials extension on (mrt_scene_scatter_materials_device): also takes the n x MRTRay that hit the surfaces and the integrator's maxBounces
+    // (1 .. 16; 0 <= bounce < maxBounces), also writes n x MRTScatterLobe {weight | lobe, emission | 0}: lobe 0 none, 1 diffuse, 2 / 3 interface reflected / refracted,
+    // 4 specular, 5 absorbed.  Diffuse rows as scatterDevice; the other lobes get zero shadow and light rows and continue along their own ray.
+    static void scatterMaterialsDevice(MRTScene committed, const void *deviceRays, const void *deviceSurfaces, const void *deviceHaltonIndex, size_t n, int32_t bounce, int32_t maxBounces,
+                                       int32_t lightCount, void *deviceShadowRays, void *deviceLight, void *deviceNextRays, void *deviceLobes, void *hipStream) {
+        check(mrt_scene_scatter_materials_device(committed, deviceRays, deviceSurfaces, deviceHaltonIndex, n, bounce, maxBounces, lightCount, deviceShadowRays, deviceLight, deviceNextRays,
+                                                 deviceLobes, hipStream));
     }
     // each mesh's first attribute row (an instance reports its source's) and, last, the number of rows: meshCount + 1 entries
     static std::vector<uint64_t> vertexOffsets(MRTScene scene, size_t meshCount) {
@@ -246,6 +254,10 @@ class Renderer {                                                     // Renderer
     void primaryRaysDevice(uint32_t sampleIndex, void *deviceRays, void *deviceHaltonIndex, void *hipStream) { check(mrt_renderer_primary_rays_device(r_, sampleIndex, deviceRays, deviceHaltonIndex, hipStream)); }
     void scatterDevice(const void *deviceSurfaces, const void *deviceHaltonIndex, size_t n, int32_t bounce, int32_t lightCount, void *deviceShadowRays, void *deviceLight, void *deviceNextRays, void *hipStream) {
         Scene::scatterDevice(scene_, deviceSurfaces, deviceHaltonIndex, n, bounce, lightCount, deviceShadowRays, deviceLight, deviceNextRays, hipStream);
+    }
+    void scatterMaterialsDevice(const void *deviceRays, const void *deviceSurfaces, const void *deviceHaltonIndex, size_t n, int32_t bounce, int32_t maxBounces, int32_t lightCount,
+                                void *deviceShadowRays, void *deviceLight, void *deviceNextRays, void *deviceLobes, void *hipStream) {
+        Scene::scatterMaterialsDevice(scene_, deviceRays, deviceSurfaces, deviceHaltonIndex, n, bounce, maxBounces, lightCount, deviceShadowRays, deviceLight, deviceNextRays, deviceLobes, hipStream);
     }
     std::vector<uint64_t> vertexOffsets() const { MRTSceneStats st; check(mrt_scene_stats(scene_, &st)); return Scene::vertexOffsets(scene_, (size_t)st.instances); }
     // deformation from device buffers on a stream (Scene::updateMeshDevice): packed or strided float3 rows; refitDevice() after one or more updates

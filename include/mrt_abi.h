@@ -382,7 +382,7 @@ int mrt_scene_vertex_offsets(MRTScene scene, uint64_t *offsets /* meshes + 1 ent
  * bounce.  With them the reference's integrator, or a variant of it, is five stream-ordered calls — generate, mrt_scene_intersect_closest_device,
  * mrt_scene_resolve_hits_device, scatter, mrt_scene_intersect_any_device — and element-wise arithmetic of the caller's (throughput = throughput * base_color; radiance +=
  * light * throughput where the shadow ray got through); composed so, the image is the renderer's own, bit for bit.  Materials extension OFF: these are the expressions of
- * the reference's diffuse path; the semantics of renderer option materials = 1 stay reachable through mrt_renderer_render alone.
+ * the reference's diffuse path; the semantics of renderer option materials = 1 are mrt_scene_scatter_materials_device's, below.
  *   mrt_renderer_primary_rays_device: for every pixel p = y * width + x of the renderer's image (row 0 at the bottom, as mrt_renderer_read_accum; the WHOLE image whatever
  *     the renderer's shard) d_halton_index[p] = (int32)(hash(seed, p) + sample_index), the renderer's own per-pixel seed plus the caller's sample index with wrap-around,
  *     and d_rays[p] = {camera position | 0, normalize((uvx * right + uvy * up) + forward) | +inf} with uv = ((x, y) + halton(index, 0 and 1)) / (width, height) * 2 - 1:
@@ -411,6 +411,36 @@ int mrt_scene_vertex_offsets(MRTScene scene, uint64_t *offsets /* meshes + 1 ent
 int mrt_renderer_primary_rays_device(MRTRenderer r, uint32_t sample_index, void *d_rays /* w*h x MRTRay */, void *d_halton_index /* w*h x int32 */, void *hip_stream);
 int mrt_scene_scatter_device(MRTScene scene, const void *d_surfaces /* n x MRTSurface */, const void *d_halton_index /* n x int32 */, size_t n, int32_t bounce, int32_t light_count,
                              void *d_shadow_rays /* n x MRTRay */, void *d_light /* n x 4 float32 */, void *d_next_rays /* n x MRTRay, may be NULL */, void *hip_stream);
+
+/* mrt_scene_scatter_device with the materials extension ON: what follows a surface when renderer option materials = 1 — emission, the lobe choice, the
+ * dielectric interface, the GGX specular lobe, and the diffuse path above with its albedo divided by the probability of having been chosen.  Row i in, row i out, no
+ * compaction.  d_rays is n x MRTRay, the rays that hit these surfaces (the direction is read); d_surfaces, d_halton_index, light_count as above; max_bounces is the
+ * renderer's option (1 .. 16) and 0 <= bounce < max_bounces: the lobe choice reads Halton dimension 2 + 5 * max_bounces + bounce, which stays below the prime table's 100.
+ * For a surface with type == 1 whose resource_slot lies in [0, instances * max_submeshes) the material is the scene's at that slot, with ONE exception: the albedo is the
+ * row's base_color (an unmodified row holds the material's; a caller may substitute their own), for kd = max(base_color) and for the diffuse weight alike.  With
+ * ks = max(specular), trn = 1 - dissolve where 0 < dissolve < 1 and refractionIndex > 0 (else 0), u = halton(index, 2 + 5 * max_bounces + bounce):
+ *   u < trn                the dielectric interface: Schlick's Fresnel term at u / trn picks reflection (lobe 2) or refraction (lobe 3; total internal reflection is lobe 2);
+ *                          weight {1, 1, 1}; continuation {position + nn * 1e-3f (reflected) or * -1e-3f (refracted) | 0, normalize(nd) | +inf}, nn the normal facing the ray
+ *   else, with ud = (u - trn) / (1 - trn) where trn > 0 (else u) and ps = ks / (ks + kd) where ks > 0 and specularExponent > 0 (else 0):
+ *   ud < ps                the specular lobe: the ray mirrored about a GGX half vector (alpha^2 = 2 / (Ns + 2)) from dimensions 2 + 5 * bounce + 3 and + 4.  Above the
+ *                          surface: lobe 4, weight specular * (1 / ps), continuation {position + normal * 1e-3f | 0, normalize(wi) | +inf}.  Below it: lobe 5, the
+ *                          path is absorbed — weight {0, 0, 0}, no continuation
+ *   else                   the diffuse path: lobe 1, weight base_color (* (1 / (1 - ps)) where ps > 0); d_shadow_rays[i], d_light[i] and the cosine-weighted
+ *                          d_next_rays[i] exactly as mrt_scene_scatter_device writes them
+ * d_lobes[i] = {weight | lobe, the material's emission | 0} (MRTScatterLobe).  The dielectric and specular lobes make no next-event estimate: their d_shadow_rays and
+ * d_light rows are zeros.  A row that is no surface — type != 1, or a resource_slot outside the scene's table (nothing is indexed with it) — gives zeros in all four
+ * outputs (lobe 0); an absorbed row gives zeros but its lobe code and emission.  d_next_rays may be NULL: every other output keeps its bits.  A frame of the
+ * renderer's integrator is then, per bounce and in this order: radiance += throughput * emission; throughput *= weight; radiance += light.rgb * throughput where
+ * light.w == 1 and the shadow ray got through; the path goes on where lobe is 1, 2, 3 or 4 — composed so, the image is mrt_renderer_render's with materials = 1, bit
+ * for bit.  One kernel per call; the contract, the refusal rules and their order are mrt_scene_scatter_device's, with d_rays and d_lobes 16-byte aligned and required,
+ * max_bounces outside 1 .. 16 and bounce outside [0, max_bounces) refused.                                                                                               */
+typedef struct {
+    float   weight[3];     int32_t lobe;           /* factor of the throughput | 0 none, 1 diffuse, 2 interface reflected, 3 interface refracted, 4 specular, 5 absorbed */
+    float   emission[3];   int32_t _pad;           /* the material's emission, not multiplied by any throughput | 0                                                   */
+} MRTScatterLobe;                                                     /* 32 B                   */
+int mrt_scene_scatter_materials_device(MRTScene scene, const void *d_rays /* n x MRTRay */, const void *d_surfaces /* n x MRTSurface */, const void *d_halton_index /* n x int32 */, size_t n,
+                                       int32_t bounce, int32_t max_bounces, int32_t light_count, void *d_shadow_rays /* n x MRTRay */, void *d_light /* n x 4 float32 */,
+                                       void *d_next_rays /* n x MRTRay, may be NULL */, void *d_lobes /* n x MRTScatterLobe */, void *hip_stream);
 
 /* ---------------------------------------------------------------- host-side geometry helpers
  * (no GPU needed) — the library's OBJ/MTL reader standing in for ModelIO (Model.swift:16-21,

@@ -99,6 +99,10 @@ class Surface(C.Structure):  # MRTSurface (include/mrt_abi.h; no counterpart in 
                 ("instance_id", C.c_int32), ("geometry_id", C.c_int32), ("primitive_id", C.c_int32), ("_pad", C.c_int32)]
 
 
+class ScatterLobe(C.Structure):  # MRTScatterLobe (include/mrt_abi.h; no counterpart in ShaderTypes.h)
+    _fields_ = [("weight", C.c_float * 3), ("lobe", C.c_int32), ("emission", C.c_float * 3), ("_pad", C.c_int32)]
+
+
 class SceneStats(C.Structure):
     _fields_ = [("triangles", C.c_uint64), ("vertices", C.c_uint64), ("bvh_nodes", C.c_uint64), ("bvh_leaves", C.c_uint64),
                 ("scene_bytes", C.c_uint64), ("build_ms", C.c_float), ("sah_cost", C.c_float), ("instances", C.c_int32),
@@ -128,7 +132,7 @@ GUIDE_NORMAL_DEPTH, GUIDE_ALBEDO, GUIDE_IDS = 0, 1, 2
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_color": 4.0, "sigma_normal": 0.25, "sigma_depth": 0.25, "demodulate": 1}      # MRT_DENOISE_DEFAULT_*
 
 assert C.sizeof(Camera) == 64 and C.sizeof(Light) == 128 and C.sizeof(Uniforms) == 96 and C.sizeof(Material) == 64
-assert C.sizeof(Ray) == 32 and C.sizeof(Intersection) == 32 and C.sizeof(DenoiseParams) == 32 and C.sizeof(Surface) == 64
+assert C.sizeof(Ray) == 32 and C.sizeof(Intersection) == 32 and C.sizeof(DenoiseParams) == 32 and C.sizeof(Surface) == 64 and C.sizeof(ScatterLobe) == 32
 
 # ---------------------------------------------------------------- function table: every symbol include/mrt_abi.h declares
 _P, _I32, _U32, _F, _SZ = C.c_void_p, C.c_int32, C.c_uint32, C.c_float, C.c_size_t
@@ -171,6 +175,7 @@ SIGNATURES = {
     "mrt_scene_interpolate_device": (C.c_int, [_P, _P, _SZ, _P, _SZ, _I32, _P, _SZ, _P]),
     "mrt_scene_vertex_offsets": (C.c_int, [_P, C.POINTER(C.c_uint64), _SZ]),
     "mrt_scene_scatter_device": (C.c_int, [_P, _P, _P, _SZ, _I32, _I32, _P, _P, _P, _P]),
+    "mrt_scene_scatter_materials_device": (C.c_int, [_P, _P, _P, _P, _SZ, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "mrt_obj_load": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "mrt_dragon_proxy": (C.c_int, [C.POINTER(_P)]),
     "mrt_dragon_proxy_irregular": (C.c_int, [C.POINTER(_P)]),

@@ -32,6 +32,9 @@ MRT_AT(MRTRay, min_distance, 12); MRT_AT(MRTRay, direction, 16); MRT_AT(MRTRay, 
 static_assert(sizeof(MRTSurface) == 64, "MRTSurface is 64 bytes");
 MRT_AT(MRTSurface, position, 0); MRT_AT(MRTSurface, distance, 12); MRT_AT(MRTSurface, normal, 16); MRT_AT(MRTSurface, type, 28);
 MRT_AT(MRTSurface, base_color, 32); MRT_AT(MRTSurface, resource_slot, 44); MRT_AT(MRTSurface, instance_id, 48); MRT_AT(MRTSurface, _pad, 60);
+// lobe rows (mrt_scene_scatter_materials_device; no counterpart in ShaderTypes.h): two 16-byte groups
+static_assert(sizeof(MRTScatterLobe) == 32, "MRTScatterLobe is 32 bytes");
+MRT_AT(MRTScatterLobe, weight, 0); MRT_AT(MRTScatterLobe, lobe, 12); MRT_AT(MRTScatterLobe, emission, 16); MRT_AT(MRTScatterLobe, _pad, 28);
 // denoiser parameters (no counterpart in ShaderTypes.h)
 static_assert(sizeof(MRTDenoiseParams) == 32, "MRTDenoiseParams is 32 bytes");
 MRT_AT(MRTDenoiseParams, iterations, 0); MRT_AT(MRTDenoiseParams, sigma_color, 4); MRT_AT(MRTDenoiseParams, sigma_normal, 8);

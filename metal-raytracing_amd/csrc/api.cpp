@@ -583,6 +583,29 @@ int mrt_scene_scatter_device(MRTScene scene, const void *d_surfaces, const void 
     MRT_CATCH
 }
 
+// The same step with the materials extension on (stages_materials.hip): mrt_scene_scatter_device's rules, plus the incoming rays, the lobe rows and max_bounces
+int mrt_scene_scatter_materials_device(MRTScene scene, const void *d_rays, const void *d_surfaces, const void *d_halton_index, size_t n, int32_t bounce, int32_t max_bounces, int32_t light_count,
+                                       void *d_shadow_rays, void *d_light, void *d_next_rays, void *d_lobes, void *hip_stream) {
+    MRT_TRY
+    const char *who = "mrt_scene_scatter_materials_device";
+    REQUIRE(n == 0 || (d_rays && d_surfaces && d_halton_index && d_shadow_rays && d_light && d_lobes),
+            "mrt_scene_scatter_materials_device: NULL buffers (d_rays, d_surfaces, d_halton_index, d_shadow_rays, d_light and d_lobes are required; only d_next_rays may be NULL)");
+    REQUIRE((uintptr_t)d_rays % 16 == 0 && (uintptr_t)d_surfaces % 16 == 0 && (uintptr_t)d_shadow_rays % 16 == 0 && (uintptr_t)d_light % 16 == 0 && (uintptr_t)d_next_rays % 16 == 0 && (uintptr_t)d_lobes % 16 == 0,
+            "mrt_scene_scatter_materials_device: d_rays, d_surfaces, d_shadow_rays, d_light, d_next_rays and d_lobes must be 16-byte aligned");
+    REQUIRE((uintptr_t)d_halton_index % 4 == 0, "mrt_scene_scatter_materials_device: d_halton_index must be 4-byte aligned");
+    REQUIRE(max_bounces >= 1 && max_bounces <= 16, "mrt_scene_scatter_materials_device: max_bounces must be in [1, 16] (the lobe choice uses Halton dimension 2 + 5 * max_bounces + bounce of a table of 100 primes)");
+    REQUIRE(bounce >= 0 && bounce < max_bounces, "mrt_scene_scatter_materials_device: bounce must be in [0, max_bounces)");
+    REQUIRE(light_count >= 0, "mrt_scene_scatter_materials_device: light_count must be >= 0 (0 = every light of the scene)");
+    if (int rc = surface_prologue(who, scene, n)) return rc;
+    REQUIRE(light_count <= scene->dev.light_count, "mrt_scene_scatter_materials_device: light_count is above the number of lights of the scene");
+    if (scene->dev.light_count < 1) { mrt::set_error("mrt_scene_scatter_materials_device: scene has no lights (lightCount must be >= 1, Raytracing.metal:273)"); return MRT_ERR_STATE; }
+    if (n == 0) return MRT_OK;
+    if (int rc = bind_device(scene->ctx)) return rc;
+    return mrt::scatter_materials_device(scene->dev, (hipStream_t)hip_stream, d_rays, d_surfaces, d_halton_index, n, bounce, max_bounces, light_count > 0 ? light_count : scene->dev.light_count,
+                                         d_shadow_rays, d_light, d_next_rays, d_lobes);
+    MRT_CATCH
+}
+
 int mrt_debug_traversal_stats(MRTScene scene, const MRTRay *rays, size_t n, int32_t any_hit, uint32_t *out4) {
     MRT_TRY
     REQUIRE(scene && (n == 0 || (rays && out4)), "mrt_debug_traversal_stats: bad argument");

@@ -438,5 +438,8 @@ int upload_lights(const MRTLight *lights, int count, hipStream_t stream, DeviceS
 // stages.hip: what follows a surface in the reference's kernel, on the caller's stream
 int scatter_device(const DeviceScene &sc, hipStream_t stream, const void *d_surfaces, const void *d_halton_index, size_t n, int bounce, int light_count, void *d_shadow_rays, void *d_light,
                    void *d_next_rays);      // one launch, nothing else; light_count in [1, sc.light_count], bounce in [0, 18]
+// stages_materials.hip: the same step with the materials extension on
+int scatter_materials_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, const void *d_surfaces, const void *d_halton_index, size_t n, int bounce, int max_bounces,
+                             int light_count, void *d_shadow_rays, void *d_light, void *d_next_rays, void *d_lobes);      // one launch, nothing else; light_count in [1, sc.light_count], max_bounces in [1, 16], bounce in [0, max_bounces)
 
 }  // namespace mrt

@@ -207,7 +207,7 @@ class DeviceScene:
         return out
 
     def scatter_device(self, surfaces, halton_index, bounce, light_count=0, next_rays=True, out=None, stream=None):
-        """What follows a surface in the reference's kernel (its diffuse path; the materials extension stays inside Renderer), on the GPU and ordered on a stream: surfaces
+        """What follows a surface in the reference's kernel (its diffuse path; the materials extension is scatter_materials_device), on the GPU and ordered on a stream: surfaces
         (n, 16) float32 as resolve_hits_device returns them, halton_index (n,) int32 as Renderer.primary_rays_device returns it, bounce the path depth of these surfaces
         (0 .. 18), light_count Uniforms.lightCount (0 = every light of the scene) -> (shadow_rays (n, 8) float32, light (n, 4) float32, next_rays (n, 8) float32 or
         None).  Row i in gives row i out: light[i] = the picked light's colour at the surface | 1.0 where the reference traces a shadow ray (else 0.0),
@@ -233,6 +233,41 @@ class DeviceScene:
         p = [C.c_void_p(t.data_ptr() if n else None) for t in (surfaces, h) + out]
         check(lib.mrt_scene_scatter_device(self.handle, p[0], p[1], n, int(bounce), int(light_count), p[2], p[3], p[4] if next_rays else None, C.c_void_p(self._stream_handle(stream))))
         return (out[0], out[1], out[2] if next_rays else None)
+
+    def scatter_materials_device(self, rays, surfaces, halton_index, bounce, max_bounces, light_count=0, next_rays=True, out=None, stream=None):
+        """scatter_device with the materials extension on — what follows a surface when Renderer's option materials = 1 — on the GPU and ordered on a stream: rays (n, 8)
+        float32, the rays that hit these surfaces (their direction is read); surfaces, halton_index, light_count as scatter_device takes them; max_bounces the path
+        length of the integrator (1 .. 16) and 0 <= bounce < max_bounces: the lobe choice reads Halton dimension 2 + 5 * max_bounces + bounce -> (shadow_rays (n, 8),
+        light (n, 4), next_rays (n, 8) or None, lobes (n, 8)), all float32.  lobes[i] = weight | lobe code (int32 bits), the material's emission | 0 (unpack_lobes gives
+        the fields): lobe 0 = no surface, 1 = diffuse, 2 / 3 = dielectric interface reflected / refracted, 4 = specular, 5 = specular sampled below the surface
+        (absorbed).  The material is the scene's at the row's resource slot, but the albedo is the row's base colour (a caller may substitute their own); a slot outside
+        the scene's table makes the row no surface.  Diffuse rows get shadow_rays, light and next_rays exactly as scatter_device writes them; the other lobes make no
+        next-event estimate (zeros there) and continue along their own ray; absorbed rows and rows that are no surface give zero rays.  A frame is, per bounce:
+        radiance += throughput * emission; throughput *= weight; radiance += light[:, :3] * throughput where light[:, 3] == 1 and the shadow ray got through; the
+        path goes on where lobe is 1 .. 4 — Renderer's image with materials = 1, bit for bit.  next_rays=False computes and writes no third buffer.  out: the tuple of
+        tensors to write, (shadow_rays, light, next_rays, lobes) or (shadow_rays, light, lobes).  Nothing is allocated (but the outputs when out is None), copied or
+        synchronised.  stream: as intersect_closest_device takes it."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        if not isinstance(surfaces, torch.Tensor) or surfaces.device != dev or surfaces.dtype != torch.float32 or surfaces.dim() != 2 or surfaces.shape[1] != 16 or not surfaces.is_contiguous():
+            raise ValueError(f"surfaces must be a contiguous torch.float32 tensor of shape (n, 16) on {dev}: the records of resolve_hits_device")
+        n = surfaces.shape[0]
+        if not isinstance(rays, torch.Tensor) or rays.device != dev or rays.dtype != torch.float32 or tuple(rays.shape) != (n, 8) or not rays.is_contiguous():
+            raise ValueError(f"rays must be a contiguous torch.float32 tensor of shape {(n, 8)} on {dev}: the rays that hit the surfaces")
+        h = halton_index
+        if not isinstance(h, torch.Tensor) or h.device != dev or h.dtype != torch.int32 or tuple(h.shape) != (n,) or not h.is_contiguous():
+            raise ValueError(f"halton_index must be a contiguous torch.int32 tensor of shape {(n,)} on {dev}")
+        shapes = [(n, 8), (n, 4)] + ([(n, 8)] if next_rays else []) + [(n, 8)]
+        if out is None:
+            out = tuple(torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes)
+        else:
+            out = tuple(out)
+            if len(out) != len(shapes) or any(not isinstance(o, torch.Tensor) or o.device != dev or o.dtype != torch.float32 or tuple(o.shape) != sh or not o.is_contiguous() for o, sh in zip(out, shapes)):
+                raise ValueError(f"out must be {len(shapes)} contiguous torch.float32 tensors of shapes {shapes} on {dev}")
+        p = [C.c_void_p(t.data_ptr() if n else None) for t in (rays, surfaces, h) + out]
+        check(lib.mrt_scene_scatter_materials_device(self.handle, p[0], p[1], p[2], n, int(bounce), int(max_bounces), int(light_count), p[3], p[4], p[5] if next_rays else None, p[-1],
+                                                     C.c_void_p(self._stream_handle(stream))))
+        return (out[0], out[1], out[2] if next_rays else None, out[-1])
 
     def vertex_offsets(self):
         """The vertex numbering interpolate_device reads attributes in: (meshes + 1,) uint64 — each mesh's first row, the source meshes concatenated in mesh-id order and
@@ -394,6 +429,18 @@ def unpack_surfaces(t):
         t = t.detach().cpu().numpy()
     t = np.ascontiguousarray(t, np.float32).reshape(-1, 16)
     return t.view(SURFACE_DTYPE).reshape(-1)
+
+
+LOBE_DTYPE = np.dtype([("weight", np.float32, 3), ("lobe", np.int32), ("emission", np.float32, 3), ("_pad", np.int32)])
+
+
+def unpack_lobes(t):
+    """The MRTScatterLobe records of DeviceScene.scatter_materials_device as a structured numpy array (LOBE_DTYPE), one per row of the (n, 8) float32 tensor: a view of a
+    numpy array, of a CPU tensor's memory, or of the host copy of a GPU tensor (which waits for the tensor's stream)."""
+    if not isinstance(t, np.ndarray):
+        t = t.detach().cpu().numpy()
+    t = np.ascontiguousarray(t, np.float32).reshape(-1, 8)
+    return t.view(LOBE_DTYPE).reshape(-1)
 
 
 class Renderer:

@@ -6,8 +6,13 @@ Renderer drawing the same frame — DESIGN.md §10i.  Per scene (DragonScene fla
   (b) one composed frame at 1920 x 1080 — generate, closest, resolve, scatter, any; three bounces; throughput and radiance as torch mul / add / where — against Renderer
       drawing one frame alone (frame index 0 both).  Host wall time from the first enqueue to the end of a device synchronize for both legs; the composed leg's HIP-event time
       and the renderer's own device time (stats.ms_gpu_last) beside them.  No bar: the composed frame has dense rows, no compaction, more launches and torch ops in between.
+and, once (the materials leg; the Cornell box with a glass sphere, a glossy sphere and an emitting quad of the materials tests, max_bounces 4):
+  (c) scatter_materials_device alone at 2^22 rows at bounce 0 against its byte floor — per row the contract reads 48 B of surface, 16 B of ray and 4 B of index and writes
+      32 + 16 + 32 + 32 B: 180 B (with whole 64-byte surface rows and 32-byte ray rows, as the lines are fetched: 212 B, reported beside it; the material and light rows are
+      gathers from tables of a few lines and are not counted) — and one composed materials frame at 1920 x 1080, four bounces, beside Renderer with materials = 1 drawing one
+      frame, timed as (b).
 3 warm + 20 timed repetitions, the legs alternating, medians.
-Usage: python tools/integrator_rate.py [--scenes dragon,dragon4] [--reps 20]      (prints one JSON line)"""
+Usage: python tools/integrator_rate.py [--scenes dragon,dragon4] [--materials 1] [--reps 20]      (prints one JSON line)"""
 import argparse
 import json
 import os
@@ -38,9 +43,31 @@ def compose(torch, r, ds, sample_index, dev, miss, bounces=3):
     return acc
 
 
+def compose_materials(torch, r, ds, sample_index, dev, miss, bounces):
+    """one frame of the renderer's integrator with materials = 1 from the public stages on torch's current stream -> (n, 3) radiance sample"""
+    rays, hidx = r.primary_rays_device(sample_index=sample_index)
+    n = rays.shape[0]
+    thr = torch.ones((n, 3), device=dev); acc = torch.zeros((n, 3), device=dev); alive = torch.ones(n, dtype=torch.bool, device=dev)
+    for b in range(bounces):
+        hits = ds.intersect_closest_device(rays)
+        surf = ds.resolve_hits_device(rays, hits)
+        surf = torch.where(alive[:, None], surf, miss)
+        shadow, light, nxt, lobes = ds.scatter_materials_device(rays, surf, hidx, b, bounces, next_rays=b + 1 < bounces)
+        occluded = ds.intersect_any_device(shadow)
+        lobe = lobes[:, 3].view(torch.int32)
+        acc = torch.add(acc, torch.mul(thr, lobes[:, 4:7]))
+        thr = torch.mul(thr, lobes[:, 0:3])
+        lit = (light[:, 3] == 1.0) & (occluded == 0)
+        acc = torch.where(lit[:, None], torch.add(acc, torch.mul(light[:, 0:3], thr)), acc)
+        alive = (lobe >= 1) & (lobe <= 4)
+        rays = nxt
+    return acc
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default="dragon,dragon4")
+    ap.add_argument("--materials", type=int, default=1, help="(c): the materials leg")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--side", type=int, default=2048, help="(a): the image is side x side pixels")
     a = ap.parse_args()
@@ -70,7 +97,7 @@ def main():
     del src, dst
     miss = torch.tensor([[0.0, 0.0, 0.0, -1.0] + [0.0] * 12], device=dev)
     miss.view(torch.int32)[0, 11] = -1; miss.view(torch.int32)[0, 12:15] = -1          # the miss record of resolve_hits_device
-    for name in a.scenes.split(","):
+    for name in [x for x in a.scenes.split(",") if x]:
         two_level = name == "dragon4"
         opts = {"instancing": 1} if two_level else None
         row = {"instancing": int(two_level)}
@@ -120,6 +147,50 @@ def main():
                     "same_bits": bool(torch.equal(acc.view(torch.int32), img.contiguous().view(torch.int32)))}
         r.close()
         res["scenes"][name] = row
+    if a.materials:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from material_scenes import cornell_with_materials          # the scene of the materials tests (test infrastructure: the tool runs from the repository)
+        bounces = 4
+        row = {"max_bounces": bounces}
+        r = m.Renderer((a.side, a.side), cornell_with_materials(m, (a.side, a.side)), ctx=ctx, max_bounces=bounces)
+        ds = r.device_scene
+        prim = r.primary_rays_device(sample_index=0, stream=0)
+        surf0 = ds.resolve_hits_device(prim[0], ds.intersect_closest_device(prim[0], stream=0), stream=0)
+        outs = (torch.empty((rows, 8), device=dev), torch.empty((rows, 4), device=dev), torch.empty((rows, 8), device=dev), torch.empty((rows, 8), device=dev))
+        ds.scatter_materials_device(prim[0], surf0, prim[1], 0, bounces, out=outs, stream=0)
+        torch.cuda.synchronize()
+        s = ts.cuda_stream
+        t = timed([lambda: ds.scatter_materials_device(prim[0], surf0, prim[1], 0, bounces, out=outs, stream=s), lambda: ds.scatter_materials_device(prim[0], surf0, prim[1], 0, bounces, next_rays=False, out=(outs[0], outs[1], outs[3]), stream=s)])
+        floor_c = 180.0 * rows / copy_gbs / 1e6; floor_l = 212.0 * rows / copy_gbs / 1e6
+        lobes = outs[3][:, 3].view(torch.int32)
+        row["c"] = {"scatter_materials_b0_ms": t[0], "no_next_rays_ms": t[1], "floor_180B_ms": floor_c, "over_floor_180B": t[0] / floor_c, "floor_212B_ms": floor_l, "over_floor_212B": t[0] / floor_l,
+                    "lobe_share": [float((lobes == k).float().mean()) for k in range(6)]}
+        del prim, outs, surf0, lobes
+        r.close()
+        r = m.Renderer((1920, 1080), cornell_with_materials(m, (1920, 1080)), ctx=ctx, max_bounces=bounces)
+        r.set_option("materials", 1)
+        ds = r.device_scene
+        wall = {"composed": [], "renderer": []}; ev = []; own = []
+        for rep in range(3 + a.reps):
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0 = time.perf_counter()
+                e0.record(ts); acc = compose_materials(torch, r, ds, 0, dev, miss, bounces); e1.record(ts); ts.synchronize()
+                t1 = time.perf_counter()
+            r.frameIndex = 0
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            r.draw(1, wait=True)
+            t3 = time.perf_counter()
+            if rep >= 3:
+                wall["composed"].append((t1 - t0) * 1e3); wall["renderer"].append((t3 - t2) * 1e3); ev.append(e0.elapsed_time(e1)); own.append(float(r.stats.ms_gpu_last))
+        img = torch.from_numpy(r.accumulation()).to(dev).reshape(-1, 4)[:, 0:3]
+        row["frame"] = {"composed_wall_ms": statistics.median(wall["composed"]), "renderer_wall_ms": statistics.median(wall["renderer"]), "composed_event_ms": statistics.median(ev),
+                        "renderer_device_ms": statistics.median(own), "composed_over_renderer_wall": statistics.median(wall["composed"]) / statistics.median(wall["renderer"]),
+                        "same_bits": bool(torch.equal(acc.view(torch.int32), img.contiguous().view(torch.int32)))}
+        r.close()
+        res["materials"] = row
     ctx.close()
     print(json.dumps(res))
 
