@@ -3,11 +3,14 @@
 //
 //   shade_entry        one queue entry: normal interpolation, light pick + evaluation, throughput, NEE shadow-ray emit,
 //                      cosine-hemisphere bounce, wave-ballot compaction of both output queues            (:249-391)
+//                      (the camera-ray direction, the light evaluation and the materials lobe choice are scatter_math.h's:
+//                      one copy, shared with the device-buffer stages of stages.hip and stages_materials.hip)
 //   k_shade_primary    bounce 0 with the primary ray generated and traced in the same launch              (:171-247 + the above)
 //   k_shade_pack       bounces >= 1: the HITS of the bounce queue compacted in LDS, shaded on full waves
 //   k_shade            one queue entry per thread (bounce 0 from hit records; A/B of the packed form; materials at bounce 0)
 #pragma once
 #include "device_math.h"
+#include "scatter_math.h"
 #include "traverse.h"
 #include "traverse_wide.h"
 #include "traverse_instanced.h"
@@ -92,10 +95,7 @@ MRT_DEV void primary_ray(const FrameParams &fp, const uint32_t *__restrict__ see
     int idx = (int)(offset + fp.sampleIndex);
     float r0, r1;                                                        // :202-203
     r0 = halton_dev(idx, 0); r1 = halton_b0(fp, idx, 1);
-    float px = (float)x + r0, py = (float)y + r1;                        // :204
-    float uvx = px / (float)fp.width, uvy = py / (float)fp.height;       // :207
-    uvx = uvx * 2.0f - 1.0f; uvy = uvy * 2.0f - 1.0f;                    // :208
-    dir = normalize3((uvx * mk3(fp.cam_right) + uvy * mk3(fp.cam_up)) + mk3(fp.cam_fwd));   // :216-218
+    dir = camera_ray_dir(x, y, r0, r1, fp.width, fp.height, mk3(fp.cam_right), mk3(fp.cam_up), mk3(fp.cam_fwd));   // :204-218
     org = mk3(fp.cam_pos);                                               // :214
 }
 
@@ -220,8 +220,7 @@ MRT_DEV void shade_entry(const SceneView &s, const FrameParams &fp, const ShadeI
         color = mk3(C);
         bool diffuse = true;
         if (MATERIALS) {
-            // the materials extension (renderer option materials = 1; not in raytracingKernel — README.md:8 lists it as open work; the
-            // fields are ShaderTypes.h:99-107).  Semantics: DESIGN.md "Materials extension"; the CPU checker restates this block expression by expression.
+            // the materials extension: emission here, the lobe choice in choose_lobe (scatter_math.h)
             const float4 *__restrict__ mp = s.materials + 3 * (size_t)(inst * (uint32_t)s.max_sub + geom);
             const float4 m0 = mp[0], m1 = mp[1], m2 = mp[2];
             const f3 em = color * mk3(m2);
@@ -229,92 +228,25 @@ MRT_DEV void shade_entry(const SceneView &s, const FrameParams &fp, const ShadeI
             // pointer (both are __restrict__: two names for one address would leave the order of the two stores to the compiler)
             if (io.sample_primary) io.sample_primary[pix] = make_float4(0.0f + em.x, 0.0f + em.y, 0.0f + em.z, 0.0f);
             else { const float4 acc = io.sample[pix]; io.sample[pix] = make_float4(acc.x + em.x, acc.y + em.y, acc.z + em.z, 0.0f); }
-            const float ul = halton_dev(idx, 2 + 5 * fp.max_bounces + fp.bounce);
-            const f3 spec = mk3(m1);
-            const float kd = fmaxf(surf.x, fmaxf(surf.y, surf.z)), ks = fmaxf(spec.x, fmaxf(spec.y, spec.z));
-            const float dis = m0.w, ns = m1.w, ni = m2.w;
-            const float trn = (dis > 0.0f && dis < 1.0f && ni > 0.0f) ? 1.0f - dis : 0.0f;
-            if (ul < trn) {                                              // dielectric interface
-                const float u2 = ul / trn;
-                const f3 dir = mk3(B);
-                const float cd = dot3(dir, nrm);
-                const bool entering = cd < 0.0f;
-                const f3 nn = entering ? nrm : neg3(nrm);
-                const float eta = entering ? 1.0f / ni : ni;
-                const float cosi = entering ? -cd : cd;
-                const float sin2t = (eta * eta) * (1.0f - cosi * cosi);
-                float r0 = (1.0f - ni) / (1.0f + ni); r0 = r0 * r0;
-                float F = 1.0f, cost = 0.0f;
-                if (sin2t < 1.0f) { cost = __builtin_sqrtf(1.0f - sin2t); const float c = entering ? cosi : cost; const float x = 1.0f - c; const float x2 = x * x; F = r0 + (1.0f - r0) * ((x2 * x2) * x); }
-                f3 nd;
-                if (u2 < F) { nd = dir + nn * (2.0f * cosi); norg = P + nn * 1e-3f; }
-                else { nd = dir * eta + nn * (eta * cosi - cost); norg = P + nn * -1e-3f; }
-                ndir = normalize3(nd);
-                diffuse = false; special = true;
-                want_next = fp.bounce + 1 < fp.max_bounces;
-            } else {
-                const float ud = trn > 0.0f ? (ul - trn) / (1.0f - trn) : ul;
-                const float ps = (ks > 0.0f && ns > 0.0f) ? ks / (ks + kd) : 0.0f;
-                if (ud < ps) {                                           // specular lobe
-                    const float hx = halton_dev(idx, dim0 + 3), hy = halton_dev(idx, dim0 + 4);
-                    const float a2 = 2.0f / (ns + 2.0f);
-                    const float ct2 = (1.0f - hy) / (1.0f + (a2 - 1.0f) * hy);
-                    const float ct = __builtin_sqrtf(ct2), st = __builtin_sqrtf(1.0f - ct2);
-                    float sp_, cp_; sincos_2pi_dev(hx, sp_, cp_);
-                    const f3 hw = align_hemisphere_dev(mk3(st * cp_, ct, st * sp_), nrm);
-                    const f3 dir = mk3(B);
-                    const float dh = dot3(dir, hw);
-                    const f3 wi = dir - hw * (2.0f * dh);
-                    diffuse = false; special = true;
-                    if (dot3(wi, nrm) > 0.0f) {
-                        color = color * (spec * (1.0f / ps));
-                        ndir = normalize3(wi);
-                        want_next = fp.bounce + 1 < fp.max_bounces;
-                    }                                                    // else: sampled below the surface, the path is absorbed
-                } else if (ps > 0.0f) surf = surf * (1.0f / (1.0f - ps));
-            }
+            const LobeChoice c = choose_lobe<true>(m0, m1, m2, mk3(B), P, nrm, idx, dim0, 2 + 5 * fp.max_bounces + fp.bounce, surf);
+            norg = c.org; ndir = c.dir;
+            diffuse = c.lobe == 1; special = !diffuse;                   // the interface and the specular lobe make no next-event estimate
+            if (special) color = color * c.weight;                       // (1, 1, 1) at the interface: the same bits
+            want_next = special && c.lobe != 5 && fp.bounce + 1 < fp.max_bounces;      // 5: absorbed
         }
         if (diffuse) {
-            float ls = B0TAB ? halton_b0(fp, idx, 2) : halton_dev(idx, dim0 + 0);               // :272 (B0TAB: bounce 0 — dimensions 2 .. 6, from the table when there is one)
+            // B0TAB: bounce 0 — dimensions 2 .. 6, from the table when there is one
+            const auto hal = [&](int k) { return B0TAB ? halton_b0(fp, idx, 2 + k) : halton_dev(idx, dim0 + k); };
+            float ls = hal(0);                                               // :272
             int li = min((int)(ls * (float)fp.lightCount), fp.lightCount - 1);   // :273
             const LightDev L = s.lights[li];
-            int ltype = __float_as_int(L.position.w);
-            if (ltype == MRTLightTypeAreaLight) {                            // :281-290, :94-128
-                float ax = (B0TAB ? halton_b0(fp, idx, 3) : halton_dev(idx, dim0 + 1)) * 2.0f - 1.0f;
-                float ay = (B0TAB ? halton_b0(fp, idx, 4) : halton_dev(idx, dim0 + 2)) * 2.0f - 1.0f;
-                f3 sp = (mk3(L.position) + mk3(L.right) * ax) + mk3(L.up) * ay;
-                ldir = sp - P;
-                ldist = length3(ldir);
-                float inv = 1.0f / (ldist > 1e-3f ? ldist : 1e-3f);
-                ldir = ldir * inv;
-                lcol = mk3(L.color) * (inv * inv);
-                lcol = lcol * saturatef(dot3(neg3(ldir), mk3(L.forward)));
-            } else if (ltype == MRTLightTypeSpotlight) {                     // :292-316
-                ldir = mk3(L.position) - P;
-                ldist = length3(ldir);
-                float inv = 1.0f / (ldist > 1e-3f ? ldist : 1e-3f);
-                ldir = ldir * inv;
-                lcol = mk3(0, 0, 0);
-                float spot = dot3(neg3(ldir), mk3(L.dirn));
-                if (spot > L.dirn.w) lcol = (mk3(L.color) * inv) * inv;
-            } else if (ltype == MRTLightTypePointlight) {                    // :317-322
-                ldir = mk3(L.position) - P;
-                ldist = length3(ldir);
-                float inv = 1.0f / (ldist > 1e-3f ? ldist : 1e-3f);
-                ldir = ldir * inv;
-                lcol = (mk3(L.color) * inv) * inv;
-            } else {                                                         // :323-327
-                ldir = neg3(mk3(L.dirn));
-                ldist = __builtin_inff();
-                lcol = mk3(L.color);
-            }
-            lcol = lcol * saturatef(dot3(nrm, ldir));                        // :331
-            lcol = lcol * (float)fp.lightCount;                              // :335
+            const LightSample e = eval_light(L, fp.lightCount, P, nrm, hal);     // :281-335
+            ldir = e.dir; lcol = e.col; ldist = e.dist;
             color = mk3(C) * surf;                                           // :339
             want_shadow = length3(lcol) > 0.0001f;                           // :341
             want_next = fp.bounce + 1 < fp.max_bounces;
             if (want_next) {
-                float hx = B0TAB ? halton_b0(fp, idx, 5) : halton_dev(idx, dim0 + 3), hy = B0TAB ? halton_b0(fp, idx, 6) : halton_dev(idx, dim0 + 4);   // :384-385
+                float hx = hal(3), hy = hal(4);                              // :384-385
                 ndir = align_hemisphere_dev(sample_cosine_hemisphere_dev(hx, hy), nrm);  // :387-388
             }
         }

@@ -1,8 +1,8 @@
 // stages_materials.hip — the scatter stage with the materials extension ON, on device buffers and ordered on a stream of the caller's (mrt_scene_scatter_materials_device;
 // DESIGN.md §10j): what follows a surface when renderer option materials = 1 — emission, the lobe choice on Halton dimension 2 + 5 * max_bounces + bounce, the dielectric
-// interface, the GGX specular lobe, and the reference's diffuse path with its albedo divided by the probability of having been chosen.  shade_entry<MATERIALS>'s block
-// (shade.h) followed by k_scatter's diffuse path (stages.hip), each expression restated in its order, in a translation unit of its own: stages.hip, every shading kernel
-// and every traversal kernel keep their code objects.
+// interface, the GGX specular lobe, and the reference's diffuse path with its albedo divided by the probability of having been chosen.  The lobe choice is
+// choose_lobe and the diffuse rows are scatter_diffuse_rows (scatter_math.h) — the functions shade_entry<MATERIALS> (shade.h) and k_scatter (stages.hip) call, not copies
+// of them; what is this file's own is the row format, the slot check and the raw emission.  A translation unit of its own: no traversal and no shading kernel is compiled here.
 //
 //   k_scatter_materials   one thread per row: three 16-byte loads of the surface row (position; normal | type; base colour | resource slot), the direction group of the
 //                         incoming ray, one dword of Halton index, three 16-byte gathers from the material table at the row's slot, the light row as 16-byte gathers from
@@ -12,8 +12,7 @@
 // A thread owns a whole row: a wave's store instruction writes every second (ray and lobe rows) or every (light rows) 16 bytes of a contiguous range and the thread's next
 // store fills the gaps.  No LDS, no atomics, no cross-lane traffic.  A caller's row is never trusted with an address: the resource slot is checked against the table's
 // extent before the table is read (a slot outside it makes the row "no surface"), and the light pick lies in [0, light_count) by construction (and is clamped).
-#include "scene_device.h"
-#include "device_math.h"
+#include "scatter_math.h"
 
 namespace mrt {
 namespace {
@@ -37,99 +36,15 @@ __global__ void __launch_bounds__(256) k_scatter_materials(const LightDev *__res
         const int idx = halton_index[i];
         const float4 *__restrict__ mp = materials + 3 * (size_t)slot;
         const float4 m0 = mp[0], m1 = mp[1], m2 = mp[2];
-        f3 norg = P + nrm * 1e-3f;                                           // :350, :390
-        f3 ndir = mk3(0, 0, 0), weight = mk3(0, 0, 0);
-        int lobe = 1;
-        const float ul = halton_dev(idx, dim_lobe);
-        const f3 spec = mk3(m1);
-        const float kd = fmaxf(surf.x, fmaxf(surf.y, surf.z)), ks = fmaxf(spec.x, fmaxf(spec.y, spec.z));
-        const float dis = m0.w, ns = m1.w, ni = m2.w;
-        const float trn = (dis > 0.0f && dis < 1.0f && ni > 0.0f) ? 1.0f - dis : 0.0f;
-        if (ul < trn) {                                                      // dielectric interface
-            const float u2 = ul / trn;
-            const float cd = dot3(dir, nrm);
-            const bool entering = cd < 0.0f;
-            const f3 nn = entering ? nrm : neg3(nrm);
-            const float eta = entering ? 1.0f / ni : ni;
-            const float cosi = entering ? -cd : cd;
-            const float sin2t = (eta * eta) * (1.0f - cosi * cosi);
-            float r0 = (1.0f - ni) / (1.0f + ni); r0 = r0 * r0;
-            float F = 1.0f, cost = 0.0f;
-            if (sin2t < 1.0f) { cost = __builtin_sqrtf(1.0f - sin2t); const float c = entering ? cosi : cost; const float x = 1.0f - c; const float x2 = x * x; F = r0 + (1.0f - r0) * ((x2 * x2) * x); }
-            f3 nd;
-            if (u2 < F) { nd = dir + nn * (2.0f * cosi); norg = P + nn * 1e-3f; lobe = 2; }
-            else { nd = dir * eta + nn * (eta * cosi - cost); norg = P + nn * -1e-3f; lobe = 3; }
-            if (NEXT) ndir = normalize3(nd);
-            weight = mk3(1.0f, 1.0f, 1.0f);
-        } else {
-            const float ud = trn > 0.0f ? (ul - trn) / (1.0f - trn) : ul;
-            const float ps = (ks > 0.0f && ns > 0.0f) ? ks / (ks + kd) : 0.0f;
-            if (ud < ps) {                                                   // specular lobe
-                const float hx = halton_dev(idx, dim0 + 3), hy = halton_dev(idx, dim0 + 4);
-                const float a2 = 2.0f / (ns + 2.0f);
-                const float ct2 = (1.0f - hy) / (1.0f + (a2 - 1.0f) * hy);
-                const float ct = __builtin_sqrtf(ct2), st = __builtin_sqrtf(1.0f - ct2);
-                float sp_, cp_; sincos_2pi_dev(hx, sp_, cp_);
-                const f3 hw = align_hemisphere_dev(mk3(st * cp_, ct, st * sp_), nrm);
-                const float dh = dot3(dir, hw);
-                const f3 wi = dir - hw * (2.0f * dh);
-                lobe = 5;                                                    // sampled below the surface: the path is absorbed
-                if (dot3(wi, nrm) > 0.0f) {
-                    weight = spec * (1.0f / ps);
-                    if (NEXT) ndir = normalize3(wi);
-                    lobe = 4;
-                }
-            } else if (ps > 0.0f) surf = surf * (1.0f / (1.0f - ps));
-        }
-        if (lobe == 1) {                                                     // the diffuse path: k_scatter's, stages.hip
+        const LobeChoice c = choose_lobe<NEXT>(m0, m1, m2, dir, P, nrm, idx, dim0, dim_lobe, surf);
+        const f3 norg = c.org;
+        f3 ndir = c.dir, weight = c.weight;
+        const int lobe = c.lobe;
+        if (lobe == 1) {                                                     // the diffuse path: k_scatter's rows (stages.hip), weighted by the albedo choose_lobe left in `surf`
             weight = surf;
-            const float ls = halton_dev(idx, dim0 + 0);                          // :272
-            int li = min((int)(ls * (float)lc), lc - 1);                         // :273
-            li = li < 0 ? 0 : li;
-            const LightDev L = lights[li];
-            const int ltype = __float_as_int(L.position.w);
-            f3 ldir, lcol; float ldist;
-            if (ltype == MRTLightTypeAreaLight) {                                // :281-290, :94-128
-                const float ax = halton_dev(idx, dim0 + 1) * 2.0f - 1.0f;
-                const float ay = halton_dev(idx, dim0 + 2) * 2.0f - 1.0f;
-                const f3 sp = (mk3(L.position) + mk3(L.right) * ax) + mk3(L.up) * ay;
-                ldir = sp - P;
-                ldist = length3(ldir);
-                const float inv = 1.0f / (ldist > 1e-3f ? ldist : 1e-3f);
-                ldir = ldir * inv;
-                lcol = mk3(L.color) * (inv * inv);
-                lcol = lcol * saturatef(dot3(neg3(ldir), mk3(L.forward)));
-            } else if (ltype == MRTLightTypeSpotlight) {                         // :292-316
-                ldir = mk3(L.position) - P;
-                ldist = length3(ldir);
-                const float inv = 1.0f / (ldist > 1e-3f ? ldist : 1e-3f);
-                ldir = ldir * inv;
-                lcol = mk3(0, 0, 0);
-                const float spot = dot3(neg3(ldir), mk3(L.dirn));
-                if (spot > L.dirn.w) lcol = (mk3(L.color) * inv) * inv;
-            } else if (ltype == MRTLightTypePointlight) {                        // :317-322
-                ldir = mk3(L.position) - P;
-                ldist = length3(ldir);
-                const float inv = 1.0f / (ldist > 1e-3f ? ldist : 1e-3f);
-                ldir = ldir * inv;
-                lcol = (mk3(L.color) * inv) * inv;
-            } else {                                                             // :323-327
-                ldir = neg3(mk3(L.dirn));
-                ldist = __builtin_inff();
-                lcol = mk3(L.color);
-            }
-            lcol = lcol * saturatef(dot3(nrm, ldir));                            // :331
-            lcol = lcol * (float)lc;                                             // :335
-            const bool wants = length3(lcol) > 0.0001f;                          // :341
-            lo = make_float4(lcol.x, lcol.y, lcol.z, wants ? 1.0f : 0.0f);
-            if (wants) {
-                s0 = make_float4(norg.x, norg.y, norg.z, 0.0f);                  // :350
-                s1 = make_float4(ldir.x, ldir.y, ldir.z, ldist - 1e-3f);         // :356
-            }
-            if (NEXT) {
-                const float hx = halton_dev(idx, dim0 + 3), hy = halton_dev(idx, dim0 + 4);         // :384-385
-                ndir = align_hemisphere_dev(sample_cosine_hemisphere_dev(hx, hy), nrm);             // :387-388
-            }
+            const DiffuseRows r = scatter_diffuse_rows<NEXT>(lights, lc, idx, dim0, P, nrm, norg);
+            s0 = r.shadow0; s1 = r.shadow1; lo = r.light;
+            ndir = r.next_dir;
         }
         if (NEXT && lobe != 5) {
             n0 = make_float4(norg.x, norg.y, norg.z, 0.0f);
@@ -151,12 +66,9 @@ int scatter_materials_device(const DeviceScene &sc, hipStream_t stream, const vo
     const dim3 grid((uint32_t)((n + 255) / 256));          // n < 2^31
     const int dim0 = 2 + 5 * bounce, dim_lobe = 2 + 5 * max_bounces + bounce;          // max_bounces <= 16, bounce < max_bounces: dim_lobe <= 97, below the prime table's 100
     const uint32_t slots = (uint32_t)(sc.materials.n / 3);          // instances x max_submeshes (three rows per resource slot)
-    if (d_next_rays) hipLaunchKernelGGL(k_scatter_materials<true>, grid, dim3(256), 0, stream, sc.lights.p, sc.materials.p, slots, light_count, dim0, dim_lobe, static_cast<const float4 *>(d_rays),
-                                        static_cast<const float4 *>(d_surfaces), static_cast<const int32_t *>(d_halton_index), (uint32_t)n, static_cast<float4 *>(d_shadow_rays),
-                                        static_cast<float4 *>(d_light), static_cast<float4 *>(d_next_rays), static_cast<float4 *>(d_lobes));
-    else hipLaunchKernelGGL(k_scatter_materials<false>, grid, dim3(256), 0, stream, sc.lights.p, sc.materials.p, slots, light_count, dim0, dim_lobe, static_cast<const float4 *>(d_rays),
-                            static_cast<const float4 *>(d_surfaces), static_cast<const int32_t *>(d_halton_index), (uint32_t)n, static_cast<float4 *>(d_shadow_rays),
-                            static_cast<float4 *>(d_light), static_cast<float4 *>(nullptr), static_cast<float4 *>(d_lobes));
+    hipLaunchKernelGGL(d_next_rays ? k_scatter_materials<true> : k_scatter_materials<false>, grid, dim3(256), 0, stream, sc.lights.p, sc.materials.p, slots, light_count, dim0, dim_lobe,
+                       static_cast<const float4 *>(d_rays), static_cast<const float4 *>(d_surfaces), static_cast<const int32_t *>(d_halton_index), (uint32_t)n,
+                       static_cast<float4 *>(d_shadow_rays), static_cast<float4 *>(d_light), static_cast<float4 *>(d_next_rays), static_cast<float4 *>(d_lobes));
     MRT_HIP(hipGetLastError());
     return MRT_OK;
 }
