@@ -36,12 +36,15 @@ int mrt_debug_intersect_stream(MRTScene scene, const MRTRay *rays, size_t n, int
 int mrt_debug_wide_histogram(MRTScene scene, uint32_t *out12);
 /* Diagnostics: the 8-wide nodes of a committed scene as they lie in device memory (80 bytes each); out == NULL: only the count.                      */
 int mrt_debug_read_wnodes(MRTScene scene, void *out, size_t nbytes, uint64_t *num_nodes);
-/* Diagnostics: one array of the committed 8-wide layout as it lies in device memory, for the exact box audit of tests/bvh_audit.py.  part: 0 = the 8-wide
+/* Diagnostics: one array of the committed layouts as it lies in device memory, for the exact audits of tests/bvh_audit.py (8-wide) and tests/rope_audit.py (rope).  part: 0 = the 8-wide
  * nodes (80 B each), 1 = wpackets as the triangle test reads them (v0 | id word, e1, e2: 48 B each), 2 = the instance rows (InstanceDev, 80 B: w2o rows,
  * node / packet / gid / shading bases, ntri, blas, wroot), 3 = inst_box (64 B per instance: object-space BLAS box lo, hi, padded world box lo, hi),
  * 4 = wtlas_index (uint32), 5 = a header of 8 uint32 {num_wnodes, tlas_wcap, num_inst, wide_depth, packets, deepest BLAS, wtlas entries, packet stride in
  * float4}, 6 = the rope TLAS nodes of a two-level scene (64 B each: lo | a, hi | b, eight escape links), 7 = tlas_index (uint32: instance ids in the rope TLAS's
- * leaf order).  *count = elements of the part; out == NULL: only the count; otherwise nbytes must be count x the element size.                            */
+ * leaf order), 8 = the rope nodes the query entries and the fallbacks walk (64 B each: lo | a, hi | b, eight escape links) — a flattened scene's own tree, or all
+ * BLAS trees of a two-level scene (child and packet indices relative to the instance rows' node_base / packet_base), 9 = their triangle packets (48 B each).
+ * Parts 8 and 9 hold nothing for a flattened scene that keeps no rope layout (8-wide layout with rope = 0; the empty scene).
+ * *count = elements of the part; out == NULL: only the count; otherwise nbytes must be count x the element size.                                          */
 int mrt_debug_read_layout(MRTScene scene, int32_t part, void *out, size_t nbytes, uint64_t *count);
 /* Diagnostics: commits of this scene served by a refit (mrt_scene_update_mesh) since its last build.   */
 int mrt_debug_scene_refits(MRTScene scene, uint32_t *out);

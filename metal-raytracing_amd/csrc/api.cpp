@@ -1094,19 +1094,30 @@ int mrt_debug_read_wnodes(MRTScene scene, void *out, size_t nbytes, uint64_t *nu
     return MRT_OK;
     MRT_CATCH
 }
-// one array of the committed 8-wide layout as it lies in device memory (tests/bvh_audit.py decodes and checks every box)
+// one array of the committed layouts as it lies in device memory (tests/bvh_audit.py decodes and checks every box of the 8-wide layout, tests/rope_audit.py every node of the rope layout)
 int mrt_debug_read_layout(MRTScene scene, int32_t part, void *out, size_t nbytes, uint64_t *count) {
     MRT_TRY
     REQUIRE(scene && count, "mrt_debug_read_layout: bad argument");
-    REQUIRE(part >= 0 && part <= 7, "mrt_debug_read_layout: part must be 0 .. 7");
+    REQUIRE(part >= 0 && part <= 9, "mrt_debug_read_layout: part must be 0 .. 9");
     if (!scene->committed) { mrt::set_error("mrt_debug_read_layout: scene not committed"); return MRT_ERR_STATE; }
     const mrt::DeviceScene &d = scene->dev;
     const size_t npk = d.wpackets.p ? d.wpackets.n / mrt::WPK : 0, ninst = d.num_inst, nwt = (d.num_inst && d.wtlas_index.p) ? d.wtlas_index.n : 0;
     uint32_t header[8] = {d.num_wnodes, d.num_inst ? d.tlas_wcap : 0u, d.num_inst, (uint32_t)d.wide_depth, (uint32_t)npk, (uint32_t)d.blas_wdepth, (uint32_t)nwt, mrt::WPK};
     const size_t nrope = d.num_inst ? d.rope_nodes : 0, ntl = d.num_inst ? d.tlas_instances : 0;          // the rope TLAS of a two-level scene: its nodes and its index array
-    const size_t elem[8] = {16 * (size_t)mrt::WNODE_STRIDE, 16 * (size_t)mrt::WPK, sizeof(mrt::InstanceDev), 64, 4, 4, 64, 4};
-    const size_t n[8] = {d.num_wnodes, npk, ninst, ninst, nwt, 8, nrope, ntl};
-    const void *src[8] = {d.wnodes.p, d.wpackets.p, d.inst.p, d.inst_box.p, d.wtlas_index.p, header, d.nodes.p, d.tlas_index.p};
+    // the rope layout the traversal of traverse.h / traverse_instanced.h walks: the flattened scene's own (none when it was released: wide layout with rope = 0, the empty scene), or the BLASes' in bnodes
+    size_t rnodes = 0, rpackets = 0; const float4 *rn = nullptr, *rp = nullptr;
+    if (d.num_inst) {
+        for (const mrt::BlasRange &r : d.blas_ranges) rpackets += r.ntri;
+        rnodes = d.bpackets_offset / 4;
+        if (d.bnodes.p) { rn = d.bnodes.p; rp = d.bnodes.p + d.bpackets_offset; } else { rnodes = 0; rpackets = 0; }
+        if (4 * rnodes + 3 * rpackets > d.bnodes.n) { mrt::set_error("mrt_debug_read_layout: the BLAS ranges exceed bnodes"); return MRT_ERR_STATE; }
+    } else if (d.nodes.p && d.rope_nodes) {
+        rnodes = d.rope_nodes; rpackets = d.num_packets; rn = d.nodes.p; rp = d.nodes.p + d.packets_offset;
+        if (d.packets_offset < 4 * rnodes || d.packets_offset + 3 * rpackets > d.nodes.n) { mrt::set_error("mrt_debug_read_layout: the rope layout exceeds its allocation"); return MRT_ERR_STATE; }
+    }
+    const size_t elem[10] = {16 * (size_t)mrt::WNODE_STRIDE, 16 * (size_t)mrt::WPK, sizeof(mrt::InstanceDev), 64, 4, 4, 64, 4, 64, 48};
+    const size_t n[10] = {d.num_wnodes, npk, ninst, ninst, nwt, 8, nrope, ntl, rnodes, rpackets};
+    const void *src[10] = {d.wnodes.p, d.wpackets.p, d.inst.p, d.inst_box.p, d.wtlas_index.p, header, d.nodes.p, d.tlas_index.p, rn, rp};
     *count = n[part];
     if (out == nullptr) return MRT_OK;
     REQUIRE(nbytes == n[part] * elem[part], "mrt_debug_read_layout: nbytes must be count x the element size of the part");

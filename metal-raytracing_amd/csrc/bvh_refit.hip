@@ -120,7 +120,9 @@ __global__ void k_refit_wide_level(float4 *__restrict__ wnodes, const float4 *__
 // ------------------------------------------------------------------ refit of a rope layout (the BLASes of a two-level scene keep one: the query API and the in-place fallbacks walk it)
 // Same topology, new boxes: every internal node notes itself as its children's parent; then one thread per LEAF takes its box from its triangles' padded boxes (by the id each
 // packet carries) and climbs — the second thread to arrive at a node (a counter per node) unions the children's boxes and goes on.  The hand-off is k_refit's: 16-byte
-// write-through stores, drained before the agent-scope arrival, sc1 loads after it.  Escape links and near-child masks are the build's: order, not correctness.
+// write-through stores, drained before the agent-scope arrival, sc1 loads after it.  The near-child masks are the build's and only order the walk; the escape links are
+// the build's too and ARE correctness (a wrong link skips or repeats a subtree for the rays of one octant): the refit must write neither, it rewrites words 3 and 7 of a node
+// from the copy k_rope_prepare took and never touches words 8 .. 15 (tests/rope_audit.py links_kept).
 __global__ void k_rope_refit(float4 *nodes, uint32_t n, const float4 *__restrict__ packets, const float4 *__restrict__ tri_lo, const float4 *__restrict__ tri_hi,
                              const uint32_t *__restrict__ parent, const uint2 *__restrict__ ab /* per node: its {a, b} words, copied before the pass */, uint32_t *__restrict__ arrived,
                              const uint4 *__restrict__ tri_shade, const uint8_t *__restrict__ inst_dirty /* both or neither: a leaf none of whose triangles' instances moved keeps the box it has (the clipped boxes of pre-split references survive) */) {

@@ -378,12 +378,14 @@ class DeviceScene:
         check(lib.mrt_debug_stream_stats(self.handle, ptr(rays), rays.shape[0], 1 if any_hit else 0, per_wave, ptr(out), nw))
         return out
 
-    _LAYOUT_PARTS = {"wnodes": 0, "wpackets": 1, "instances": 2, "inst_box": 3, "wtlas_index": 4, "header": 5, "tlas_nodes": 6, "tlas_index": 7}
+    _LAYOUT_PARTS = {"wnodes": 0, "wpackets": 1, "instances": 2, "inst_box": 3, "wtlas_index": 4, "header": 5, "tlas_nodes": 6, "tlas_index": 7,
+                     "rope_nodes": 8, "rope_packets": 9}
 
     def read_layout(self, part):
-        """Diagnostics: one array of the committed 8-wide layout (mrt_debug_read_layout) as numpy — "wnodes" (n, 20) uint32, "wpackets" (n, 4 x stride)
+        """Diagnostics: one array of the committed layouts (mrt_debug_read_layout) as numpy — "wnodes" (n, 20) uint32, "wpackets" (n, 4 x stride)
         uint32, "instances" (n, 20) uint32 (InstanceDev), "inst_box" (n, 16) float32, "wtlas_index" (n,) uint32, "header" (8,) uint32,
-        "tlas_nodes" (n, 16) uint32 (the rope TLAS of a two-level scene), "tlas_index" (n,) uint32."""
+        "tlas_nodes" (n, 16) uint32 (the rope TLAS of a two-level scene), "tlas_index" (n,) uint32, "rope_nodes" (n, 16) uint32 (the rope layout of a
+        flattened scene, or every BLAS's of a two-level scene; n = 0 when the scene keeps none), "rope_packets" (n, 12) uint32 (its triangle packets)."""
         k = self._LAYOUT_PARTS[part] if isinstance(part, str) else int(part)
         n = C.c_uint64()
         check(lib.mrt_debug_read_layout(self.handle, k, None, 0, C.byref(n)))
@@ -392,7 +394,7 @@ class DeviceScene:
         elif k in (4, 7):
             out = np.zeros(n.value, np.uint32)
         else:
-            words = {0: 20, 2: 20, 3: 16, 6: 16}.get(k)
+            words = {0: 20, 2: 20, 3: 16, 6: 16, 8: 16, 9: 12}.get(k)
             if words is None:
                 hdr = self.read_layout(5)
                 words = 4 * int(hdr[7])

@@ -23,6 +23,10 @@ Checks (names as in Report.margins):
   world_box   the world box contains the exact image, under M' (the float64 inverse of the stored float32 w2o rows), of the object box grown by the
               rounding bound of the device's fma chain: delta_k = gamma_4 (sum_j |R_kj| max|X_j| + |w_k|), X over the world box.
 Margins are reported in float32 ulps of the coordinate and as a fraction of the pad.
+
+Which layout: this audit covers the 8-wide layout only (wnodes / wpackets, the 8-wide TLAS slots, inst_box).  The rope layout — the 64-byte binary nodes
+with escape links of a flattened scene built with rope = 1 or wide = 0, and of every BLAS — is audited by rope_audit.py, which imports Report, pad_of,
+the packet decoding and check_split from here; the rope TLAS's links are checked by tlas_resort_reference.py.
 """
 import numpy as np
 
@@ -205,6 +209,57 @@ def _clip_extent(v, axis, a, b):
     return P.min(0), P.max(0)
 
 
+def check_split(rep, g, refs, v, lo, hi, chain, name):
+    """One pre-split triangle g (exact vertices v) whose references are the packets refs with the leaf boxes lo / hi (one row per reference): ordered along
+    some axis the boxes cover the triangle's extent there without a gap, and the triangle clipped to each reference's share of that axis lies inside every
+    box of chain(j) — (tag, lo, hi) of reference j's leaf box and whatever encloses it — within 1e-12 relative.  name(tag) words a box for the messages.
+    Shared by the audits of both layouts (the 8-wide one here, the rope one in rope_audit.py)."""
+    tl_, th_ = v.min(0), v.max(0)
+    scale = max(1.0, float(np.abs(v).max()))
+    tol = 1e-12 * scale
+    best = None
+    for ax in range(3):
+        o = np.argsort(lo[:, ax], kind="stable")
+        L, H = lo[o, ax], hi[o, ax]
+        if L[0] > tl_[ax] + tol or H.max() < th_[ax] - tol:
+            continue
+        cuts = [tl_[ax]]
+        ok = True
+        for k in range(len(o) - 1):
+            reach = H[:k + 1].max()
+            if reach < L[k + 1] - tol and reach < th_[ax]:
+                ok = False; break
+            cuts.append(min(max(0.5 * (min(H[k], reach) + L[k + 1]), cuts[-1]), th_[ax]))
+        cuts.append(th_[ax])
+        if not ok:
+            continue
+        worst, where = np.inf, None
+        for k, j in enumerate(o):
+            a, b = cuts[k], cuts[k + 1]
+            if b < a:
+                continue
+            ext = _clip_extent(v, ax, a, b)
+            if ext is None:
+                continue
+            r = refs[j]
+            for tag, blo, bhi in chain(j):
+                mm = np.minimum(ext[0] - blo, bhi - ext[1])
+                mm[ax] = min(a - blo[ax], bhi[ax] - b)
+                if mm.min() < worst:
+                    worst, where = float(mm.min()), (r, tag, int(np.argmin(mm)))
+        if best is None or worst > best[0]:
+            best = (worst, where, ax)
+    if best is None:
+        rep.fail(f"split: triangle {g}: its {len(refs)} references leave a gap along every axis"); return
+    worst, where, ax = best
+    if worst < -tol:
+        r, tag, a = where
+        rep.fail(f"split: triangle {g} clipped to reference packet {r}'s share of axis {'xyz'[ax]} leaves {name(tag)} on axis {'xyz'[a]} by {-worst:.3e}")
+    elif where is not None:
+        a = where[2]
+        rep.note("split", worst, worst / ulp_of(scale), worst / pad_of(scale), f"triangle {g} packet {where[0]} {name(where[1])} axis {'xyz'[a]}")
+
+
 def audit(lay, presplit=False, num_tris=None, check_pad=True):
     """Audit one layout (layout_of).  presplit: the scene was built with pre-splitting allowed (flattened scenes only; BLASes never are).
     num_tris: triangles of a flattened scene (every id 0 .. num_tris - 1 must be referenced)."""
@@ -339,52 +394,9 @@ def audit(lay, presplit=False, num_tris=None, check_pad=True):
         for g, b0, b1 in zip(split_ids, *bounds):
             refs = order[b0:b1]
             refs = refs[pk_leaf[refs, 0] >= 0]
-            v = V[refs[0]]
             lo = np.array([D["lo"][pk_leaf[r, 0], pk_leaf[r, 1]] for r in refs]); hi = np.array([D["hi"][pk_leaf[r, 0], pk_leaf[r, 1]] for r in refs])
-            tl_, th_ = v.min(0), v.max(0)
-            scale = max(1.0, float(np.abs(v).max()))
-            tol = 1e-12 * scale
-            best = None
-            for ax in range(3):
-                o = np.argsort(lo[:, ax], kind="stable")
-                L, H = lo[o, ax], hi[o, ax]
-                if L[0] > tl_[ax] + tol or H.max() < th_[ax] - tol:
-                    continue
-                cuts = [tl_[ax]]
-                ok = True
-                for k in range(len(o) - 1):
-                    reach = H[:k + 1].max()
-                    if reach < L[k + 1] - tol and reach < th_[ax]:
-                        ok = False; break
-                    cuts.append(min(max(0.5 * (min(H[k], reach) + L[k + 1]), cuts[-1]), th_[ax]))
-                cuts.append(th_[ax])
-                if not ok:
-                    continue
-                worst, where = np.inf, None
-                for k, j in enumerate(o):
-                    a, b = cuts[k], cuts[k + 1]
-                    if b < a:
-                        continue
-                    ext = _clip_extent(v, ax, a, b)
-                    if ext is None:
-                        continue
-                    r = refs[j]
-                    for nd, sl, blo, bhi in _chain_boxes(D, parent, pk_leaf[r, 0], pk_leaf[r, 1]):
-                        mm = np.minimum(ext[0] - blo, bhi - ext[1])
-                        mm[ax] = min(a - blo[ax], bhi[ax] - b)
-                        if mm.min() < worst:
-                            worst, where = float(mm.min()), (r, nd, sl, int(np.argmin(mm)))
-                if best is None or worst > best[0]:
-                    best = (worst, where, ax)
-            if best is None:
-                rep.fail(f"split: triangle {g}: its {len(refs)} references leave a gap along every axis"); continue
-            worst, where, ax = best
-            if worst < -tol:
-                r, nd, sl, a = where
-                rep.fail(f"split: triangle {g} clipped to reference packet {r}'s share of axis {'xyz'[ax]} leaves node {nd} slot {sl} on axis {'xyz'[a]} by {-worst:.3e}")
-            elif where is not None:
-                a = where[3]
-                rep.note("split", worst, worst / ulp_of(scale), worst / pad_of(scale), f"triangle {g} packet {where[0]} node {where[1]} slot {where[2]} axis {'xyz'[a]}")
+            check_split(rep, g, refs, V[refs[0]], lo, hi, lambda j: (((nd, sl), blo, bhi) for nd, sl, blo, bhi in _chain_boxes(D, parent, pk_leaf[refs[j], 0], pk_leaf[refs[j], 1])),
+                        lambda tag: f"node {tag[0]} slot {tag[1]}")
     # ---- TLAS
     if two:
         for i, (nd, sl) in tl_leaf.items():
