@@ -146,6 +146,29 @@ static bool all_finite(const float *p, size_t stride_bytes, size_t n, int comps)
     }
     return bad == 0;
 }
+static void mark_changed(MRTScene scene) { scene->committed = false; scene->only_transforms_changed = false; scene->only_vertices_changed = false; }      // a mesh, a submesh or an option changed: the next commit builds
+static void grow_stage(MRTScene scene, size_t bytes) {          // the pinned staging area of the commit's uploads (see mrt_mesh_add_submesh)
+    scene->stage_need += bytes;
+    if (scene->stage_need > scene->dev.stage.cap && bind_device(scene->ctx) == MRT_OK) { if (scene->dev.stage.reserve(std::max(scene->stage_need, 2 * scene->dev.stage.cap)) != hipSuccess) (void)hipGetLastError(); }
+}
+// nverts rows of positions and normals, any multiple of 4 bytes apart, into a mesh's packed arrays
+static void copy_vertex_rows(mrt::HostMesh &m, const float *positions, size_t pos_stride, const float *normals, size_t nrm_stride, size_t nverts) {
+    for (size_t i = 0; i < nverts; i++) {
+        const float *p = (const float *)((const char *)positions + i * pos_stride);
+        const float *n = (const float *)((const char *)normals + i * nrm_stride);
+        for (int k = 0; k < 3; k++) { m.positions[i * 3 + k] = p[k]; m.normals[i * 3 + k] = n[k]; }
+    }
+}
+// What mrt_scene_update_mesh, _update_mesh_device and _update_blas_device ask of their rows, in this order: the mesh exists, the strides, the buffers' alignment (device_ptrs: the two device pointers, or null for host arrays, which may lie anywhere), the mesh has vertices of its own, and as many as before.
+static int check_vertex_rows(const char *who, MRTScene scene, int32_t mesh_id, size_t pos_stride, size_t nrm_stride, size_t nverts, const void *const *device_ptrs) {
+    REQUIRE(mesh_id >= 0 && (size_t)mesh_id < scene->meshes.size(), std::string(who) + ": mesh_id out of range");
+    REQUIRE(pos_stride >= 12 && nrm_stride >= 12 && pos_stride % 4 == 0 && nrm_stride % 4 == 0, std::string(who) + ": strides must be multiples of 4 and >= 12");
+    REQUIRE(!device_ptrs || ((uintptr_t)device_ptrs[0] % 4 == 0 && (uintptr_t)device_ptrs[1] % 4 == 0), std::string(who) + ": buffers must be 4-byte aligned");
+    const mrt::HostMesh &m = scene->meshes[(size_t)mesh_id];
+    REQUIRE(m.source < 0, std::string(who) + ": an instance has no vertices of its own (update its source mesh)");
+    REQUIRE(nverts * 3 == m.positions.size(), std::string(who) + ": the vertex count must stay the same (the topology is kept)");
+    return MRT_OK;
+}
 int mrt_scene_add_mesh(MRTScene scene, const float *positions, size_t pos_stride, const float *normals, size_t nrm_stride,
                        size_t nverts, const float *xf, int32_t *mesh_id) {
     MRT_TRY
@@ -157,15 +180,11 @@ int mrt_scene_add_mesh(MRTScene scene, const float *positions, size_t pos_stride
     REQUIRE(nverts == 0 || (all_finite(positions, pos_stride, nverts, 3) && all_finite(normals, nrm_stride, nverts, 3)), "mrt_scene_add_mesh: a position or a normal is NaN or infinite");
     mrt::HostMesh m;
     m.positions.resize(nverts * 3); m.normals.resize(nverts * 3);
-    for (size_t i = 0; i < nverts; i++) {
-        const float *p = (const float *)((const char *)positions + i * pos_stride);
-        const float *n = (const float *)((const char *)normals + i * nrm_stride);
-        for (int k = 0; k < 3; k++) { m.positions[i * 3 + k] = p[k]; m.normals[i * 3 + k] = n[k]; }
-    }
+    copy_vertex_rows(m, positions, pos_stride, normals, nrm_stride, nverts);
     memcpy(m.xf, xf, 64);
     m.xf[3] = m.xf[7] = m.xf[11] = 0.0f; m.xf[15] = 1.0f;              // matrix4x4_drop_last_row (Utilities.swift:92-101)
     scene->meshes.push_back(std::move(m));
-    scene->committed = false; scene->only_transforms_changed = false; scene->only_vertices_changed = false;
+    mark_changed(scene);
     if (mesh_id) *mesh_id = (int32_t)scene->meshes.size() - 1;
     return MRT_OK;
     MRT_CATCH
@@ -183,14 +202,13 @@ int mrt_scene_add_instance(MRTScene scene, int32_t source_mesh_id, const float *
     m.xf[3] = m.xf[7] = m.xf[11] = 0.0f; m.xf[15] = 1.0f;
     const int geometry_of = m.source;
     scene->meshes.push_back(std::move(m));
-    scene->committed = false; scene->only_transforms_changed = false; scene->only_vertices_changed = false;
+    mark_changed(scene);
     if (mesh_id) *mesh_id = (int32_t)scene->meshes.size() - 1;
     if (!scene->opt.instancing) {           // a flattened scene stages a copy of the source's geometry per instance: the pinned area grows here (see mrt_mesh_add_submesh)
         const mrt::HostMesh &g = scene->meshes[geometry_of];
         size_t bytes = g.positions.size() / 3 * 28 + 4096;
         for (auto &ix : g.sub_indices) bytes += ix.size() * 4;
-        scene->stage_need += bytes;
-        if (scene->stage_need > scene->dev.stage.cap && bind_device(scene->ctx) == MRT_OK) { if (scene->dev.stage.reserve(std::max(scene->stage_need, 2 * scene->dev.stage.cap)) != hipSuccess) (void)hipGetLastError(); }
+        grow_stage(scene, bytes);
     }
     return MRT_OK;
     MRT_CATCH
@@ -207,14 +225,11 @@ int mrt_mesh_add_submesh(MRTScene scene, int32_t mesh_id, const uint32_t *indice
     for (size_t i = 0; i < ntris * 3; i++) REQUIRE(indices[i] < nv, "mrt_mesh_add_submesh: vertex index out of range");
     m.sub_indices.emplace_back(indices, indices + ntris * 3);
     m.sub_materials.push_back(*material);
-    scene->committed = false; scene->only_transforms_changed = false; scene->only_vertices_changed = false;
+    mark_changed(scene);
     if (geometry_id) *geometry_id = (int32_t)m.sub_indices.size() - 1;
     // the pinned staging area the commit uploads from grows HERE, as the geometry is handed over (by doubling: a handful of allocations whatever the mesh count), not inside
     // mrt_scene_commit: pinning 25 MB is ~1.1 ms, a fifth of DragonScene's commit.  Flattened scenes stage every instance's copy; a failure here is not an error (the commit retries).
-    if (!scene->opt.instancing || m.source < 0) {
-        scene->stage_need += ntris * 12 + (m.sub_indices.size() == 1 ? nv * 28 : 0) + 4096;
-        if (scene->stage_need > scene->dev.stage.cap && bind_device(scene->ctx) == MRT_OK) { if (scene->dev.stage.reserve(std::max(scene->stage_need, 2 * scene->dev.stage.cap)) != hipSuccess) (void)hipGetLastError(); }
-    }
+    if (!scene->opt.instancing || m.source < 0) grow_stage(scene, ntris * 12 + (m.sub_indices.size() == 1 ? nv * 28 : 0) + 4096);
     return MRT_OK;
     MRT_CATCH
 }
@@ -262,7 +277,7 @@ int mrt_scene_set_option(MRTScene scene, const char *key, double value) {
     else if (k == "refit_max_cost_ratio") { REQUIRE(value == 0 || value >= 1, "refit_max_cost_ratio must be 0 (off) or >= 1"); scene->opt.refit_max_cost_ratio = (float)value; }
     else if (k == "ploc_radius") { REQUIRE(value >= 1 && value <= 256, "ploc_radius must be in [1,256]"); scene->opt.ploc_radius = (int)value; }
     else { mrt::set_error("mrt_scene_set_option: unknown key " + k); return MRT_ERR_INVALID_ARGUMENT; }
-    scene->committed = false; scene->only_transforms_changed = false; scene->only_vertices_changed = false;
+    mark_changed(scene);
     return MRT_OK;
     MRT_CATCH
 }
@@ -294,17 +309,10 @@ int mrt_scene_commit(MRTScene scene) {
 int mrt_scene_update_mesh(MRTScene scene, int32_t mesh_id, const float *positions, size_t pos_stride, const float *normals, size_t nrm_stride, size_t nverts) {
     MRT_TRY
     REQUIRE(scene && positions && normals, "mrt_scene_update_mesh: bad argument");
-    REQUIRE(mesh_id >= 0 && (size_t)mesh_id < scene->meshes.size(), "mrt_scene_update_mesh: mesh_id out of range");
-    REQUIRE(pos_stride >= 12 && nrm_stride >= 12 && pos_stride % 4 == 0 && nrm_stride % 4 == 0, "mrt_scene_update_mesh: strides must be multiples of 4 and >= 12");
+    if (int rc = check_vertex_rows("mrt_scene_update_mesh", scene, mesh_id, pos_stride, nrm_stride, nverts, nullptr)) return rc;
     mrt::HostMesh &m = scene->meshes[(size_t)mesh_id];
-    REQUIRE(m.source < 0, "mrt_scene_update_mesh: an instance has no vertices of its own (update its source mesh)");
-    REQUIRE(nverts * 3 == m.positions.size(), "mrt_scene_update_mesh: the vertex count must stay the same (the topology is kept)");
     REQUIRE(all_finite(positions, pos_stride, nverts, 3) && all_finite(normals, nrm_stride, nverts, 3), "mrt_scene_update_mesh: a position or a normal is NaN or infinite (the mesh keeps what it had)");
-    for (size_t i = 0; i < nverts; i++) {
-        const float *p = (const float *)((const char *)positions + i * pos_stride);
-        const float *n = (const float *)((const char *)normals + i * nrm_stride);
-        for (int k = 0; k < 3; k++) { m.positions[i * 3 + k] = p[k]; m.normals[i * 3 + k] = n[k]; }
-    }
+    copy_vertex_rows(m, positions, pos_stride, normals, nrm_stride, nverts);
     if (scene->dev.refit_ws && (size_t)mesh_id < scene->dev.refit_ws->host_stale.size()) scene->dev.refit_ws->host_stale[(size_t)mesh_id] = 0;      // (replaced on the device before: this copy is the newer one now)
     if (scene->dev.blas_ws && (size_t)mesh_id < scene->dev.blas_ws->blas_of_mesh.size() && scene->dev.blas_ws->blas_of_mesh[(size_t)mesh_id] >= 0) scene->dev.blas_ws->host_stale[(size_t)scene->dev.blas_ws->blas_of_mesh[(size_t)mesh_id]] = 0;
     // a committed scene in which nothing else changes until the next commit keeps its tree: that commit refits (flattened scenes with the 8-wide layout; others build again)
@@ -335,13 +343,11 @@ int mrt_scene_set_instance_transform(MRTScene scene, int32_t mesh_id, const floa
 int mrt_scene_stats(MRTScene scene, MRTSceneStats *out) {
     REQUIRE(scene && out, "mrt_scene_stats: bad argument");
     if (!scene->committed) { mrt::set_error("mrt_scene_stats: scene not committed"); return MRT_ERR_STATE; }
-    if (scene->dev.refit_ws && scene->dev.refit_ws->unresolved) {          // refits enqueued by mrt_scene_refit_device: wait for the last one and read what it left (the only place this blocks)
+    // refits enqueued by mrt_scene_refit_device or by mrt_scene_refit_blas_device: wait for the last one and read what it left (the only place this blocks)
+    const bool unresolved[2] = {scene->dev.refit_ws && scene->dev.refit_ws->unresolved, scene->dev.blas_ws && scene->dev.blas_ws->unresolved};
+    for (int k = 0; k < 2; k++) if (unresolved[k]) {
         int rc = bind_device(scene->ctx); if (rc) return rc;
-        rc = mrt::resolve_device_refits(scene->dev, scene->opt, scene->ctx->stream); if (rc) return rc;
-    }
-    if (scene->dev.blas_ws && scene->dev.blas_ws->unresolved) {          // ... or by mrt_scene_refit_blas_device
-        int rc = bind_device(scene->ctx); if (rc) return rc;
-        rc = mrt::resolve_blas_refits(scene->dev, scene->opt, scene->ctx->stream); if (rc) return rc;
+        rc = (k == 0 ? mrt::resolve_device_refits : mrt::resolve_blas_refits)(scene->dev, scene->opt, scene->ctx->stream); if (rc) return rc;
     }
     *out = scene->dev.stats;
     out->wide_layout = scene->dev.num_wnodes > 0 ? 1 : 0; out->wide_depth = scene->dev.wide_depth;
@@ -390,53 +396,47 @@ int mrt_scene_intersect_any_device(MRTScene scene, const void *d_rays, size_t n,
     MRT_CATCH
 }
 
-// The stream-ordered refit: vertices from device buffers, the refit kernels on the caller's stream (0 = HIP's null stream), nothing of the host in between.
-static int device_refit_prologue(const char *who, MRTScene scene) {
+// The three families of stream-ordered updates (§10d - §10f) look at the scene before anything else: it exists, it is committed, nothing the host changed waits for a commit.  The family's *_supported call and bind_device follow at the call site.
+static int device_entry_prologue(const char *who, MRTScene scene) {
     if (!scene) { mrt::set_error(std::string(who) + ": scene is NULL"); return MRT_ERR_INVALID_ARGUMENT; }
     if (!scene->committed) {
         mrt::set_error(std::string(who) + (scene->only_vertices_changed || scene->only_transforms_changed ? ": host-side changes are pending (mrt_scene_commit first)" : ": scene not committed"));
         return MRT_ERR_STATE;
     }
-    if (int rc = mrt::device_refit_supported(scene->dev, scene->opt, who)) return rc;
-    return bind_device(scene->ctx);
+    return MRT_OK;
 }
+// The stream-ordered refit: vertices from device buffers, the refit kernels on the caller's stream (0 = HIP's null stream), nothing of the host in between.
 int mrt_scene_update_mesh_device(MRTScene scene, int32_t mesh_id, const void *d_positions, size_t pos_stride, const void *d_normals, size_t nrm_stride, size_t nverts, void *hip_stream) {
     MRT_TRY
     const char *who = "mrt_scene_update_mesh_device";
-    if (int rc = device_refit_prologue(who, scene)) return rc;
+    if (int rc = device_entry_prologue(who, scene)) return rc;
+    if (int rc = mrt::device_refit_supported(scene->dev, scene->opt, who)) return rc;
+    if (int rc = bind_device(scene->ctx)) return rc;
     REQUIRE(d_positions && d_normals, "mrt_scene_update_mesh_device: NULL buffers");
-    REQUIRE(mesh_id >= 0 && (size_t)mesh_id < scene->meshes.size(), "mrt_scene_update_mesh_device: mesh_id out of range");
-    REQUIRE(pos_stride >= 12 && nrm_stride >= 12 && pos_stride % 4 == 0 && nrm_stride % 4 == 0, "mrt_scene_update_mesh_device: strides must be multiples of 4 and >= 12");
-    REQUIRE((uintptr_t)d_positions % 4 == 0 && (uintptr_t)d_normals % 4 == 0, "mrt_scene_update_mesh_device: buffers must be 4-byte aligned");
-    const mrt::HostMesh &m = scene->meshes[(size_t)mesh_id];
-    REQUIRE(m.source < 0, "mrt_scene_update_mesh_device: an instance has no vertices of its own (update its source mesh)");
-    REQUIRE(nverts * 3 == m.positions.size(), "mrt_scene_update_mesh_device: the vertex count must stay the same (the topology is kept)");
+    const void *const rows[2] = {d_positions, d_normals};
+    if (int rc = check_vertex_rows(who, scene, mesh_id, pos_stride, nrm_stride, nverts, rows)) return rc;
     if (int rc = mrt::device_refit_prepare(scene->meshes, scene->opt, scene->dev)) return rc;          // (the first call after a build allocates the workspace; later ones find it)
     return mrt::device_update_mesh(scene->dev, (size_t)mesh_id, d_positions, pos_stride, d_normals, nrm_stride, nverts, (hipStream_t)hip_stream);
     MRT_CATCH
 }
 int mrt_scene_refit_device(MRTScene scene, void *hip_stream) {
     MRT_TRY
-    if (int rc = device_refit_prologue("mrt_scene_refit_device", scene)) return rc;
+    const char *who = "mrt_scene_refit_device";
+    if (int rc = device_entry_prologue(who, scene)) return rc;
+    if (int rc = mrt::device_refit_supported(scene->dev, scene->opt, who)) return rc;
+    if (int rc = bind_device(scene->ctx)) return rc;
     if (int rc = mrt::device_refit_prepare(scene->meshes, scene->opt, scene->dev)) return rc;
     return mrt::device_refit(scene->dev, (hipStream_t)hip_stream);
     MRT_CATCH
 }
 
 // Instances of a two-level scene moved from device buffers (tlas_refit.hip)
-static int device_instances_prologue(const char *who, MRTScene scene) {
-    if (!scene) { mrt::set_error(std::string(who) + ": scene is NULL"); return MRT_ERR_INVALID_ARGUMENT; }
-    if (!scene->committed) {
-        mrt::set_error(std::string(who) + (scene->only_vertices_changed || scene->only_transforms_changed ? ": host-side changes are pending (mrt_scene_commit first)" : ": scene not committed"));
-        return MRT_ERR_STATE;
-    }
-    if (int rc = mrt::instances_device_supported(scene->dev, scene->opt, who)) return rc;
-    return bind_device(scene->ctx);
-}
 int mrt_scene_set_instance_transforms_device(MRTScene scene, int32_t first_mesh_id, size_t count, const void *d_transforms, size_t stride_bytes, void *hip_stream) {
     MRT_TRY
     const char *who = "mrt_scene_set_instance_transforms_device";
-    if (int rc = device_instances_prologue(who, scene)) return rc;
+    if (int rc = device_entry_prologue(who, scene)) return rc;
+    if (int rc = mrt::instances_device_supported(scene->dev, scene->opt, who)) return rc;
+    if (int rc = bind_device(scene->ctx)) return rc;
     REQUIRE(first_mesh_id >= 0 && (size_t)first_mesh_id <= scene->dev.in_tlas.size() && count <= scene->dev.in_tlas.size() - (size_t)first_mesh_id, "mrt_scene_set_instance_transforms_device: mesh ids out of range");
     if (count == 0) return MRT_OK;
     REQUIRE(d_transforms, "mrt_scene_set_instance_transforms_device: NULL buffer");
@@ -453,7 +453,10 @@ int mrt_scene_set_instance_transforms_device(MRTScene scene, int32_t first_mesh_
 }
 int mrt_scene_refit_instances_device(MRTScene scene, void *hip_stream) {
     MRT_TRY
-    if (int rc = device_instances_prologue("mrt_scene_refit_instances_device", scene)) return rc;
+    const char *who = "mrt_scene_refit_instances_device";
+    if (int rc = device_entry_prologue(who, scene)) return rc;
+    if (int rc = mrt::instances_device_supported(scene->dev, scene->opt, who)) return rc;
+    if (int rc = bind_device(scene->ctx)) return rc;
     if (int rc = mrt::instances_device_prepare(scene->dev)) return rc;
     return mrt::device_refit_instances(scene->dev, (hipStream_t)hip_stream);
     MRT_CATCH
@@ -461,7 +464,9 @@ int mrt_scene_refit_instances_device(MRTScene scene, void *hip_stream) {
 int mrt_scene_rebuild_tlas_device(MRTScene scene, void *hip_stream) {
     MRT_TRY
     const char *who = "mrt_scene_rebuild_tlas_device";
-    if (int rc = device_instances_prologue(who, scene)) return rc;
+    if (int rc = device_entry_prologue(who, scene)) return rc;
+    if (int rc = mrt::instances_device_supported(scene->dev, scene->opt, who)) return rc;
+    if (int rc = bind_device(scene->ctx)) return rc;
     if (int rc = mrt::tlas_rebuild_supported(scene->dev, who)) return rc;
     if (int rc = mrt::instances_device_prepare(scene->dev)) return rc;          // (the first call after a commit allocates the workspace; later ones find it)
     return mrt::device_rebuild_tlas(scene->dev, (hipStream_t)hip_stream);
@@ -469,26 +474,15 @@ int mrt_scene_rebuild_tlas_device(MRTScene scene, void *hip_stream) {
 }
 
 // Meshes of a two-level scene deformed from device buffers (bvh_refit.hip, tlas_refit.hip)
-static int device_blas_prologue(const char *who, MRTScene scene) {
-    if (!scene) { mrt::set_error(std::string(who) + ": scene is NULL"); return MRT_ERR_INVALID_ARGUMENT; }
-    if (!scene->committed) {
-        mrt::set_error(std::string(who) + (scene->only_vertices_changed || scene->only_transforms_changed ? ": host-side changes are pending (mrt_scene_commit first)" : ": scene not committed"));
-        return MRT_ERR_STATE;
-    }
-    if (int rc = mrt::blas_device_supported(scene->dev, scene->opt, scene->meshes.size(), who)) return rc;
-    return bind_device(scene->ctx);
-}
 int mrt_scene_update_blas_device(MRTScene scene, int32_t mesh_id, const void *d_positions, size_t pos_stride, const void *d_normals, size_t nrm_stride, size_t nverts, void *hip_stream) {
     MRT_TRY
     const char *who = "mrt_scene_update_blas_device";
-    if (int rc = device_blas_prologue(who, scene)) return rc;
+    if (int rc = device_entry_prologue(who, scene)) return rc;
+    if (int rc = mrt::blas_device_supported(scene->dev, scene->opt, scene->meshes.size(), who)) return rc;
+    if (int rc = bind_device(scene->ctx)) return rc;
     REQUIRE(d_positions && d_normals, "mrt_scene_update_blas_device: NULL buffers");
-    REQUIRE(mesh_id >= 0 && (size_t)mesh_id < scene->meshes.size(), "mrt_scene_update_blas_device: mesh_id out of range");
-    REQUIRE(pos_stride >= 12 && nrm_stride >= 12 && pos_stride % 4 == 0 && nrm_stride % 4 == 0, "mrt_scene_update_blas_device: strides must be multiples of 4 and >= 12");
-    REQUIRE((uintptr_t)d_positions % 4 == 0 && (uintptr_t)d_normals % 4 == 0, "mrt_scene_update_blas_device: buffers must be 4-byte aligned");
-    const mrt::HostMesh &m = scene->meshes[(size_t)mesh_id];
-    REQUIRE(m.source < 0, "mrt_scene_update_blas_device: an instance has no vertices of its own (update its source mesh)");
-    REQUIRE(nverts * 3 == m.positions.size(), "mrt_scene_update_blas_device: the vertex count must stay the same (the topology is kept)");
+    const void *const rows[2] = {d_positions, d_normals};
+    if (int rc = check_vertex_rows(who, scene, mesh_id, pos_stride, nrm_stride, nverts, rows)) return rc;
     size_t b = 0;
     while (b < scene->dev.blas_ranges.size() && scene->dev.blas_ranges[b].src_mesh != (uint32_t)mesh_id) b++;
     if (b == scene->dev.blas_ranges.size() || !mrt::blas_refittable(scene->dev.blas_ranges[b], nverts) || scene->dev.blas_ranges[b].ntri == 0) {
@@ -502,7 +496,9 @@ int mrt_scene_update_blas_device(MRTScene scene, int32_t mesh_id, const void *d_
 int mrt_scene_refit_blas_device(MRTScene scene, void *hip_stream) {
     MRT_TRY
     const char *who = "mrt_scene_refit_blas_device";
-    if (int rc = device_blas_prologue(who, scene)) return rc;
+    if (int rc = device_entry_prologue(who, scene)) return rc;
+    if (int rc = mrt::blas_device_supported(scene->dev, scene->opt, scene->meshes.size(), who)) return rc;
+    if (int rc = bind_device(scene->ctx)) return rc;
     if (int rc = mrt::instances_device_supported(scene->dev, scene->opt, who)) return rc;          // (its last step is the TLAS refit of §10e)
     if (int rc = mrt::blas_device_prepare(scene->meshes, scene->dev)) return rc;
     if (int rc = mrt::instances_device_prepare(scene->dev)) return rc;
@@ -564,6 +560,17 @@ int mrt_scene_vertex_offsets(MRTScene scene, uint64_t *offsets, size_t count) {
 }
 
 // What follows a surface, on the caller's stream (stages.hip).  Plain arguments first, as the surface entries: a refusal of theirs needs no device.
+// What the two scatter entries share once their own buffers and bounce counts have passed (those come first, in each entry's order): light_count as a plain argument, the scene (surface_prologue), its lights, the exit for n = 0 (*done, with MRT_OK) and the device.
+static int scatter_prologue(const char *who, MRTScene scene, size_t n, int32_t light_count, bool *done) {
+    *done = true;
+    REQUIRE(light_count >= 0, std::string(who) + ": light_count must be >= 0 (0 = every light of the scene)");
+    if (int rc = surface_prologue(who, scene, n)) return rc;
+    REQUIRE(light_count <= scene->dev.light_count, std::string(who) + ": light_count is above the number of lights of the scene");
+    if (scene->dev.light_count < 1) { mrt::set_error(std::string(who) + ": scene has no lights (lightCount must be >= 1, Raytracing.metal:273)"); return MRT_ERR_STATE; }
+    if (n == 0) return MRT_OK;
+    *done = false;
+    return bind_device(scene->ctx);
+}
 int mrt_scene_scatter_device(MRTScene scene, const void *d_surfaces, const void *d_halton_index, size_t n, int32_t bounce, int32_t light_count, void *d_shadow_rays, void *d_light,
                              void *d_next_rays, void *hip_stream) {
     MRT_TRY
@@ -573,12 +580,8 @@ int mrt_scene_scatter_device(MRTScene scene, const void *d_surfaces, const void 
             "mrt_scene_scatter_device: d_surfaces, d_shadow_rays, d_light and d_next_rays must be 16-byte aligned");
     REQUIRE((uintptr_t)d_halton_index % 4 == 0, "mrt_scene_scatter_device: d_halton_index must be 4-byte aligned");
     REQUIRE(bounce >= 0 && bounce <= 18, "mrt_scene_scatter_device: bounce must be in [0, 18] (Halton dimensions 2 + 5 * bounce .. + 4 of a table of 100 primes)");
-    REQUIRE(light_count >= 0, "mrt_scene_scatter_device: light_count must be >= 0 (0 = every light of the scene)");
-    if (int rc = surface_prologue(who, scene, n)) return rc;
-    REQUIRE(light_count <= scene->dev.light_count, "mrt_scene_scatter_device: light_count is above the number of lights of the scene");
-    if (scene->dev.light_count < 1) { mrt::set_error("mrt_scene_scatter_device: scene has no lights (lightCount must be >= 1, Raytracing.metal:273)"); return MRT_ERR_STATE; }
-    if (n == 0) return MRT_OK;
-    if (int rc = bind_device(scene->ctx)) return rc;
+    bool done = false;
+    if (const int rc = scatter_prologue(who, scene, n, light_count, &done); rc || done) return rc;
     return mrt::scatter_device(scene->dev, (hipStream_t)hip_stream, d_surfaces, d_halton_index, n, bounce, light_count > 0 ? light_count : scene->dev.light_count, d_shadow_rays, d_light, d_next_rays);
     MRT_CATCH
 }
@@ -595,12 +598,8 @@ int mrt_scene_scatter_materials_device(MRTScene scene, const void *d_rays, const
     REQUIRE((uintptr_t)d_halton_index % 4 == 0, "mrt_scene_scatter_materials_device: d_halton_index must be 4-byte aligned");
     REQUIRE(max_bounces >= 1 && max_bounces <= 16, "mrt_scene_scatter_materials_device: max_bounces must be in [1, 16] (the lobe choice uses Halton dimension 2 + 5 * max_bounces + bounce of a table of 100 primes)");
     REQUIRE(bounce >= 0 && bounce < max_bounces, "mrt_scene_scatter_materials_device: bounce must be in [0, max_bounces)");
-    REQUIRE(light_count >= 0, "mrt_scene_scatter_materials_device: light_count must be >= 0 (0 = every light of the scene)");
-    if (int rc = surface_prologue(who, scene, n)) return rc;
-    REQUIRE(light_count <= scene->dev.light_count, "mrt_scene_scatter_materials_device: light_count is above the number of lights of the scene");
-    if (scene->dev.light_count < 1) { mrt::set_error("mrt_scene_scatter_materials_device: scene has no lights (lightCount must be >= 1, Raytracing.metal:273)"); return MRT_ERR_STATE; }
-    if (n == 0) return MRT_OK;
-    if (int rc = bind_device(scene->ctx)) return rc;
+    bool done = false;
+    if (const int rc = scatter_prologue(who, scene, n, light_count, &done); rc || done) return rc;
     return mrt::scatter_materials_device(scene->dev, (hipStream_t)hip_stream, d_rays, d_surfaces, d_halton_index, n, bounce, max_bounces, light_count > 0 ? light_count : scene->dev.light_count,
                                          d_shadow_rays, d_light, d_next_rays, d_lobes);
     MRT_CATCH

@@ -1087,16 +1087,14 @@ struct FlatBuild {
         for (size_t mi = 0; mi < I; mi++) h_dirty[mi] = refs[mi].g->dirty ? 1 : 0;
         MRT_HIP(hipMemcpyAsync(inst_dirty.p, h_dirty.data(), h_dirty.size(), hipMemcpyHostToDevice, stream));
         const std::vector<uint32_t> first = level_first(out.wide_levels, 0u);
-        RefitTarget tg;
-        tg.packets = out.num_packets; tg.tri_shade = out.tri_shade.p; tg.dirty = inst_dirty.p;
-        if (there.wide) { tg.wnodes = out.wnodes.p; tg.wpackets = out.wpackets.p; tg.level_first = first.data(); tg.level_count = out.wide_levels.data(); tg.levels = out.wide_levels.size(); }
         DevBuf<uint32_t> rparent, arrived; DevBuf<uint2> ab;
         if (there.rope) {          // [r6] the rope layout beside it (rope = 1) or alone (wide = 0)
             MRT_HIP(rparent.alloc_in(arena, out.rope_nodes)); MRT_HIP(arrived.alloc_in(arena, out.rope_nodes)); MRT_HIP(ab.alloc_in(arena, out.rope_nodes));
             MRT_HIP(hipMemsetAsync(arrived.p, 0, arrived.bytes(), stream));
-            tg.rope_nodes = out.nodes.p; tg.rope_packets = out.nodes.p + out.packets_offset; tg.rope_nodes_n = out.rope_nodes;
         }
-        enqueue_refit(tg, RefitScratch{tri_world.p, tri_lo.p, tri_hi.p, nbox.p, growth.p, rparent.p, arrived.p, ab.p}, stream);
+        RefitScratch scratch{};          // the build's own k_flatten outputs, the rest from its arena
+        scratch.tri_world = tri_world.p; scratch.tri_lo = tri_lo.p; scratch.tri_hi = tri_hi.p; scratch.nbox = nbox.p; scratch.growth = growth.p; scratch.parent = rparent.p; scratch.arrived = arrived.p; scratch.ab = ab.p;
+        enqueue_refit(flat_refit_target(out, there, first.data(), inst_dirty.p), scratch, stream);
         MRT_HIP(hipEventRecord(evs.b, stream));
         float4 h_box[2];
         if (there.wide) MRT_HIP(hipMemcpyAsync(h_box, nbox.p, sizeof h_box, hipMemcpyDeviceToHost, stream));

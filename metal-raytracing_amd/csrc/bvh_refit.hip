@@ -1,10 +1,11 @@
 // bvh_refit.hip — refit of the resident layouts for deformed geometry (same topology, new vertices), for gfx950.
 //
-// The tree bvh_build.hip made keeps its shape; its packets and boxes follow the vertices.  One enqueue (enqueue_refit) serves the three ways in:
-//   a commit of a flattened scene after mrt_scene_update_mesh alone   (bvh_build.hip FlatBuild::refit_resident)
-//   a commit of a two-level scene, per BLAS of an updated mesh        (refit_blas, called by two_level.hip refit_two_level)
-//   mrt_scene_update_mesh_device / mrt_scene_refit_device             (the stream-ordered refit at the end of this file)
-// and one function (apply_refit_result) writes what a refit of a flattened scene leaves in the statistics.
+// The tree bvh_build.hip made keeps its shape; its packets and boxes follow the vertices.  One enqueue (enqueue_refit) and one recipe per scene form serve the four ways in:
+//   a flattened scene (flat_refit_target; apply_refit_result writes its statistics): a commit after mrt_scene_update_mesh alone (bvh_build.hip FlatBuild::refit_resident), and
+//     mrt_scene_update_mesh_device / mrt_scene_refit_device (device_refit)
+//   a BLAS of a two-level scene (enqueue_blas_refit; fold_blas_stats writes the scene's statistics): a commit, per updated mesh (refit_blas, called by two_level.hip refit_two_level), and
+//     mrt_scene_update_blas_device / mrt_scene_refit_blas_device (device_refit_blas)
+// The device entries' update calls share one vertex ingest (enqueue_vertex_ingest) and, with the instance moves of tlas_refit.hip, one gate (UpdateGate, retire_gate).
 #include "build_common.h"
 
 namespace mrt {
@@ -314,6 +315,38 @@ int apply_refit_result(DeviceScene &sc, const BuildOptions &opt, bool wide, floa
     return MRT_OK;
 }
 
+// What a refit of a flattened scene works on: the resident layouts `layouts` names, whole; a leaf keeps its box unless an instance marked in `dirty` has a triangle in it.
+RefitTarget flat_refit_target(const DeviceScene &sc, RefitLayouts layouts, const uint32_t *level_first, const uint8_t *dirty) {
+    RefitTarget tg;
+    if (layouts.wide) { tg.wnodes = sc.wnodes.p; tg.wpackets = sc.wpackets.p; tg.level_first = level_first; tg.level_count = sc.wide_levels.data(); tg.levels = sc.wide_levels.size(); }
+    if (layouts.rope) { tg.rope_nodes = sc.nodes.p; tg.rope_packets = sc.nodes.p + sc.packets_offset; tg.rope_nodes_n = sc.rope_nodes; }          // the rope layout beside it (rope = 1) or alone (wide = 0)
+    tg.packets = sc.num_packets; tg.tri_shade = sc.tri_shade.p; tg.dirty = dirty;
+    return tg;
+}
+// ... and of ONE BLAS in a two-level scene's shared arrays, both layouts: the 8-wide levels start at the BLAS's first node (level_first: absolute), its packets at packet_base in both packet arrays; every rope leaf is
+// recomputed (the BLAS's one mesh moved), the rope packets are rewritten whether or not the BLAS has rope nodes.  tri_shade and dirty are of the BLAS's own numbering (k_flatten under the identity; one "instance", marked).
+static RefitTarget blas_refit_target(const DeviceScene &sc, const BlasRange &br, const uint32_t *level_first, const uint4 *tri_shade, const uint8_t *dirty) {
+    RefitTarget tg;
+    tg.wnodes = sc.wnodes.p; tg.wpackets = sc.wpackets.p; tg.wpacket_first = br.packet_base; tg.level_first = level_first; tg.level_count = br.wide_levels.data(); tg.levels = br.wide_levels.size();
+    tg.rope_nodes = sc.bnodes.p + 4 * (size_t)br.node_base; tg.rope_packets = sc.bnodes.p + sc.bpackets_offset + 3 * (size_t)br.packet_base; tg.rope_nodes_n = br.rope_nodes;
+    tg.packets = br.ntri; tg.tri_shade = tri_shade; tg.dirty = dirty; tg.rope_every_leaf = true;
+    return tg;
+}
+// The refit of one BLAS from its object-space geometry on the device: the mesh's triangles by k_flatten under the identity, then enqueue_refit on blas_refit_target.  The one sequence of a refitting commit (refit_blas:
+// an arena filled per call) and of the stream-ordered BLAS refit (device_refit_blas: the resident BlasWorkspace); what is cleared before it, timed around it and read back after it is the caller's.
+struct BlasRefitInputs {
+    const uint32_t *recs; int nrec; const float *pos; const uint32_t *idx; const float4 *cols;      // the BLAS's SubRecs, its mesh's positions and indices, the identity
+    uint4 *tri_shade; uint32_t *cbounds; const uint8_t *dirty; RefitScratch scratch; const uint32_t *level_first;      // k_flatten's shading records and centroid bounds (scratch: written, never read), the marked "instance", ...
+};
+static void enqueue_blas_refit(const DeviceScene &sc, const BlasRange &br, const BlasRefitInputs &in, hipStream_t stream) {
+    static_assert(WPK == 3, "k_refit_wide_packets serves both packet arrays at a stride of three float4");
+    hipLaunchKernelGGL(k_flatten, dim3(cdiv(br.ntri, 1024)), dim3(1024), 0, stream, reinterpret_cast<const SubRec *>(in.recs), in.nrec, in.pos, in.idx, in.cols, br.ntri, in.scratch.tri_world, in.tri_shade, in.scratch.tri_lo, in.scratch.tri_hi, in.cbounds);
+    enqueue_refit(blas_refit_target(sc, br, in.level_first, in.tri_shade, in.dirty), in.scratch, stream);
+}
+
+static const float4 ident[4] = {make_float4(1, 0, 0, 0), make_float4(0, 1, 0, 0), make_float4(0, 0, 1, 0), make_float4(0, 0, 0, 0)};      // k_flatten's instance columns for a BLAS: object space
+static size_t piece(size_t bytes) { return (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; }      // what a ScratchArena hands out for `bytes`
+
 // The index list and the submesh records of a BLAS's mesh in the BLAS's own numbering (one "instance", vertices from 0), appended to `recs` / `idx` with index offsets
 // relative to where this mesh's indices start: what k_flatten reads in refit_blas and in the stream-ordered BLAS refit.  Returns the triangle count.
 static size_t blas_geometry(const HostMesh &g, std::vector<SubRec> &recs, std::vector<uint32_t> &idx) {
@@ -334,49 +367,39 @@ static size_t blas_geometry(const HostMesh &g, std::vector<SubRec> &recs, std::v
 int refit_blas(const HostMesh &g, const BlasRange &br, hipStream_t stream, DeviceScene &out, float root_lo[3], float root_hi[3], float *ms_out, float *growth_out) {
     const size_t nv = g.positions.size() / 3, T = br.ntri;
     if (T == 0 || br.wnodes == 0 || g.normals.size() != g.positions.size()) { set_error("refit_blas: nothing to refit"); return MRT_ERR_STATE; }
-    static_assert(WPK == 3, "k_refit_wide_packets serves both packet arrays at a stride of three float4");
     std::vector<SubRec> recs; std::vector<uint32_t> idx; idx.reserve(3 * T);
     if (blas_geometry(g, recs, idx) != T) { set_error("refit_blas: the mesh's triangle count changed"); return MRT_ERR_STATE; }
     std::vector<float4> h_nrm(nv);
     for (size_t v = 0; v < nv; v++) h_nrm[v] = make_float4(g.normals[3 * v], g.normals[3 * v + 1], g.normals[3 * v + 2], 0.0f);
-    const float4 ident[4] = {make_float4(1, 0, 0, 0), make_float4(0, 1, 0, 0), make_float4(0, 0, 1, 0), make_float4(0, 0, 0, 0)};
-    ScratchArena arena; arena.chunk_bytes = ((size_t)T * (48 + 16 + 32 + 12) + nv * 12 + (size_t)out.wnodes.n / WNODE_STRIDE * 32 + (size_t)br.rope_nodes * 16 + ((size_t)1 << 20) + 255) & ~(size_t)255;
-    DevBuf<float> d_pos; DevBuf<uint32_t> d_idx, d_recs, cbounds, parent, arrived; DevBuf<uint2> ab; DevBuf<float4> cols, tri_world, tri_lo, tri_hi, nbox; DevBuf<uint4> ts_tmp; DevBuf<uint8_t> dirty;
-    MRT_HIP(d_pos.alloc_in(arena, 3 * nv)); MRT_HIP(d_idx.alloc_in(arena, idx.size())); MRT_HIP(d_recs.alloc_in(arena, 6 * recs.size())); MRT_HIP(cbounds.alloc_in(arena, 6)); MRT_HIP(cols.alloc_in(arena, 4));
-    MRT_HIP(tri_world.alloc_in(arena, 3 * T)); MRT_HIP(tri_lo.alloc_in(arena, T)); MRT_HIP(tri_hi.alloc_in(arena, T)); MRT_HIP(ts_tmp.alloc_in(arena, T));
-    MRT_HIP(nbox.alloc_in(arena, 2 * (out.wnodes.n / WNODE_STRIDE))); MRT_HIP(dirty.alloc_in(arena, 4));
-    DevBuf<double> growth; MRT_HIP(growth.alloc_in(arena, 2)); MRT_HIP(hipMemsetAsync(growth.p, 0, 16, stream));
-    MRT_HIP(parent.alloc_in(arena, std::max<size_t>(br.rope_nodes, 1))); MRT_HIP(arrived.alloc_in(arena, std::max<size_t>(br.rope_nodes, 1))); MRT_HIP(ab.alloc_in(arena, std::max<size_t>(br.rope_nodes, 1)));
-    EventPair evs;
-    MRT_HIP(hipEventCreate(&evs.a)); MRT_HIP(hipEventCreate(&evs.b));
+    RefitBuffers w;          // (its scratch and its event pair: the host marks are the resident workspaces')
+    w.arena.chunk_bytes = ((size_t)T * (48 + 16 + 32 + 12) + nv * 12 + (size_t)out.wnodes.n / WNODE_STRIDE * 32 + (size_t)br.rope_nodes * 16 + ((size_t)1 << 20) + 255) & ~(size_t)255;
+    DevBuf<float> d_pos; DevBuf<uint32_t> d_idx, d_recs; DevBuf<float4> cols; DevBuf<uint4> ts_tmp; DevBuf<uint8_t> dirty;
+    MRT_HIP(d_pos.alloc_in(w.arena, 3 * nv)); MRT_HIP(d_idx.alloc_in(w.arena, idx.size())); MRT_HIP(d_recs.alloc_in(w.arena, 6 * recs.size())); MRT_HIP(w.cbounds.alloc_in(w.arena, 6)); MRT_HIP(cols.alloc_in(w.arena, 4));
+    MRT_HIP(w.tri_world.alloc_in(w.arena, 3 * T)); MRT_HIP(w.tri_lo.alloc_in(w.arena, T)); MRT_HIP(w.tri_hi.alloc_in(w.arena, T)); MRT_HIP(ts_tmp.alloc_in(w.arena, T));
+    MRT_HIP(w.nbox.alloc_in(w.arena, 2 * (out.wnodes.n / WNODE_STRIDE))); MRT_HIP(dirty.alloc_in(w.arena, 4));
+    MRT_HIP(w.growth.alloc_in(w.arena, 2)); MRT_HIP(hipMemsetAsync(w.growth.p, 0, 16, stream));
+    MRT_HIP(w.parent.alloc_in(w.arena, std::max<size_t>(br.rope_nodes, 1))); MRT_HIP(w.arrived.alloc_in(w.arena, std::max<size_t>(br.rope_nodes, 1))); MRT_HIP(w.ab.alloc_in(w.arena, std::max<size_t>(br.rope_nodes, 1)));
+    MRT_HIP(hipEventCreate(&w.ev_begin)); MRT_HIP(hipEventCreate(&w.ev_end));
     MRT_HIP(hipMemcpyAsync(d_pos.p, g.positions.data(), 12 * nv, hipMemcpyHostToDevice, stream));
     MRT_HIP(hipMemcpyAsync(d_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, stream));
     MRT_HIP(hipMemcpyAsync(d_recs.p, recs.data(), recs.size() * sizeof(SubRec), hipMemcpyHostToDevice, stream));
     MRT_HIP(hipMemcpyAsync(cols.p, ident, sizeof ident, hipMemcpyHostToDevice, stream));
     MRT_HIP(hipMemsetAsync(dirty.p, 1, 4, stream));                       // the one "instance" of the BLAS's own triangle arrays moved
-    MRT_HIP(hipMemsetAsync(cbounds.p, 0, 24, stream));
-    MRT_HIP(hipMemsetAsync(arrived.p, 0, arrived.bytes(), stream));
-    MRT_HIP(hipEventRecord(evs.a, stream));
-    const uint32_t T32 = (uint32_t)T;
-    hipLaunchKernelGGL(k_flatten, dim3(cdiv(T32, 1024)), dim3(1024), 0, stream, reinterpret_cast<const SubRec *>(d_recs.p), (int)recs.size(), d_pos.p, d_idx.p, cols.p, T32, tri_world.p, ts_tmp.p, tri_lo.p, tri_hi.p, cbounds.p);
-    // both layouts: the 8-wide levels start at the BLAS's first node, its packets at packet_base in both packet arrays; every rope leaf is recomputed (no dirty bytes: the
-    // BLAS's one mesh moved), and the rope packets are rewritten whether or not the BLAS has rope nodes
+    MRT_HIP(hipMemsetAsync(w.cbounds.p, 0, 24, stream));
+    MRT_HIP(hipMemsetAsync(w.arrived.p, 0, w.arrived.bytes(), stream));
+    MRT_HIP(hipEventRecord(w.ev_begin, stream));
     const std::vector<uint32_t> first = level_first(br.wide_levels, br.wnode_base);
-    RefitTarget tg;
-    tg.wnodes = out.wnodes.p; tg.wpackets = out.wpackets.p; tg.wpacket_first = br.packet_base; tg.level_first = first.data(); tg.level_count = br.wide_levels.data(); tg.levels = br.wide_levels.size();
-    tg.rope_nodes = out.bnodes.p + 4 * (size_t)br.node_base; tg.rope_packets = out.bnodes.p + out.bpackets_offset + 3 * (size_t)br.packet_base; tg.rope_nodes_n = br.rope_nodes;
-    tg.packets = T32; tg.tri_shade = ts_tmp.p; tg.dirty = dirty.p; tg.rope_every_leaf = true;
-    enqueue_refit(tg, RefitScratch{tri_world.p, tri_lo.p, tri_hi.p, nbox.p, growth.p, parent.p, arrived.p, ab.p}, stream);
-    MRT_HIP(hipEventRecord(evs.b, stream));
+    enqueue_blas_refit(out, br, BlasRefitInputs{d_recs.p, (int)recs.size(), d_pos.p, d_idx.p, cols.p, ts_tmp.p, w.cbounds.p, dirty.p, w.scratch(), first.data()}, stream);
+    MRT_HIP(hipEventRecord(w.ev_end, stream));
     MRT_HIP(hipMemcpyAsync(out.normals.p + br.vbase, h_nrm.data(), nv * 16, hipMemcpyHostToDevice, stream));
     float4 h_box[2];
-    MRT_HIP(hipMemcpyAsync(h_box, nbox.p + 2 * (size_t)br.wnode_base, sizeof h_box, hipMemcpyDeviceToHost, stream));
+    MRT_HIP(hipMemcpyAsync(h_box, w.nbox.p + 2 * (size_t)br.wnode_base, sizeof h_box, hipMemcpyDeviceToHost, stream));
     double h_growth[2] = {0.0, 0.0};
-    MRT_HIP(hipMemcpyAsync(h_growth, growth.p, sizeof h_growth, hipMemcpyDeviceToHost, stream));
+    MRT_HIP(hipMemcpyAsync(h_growth, w.growth.p, sizeof h_growth, hipMemcpyDeviceToHost, stream));
     MRT_HIP(hipStreamSynchronize(stream));
     if (growth_out) *growth_out = h_growth[0] > 0.0 ? (float)(h_growth[1] / h_growth[0]) : 1.0f;
     MRT_HIP(hipGetLastError());
-    float ms = 0; MRT_HIP(hipEventElapsedTime(&ms, evs.a, evs.b));
+    float ms = 0; MRT_HIP(hipEventElapsedTime(&ms, w.ev_begin, w.ev_end));
     if (ms_out) *ms_out = ms;
     set_root_box(root_lo, root_hi, h_box[0], h_box[1]);
     return MRT_OK;
@@ -419,27 +442,24 @@ int device_refit_supported(const DeviceScene &sc, const BuildOptions &opt, const
     return MRT_ERR_UNSUPPORTED;
 }
 
+void retire_gate(DeviceScene &sc, UpdateGate &gate) {          // a workspace goes: what its gate counted stays with the scene (a count that cannot be read is dropped with the error)
+    uint64_t h = 0;
+    if (gate.rejected_so_far(&h) == hipSuccess) sc.rejected_before += h; else (void)hipGetLastError();
+}
 void drop_refit_workspace(DeviceScene &sc) {
-    if (!sc.refit_ws) return;
-    unsigned long long h = 0;
-    if (hipEventSynchronize(sc.refit_ws->ev_last) == hipSuccess && hipMemcpy(&h, sc.refit_ws->rejected.p, 8, hipMemcpyDeviceToHost) == hipSuccess) sc.rejected_before += h; else (void)hipGetLastError();
+    if (sc.refit_ws) retire_gate(sc, sc.refit_ws->gate);
     sc.refit_ws.reset();
 }
 
 int device_updates_rejected(DeviceScene &sc, uint64_t *count) {
     *count = sc.rejected_before;
-    // every workspace that exists has a counter of its own: set calls refused by k_inst_check (tlas_refit.hip), update calls refused by k_ingest_check for a flattened scene
+    // every workspace that exists has a gate of its own: set calls refused by k_inst_check (tlas_refit.hip), update calls refused by k_ingest_check for a flattened scene
     // (refit_ws) or for the BLASes of a two-level one (blas_ws)
-    const auto add = [count](hipEvent_t ev_last, const unsigned long long *d) {
-        unsigned long long h = 0;
-        MRT_HIP(hipEventSynchronize(ev_last));
-        MRT_HIP(hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost));
+    for (const UpdateGate *g : {sc.inst_ws ? &sc.inst_ws->gate : nullptr, sc.blas_ws ? &sc.blas_ws->gate : nullptr, sc.refit_ws ? &sc.refit_ws->gate : nullptr}) {
+        uint64_t h = 0;
+        if (g) MRT_HIP(g->rejected_so_far(&h));
         *count += h;
-        return (int)MRT_OK;
-    };
-    if (sc.inst_ws) { if (int rc = add(sc.inst_ws->ev_last, sc.inst_ws->rejected.p)) return rc; }
-    if (sc.blas_ws) { if (int rc = add(sc.blas_ws->ev_last, sc.blas_ws->rejected.p)) return rc; }
-    if (sc.refit_ws) { if (int rc = add(sc.refit_ws->ev_last, sc.refit_ws->rejected.p)) return rc; }
+    }
     return MRT_OK;
 }
 
@@ -464,36 +484,40 @@ int device_refit_prepare(const std::vector<HostMesh> &meshes, const BuildOptions
     const size_t nw = std::max<uint32_t>(sc.num_wnodes, 1u), nr = std::max<uint32_t>(sc.rope_nodes, 1u);
     // one allocation: 80 B per triangle + 32 B per 8-wide node + 16 B per rope node, every piece below rounded up as the arena hands it out (a piece added below and forgotten
     // here costs a second chunk, nothing else)
-    const auto piece = [](size_t bytes) { return (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; };
     const size_t nref = std::max<size_t>(table.size(), 1), ninst = std::max<size_t>(I, 1);
     w->arena.chunk_bytes = piece(48 * T) + 2 * piece(16 * T) + piece(32 * nw) + 2 * piece(4 * nr) + piece(8 * nr) + piece(sizeof(uint2) * nref) + piece(ninst)
                          + piece(6 * 4) + piece(4 * 4) + piece(6 * 8) + piece(8) + piece(4);
     MRT_HIP(w->tri_world.alloc_in(w->arena, 3 * T)); MRT_HIP(w->tri_lo.alloc_in(w->arena, T)); MRT_HIP(w->tri_hi.alloc_in(w->arena, T)); MRT_HIP(w->nbox.alloc_in(w->arena, 2 * nw));
     MRT_HIP(w->parent.alloc_in(w->arena, nr)); MRT_HIP(w->arrived.alloc_in(w->arena, nr)); MRT_HIP(w->ab.alloc_in(w->arena, nr));
     MRT_HIP(w->ref_table.alloc_in(w->arena, nref)); MRT_HIP(w->inst_dirty.alloc_in(w->arena, ninst));
-    MRT_HIP(w->cbounds.alloc_in(w->arena, 6)); MRT_HIP(w->words.alloc_in(w->arena, 4)); MRT_HIP(w->growth.alloc_in(w->arena, 6)); MRT_HIP(w->rejected.alloc_in(w->arena, 1)); MRT_HIP(w->leaf_growth.alloc_in(w->arena, 1));
-    MRT_HIP(hipEventCreate(&w->ev_begin)); MRT_HIP(hipEventCreate(&w->ev_end)); MRT_HIP(hipEventCreateWithFlags(&w->ev_last, hipEventDisableTiming));
+    MRT_HIP(w->cbounds.alloc_in(w->arena, 6)); MRT_HIP(w->gate.words.alloc_in(w->arena, 4)); MRT_HIP(w->growth.alloc_in(w->arena, 6)); MRT_HIP(w->gate.rejected.alloc_in(w->arena, 1)); MRT_HIP(w->leaf_growth.alloc_in(w->arena, 1));
+    MRT_HIP(hipEventCreate(&w->ev_begin)); MRT_HIP(hipEventCreate(&w->ev_end)); MRT_HIP(hipEventCreateWithFlags(&w->gate.ev_last, hipEventDisableTiming));
     if (!table.empty()) MRT_HIP(hipMemcpy(w->ref_table.p, table.data(), table.size() * sizeof(uint2), hipMemcpyHostToDevice));
-    MRT_HIP(hipMemset(w->inst_dirty.p, 0, w->inst_dirty.bytes())); MRT_HIP(hipMemset(w->words.p, 0, w->words.bytes())); MRT_HIP(hipMemset(w->growth.p, 0, w->growth.bytes())); MRT_HIP(hipMemset(w->rejected.p, 0, 8));
+    MRT_HIP(hipMemset(w->inst_dirty.p, 0, w->inst_dirty.bytes())); MRT_HIP(hipMemset(w->gate.words.p, 0, w->gate.words.bytes())); MRT_HIP(hipMemset(w->growth.p, 0, w->growth.bytes())); MRT_HIP(hipMemset(w->gate.rejected.p, 0, 8));
     MRT_HIP(hipMemcpy(w->leaf_growth.p, &sc.stats.leaf_growth, 4, hipMemcpyHostToDevice));
     MRT_HIP(hipDeviceSynchronize());          // (the first call after a build may block: from here on the caller's stream finds the workspace as the lines above left it)
-    MRT_HIP(hipEventRecord(w->ev_last, nullptr));
+    MRT_HIP(hipEventRecord(w->gate.ev_last, nullptr));
     sc.refit_ws = std::move(w);
+    return MRT_OK;
+}
+
+// One update call's two launches on the caller's stream, the gate's event behind them: nverts rows into dst_pos / normals at every vertex base refs[0 .. nrefs) names, the instances it names marked in `dirty`.  (gate.next() is the caller's.)
+struct VertexRows { const void *pos; size_t pos_stride; const void *nrm; size_t nrm_stride; };
+static int enqueue_vertex_ingest(UpdateGate &gate, const VertexRows &rows, size_t nverts, const uint2 *refs, uint32_t nrefs, float *dst_pos, float4 *normals, uint8_t *dirty, hipStream_t stream) {
+    const uint32_t nv = (uint32_t)nverts;
+    const dim3 grid(cdiv(nv, 256)), block(256);
+    const uint8_t *pos = static_cast<const uint8_t *>(rows.pos), *nrm = static_cast<const uint8_t *>(rows.nrm);
+    hipLaunchKernelGGL(k_ingest_check, grid, block, 0, stream, pos, rows.pos_stride, nrm, rows.nrm_stride, nv, gate.seq, gate.words.p);
+    hipLaunchKernelGGL(k_ingest_write, grid, block, 0, stream, pos, rows.pos_stride, nrm, rows.nrm_stride, nv, gate.seq, (const uint32_t *)gate.words.p, gate.rejected.p, refs, nrefs, dst_pos, normals, dirty);
+    MRT_HIP(hipGetLastError());
+    MRT_HIP(hipEventRecord(gate.ev_last, stream));
     return MRT_OK;
 }
 
 int device_update_mesh(DeviceScene &sc, size_t mesh, const void *d_pos, size_t pos_stride, const void *d_nrm, size_t nrm_stride, size_t nverts, hipStream_t stream) {
     RefitWorkspace &ws = *sc.refit_ws;
-    if (++ws.seq == 0u) ws.seq = 1u;          // (0 is what words[0] starts as)
-    if (nverts != 0 && ws.ref_count[mesh] != 0) {
-        const uint32_t nv = (uint32_t)nverts;
-        const dim3 grid(cdiv(nv, 256)), block(256);
-        hipLaunchKernelGGL(k_ingest_check, grid, block, 0, stream, static_cast<const uint8_t *>(d_pos), pos_stride, static_cast<const uint8_t *>(d_nrm), nrm_stride, nv, ws.seq, ws.words.p);
-        hipLaunchKernelGGL(k_ingest_write, grid, block, 0, stream, static_cast<const uint8_t *>(d_pos), pos_stride, static_cast<const uint8_t *>(d_nrm), nrm_stride, nv, ws.seq, (const uint32_t *)ws.words.p,
-                           ws.rejected.p, (const uint2 *)(ws.ref_table.p + ws.ref_first[mesh]), ws.ref_count[mesh], sc.g_pos.p, sc.normals.p, ws.inst_dirty.p);
-        MRT_HIP(hipGetLastError());
-        MRT_HIP(hipEventRecord(ws.ev_last, stream));
-    }
+    ws.gate.next();
+    if (nverts != 0 && ws.ref_count[mesh] != 0) { if (int rc = enqueue_vertex_ingest(ws.gate, VertexRows{d_pos, pos_stride, d_nrm, nrm_stride}, nverts, ws.ref_table.p + ws.ref_first[mesh], ws.ref_count[mesh], sc.g_pos.p, sc.normals.p, ws.inst_dirty.p, stream)) return rc; }
     // (set for a call the device refuses too: the host cannot know without a read-back.  The bits on the device are then the old ones, so all it costs is a download of
     // vertices the host already has and a refit of an unchanged mesh at the next commit)
     ws.host_stale[mesh] = 1; ws.pending[mesh] = 1;
@@ -502,23 +526,18 @@ int device_update_mesh(DeviceScene &sc, size_t mesh, const void *d_pos, size_t p
 
 int device_refit(DeviceScene &sc, hipStream_t stream) {
     RefitWorkspace &ws = *sc.refit_ws;
-    const bool wide_there = ws.layouts.wide, rope_there = ws.layouts.rope;
     const uint32_t T32 = (uint32_t)sc.stats.triangles;
     const int nrec = (int)(sc.g_recs.n / 6);
     MRT_HIP(hipMemsetAsync(ws.cbounds.p, 0, 24, stream));          // (k_flatten's centroid bounds: written, never read here)
-    if (rope_there) MRT_HIP(hipMemsetAsync(ws.arrived.p, 0, (size_t)sc.rope_nodes * 4, stream));
+    if (ws.layouts.rope) MRT_HIP(hipMemsetAsync(ws.arrived.p, 0, (size_t)sc.rope_nodes * 4, stream));
     MRT_HIP(hipEventRecord(ws.ev_begin, stream));
     hipLaunchKernelGGL(k_flatten, dim3(cdiv(T32, 1024)), dim3(1024), 0, stream, reinterpret_cast<const SubRec *>(sc.g_recs.p), nrec, (const float *)sc.g_pos.p, (const uint32_t *)sc.g_idx.p, (const float4 *)sc.inst_cols.p, T32,
                        ws.tri_world.p, sc.tri_shade.p, ws.tri_lo.p, ws.tri_hi.p, ws.cbounds.p);
-    RefitTarget tg;
-    if (wide_there) { tg.wnodes = sc.wnodes.p; tg.wpackets = sc.wpackets.p; tg.level_first = ws.level_first.data(); tg.level_count = sc.wide_levels.data(); tg.levels = sc.wide_levels.size(); }
-    if (rope_there) { tg.rope_nodes = sc.nodes.p; tg.rope_packets = sc.nodes.p + sc.packets_offset; tg.rope_nodes_n = sc.rope_nodes; }
-    tg.packets = sc.num_packets; tg.tri_shade = sc.tri_shade.p; tg.dirty = ws.inst_dirty.p;
-    enqueue_refit(tg, RefitScratch{ws.tri_world.p, ws.tri_lo.p, ws.tri_hi.p, ws.nbox.p, ws.growth.p, ws.parent.p, ws.arrived.p, ws.ab.p}, stream);
+    enqueue_refit(flat_refit_target(sc, ws.layouts, ws.level_first.data(), ws.inst_dirty.p), ws.scratch(), stream);
     hipLaunchKernelGGL(k_refit_fold, dim3(1), dim3(64), 0, stream, ws.growth.p, ws.leaf_growth.p);
     MRT_HIP(hipMemsetAsync(ws.inst_dirty.p, 0, ws.inst_dirty.bytes(), stream));          // the marks are spent
     MRT_HIP(hipEventRecord(ws.ev_end, stream));
-    MRT_HIP(hipEventRecord(ws.ev_last, stream));
+    MRT_HIP(hipEventRecord(ws.gate.ev_last, stream));
     MRT_HIP(hipGetLastError());
     std::fill(ws.pending.begin(), ws.pending.end(), 0);
     sc.refits++; ws.unresolved = true;
@@ -540,6 +559,16 @@ int resolve_device_refits(DeviceScene &sc, const BuildOptions &opt, hipStream_t 
     return MRT_OK;
 }
 
+static int download_mesh_vertices(HostMesh &m, const float *d_pos, const float4 *d_nrm) {          // a mesh's host copy from where the device keeps its vertices (packed positions, float4 normals); blocks
+    const size_t nv = m.positions.size() / 3;
+    if (!nv) return MRT_OK;
+    std::vector<float4> n4(nv);
+    MRT_HIP(hipMemcpy(m.positions.data(), d_pos, nv * 12, hipMemcpyDeviceToHost));
+    MRT_HIP(hipMemcpy(n4.data(), d_nrm, nv * 16, hipMemcpyDeviceToHost));
+    for (size_t v = 0; v < nv; v++) { m.normals[3 * v] = n4[v].x; m.normals[3 * v + 1] = n4[v].y; m.normals[3 * v + 2] = n4[v].z; }
+    return MRT_OK;
+}
+
 // The scene's host copy of a mesh is stale once its vertices were replaced on the device: whoever reads HostMesh::positions / normals (a commit, the replication of a scene
 // for a device group) calls this first.  A mesh updated and not yet refitted counts as changed for the commit that follows.
 int download_stale_meshes(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *pending_found) {
@@ -550,19 +579,11 @@ int download_stale_meshes(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *
     // knows are the first host_stale.size() of the scene, whatever was added behind them since
     const size_t known = std::min(ws.host_stale.size(), meshes.size());
     bool waited = false;
-    std::vector<float4> n4;
     for (size_t mi = 0; mi < known; mi++) {
         if (ws.pending[mi]) { meshes[mi].dirty = true; ws.pending[mi] = 0; if (pending_found) *pending_found = true; }
         if (!ws.host_stale[mi]) continue;
-        if (!waited) { MRT_HIP(hipEventSynchronize(ws.ev_last)); waited = true; }
-        HostMesh &m = meshes[mi];
-        const size_t nv = m.positions.size() / 3;
-        if (nv) {
-            n4.resize(nv);
-            MRT_HIP(hipMemcpy(m.positions.data(), sc.g_pos.p + 3 * (size_t)ws.mesh_vbase[mi], nv * 12, hipMemcpyDeviceToHost));
-            MRT_HIP(hipMemcpy(n4.data(), sc.normals.p + ws.mesh_vbase[mi], nv * 16, hipMemcpyDeviceToHost));
-            for (size_t v = 0; v < nv; v++) { m.normals[3 * v] = n4[v].x; m.normals[3 * v + 1] = n4[v].y; m.normals[3 * v + 2] = n4[v].z; }
-        }
+        if (!waited) { MRT_HIP(hipEventSynchronize(ws.gate.ev_last)); waited = true; }
+        if (int rc = download_mesh_vertices(meshes[mi], sc.g_pos.p + 3 * (size_t)ws.mesh_vbase[mi], sc.normals.p + ws.mesh_vbase[mi])) return rc;
         ws.host_stale[mi] = 0;
     }
     return MRT_OK;
@@ -570,7 +591,7 @@ int download_stale_meshes(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *
 
 // ------------------------------------------------------------------ meshes of two-level scenes deformed on the stream (mrt_scene_update_blas_device / mrt_scene_refit_blas_device)
 // refit_two_level with nothing of the host in it.  The vertices of a mesh exist once, in its BLAS: k_ingest_write puts them into the workspace's resident positions and the
-// scene's normals (a one-row reference table per BLAS).  The refit then runs refit_blas's kernel sequence per updated BLAS with refit_blas's arguments — so nodes and packets
+// scene's normals (a one-row reference table per BLAS).  The refit then runs refit_blas's sequence (enqueue_blas_refit) per updated BLAS, from the resident geometry — so nodes and packets
 // come out as a refitting commit leaves them —, hands the new root box to the BLAS's instances (tlas_refit.hip k_blas_instance_boxes) and refits both TLAS forms with their
 // topology kept (device_refit_instances).  What the host path reads back at once — root boxes, growth sums, the trees' costs — waits on the device for resolve_blas_refits.
 int blas_device_supported(const DeviceScene &sc, const BuildOptions &opt, size_t meshes, const char *who) {
@@ -586,9 +607,7 @@ int blas_device_supported(const DeviceScene &sc, const BuildOptions &opt, size_t
 }
 
 void drop_blas_workspace(DeviceScene &sc) {
-    if (!sc.blas_ws) return;
-    unsigned long long h = 0;
-    if (hipEventSynchronize(sc.blas_ws->ev_last) == hipSuccess && hipMemcpy(&h, sc.blas_ws->rejected.p, 8, hipMemcpyDeviceToHost) == hipSuccess) sc.rejected_before += h; else (void)hipGetLastError();
+    if (sc.blas_ws) retire_gate(sc, sc.blas_ws->gate);
     sc.blas_ws.reset();
 }
 
@@ -622,17 +641,15 @@ int blas_device_prepare(const std::vector<HostMesh> &meshes, DeviceScene &sc) {
     for (size_t b = 1; b < B; b++) w->inst_first[b] = w->inst_first[b - 1] + w->inst_count[b - 1];
     { std::vector<uint32_t> at = w->inst_first; for (size_t i = 0; i < I; i++) if (sc.h_inst[i].blas < B) list[at[sc.h_inst[i].blas]++] = (uint32_t)i; }
     const size_t nw = std::max<size_t>(sc.wnodes.n / WNODE_STRIDE, 1), nrec = std::max<size_t>(recs.size(), 1), nidx = std::max<size_t>(idx.size(), 3);
-    const auto piece = [](size_t bytes) { return (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; };
     w->arena.chunk_bytes = piece(4 * h_pos.size()) + piece(4 * nidx) + piece(sizeof(SubRec) * nrec) + piece(64) + piece(48 * maxT) + 3 * piece(16 * maxT) + piece(32 * nw) + 2 * piece(4 * maxR) + piece(8 * maxR)
                          + piece(8 * table.size()) + piece(4 * list.size()) + piece(6 * 4) + piece(4 * 4) + piece(8 * (2 * B + 4)) + piece(8) + piece(4 * lg.size()) + piece(4);
     MRT_HIP(w->pos.alloc_in(w->arena, h_pos.size())); MRT_HIP(w->idx.alloc_in(w->arena, nidx)); MRT_HIP(w->recs.alloc_in(w->arena, 6 * nrec)); MRT_HIP(w->cols.alloc_in(w->arena, 4));
     MRT_HIP(w->tri_world.alloc_in(w->arena, 3 * maxT)); MRT_HIP(w->tri_lo.alloc_in(w->arena, maxT)); MRT_HIP(w->tri_hi.alloc_in(w->arena, maxT)); MRT_HIP(w->tri_shade.alloc_in(w->arena, maxT));
     MRT_HIP(w->nbox.alloc_in(w->arena, 2 * nw)); MRT_HIP(w->parent.alloc_in(w->arena, maxR)); MRT_HIP(w->arrived.alloc_in(w->arena, maxR)); MRT_HIP(w->ab.alloc_in(w->arena, maxR));
     MRT_HIP(w->ref_table.alloc_in(w->arena, table.size())); MRT_HIP(w->inst_list.alloc_in(w->arena, list.size()));
-    MRT_HIP(w->cbounds.alloc_in(w->arena, 6)); MRT_HIP(w->words.alloc_in(w->arena, 4)); MRT_HIP(w->growth.alloc_in(w->arena, 2 * B + 4)); MRT_HIP(w->rejected.alloc_in(w->arena, 1));
+    MRT_HIP(w->cbounds.alloc_in(w->arena, 6)); MRT_HIP(w->gate.words.alloc_in(w->arena, 4)); MRT_HIP(w->growth.alloc_in(w->arena, 2 * B + 4)); MRT_HIP(w->gate.rejected.alloc_in(w->arena, 1));
     MRT_HIP(w->leaf_growth.alloc_in(w->arena, lg.size())); MRT_HIP(w->dirty.alloc_in(w->arena, 4));
-    MRT_HIP(hipEventCreate(&w->ev_begin)); MRT_HIP(hipEventCreate(&w->ev_end)); MRT_HIP(hipEventCreateWithFlags(&w->ev_last, hipEventDisableTiming));
-    const float4 ident[4] = {make_float4(1, 0, 0, 0), make_float4(0, 1, 0, 0), make_float4(0, 0, 1, 0), make_float4(0, 0, 0, 0)};
+    MRT_HIP(hipEventCreate(&w->ev_begin)); MRT_HIP(hipEventCreate(&w->ev_end)); MRT_HIP(hipEventCreateWithFlags(&w->gate.ev_last, hipEventDisableTiming));
     MRT_HIP(hipMemcpy(w->pos.p, h_pos.data(), h_pos.size() * 4, hipMemcpyHostToDevice));
     if (!idx.empty()) MRT_HIP(hipMemcpy(w->idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
     if (!recs.empty()) MRT_HIP(hipMemcpy(w->recs.p, recs.data(), recs.size() * sizeof(SubRec), hipMemcpyHostToDevice));
@@ -640,23 +657,17 @@ int blas_device_prepare(const std::vector<HostMesh> &meshes, DeviceScene &sc) {
     MRT_HIP(hipMemcpy(w->ref_table.p, table.data(), table.size() * sizeof(uint2), hipMemcpyHostToDevice));
     MRT_HIP(hipMemcpy(w->inst_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice));
     MRT_HIP(hipMemcpy(w->leaf_growth.p, lg.data(), lg.size() * 4, hipMemcpyHostToDevice));
-    MRT_HIP(hipMemset(w->dirty.p, 1, 4)); MRT_HIP(hipMemset(w->words.p, 0, w->words.bytes())); MRT_HIP(hipMemset(w->growth.p, 0, w->growth.bytes())); MRT_HIP(hipMemset(w->rejected.p, 0, 8));
+    MRT_HIP(hipMemset(w->dirty.p, 1, 4)); MRT_HIP(hipMemset(w->gate.words.p, 0, w->gate.words.bytes())); MRT_HIP(hipMemset(w->growth.p, 0, w->growth.bytes())); MRT_HIP(hipMemset(w->gate.rejected.p, 0, 8));
     MRT_HIP(hipDeviceSynchronize());          // (the first call after a commit may block: from here on the caller's stream finds the workspace as the lines above left it)
-    MRT_HIP(hipEventRecord(w->ev_last, nullptr));
+    MRT_HIP(hipEventRecord(w->gate.ev_last, nullptr));
     sc.blas_ws = std::move(w);
     return MRT_OK;
 }
 
 int device_update_blas(DeviceScene &sc, size_t blas, const void *d_pos, size_t pos_stride, const void *d_nrm, size_t nrm_stride, size_t nverts, hipStream_t stream) {
     BlasWorkspace &ws = *sc.blas_ws;
-    if (++ws.seq == 0u) ws.seq = 1u;          // (0 is what words[0] starts as)
-    const uint32_t nv = (uint32_t)nverts;
-    const dim3 grid(cdiv(nv, 256)), block(256);
-    hipLaunchKernelGGL(k_ingest_check, grid, block, 0, stream, static_cast<const uint8_t *>(d_pos), pos_stride, static_cast<const uint8_t *>(d_nrm), nrm_stride, nv, ws.seq, ws.words.p);
-    hipLaunchKernelGGL(k_ingest_write, grid, block, 0, stream, static_cast<const uint8_t *>(d_pos), pos_stride, static_cast<const uint8_t *>(d_nrm), nrm_stride, nv, ws.seq, (const uint32_t *)ws.words.p,
-                       ws.rejected.p, (const uint2 *)(ws.ref_table.p + blas), 1u, ws.pos.p, sc.normals.p, ws.dirty.p);
-    MRT_HIP(hipGetLastError());
-    MRT_HIP(hipEventRecord(ws.ev_last, stream));
+    ws.gate.next();
+    if (int rc = enqueue_vertex_ingest(ws.gate, VertexRows{d_pos, pos_stride, d_nrm, nrm_stride}, nverts, ws.ref_table.p + blas, 1u, ws.pos.p, sc.normals.p, ws.dirty.p, stream)) return rc;
     ws.host_stale[blas] = 1; ws.pending[blas] = 1;          // (for a call the device refuses too, as device_update_mesh)
     return MRT_OK;
 }
@@ -667,16 +678,10 @@ int device_refit_blas(DeviceScene &sc, hipStream_t stream) {
     for (size_t b = 0; b < sc.blas_ranges.size(); b++) {
         if (!ws.pending[b]) continue;
         const BlasRange &br = sc.blas_ranges[b];
-        const uint32_t T32 = br.ntri;
         MRT_HIP(hipMemsetAsync(ws.cbounds.p, 0, 24, stream));          // (k_flatten's centroid bounds: written, never read here)
         if (br.rope_nodes) MRT_HIP(hipMemsetAsync(ws.arrived.p, 0, (size_t)br.rope_nodes * 4, stream));
-        hipLaunchKernelGGL(k_flatten, dim3(cdiv(T32, 1024)), dim3(1024), 0, stream, reinterpret_cast<const SubRec *>(ws.recs.p) + ws.rec_first[b], (int)ws.rec_count[b], (const float *)(ws.pos.p + 3 * (size_t)br.vbase),
-                           (const uint32_t *)(ws.idx.p + ws.idx_first[b]), (const float4 *)ws.cols.p, T32, ws.tri_world.p, ws.tri_shade.p, ws.tri_lo.p, ws.tri_hi.p, ws.cbounds.p);
-        RefitTarget tg;          // refit_blas's, field for field
-        tg.wnodes = sc.wnodes.p; tg.wpackets = sc.wpackets.p; tg.wpacket_first = br.packet_base; tg.level_first = ws.level_first[b].data(); tg.level_count = br.wide_levels.data(); tg.levels = br.wide_levels.size();
-        tg.rope_nodes = sc.bnodes.p + 4 * (size_t)br.node_base; tg.rope_packets = sc.bnodes.p + sc.bpackets_offset + 3 * (size_t)br.packet_base; tg.rope_nodes_n = br.rope_nodes;
-        tg.packets = T32; tg.tri_shade = ws.tri_shade.p; tg.dirty = ws.dirty.p; tg.rope_every_leaf = true;
-        enqueue_refit(tg, RefitScratch{ws.tri_world.p, ws.tri_lo.p, ws.tri_hi.p, ws.nbox.p, ws.growth.p + 2 * b, ws.parent.p, ws.arrived.p, ws.ab.p}, stream);
+        enqueue_blas_refit(sc, br, BlasRefitInputs{ws.recs.p + 6 * (size_t)ws.rec_first[b], (int)ws.rec_count[b], ws.pos.p + 3 * (size_t)br.vbase, ws.idx.p + ws.idx_first[b], ws.cols.p, ws.tri_shade.p, ws.cbounds.p,
+                                                   ws.dirty.p, ws.scratch(2 * b), ws.level_first[b].data()}, stream);
         hipLaunchKernelGGL(k_refit_fold, dim3(1), dim3(64), 0, stream, ws.growth.p + 2 * b, ws.leaf_growth.p + b);
         enqueue_blas_instance_boxes(sc, ws.nbox.p, br.wnode_base, ws.inst_list.p + ws.inst_first[b], ws.inst_count[b], stream);
         MRT_HIP(hipGetLastError());
@@ -684,13 +689,23 @@ int device_refit_blas(DeviceScene &sc, hipStream_t stream) {
     }
     if (int rc = device_refit_instances(sc, stream)) return rc;          // both TLAS forms follow the instances' world boxes (and whatever poses were set since the last refit)
     MRT_HIP(hipEventRecord(ws.ev_end, stream));
-    MRT_HIP(hipEventRecord(ws.ev_last, stream));
+    MRT_HIP(hipEventRecord(ws.gate.ev_last, stream));
     sc.refits++; ws.unresolved = true;
     return MRT_OK;
 }
 
+// The scene's figures after BLAS refits, from the BlasRanges in their order: the loosest BLAS's chained leaf_growth, the mean of the trees' costs as they lie now and of their build-time SAH figures scaled alike (double
+// sums, float results), the refits so far (counted by the caller) and their time.  The one writer, for the refitting commit (two_level.hip refit_two_level) and for the stream-ordered refits (resolve_blas_refits).
+void fold_blas_stats(DeviceScene &sc, float ms) {
+    float growth_max = 1.0f; double sah = 0, wcost = 0;
+    for (const BlasRange &r : sc.blas_ranges) { growth_max = std::max(growth_max, r.leaf_growth); wcost += r.wide_cost; sah += r.wide_cost_built > 0.0f ? r.sah_cost_built * (r.wide_cost / r.wide_cost_built) : r.sah_cost_built; }
+    const size_t B = sc.blas_ranges.size();
+    sc.stats.build_ms = ms; sc.stats.wide_cost = (float)(wcost / (double)B); sc.stats.sah_cost = (float)(sah / (double)B);
+    sc.stats.refits = sc.refits; sc.stats.leaf_growth = growth_max;
+}
+
 // What refit_two_level reads back at once, read when somebody asks: per refitted BLAS its root box (update_tlas builds the next TLAS from blas_lo / blas_hi), its chained
-// leaf_growth and its tree's cost as it lies now; then the scene's figures by refit_two_level's arithmetic in its order.  Blocks on the last refit's end.
+// leaf_growth and its tree's cost as it lies now; then the scene's figures by refit_two_level's fold (fold_blas_stats).  Blocks on the last refit's end.
 // wide_tree_cost runs on the context's stream, ordered behind the caller's stream only by the host's wait for ev_end: that rests on no refit being enqueued between the wait
 // and the cost kernel (the caller owes it: one thread drives a scene), and on update calls touching neither wnodes nor the cost words — they write pos and normals only.
 int resolve_blas_refits(DeviceScene &sc, const BuildOptions &opt, hipStream_t stream) {
@@ -699,7 +714,6 @@ int resolve_blas_refits(DeviceScene &sc, const BuildOptions &opt, hipStream_t st
     const size_t B = sc.blas_ranges.size();
     MRT_HIP(hipEventSynchronize(ws.ev_end));
     float ms = 0; MRT_HIP(hipEventElapsedTime(&ms, ws.ev_begin, ws.ev_end));
-    float growth_max = 1.0f; double sah = 0, wcost = 0;
     for (size_t b = 0; b < B; b++) {
         BlasRange &r = sc.blas_ranges[b];
         if (ws.refitted[b]) {
@@ -710,10 +724,8 @@ int resolve_blas_refits(DeviceScene &sc, const BuildOptions &opt, hipStream_t st
             if (int rc = wide_tree_cost(sc.wnodes.p, r.wnode_base, r.wnodes, r.wnode_base, opt.wide_cost_node, opt.wide_cost_tri, stream, ws.growth.p + 2 * B, &r.wide_cost)) return rc;
             ws.refitted[b] = 0;
         }
-        growth_max = std::max(growth_max, r.leaf_growth); wcost += r.wide_cost; sah += r.wide_cost_built > 0.0f ? r.sah_cost_built * (r.wide_cost / r.wide_cost_built) : r.sah_cost_built;
     }
-    sc.stats.build_ms = ms; sc.stats.wide_cost = (float)(wcost / (double)B); sc.stats.sah_cost = (float)(sah / (double)B);
-    sc.stats.refits = sc.refits; sc.stats.leaf_growth = growth_max;
+    fold_blas_stats(sc, ms);
     ws.unresolved = false;
     return MRT_OK;
 }
@@ -725,21 +737,14 @@ int download_stale_blas_meshes(std::vector<HostMesh> &meshes, DeviceScene &sc, b
     if (!sc.blas_ws) return MRT_OK;
     BlasWorkspace &ws = *sc.blas_ws;
     bool waited = false;
-    std::vector<float4> n4;
     for (size_t b = 0; b < sc.blas_ranges.size() && b < ws.host_stale.size(); b++) {
         const BlasRange &r = sc.blas_ranges[b];
         if (r.src_mesh >= meshes.size()) continue;
         HostMesh &m = meshes[r.src_mesh];
         if (ws.pending[b]) { m.dirty = true; ws.pending[b] = 0; if (pending_found) *pending_found = true; }
         if (!ws.host_stale[b]) continue;
-        if (!waited) { MRT_HIP(hipEventSynchronize(ws.ev_last)); waited = true; }
-        const size_t nv = m.positions.size() / 3;
-        if (nv) {
-            n4.resize(nv);
-            MRT_HIP(hipMemcpy(m.positions.data(), ws.pos.p + 3 * (size_t)r.vbase, nv * 12, hipMemcpyDeviceToHost));
-            MRT_HIP(hipMemcpy(n4.data(), sc.normals.p + r.vbase, nv * 16, hipMemcpyDeviceToHost));
-            for (size_t v = 0; v < nv; v++) { m.normals[3 * v] = n4[v].x; m.normals[3 * v + 1] = n4[v].y; m.normals[3 * v + 2] = n4[v].z; }
-        }
+        if (!waited) { MRT_HIP(hipEventSynchronize(ws.gate.ev_last)); waited = true; }
+        if (int rc = download_mesh_vertices(m, ws.pos.p + 3 * (size_t)r.vbase, sc.normals.p + r.vbase)) return rc;
         ws.host_stale[b] = 0;
     }
     return MRT_OK;

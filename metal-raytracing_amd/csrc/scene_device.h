@@ -225,10 +225,6 @@ struct BlasRange {
     float wide_cost = 0.0f, leaf_growth = 1.0f;              // leaf_growth: its leaf boxes' area against the build's, chained over its refits
 };
 
-// What the stream-ordered refit (mrt_scene_update_mesh_device / mrt_scene_refit_device) keeps on the device between calls, so that a call allocates nothing,
-// copies nothing from the host and waits for nothing: k_flatten's outputs (tri_world 48 B, tri_lo / tri_hi 32 B per triangle), the refit's node boxes (32 B per 8-wide node),
-// the rope refit's parent / arrived / ab (16 B per rope node), the dirty byte per flattened instance and a handful of words.  Made by the first device update after a build
-// (which may allocate), dropped by the next build and by mrt_scene_destroy.
 struct RefitLayouts { bool wide = false, rope = false; };          // which resident layouts a refit works on (refit_layouts)
 // One refit enqueue (enqueue_refit, bvh_refit.hip) for the commit of a flattened scene, a BLAS of a two-level scene and the stream-ordered refit: what is refitted ...
 struct RefitTarget {
@@ -242,36 +238,51 @@ struct RefitTarget {
     bool rope_every_leaf = false;                          // k_rope_refit recomputes every leaf (it gets neither tri_shade nor dirty)
 };
 // ... and the scratch it works in: k_flatten's outputs, a box per 8-wide node, the two growth sums, and per rope node its parent, arrival counter (zeroed) and {a, b} words
-struct RefitScratch { const float4 *tri_world, *tri_lo, *tri_hi; float4 *nbox; double *growth; uint32_t *parent, *arrived; uint2 *ab; };
-struct RefitWorkspace {
+struct RefitScratch { float4 *tri_world, *tri_lo, *tri_hi, *nbox; double *growth; uint32_t *parent, *arrived; uint2 *ab; };
+// What the three stream-ordered update families share: how an update call's check kernel refuses its input, and what a blocking reader waits for.
+// The owner allocates the two buffers (from its arena, or by alloc) and creates the event; the gate waits for the event before it goes.
+struct UpdateGate {
+    DevBuf<uint32_t> words;                                // [0]: sequence number of the last update call the device refused (k_ingest_check or k_inst_check)
+    DevBuf<unsigned long long> rejected;                   // update calls refused on the device since the workspace was made (sticky)
+    hipEvent_t ev_last = nullptr;                          // behind the last update or refit enqueued: what a blocking reader waits for
+    uint32_t seq = 0;                                      // update calls so far
+    ~UpdateGate() { if (ev_last) { (void)hipEventSynchronize(ev_last); (void)hipEventDestroy(ev_last); } }
+    uint32_t next() { if (++seq == 0u) seq = 1u; return seq; }          // (0 is what words[0] starts as)
+    hipError_t rejected_so_far(uint64_t *count) const {    // blocks on ev_last
+        *count = 0;
+        const hipError_t e = hipEventSynchronize(ev_last);
+        return e != hipSuccess ? e : hipMemcpy(count, rejected.p, 8, hipMemcpyDeviceToHost);
+    }
+};
+// The scratch of a refit, resident for a flattened scene (RefitWorkspace) and for the BLASes of a two-level one (BlasWorkspace): k_flatten's outputs (tri_world 48 B, tri_lo /
+// tri_hi 32 B per triangle), the refit's node boxes (32 B per 8-wide node), the rope refit's parent / arrived / ab (16 B per rope node), and what both keep per mesh on the host.
+struct RefitBuffers {
     ScratchArena arena;                                    // before the buffers that borrow from it
     DevBuf<float4> tri_world, tri_lo, tri_hi, nbox;
-    DevBuf<uint32_t> cbounds, parent, arrived;
-    DevBuf<uint32_t> words;                                // [0]: sequence number of the last update call whose input held a NaN or an infinity (k_ingest_check)
-    DevBuf<uint2> ab, ref_table;                           // ref_table: {flattened instance, its first vertex in g_pos / normals}, grouped by source mesh
-    DevBuf<double> growth;                                 // [0 .. 1]: k_refit_wide_level's sums of one refit (folded and cleared by k_refit_fold); [2 .. 5]: wide_tree_cost's 8 + 24 bytes
-    DevBuf<unsigned long long> rejected;                   // update calls refused on the device since the workspace was made (sticky)
-    DevBuf<float> leaf_growth;                             // MRTSceneStats.leaf_growth, chained on the device over the refits
+    DevBuf<uint32_t> cbounds, parent, arrived; DevBuf<uint2> ab;
+    DevBuf<double> growth;                                 // k_refit_wide_level's two sums per refitted tree (folded and cleared by k_refit_fold), then wide_tree_cost's 8 + 24 bytes
+    DevBuf<float> leaf_growth;                             // MRTSceneStats.leaf_growth (per BLAS: BlasRange::leaf_growth), chained on the device over the refits
+    std::vector<uint8_t> host_stale, pending;              // per mesh / BLAS: the HostMesh copy is older than the device's vertices; updated on the device and not yet refitted
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;       // around the last refit (MRTSceneStats.build_ms)
+    bool unresolved = false;                               // refits enqueued whose results the host has not read yet (resolve_device_refits, resolve_blas_refits)
+    ~RefitBuffers() { for (hipEvent_t e : {ev_begin, ev_end}) if (e) (void)hipEventDestroy(e); }
+    RefitScratch scratch(size_t growth_at = 0) const { return RefitScratch{tri_world.p, tri_lo.p, tri_hi.p, nbox.p, growth.p + growth_at, parent.p, arrived.p, ab.p}; }
+};
+// What the stream-ordered refit (mrt_scene_update_mesh_device / mrt_scene_refit_device) keeps on the device between calls, so that a call allocates nothing, copies nothing from the host and
+// waits for nothing: the scratch above, the dirty byte per flattened instance and a handful of words.  Made by the first device update after a build (which may allocate), dropped by the next build and by mrt_scene_destroy.
+struct RefitWorkspace : RefitBuffers {                     // growth: [0 .. 1] the sums, [2 .. 5] wide_tree_cost's
+    DevBuf<uint2> ref_table;                               // {flattened instance, its first vertex in g_pos / normals}, grouped by source mesh
     DevBuf<uint8_t> inst_dirty;                            // per flattened instance: its vertices were replaced since the last refit
     std::vector<uint32_t> ref_first, ref_count, mesh_vbase;   // per mesh of the scene: its range of ref_table (instances: empty), its first vertex
     std::vector<uint32_t> level_first;                     // first node of every level of the 8-wide tree
-    std::vector<uint8_t> host_stale, pending;              // per mesh: the HostMesh copy is older than the device's vertices; updated on the device and not yet refitted
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;       // around the last refit (MRTSceneStats.build_ms)
-    hipEvent_t ev_last = nullptr;                          // behind the last update or refit enqueued: what a blocking reader waits for
-    uint32_t seq = 0;                                      // update calls so far
     uint32_t instances = 0;
     RefitLayouts layouts;                                  // refit_layouts() of the tree the workspace was made for
-    bool unresolved = false;                               // refits enqueued whose statistics the host has not read yet (resolve_device_refits)
-    RefitWorkspace() = default;
-    RefitWorkspace(const RefitWorkspace &) = delete; RefitWorkspace &operator=(const RefitWorkspace &) = delete;
-    ~RefitWorkspace() { if (ev_last) (void)hipEventSynchronize(ev_last); for (hipEvent_t e : {ev_begin, ev_end, ev_last}) if (e) (void)hipEventDestroy(e); }
+    UpdateGate gate;                                       // (last: its destructor waits for the stream before anything above is freed)
 };
 
 // What the stream-ordered instance moves (mrt_scene_set_instance_transforms_device / mrt_scene_refit_instances_device, tlas_refit.hip) keep between calls.
 // Made by the first such call after a commit (which may allocate and block), dropped by the next commit's update_tlas and by mrt_scene_destroy.
 struct InstanceWorkspace {
-    DevBuf<uint32_t> words;                                // [0]: sequence number of the last set call the device refused (k_inst_check)
-    DevBuf<unsigned long long> rejected;                   // set calls refused on the device since the workspace was made (sticky)
     DevBuf<uint32_t> rope_order;                           // the rope TLAS's nodes grouped by depth (DeviceScene::tlas_rope_order)
     DevBuf<float4> nbox;                                   // the 8-wide TLAS refit's box per node (lo, hi)
     std::vector<uint32_t> rope_first;                      // first entry of every depth in rope_order
@@ -279,11 +290,7 @@ struct InstanceWorkspace {
     std::vector<uint8_t> moved;                            // per instance: the HostMesh::xf copy is older than the device's inst_cols
     DevBuf<uint32_t> wide_of_pos;                          // mrt_scene_rebuild_tlas_device (tlas_rebuild.hip): per leaf position of the binary median order, the entry of wtlas_index that names it (the inverse of DeviceScene::tlas_wide_pos)
     DevBuf<uint32_t> ids[2], seg_axis;                     // ... and, above TLAS_RESORT_LDS_LIMIT instances only, the ping-pong id buffers of its one-level-per-step part and the split axis per range of a level
-    hipEvent_t ev_last = nullptr;                          // behind the last set or refit enqueued: what a blocking reader waits for
-    uint32_t seq = 0;                                      // set calls so far
-    InstanceWorkspace() = default;
-    InstanceWorkspace(const InstanceWorkspace &) = delete; InstanceWorkspace &operator=(const InstanceWorkspace &) = delete;
-    ~InstanceWorkspace() { if (ev_last) { (void)hipEventSynchronize(ev_last); (void)hipEventDestroy(ev_last); } }
+    UpdateGate gate;                                       // (last, as RefitWorkspace's)
 };
 
 // What the stream-ordered BLAS refit of a two-level scene (mrt_scene_update_blas_device / mrt_scene_refit_blas_device) keeps between calls: the object-space
@@ -291,32 +298,19 @@ struct InstanceWorkspace {
 // for the largest BLAS (the BLASes are refitted in sequence on the stream), a box per 8-wide node of the whole shared array (refit indices are absolute) and a few words per
 // BLAS.  Made by the first such call after a commit from the HostMesh copies (which may allocate and block), kept by a transforms-only commit (update_tlas), dropped by
 // build_two_level, by refit_two_level (whose uploads would leave `pos` stale) and by mrt_scene_destroy.
-struct BlasWorkspace {
-    ScratchArena arena;                                    // before the buffers that borrow from it
+struct BlasWorkspace : RefitBuffers {                      // growth: [2b, 2b + 1] the sums of BLAS b, [2B .. 2B + 3] wide_tree_cost's; leaf_growth: per BLAS
     DevBuf<float> pos;                                     // packed positions of every BLAS's mesh, at 3 * BlasRange::vbase
     DevBuf<uint32_t> idx, recs;                            // per BLAS: its index list (at idx_first) and its SubRecs (at rec_first), BLAS-local as refit_blas uploads them
     DevBuf<float4> cols;                                   // the identity, for k_flatten
-    DevBuf<float4> tri_world, tri_lo, tri_hi, nbox;        // scratch of the largest BLAS; nbox: 2 per 8-wide node of the shared array
     DevBuf<uint4> tri_shade;                               // k_flatten's shading records of the BLAS's own numbering (scratch: the scene's are the build's)
-    DevBuf<uint32_t> cbounds, parent, arrived;
-    DevBuf<uint32_t> words;                                // [0]: sequence number of the last update call whose input held a NaN or an infinity (k_ingest_check)
-    DevBuf<uint2> ab, ref_table;                           // ref_table[b] = {0, vbase of BLAS b}: k_ingest_write's one-row table
+    DevBuf<uint2> ref_table;                               // ref_table[b] = {0, vbase of BLAS b}: k_ingest_write's one-row table
     DevBuf<uint32_t> inst_list;                            // instance ids grouped by BLAS (inst_first / inst_count)
-    DevBuf<double> growth;                                 // [2b, 2b + 1]: k_refit_wide_level's sums of BLAS b (folded and cleared by k_refit_fold); [2B .. 2B + 3]: wide_tree_cost's 8 + 24 bytes
-    DevBuf<unsigned long long> rejected;                   // update calls refused on the device since the workspace was made (sticky)
-    DevBuf<float> leaf_growth;                             // per BLAS: BlasRange::leaf_growth, chained on the device over the refits
     DevBuf<uint8_t> dirty;                                 // 4 bytes of 1: the one "instance" of a BLAS's own triangle arrays moved
     std::vector<int> blas_of_mesh;                         // per mesh known at the commit: its BLAS, -1 for an instance
     std::vector<uint32_t> idx_first, rec_first, rec_count, inst_first, inst_count;      // per BLAS
     std::vector<std::vector<uint32_t>> level_first;        // per BLAS: first node of every level of its 8-wide tree (absolute)
-    std::vector<uint8_t> host_stale, pending, refitted;    // per BLAS: the HostMesh copy is older than the device's vertices; updated and not yet refitted; refitted since the host last read its root box and statistics
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;       // around the last refit (MRTSceneStats.build_ms)
-    hipEvent_t ev_last = nullptr;                          // behind the last update or refit enqueued: what a blocking reader waits for
-    uint32_t seq = 0;                                      // update calls so far
-    bool unresolved = false;                               // refits enqueued whose results the host has not read yet (resolve_blas_refits)
-    BlasWorkspace() = default;
-    BlasWorkspace(const BlasWorkspace &) = delete; BlasWorkspace &operator=(const BlasWorkspace &) = delete;
-    ~BlasWorkspace() { if (ev_last) (void)hipEventSynchronize(ev_last); for (hipEvent_t e : {ev_begin, ev_end, ev_last}) if (e) (void)hipEventDestroy(e); }
+    std::vector<uint8_t> refitted;                         // per BLAS: refitted since the host last read its root box and statistics
+    UpdateGate gate;                                       // (last, as RefitWorkspace's)
 };
 
 // What the surface entries (mrt_scene_resolve_hits_device / mrt_scene_interpolate_device, surface.hip) keep between calls: one row per resource slot —
@@ -396,6 +390,9 @@ int wide_histogram(const DeviceScene &sc, hipStream_t stream, uint32_t out12[12]
 int wide_tree_cost(const float4 *wnodes, uint32_t first, uint32_t count, uint32_t root, float c_node, float c_tri, hipStream_t stream, void *scratch32, float *out);      // SAH cost of the 8-wide subtree [first, first + count) rooted at `root`, as it lies in memory, per unit of root area; scratch32: 32 bytes of device memory, 8-byte aligned (the caller's arena or workspace)
 RefitLayouts refit_layouts(const DeviceScene &sc, const BuildOptions &opt);
 void enqueue_refit(const RefitTarget &tg, const RefitScratch &s, hipStream_t stream);      // the five refit kernels on the stream, nothing else
+RefitTarget flat_refit_target(const DeviceScene &sc, RefitLayouts layouts, const uint32_t *level_first, const uint8_t *dirty);      // what a refit of a flattened scene works on: a refitting commit's and the stream-ordered refit's
+void fold_blas_stats(DeviceScene &sc, float ms);      // what BLAS refits leave in a two-level scene's statistics, from its BlasRanges: refit_two_level's and resolve_blas_refits'
+void retire_gate(DeviceScene &sc, UpdateGate &gate);      // blocks; a workspace goes: its rejected count is kept in sc.rejected_before
 int apply_refit_result(DeviceScene &sc, const BuildOptions &opt, bool wide, float ms, const float4 box[2], float leaf_growth, void *scratch32, hipStream_t stream);      // what a refit of a flattened scene leaves in sc.stats and the root box; blocks (wide_tree_cost)
 // the stream-ordered refit (bvh_refit.hip)
 int device_refit_supported(const DeviceScene &sc, const BuildOptions &opt, const char *who);      // MRT_OK, or MRT_ERR_UNSUPPORTED + message: what a refitting commit (build_flat) would not take

@@ -259,9 +259,7 @@ void enqueue_blas_instance_boxes(DeviceScene &sc, const float4 *nbox, uint32_t r
 }
 
 void drop_instance_workspace(DeviceScene &sc) {
-    if (!sc.inst_ws) return;
-    unsigned long long h = 0;
-    if (hipEventSynchronize(sc.inst_ws->ev_last) == hipSuccess && hipMemcpy(&h, sc.inst_ws->rejected.p, 8, hipMemcpyDeviceToHost) == hipSuccess) sc.rejected_before += h; else (void)hipGetLastError();
+    if (sc.inst_ws) retire_gate(sc, sc.inst_ws->gate);
     sc.inst_ws.reset();
 }
 
@@ -273,9 +271,9 @@ int instances_device_prepare(DeviceScene &sc) {
     for (uint32_t n : sc.tlas_rope_levels) { w->rope_first.push_back(at); at += n; }
     at = 0;
     for (uint32_t n : sc.tlas_wide_levels) { w->wide_first.push_back(at); at += n; }
-    MRT_HIP(w->words.alloc(4)); MRT_HIP(w->rejected.alloc(1));
+    MRT_HIP(w->gate.words.alloc(4)); MRT_HIP(w->gate.rejected.alloc(1));
     MRT_HIP(w->rope_order.alloc(sc.tlas_rope_order.size())); MRT_HIP(w->nbox.alloc(2 * std::max<size_t>(at, 1)));
-    MRT_HIP(hipMemset(w->words.p, 0, w->words.bytes())); MRT_HIP(hipMemset(w->rejected.p, 0, 8));
+    MRT_HIP(hipMemset(w->gate.words.p, 0, w->gate.words.bytes())); MRT_HIP(hipMemset(w->gate.rejected.p, 0, 8));
     if (!sc.tlas_rope_order.empty()) MRT_HIP(hipMemcpy(w->rope_order.p, sc.tlas_rope_order.data(), sc.tlas_rope_order.size() * 4, hipMemcpyHostToDevice));
     // what mrt_scene_rebuild_tlas_device adds (tlas_rebuild.hip): 4 bytes per instance, and 8 more above the LDS limit
     const uint32_t live = sc.tlas_instances;
@@ -289,21 +287,21 @@ int instances_device_prepare(DeviceScene &sc) {
         MRT_HIP(w->ids[0].alloc(live)); MRT_HIP(w->ids[1].alloc(live));
         MRT_HIP(w->seg_axis.alloc((live + TLAS_RESORT_LDS_LIMIT - 1) / TLAS_RESORT_LDS_LIMIT));          // (a level handled one step at a time has fewer ranges than that)
     }
-    MRT_HIP(hipEventCreateWithFlags(&w->ev_last, hipEventDisableTiming));
+    MRT_HIP(hipEventCreateWithFlags(&w->gate.ev_last, hipEventDisableTiming));
     MRT_HIP(hipDeviceSynchronize());          // (the first call after a commit may block: from here on the caller's stream finds the workspace as the lines above left it)
-    MRT_HIP(hipEventRecord(w->ev_last, nullptr));
+    MRT_HIP(hipEventRecord(w->gate.ev_last, nullptr));
     sc.inst_ws = std::move(w);
     return MRT_OK;
 }
 
 int device_set_instance_transforms(DeviceScene &sc, uint32_t first, uint32_t count, const void *d_xf, size_t stride, hipStream_t stream) {
     InstanceWorkspace &ws = *sc.inst_ws;
-    if (++ws.seq == 0u) ws.seq = 1u;          // (0 is what words[0] starts as)
+    const uint32_t seq = ws.gate.next();
     const dim3 grid(blocks_of(count, 64)), block(64);
-    hipLaunchKernelGGL(k_inst_check, grid, block, 0, stream, static_cast<const uint8_t *>(d_xf), stride, count, ws.seq, ws.words.p);
-    hipLaunchKernelGGL(k_inst_write, grid, block, 0, stream, static_cast<const uint8_t *>(d_xf), stride, first, count, ws.seq, (const uint32_t *)ws.words.p, ws.rejected.p, sc.inst_cols.p, sc.inst.p, sc.inst_box.p);
+    hipLaunchKernelGGL(k_inst_check, grid, block, 0, stream, static_cast<const uint8_t *>(d_xf), stride, count, seq, ws.gate.words.p);
+    hipLaunchKernelGGL(k_inst_write, grid, block, 0, stream, static_cast<const uint8_t *>(d_xf), stride, first, count, seq, (const uint32_t *)ws.gate.words.p, ws.gate.rejected.p, sc.inst_cols.p, sc.inst.p, sc.inst_box.p);
     MRT_HIP(hipGetLastError());
-    MRT_HIP(hipEventRecord(ws.ev_last, stream));
+    MRT_HIP(hipEventRecord(ws.gate.ev_last, stream));
     // (marked for a call the device refuses too: the host cannot know without a read-back, and the columns it then reads back are the ones it has)
     std::fill(ws.moved.begin() + first, ws.moved.begin() + first + count, (uint8_t)1);
     return MRT_OK;
@@ -319,7 +317,7 @@ int device_refit_instances(DeviceScene &sc, hipStream_t stream) {
             hipLaunchKernelGGL(k_tlas_wide_level, dim3(blocks_of(sc.tlas_wide_levels[L], 64)), dim3(64), 0, stream, sc.wnodes.p, (const uint32_t *)sc.wtlas_index.p, (const float4 *)sc.inst_box.p, ws.nbox.p,
                                ws.wide_first[L], sc.tlas_wide_levels[L]);
     MRT_HIP(hipGetLastError());
-    MRT_HIP(hipEventRecord(ws.ev_last, stream));
+    MRT_HIP(hipEventRecord(ws.gate.ev_last, stream));
     return MRT_OK;
 }
 
@@ -330,7 +328,7 @@ int download_moved_transforms(std::vector<HostMesh> &meshes, DeviceScene &sc, bo
     InstanceWorkspace &ws = *sc.inst_ws;
     const size_t known = std::min(ws.moved.size(), meshes.size());          // (meshes are only ever appended)
     if (std::find(ws.moved.begin(), ws.moved.begin() + known, (uint8_t)1) == ws.moved.begin() + known) return MRT_OK;
-    MRT_HIP(hipEventSynchronize(ws.ev_last));
+    MRT_HIP(hipEventSynchronize(ws.gate.ev_last));
     std::vector<float4> cols(4 * known);
     MRT_HIP(hipMemcpy(cols.data(), sc.inst_cols.p, cols.size() * 16, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < known; i++) {

@@ -640,26 +640,23 @@ int refit_two_level(const std::vector<HostMesh> &meshes, const BuildOptions &opt
     if (!two_level_refittable(out, meshes.size())) return MRT_ERR_UNSUPPORTED;
     for (const BlasRange &r : out.blas_ranges) if (r.src_mesh >= meshes.size() || (meshes[r.src_mesh].dirty && !blas_refittable(r, meshes[r.src_mesh].positions.size() / 3))) return MRT_ERR_UNSUPPORTED;
     drop_blas_workspace(out);          // (refit_blas uploads the changed meshes' vertices into scratch of its own: the workspace's resident copies would be stale.  The next mrt_scene_update_blas_device makes it again)
-    float ms_total = 0, growth_max = 1.0f; double sah = 0, wcost = 0;
+    float ms_total = 0;
     MRT_HIP(out.cost_words.alloc(4));          // wide_tree_cost's sum and root box: the scene's, allocated by its first refit and found by every later one
     for (size_t b = 0; b < out.blas_ranges.size(); b++) {
         BlasRange &r = out.blas_ranges[b];
-        if (meshes[r.src_mesh].dirty && r.ntri != 0) {
-            float ms = 0, gr = 1.0f;
-            if (int rc = refit_blas(meshes[r.src_mesh], r, stream, out, &out.blas_lo[3 * b], &out.blas_hi[3 * b], &ms, &gr)) return rc;
-            r.leaf_growth *= gr;
-            if (int rc = wide_tree_cost(out.wnodes.p, r.wnode_base, r.wnodes, r.wnode_base, opt.wide_cost_node, opt.wide_cost_tri, stream, out.cost_words.p, &r.wide_cost)) return rc;
-            ms_total += ms;
-        }
-        growth_max = std::max(growth_max, r.leaf_growth); wcost += r.wide_cost; sah += r.wide_cost_built > 0.0f ? r.sah_cost_built * (r.wide_cost / r.wide_cost_built) : r.sah_cost_built;
+        if (!meshes[r.src_mesh].dirty || r.ntri == 0) continue;
+        float ms = 0, gr = 1.0f;
+        if (int rc = refit_blas(meshes[r.src_mesh], r, stream, out, &out.blas_lo[3 * b], &out.blas_hi[3 * b], &ms, &gr)) return rc;
+        r.leaf_growth *= gr;
+        if (int rc = wide_tree_cost(out.wnodes.p, r.wnode_base, r.wnodes, r.wnode_base, opt.wide_cost_node, opt.wide_cost_tri, stream, out.cost_words.p, &r.wide_cost)) return rc;
+        ms_total += ms;
     }
     const MRTSceneStats before = out.stats;
+    fold_blas_stats(out, ms_total);          // (the refits are counted below, once the commit is certain)
     // scene option refit_max_cost_ratio: the refits have loosened the BLASes beyond that factor of their build-time cost — the caller builds the scene again
-    if (opt.refit_max_cost_ratio > 0.0f && before.wide_cost_built > 0.0f && ((float)(wcost / (double)out.blas_ranges.size()) > opt.refit_max_cost_ratio * before.wide_cost_built || growth_max > opt.refit_max_cost_ratio)) return MRT_ERR_UNSUPPORTED;
+    if (opt.refit_max_cost_ratio > 0.0f && before.wide_cost_built > 0.0f && (out.stats.wide_cost > opt.refit_max_cost_ratio * before.wide_cost_built || out.stats.leaf_growth > opt.refit_max_cost_ratio)) { out.stats = before; return MRT_ERR_UNSUPPORTED; }
     if (int rc = update_tlas(meshes, stream, out)) return rc;          // the instances' world boxes follow their BLAS's new root box
-    const size_t B = out.blas_ranges.size();
-    out.stats.build_ms = ms_total; out.stats.wide_cost = (float)(wcost / (double)B); out.stats.wide_cost_built = before.wide_cost_built; out.stats.sah_cost = (float)(sah / (double)B);
-    out.refits++; out.stats.refits = out.refits; out.stats.leaf_growth = growth_max;
+    out.stats.wide_cost_built = before.wide_cost_built; out.refits++; out.stats.refits = out.refits;
     return MRT_OK;
 }
 

@@ -52,7 +52,7 @@ def _links(ds):
 
 
 def _layout(ds):
-    return {p: ds.read_layout(p) for p in ("instances", "inst_box", "wnodes", "wpackets")}
+    return {p: ds.read_layout(p) for p in ("instances", "inst_box", "wnodes", "wpackets", "rope_nodes", "rope_packets")}          # (the rope arrays hold the BLASes only: compared in full)
 
 
 def _same_layout(a, b, n, what, tlas_too=False):

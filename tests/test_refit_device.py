@@ -88,8 +88,12 @@ def _canonical(ds):
     return np.array(nodes), np.array(packets)
 
 
-def _same_layout(a, b):
+def _same_layout(a, b, rope=False):
     assert a.stats.wide_layout == b.stats.wide_layout
+    if rope:          # the rope layout beside the 8-wide one or alone: every word of every node (boxes, links, escapes) and packet
+        for part in ("rope_nodes", "rope_packets"):
+            pa, pb = a.read_layout(part), b.read_layout(part)
+            assert pa.shape == pb.shape and len(pa) > 0 and np.array_equal(_bits(pa), _bits(pb)), part
     if a.stats.wide_layout:
         (na, pa), (nb, pb) = _canonical(a), _canonical(b)
         assert na.shape == nb.shape and len(na) > 0 and np.array_equal(na, nb), "wnodes"
@@ -151,7 +155,7 @@ def test_parity_with_the_host_path(mrt, orc, gpu_ctx, layout):
         gc = b.intersect_closest_device(d_rays); ga = b.intersect_any_device(d_rays)          # torch's current stream: behind the refit
         torch.cuda.synchronize()
         assert a.refits == step + 1 and b.refits == step + 1
-        _same_layout(a, b)
+        _same_layout(a, b, rope=layout != "wide")
         assert links is None or np.array_equal(_links(b), links), "a refit moves boxes, never the links between the nodes and to the packets"
         hc, ha = a.intersect_closest(r), a.intersect_any(r)
         _same_records(b.intersect_closest(r), hc, f"step {step} host entry ")
