@@ -161,6 +161,37 @@ struct Scene {                                                       // Scene.sw
         check(mrt_scene_scatter_materials_device(committed, deviceRays, deviceSurfaces, deviceHaltonIndex, n, bounce, maxBounces, lightCount, deviceShadowRays, deviceLight, deviceNextRays,
                                                  deviceLobes, hipStream));
     }
+    // Row queues between the stages (mrt_context_compact_rows_device and the *_device_counted twins of the six entries above): the rows of up to eight columns whose keep
+    // byte is not 0 moved to the front of the columns' destinations in their order, and their number left in *deviceCountOut, a uint32 ON THE DEVICE; the counted forms
+    // then take n as the capacity and handle the rows below min(n, *deviceCount), touching no other.  No host read, no allocation, no wait; the workspace
+    // (compactWorkspaceBytes(n) bytes, 16-byte aligned) is the caller's.  deviceCountIn may be nullptr (all n rows); `columns` is a host array of device pointers.
+    static size_t compactWorkspaceBytes(size_t n) { return mrt_compact_workspace_bytes(n); }
+    static void compactRowsDevice(MRTContext ctx, const void *deviceKeep, size_t n, const void *deviceCountIn, const MRTRowColumn *columns, int32_t columnCount, void *deviceCountOut,
+                                  void *deviceWorkspace, size_t workspaceBytes, void *hipStream) {
+        check(mrt_context_compact_rows_device(ctx, deviceKeep, n, deviceCountIn, columns, columnCount, deviceCountOut, deviceWorkspace, workspaceBytes, hipStream));
+    }
+    static void intersectClosestDeviceCounted(MRTScene committed, const void *deviceRays, size_t n, void *deviceOut, void *hipStream, const void *deviceCount) {
+        check(mrt_scene_intersect_closest_device_counted(committed, deviceRays, n, deviceOut, hipStream, deviceCount));
+    }
+    static void intersectAnyDeviceCounted(MRTScene committed, const void *deviceRays, size_t n, void *deviceOccluded, void *hipStream, const void *deviceCount) {
+        check(mrt_scene_intersect_any_device_counted(committed, deviceRays, n, deviceOccluded, hipStream, deviceCount));
+    }
+    static void resolveHitsDeviceCounted(MRTScene committed, const void *deviceRays, const void *deviceHits, size_t n, void *deviceSurfaces, void *hipStream, const void *deviceCount) {
+        check(mrt_scene_resolve_hits_device_counted(committed, deviceRays, deviceHits, n, deviceSurfaces, hipStream, deviceCount));
+    }
+    static void interpolateDeviceCounted(MRTScene committed, const void *deviceHits, size_t n, const void *deviceAttributes, size_t attributeStrideBytes, int32_t channels, void *deviceOut,
+                                         size_t outStrideBytes, void *hipStream, const void *deviceCount) {
+        check(mrt_scene_interpolate_device_counted(committed, deviceHits, n, deviceAttributes, attributeStrideBytes, channels, deviceOut, outStrideBytes, hipStream, deviceCount));
+    }
+    static void scatterDeviceCounted(MRTScene committed, const void *deviceSurfaces, const void *deviceHaltonIndex, size_t n, int32_t bounce, int32_t lightCount, void *deviceShadowRays,
+                                     void *deviceLight, void *deviceNextRays, void *hipStream, const void *deviceCount) {
+        check(mrt_scene_scatter_device_counted(committed, deviceSurfaces, deviceHaltonIndex, n, bounce, lightCount, deviceShadowRays, deviceLight, deviceNextRays, hipStream, deviceCount));
+    }
+    static void scatterMaterialsDeviceCounted(MRTScene committed, const void *deviceRays, const void *deviceSurfaces, const void *deviceHaltonIndex, size_t n, int32_t bounce, int32_t maxBounces,
+                                              int32_t lightCount, void *deviceShadowRays, void *deviceLight, void *deviceNextRays, void *deviceLobes, void *hipStream, const void *deviceCount) {
+        check(mrt_scene_scatter_materials_device_counted(committed, deviceRays, deviceSurfaces, deviceHaltonIndex, n, bounce, maxBounces, lightCount, deviceShadowRays, deviceLight,
+                                                         deviceNextRays, deviceLobes, hipStream, deviceCount));
+    }
     // each mesh's first attribute row (an instance reports its source's) and, last, the number of rows: meshCount + 1 entries
     static std::vector<uint64_t> vertexOffsets(MRTScene scene, size_t meshCount) {
         std::vector<uint64_t> o(meshCount + 1); check(mrt_scene_vertex_offsets(scene, o.data(), o.size())); return o;

@@ -442,6 +442,45 @@ int mrt_scene_scatter_materials_device(MRTScene scene, const void *d_rays /* n x
                                        int32_t bounce, int32_t max_bounces, int32_t light_count, void *d_shadow_rays /* n x MRTRay */, void *d_light /* n x 4 float32 */,
                                        void *d_next_rays /* n x MRTRay, may be NULL */, void *d_lobes /* n x MRTScatterLobe */, void *hip_stream);
 
+/* Row queues on DEVICE buffers, ordered on a stream of the caller's: what a wavefront integrator needs between two of the stage entries above — the rows
+ * that go on (the surviving paths, the wanted shadow rays) moved to the front of their buffers, and their number left in a word ON THE DEVICE that the next stage reads.
+ *   mrt_context_compact_rows_device: with m = min(n, *d_count_in) (n when d_count_in is NULL) and k_0 < k_1 < ... the rows i < m whose byte d_keep[i] is not 0,
+ *     *d_count_out is their number and, for each of the `ncolumns` (0 .. 8) columns, dst row j is src row k_j, byte for byte: the ORDER IS KEPT (what x[:m][mask[:m]] gives),
+ *     so a frame composed from queues is the same from run to run.  A column is {src, dst, row_bytes}: row_bytes a multiple of 4 in 4 .. 64; src and dst 16-byte aligned
+ *     where row_bytes is a multiple of 16 (the rows then move as 16-byte vectors), 4-byte aligned otherwise (dwords).  dst rows from *d_count_out on are neither read nor
+ *     written; src, d_keep and d_count_in are only read.  ncolumns == 0 is a count alone.  `columns` is a HOST array, read during the call; the pointers in it, d_keep
+ *     (n x uint8; a torch.bool tensor is one), d_count_in, d_count_out (one uint32 each, 4-byte aligned) and d_workspace are device pointers.  The count word is read as
+ *     unsigned: one above n, or negative, is clamped to n.
+ *     d_workspace is the call's scratch memory: at least mrt_compact_workspace_bytes(n) bytes (4 bytes per 2048 rows, rounded up to 16; never 0; it does not decrease with
+ *     n), 16-byte aligned, the caller's — nothing hides inside the handle, so two streams may compact at once, each with a workspace of its own.
+ *     Three kernels on hip_stream — count per workgroup, one scan of the totals, the move — and nothing else: no allocation, no copy from host memory, no wait, no atomics,
+ *     and no workgroup ever waits for another.  hip_stream is taken literally (0 is HIP's null stream).  The caller owes buffers on the context's device that stay alive until
+ *     the stream has passed the call.
+ *     Plain arguments are checked first, the message names the argument, and a NULL context is refused last.  MRT_ERR_INVALID_ARGUMENT: n >= 2^31; NULL d_keep, d_count_out
+ *     or d_workspace with n > 0; d_count_in or d_count_out not 4-byte aligned; d_count_out == d_count_in; ncolumns outside 0 .. 8, NULL columns with ncolumns > 0; a
+ *     row_bytes that is 0, above 64 or no multiple of 4; a misaligned or NULL src or dst; a dst range [dst, dst + n * row_bytes) that overlaps its own src range, another
+ *     column's dst range, d_keep or either count word; a workspace that is misaligned or too small.  n == 0: 0 is written to *d_count_out (where it is given), MRT_OK.
+ *   The *_device_counted entries are their twins above with one more argument, d_count: one uint32 on the device, 4-byte aligned, REQUIRED (the twin is the form without
+ *     it).  n is then the CAPACITY of the buffers: the kernels handle the rows i < min(n, *d_count) — the word is read as unsigned, once, when a kernel starts; too large or
+ *     negative is clamped to n — and give for them exactly what the twin writes for them; no row from there on is read or written.  Everything else is the twin's:
+ *     arguments, refusal rules and their order (d_count is looked at first), first-call behaviour, which walk a ray takes.  Grids are sized by n: a workgroup past the
+ *     count leaves at once, so a call costs its launch however short the queue.                                                                                          */
+typedef struct { const void *src; void *dst; uint32_t row_bytes; uint32_t _pad; } MRTRowColumn;   /* 24 B */
+size_t mrt_compact_workspace_bytes(size_t n);
+int mrt_context_compact_rows_device(MRTContext ctx, const void *d_keep /* n x uint8, non-zero keeps */, size_t n, const void *d_count_in /* 1 x uint32, may be NULL */,
+                                    const MRTRowColumn *columns, int32_t ncolumns /* 0 .. 8 */, void *d_count_out /* 1 x uint32 */, void *d_workspace, size_t workspace_bytes,
+                                    void *hip_stream);
+int mrt_scene_intersect_closest_device_counted(MRTScene scene, const void *d_rays, size_t n, void *d_out, void *hip_stream, const void *d_count);
+int mrt_scene_intersect_any_device_counted(MRTScene scene, const void *d_rays, size_t n, void *d_occluded, void *hip_stream, const void *d_count);
+int mrt_scene_resolve_hits_device_counted(MRTScene scene, const void *d_rays, const void *d_hits, size_t n, void *d_surfaces, void *hip_stream, const void *d_count);
+int mrt_scene_interpolate_device_counted(MRTScene scene, const void *d_hits, size_t n, const void *d_attributes, size_t attr_stride_bytes, int32_t channels,
+                                         void *d_out, size_t out_stride_bytes, void *hip_stream, const void *d_count);
+int mrt_scene_scatter_device_counted(MRTScene scene, const void *d_surfaces, const void *d_halton_index, size_t n, int32_t bounce, int32_t light_count,
+                                     void *d_shadow_rays, void *d_light, void *d_next_rays /* may be NULL */, void *hip_stream, const void *d_count);
+int mrt_scene_scatter_materials_device_counted(MRTScene scene, const void *d_rays, const void *d_surfaces, const void *d_halton_index, size_t n, int32_t bounce, int32_t max_bounces,
+                                               int32_t light_count, void *d_shadow_rays, void *d_light, void *d_next_rays /* may be NULL */, void *d_lobes, void *hip_stream,
+                                               const void *d_count);
+
 /* ---------------------------------------------------------------- host-side geometry helpers
  * (no GPU needed) — the library's OBJ/MTL reader standing in for ModelIO (Model.swift:16-21,
  * SubMesh.swift:37-54) and the procedural dragon proxy (dragon.obj is absent upstream).        */

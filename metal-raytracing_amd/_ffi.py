@@ -103,6 +103,10 @@ class ScatterLobe(C.Structure):  # MRTScatterLobe (include/mrt_abi.h; no counter
     _fields_ = [("weight", C.c_float * 3), ("lobe", C.c_int32), ("emission", C.c_float * 3), ("_pad", C.c_int32)]
 
 
+class RowColumn(C.Structure):  # MRTRowColumn (include/mrt_abi.h): one column of mrt_context_compact_rows_device
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class SceneStats(C.Structure):
     _fields_ = [("triangles", C.c_uint64), ("vertices", C.c_uint64), ("bvh_nodes", C.c_uint64), ("bvh_leaves", C.c_uint64),
                 ("scene_bytes", C.c_uint64), ("build_ms", C.c_float), ("sah_cost", C.c_float), ("instances", C.c_int32),
@@ -133,6 +137,7 @@ DENOISE_DEFAULTS = {"iterations": 5, "sigma_color": 4.0, "sigma_normal": 0.25, "
 
 assert C.sizeof(Camera) == 64 and C.sizeof(Light) == 128 and C.sizeof(Uniforms) == 96 and C.sizeof(Material) == 64
 assert C.sizeof(Ray) == 32 and C.sizeof(Intersection) == 32 and C.sizeof(DenoiseParams) == 32 and C.sizeof(Surface) == 64 and C.sizeof(ScatterLobe) == 32
+assert C.sizeof(RowColumn) == 24
 
 # ---------------------------------------------------------------- function table: every symbol include/mrt_abi.h declares
 _P, _I32, _U32, _F, _SZ = C.c_void_p, C.c_int32, C.c_uint32, C.c_float, C.c_size_t
@@ -176,6 +181,14 @@ SIGNATURES = {
     "mrt_scene_vertex_offsets": (C.c_int, [_P, C.POINTER(C.c_uint64), _SZ]),
     "mrt_scene_scatter_device": (C.c_int, [_P, _P, _P, _SZ, _I32, _I32, _P, _P, _P, _P]),
     "mrt_scene_scatter_materials_device": (C.c_int, [_P, _P, _P, _P, _SZ, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "mrt_compact_workspace_bytes": (_SZ, [_SZ]),
+    "mrt_context_compact_rows_device": (C.c_int, [_P, _P, _SZ, _P, C.POINTER(RowColumn), _I32, _P, _P, _SZ, _P]),
+    "mrt_scene_intersect_closest_device_counted": (C.c_int, [_P, _P, _SZ, _P, _P, _P]),
+    "mrt_scene_intersect_any_device_counted": (C.c_int, [_P, _P, _SZ, _P, _P, _P]),
+    "mrt_scene_resolve_hits_device_counted": (C.c_int, [_P, _P, _P, _SZ, _P, _P, _P]),
+    "mrt_scene_interpolate_device_counted": (C.c_int, [_P, _P, _SZ, _P, _SZ, _I32, _P, _SZ, _P, _P]),
+    "mrt_scene_scatter_device_counted": (C.c_int, [_P, _P, _P, _SZ, _I32, _I32, _P, _P, _P, _P, _P]),
+    "mrt_scene_scatter_materials_device_counted": (C.c_int, [_P, _P, _P, _P, _SZ, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "mrt_obj_load": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "mrt_dragon_proxy": (C.c_int, [C.POINTER(_P)]),
     "mrt_dragon_proxy_irregular": (C.c_int, [C.POINTER(_P)]),

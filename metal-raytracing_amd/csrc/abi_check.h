@@ -35,6 +35,9 @@ MRT_AT(MRTSurface, base_color, 32); MRT_AT(MRTSurface, resource_slot, 44); MRT_A
 // lobe rows (mrt_scene_scatter_materials_device; no counterpart in ShaderTypes.h): two 16-byte groups
 static_assert(sizeof(MRTScatterLobe) == 32, "MRTScatterLobe is 32 bytes");
 MRT_AT(MRTScatterLobe, weight, 0); MRT_AT(MRTScatterLobe, lobe, 12); MRT_AT(MRTScatterLobe, emission, 16); MRT_AT(MRTScatterLobe, _pad, 28);
+// a column of mrt_context_compact_rows_device (no counterpart in ShaderTypes.h): two pointers, the row's size, padding
+static_assert(sizeof(MRTRowColumn) == 24, "MRTRowColumn is 24 bytes");
+MRT_AT(MRTRowColumn, src, 0); MRT_AT(MRTRowColumn, dst, 8); MRT_AT(MRTRowColumn, row_bytes, 16); MRT_AT(MRTRowColumn, _pad, 20);
 // denoiser parameters (no counterpart in ShaderTypes.h)
 static_assert(sizeof(MRTDenoiseParams) == 32, "MRTDenoiseParams is 32 bytes");
 MRT_AT(MRTDenoiseParams, iterations, 0); MRT_AT(MRTDenoiseParams, sigma_color, 4); MRT_AT(MRTDenoiseParams, sigma_normal, 8);

@@ -377,13 +377,31 @@ int mrt_scene_intersect_any(MRTScene scene, const MRTRay *rays, size_t n, int32_
     MRT_CATCH
 }
 // The stream-ordered forms: device buffers, the caller's stream (0 = HIP's null stream), two launches and nothing else.
-static int intersect_device(const char *who, MRTScene scene, const void *d_rays, size_t n, void *d_out, void *hip_stream, bool any) {
+// The *_device_counted twins share their twin's body and pass one more pointer: the row count on the device, required there and looked at first.
+static int check_count_word(const char *who, const void *d_count, bool counted) {
+    if (!counted) return MRT_OK;
+    REQUIRE(d_count, std::string(who) + ": d_count is NULL (one uint32 on the device; the entry without _counted takes none)");
+    REQUIRE((uintptr_t)d_count % 4 == 0, std::string(who) + ": d_count must be 4-byte aligned");
+    return MRT_OK;
+}
+static int intersect_device(const char *who, MRTScene scene, const void *d_rays, size_t n, void *d_out, void *hip_stream, bool any, const void *d_count = nullptr, bool counted = false) {
+    if (int rc = check_count_word(who, d_count, counted)) return rc;
     if (!(scene && (n == 0 || (d_rays && d_out)))) { mrt::set_error(std::string(who) + ": bad argument"); return MRT_ERR_INVALID_ARGUMENT; }
     if (n >= (size_t(1) << 31)) { mrt::set_error(std::string(who) + ": too many rays (n must be below 2^31)"); return MRT_ERR_INVALID_ARGUMENT; }
     if (!scene->committed) { mrt::set_error(std::string(who) + ": scene not committed"); return MRT_ERR_STATE; }
     if (n == 0) return MRT_OK;
     int rc = bind_device(scene->ctx); if (rc) return rc;
-    return any ? mrt::query_any_device(scene->dev, (hipStream_t)hip_stream, d_rays, n, d_out) : mrt::query_closest_device(scene->dev, (hipStream_t)hip_stream, d_rays, n, d_out);
+    return any ? mrt::query_any_device(scene->dev, (hipStream_t)hip_stream, d_rays, n, d_out, d_count) : mrt::query_closest_device(scene->dev, (hipStream_t)hip_stream, d_rays, n, d_out, d_count);
+}
+int mrt_scene_intersect_closest_device_counted(MRTScene scene, const void *d_rays, size_t n, void *d_out, void *hip_stream, const void *d_count) {
+    MRT_TRY
+    return intersect_device("mrt_scene_intersect_closest_device_counted", scene, d_rays, n, d_out, hip_stream, false, d_count, true);
+    MRT_CATCH
+}
+int mrt_scene_intersect_any_device_counted(MRTScene scene, const void *d_rays, size_t n, void *d_occluded, void *hip_stream, const void *d_count) {
+    MRT_TRY
+    return intersect_device("mrt_scene_intersect_any_device_counted", scene, d_rays, n, d_occluded, hip_stream, true, d_count, true);
+    MRT_CATCH
 }
 int mrt_scene_intersect_closest_device(MRTScene scene, const void *d_rays, size_t n, void *d_out, void *hip_stream) {
     MRT_TRY
@@ -521,32 +539,51 @@ static int surface_prologue(const char *who, MRTScene scene, size_t n) {
     if (!scene->committed) { mrt::set_error(std::string(who) + ": scene not committed"); return MRT_ERR_STATE; }
     return MRT_OK;
 }
-int mrt_scene_resolve_hits_device(MRTScene scene, const void *d_rays, const void *d_hits, size_t n, void *d_surfaces, void *hip_stream) {
-    MRT_TRY
-    const char *who = "mrt_scene_resolve_hits_device";
-    REQUIRE(n == 0 || (d_rays && d_hits && d_surfaces), "mrt_scene_resolve_hits_device: NULL buffers");
-    REQUIRE((uintptr_t)d_rays % 16 == 0 && (uintptr_t)d_hits % 16 == 0 && (uintptr_t)d_surfaces % 16 == 0, "mrt_scene_resolve_hits_device: buffers must be 16-byte aligned");
+static int resolve_hits_entry(const char *who, MRTScene scene, const void *d_rays, const void *d_hits, size_t n, void *d_surfaces, void *hip_stream, const void *d_count, bool counted) {
+    if (int rc = check_count_word(who, d_count, counted)) return rc;
+    REQUIRE(n == 0 || (d_rays && d_hits && d_surfaces), std::string(who) + ": NULL buffers");
+    REQUIRE((uintptr_t)d_rays % 16 == 0 && (uintptr_t)d_hits % 16 == 0 && (uintptr_t)d_surfaces % 16 == 0, std::string(who) + ": buffers must be 16-byte aligned");
     if (int rc = surface_prologue(who, scene, n)) return rc;
     if (n == 0) return MRT_OK;
     if (int rc = bind_device(scene->ctx)) return rc;
     if (int rc = mrt::surface_prepare(scene->meshes, scene->dev)) return rc;          // (the first call after a commit makes the slot table; later ones find it)
-    return mrt::resolve_hits_device(scene->dev, (hipStream_t)hip_stream, d_rays, d_hits, n, d_surfaces);
+    return mrt::resolve_hits_device(scene->dev, (hipStream_t)hip_stream, d_rays, d_hits, n, d_surfaces, d_count);
+}
+int mrt_scene_resolve_hits_device(MRTScene scene, const void *d_rays, const void *d_hits, size_t n, void *d_surfaces, void *hip_stream) {
+    MRT_TRY
+    return resolve_hits_entry("mrt_scene_resolve_hits_device", scene, d_rays, d_hits, n, d_surfaces, hip_stream, nullptr, false);
     MRT_CATCH
 }
-int mrt_scene_interpolate_device(MRTScene scene, const void *d_hits, size_t n, const void *d_attributes, size_t attr_stride, int32_t channels, void *d_out, size_t out_stride, void *hip_stream) {
+int mrt_scene_resolve_hits_device_counted(MRTScene scene, const void *d_rays, const void *d_hits, size_t n, void *d_surfaces, void *hip_stream, const void *d_count) {
     MRT_TRY
-    const char *who = "mrt_scene_interpolate_device";
-    REQUIRE(channels >= 1 && channels <= 64, "mrt_scene_interpolate_device: channels must be 1 .. 64");
-    REQUIRE(attr_stride >= 4 * (size_t)channels && out_stride >= 4 * (size_t)channels, "mrt_scene_interpolate_device: a row stride is below 4 x channels bytes");
-    REQUIRE(attr_stride % 4 == 0 && out_stride % 4 == 0, "mrt_scene_interpolate_device: row strides must be multiples of 4");
-    REQUIRE(n == 0 || (d_hits && d_attributes && d_out), "mrt_scene_interpolate_device: NULL buffers");
-    REQUIRE((uintptr_t)d_hits % 16 == 0, "mrt_scene_interpolate_device: the hit records must be 16-byte aligned");
-    REQUIRE((uintptr_t)d_attributes % 4 == 0 && (uintptr_t)d_out % 4 == 0, "mrt_scene_interpolate_device: attributes and output must be 4-byte aligned");
-    if (int rc = surface_prologue(who, scene, n)) return rc;
+    return resolve_hits_entry("mrt_scene_resolve_hits_device_counted", scene, d_rays, d_hits, n, d_surfaces, hip_stream, d_count, true);
+    MRT_CATCH
+}
+static int interpolate_entry(const char *who_c, MRTScene scene, const void *d_hits, size_t n, const void *d_attributes, size_t attr_stride, int32_t channels, void *d_out, size_t out_stride, void *hip_stream,
+                             const void *d_count, bool counted) {
+    const std::string who(who_c);
+    if (int rc = check_count_word(who_c, d_count, counted)) return rc;
+    REQUIRE(channels >= 1 && channels <= 64, who + ": channels must be 1 .. 64");
+    REQUIRE(attr_stride >= 4 * (size_t)channels && out_stride >= 4 * (size_t)channels, who + ": a row stride is below 4 x channels bytes");
+    REQUIRE(attr_stride % 4 == 0 && out_stride % 4 == 0, who + ": row strides must be multiples of 4");
+    REQUIRE(n == 0 || (d_hits && d_attributes && d_out), who + ": NULL buffers");
+    REQUIRE((uintptr_t)d_hits % 16 == 0, who + ": the hit records must be 16-byte aligned");
+    REQUIRE((uintptr_t)d_attributes % 4 == 0 && (uintptr_t)d_out % 4 == 0, who + ": attributes and output must be 4-byte aligned");
+    if (int rc = surface_prologue(who_c, scene, n)) return rc;
     if (n == 0) return MRT_OK;
     if (int rc = bind_device(scene->ctx)) return rc;
     if (int rc = mrt::surface_prepare(scene->meshes, scene->dev)) return rc;
-    return mrt::interpolate_device(scene->dev, (hipStream_t)hip_stream, d_hits, n, d_attributes, attr_stride, (uint32_t)channels, d_out, out_stride);
+    return mrt::interpolate_device(scene->dev, (hipStream_t)hip_stream, d_hits, n, d_attributes, attr_stride, (uint32_t)channels, d_out, out_stride, d_count);
+}
+int mrt_scene_interpolate_device(MRTScene scene, const void *d_hits, size_t n, const void *d_attributes, size_t attr_stride, int32_t channels, void *d_out, size_t out_stride, void *hip_stream) {
+    MRT_TRY
+    return interpolate_entry("mrt_scene_interpolate_device", scene, d_hits, n, d_attributes, attr_stride, channels, d_out, out_stride, hip_stream, nullptr, false);
+    MRT_CATCH
+}
+int mrt_scene_interpolate_device_counted(MRTScene scene, const void *d_hits, size_t n, const void *d_attributes, size_t attr_stride, int32_t channels, void *d_out, size_t out_stride, void *hip_stream,
+                                         const void *d_count) {
+    MRT_TRY
+    return interpolate_entry("mrt_scene_interpolate_device_counted", scene, d_hits, n, d_attributes, attr_stride, channels, d_out, out_stride, hip_stream, d_count, true);
     MRT_CATCH
 }
 int mrt_scene_vertex_offsets(MRTScene scene, uint64_t *offsets, size_t count) {
@@ -571,37 +608,107 @@ static int scatter_prologue(const char *who, MRTScene scene, size_t n, int32_t l
     *done = false;
     return bind_device(scene->ctx);
 }
+static int scatter_entry(const char *who_c, MRTScene scene, const void *d_surfaces, const void *d_halton_index, size_t n, int32_t bounce, int32_t light_count, void *d_shadow_rays, void *d_light,
+                         void *d_next_rays, void *hip_stream, const void *d_count, bool counted) {
+    const std::string who(who_c);
+    if (int rc = check_count_word(who_c, d_count, counted)) return rc;
+    REQUIRE(n == 0 || (d_surfaces && d_halton_index && d_shadow_rays && d_light), who + ": NULL buffers (d_surfaces, d_halton_index, d_shadow_rays and d_light are required; only d_next_rays may be NULL)");
+    REQUIRE((uintptr_t)d_surfaces % 16 == 0 && (uintptr_t)d_shadow_rays % 16 == 0 && (uintptr_t)d_light % 16 == 0 && (uintptr_t)d_next_rays % 16 == 0,
+            who + ": d_surfaces, d_shadow_rays, d_light and d_next_rays must be 16-byte aligned");
+    REQUIRE((uintptr_t)d_halton_index % 4 == 0, who + ": d_halton_index must be 4-byte aligned");
+    REQUIRE(bounce >= 0 && bounce <= 18, who + ": bounce must be in [0, 18] (Halton dimensions 2 + 5 * bounce .. + 4 of a table of 100 primes)");
+    bool done = false;
+    if (const int rc = scatter_prologue(who_c, scene, n, light_count, &done); rc || done) return rc;
+    return mrt::scatter_device(scene->dev, (hipStream_t)hip_stream, d_surfaces, d_halton_index, n, bounce, light_count > 0 ? light_count : scene->dev.light_count, d_shadow_rays, d_light, d_next_rays, d_count);
+}
 int mrt_scene_scatter_device(MRTScene scene, const void *d_surfaces, const void *d_halton_index, size_t n, int32_t bounce, int32_t light_count, void *d_shadow_rays, void *d_light,
                              void *d_next_rays, void *hip_stream) {
     MRT_TRY
-    const char *who = "mrt_scene_scatter_device";
-    REQUIRE(n == 0 || (d_surfaces && d_halton_index && d_shadow_rays && d_light), "mrt_scene_scatter_device: NULL buffers (d_surfaces, d_halton_index, d_shadow_rays and d_light are required; only d_next_rays may be NULL)");
-    REQUIRE((uintptr_t)d_surfaces % 16 == 0 && (uintptr_t)d_shadow_rays % 16 == 0 && (uintptr_t)d_light % 16 == 0 && (uintptr_t)d_next_rays % 16 == 0,
-            "mrt_scene_scatter_device: d_surfaces, d_shadow_rays, d_light and d_next_rays must be 16-byte aligned");
-    REQUIRE((uintptr_t)d_halton_index % 4 == 0, "mrt_scene_scatter_device: d_halton_index must be 4-byte aligned");
-    REQUIRE(bounce >= 0 && bounce <= 18, "mrt_scene_scatter_device: bounce must be in [0, 18] (Halton dimensions 2 + 5 * bounce .. + 4 of a table of 100 primes)");
-    bool done = false;
-    if (const int rc = scatter_prologue(who, scene, n, light_count, &done); rc || done) return rc;
-    return mrt::scatter_device(scene->dev, (hipStream_t)hip_stream, d_surfaces, d_halton_index, n, bounce, light_count > 0 ? light_count : scene->dev.light_count, d_shadow_rays, d_light, d_next_rays);
+    return scatter_entry("mrt_scene_scatter_device", scene, d_surfaces, d_halton_index, n, bounce, light_count, d_shadow_rays, d_light, d_next_rays, hip_stream, nullptr, false);
+    MRT_CATCH
+}
+int mrt_scene_scatter_device_counted(MRTScene scene, const void *d_surfaces, const void *d_halton_index, size_t n, int32_t bounce, int32_t light_count, void *d_shadow_rays, void *d_light,
+                                     void *d_next_rays, void *hip_stream, const void *d_count) {
+    MRT_TRY
+    return scatter_entry("mrt_scene_scatter_device_counted", scene, d_surfaces, d_halton_index, n, bounce, light_count, d_shadow_rays, d_light, d_next_rays, hip_stream, d_count, true);
     MRT_CATCH
 }
 
 // The same step with the materials extension on (stages_materials.hip): mrt_scene_scatter_device's rules, plus the incoming rays, the lobe rows and max_bounces
+static int scatter_materials_entry(const char *who_c, MRTScene scene, const void *d_rays, const void *d_surfaces, const void *d_halton_index, size_t n, int32_t bounce, int32_t max_bounces, int32_t light_count,
+                                   void *d_shadow_rays, void *d_light, void *d_next_rays, void *d_lobes, void *hip_stream, const void *d_count, bool counted) {
+    const std::string who(who_c);
+    if (int rc = check_count_word(who_c, d_count, counted)) return rc;
+    REQUIRE(n == 0 || (d_rays && d_surfaces && d_halton_index && d_shadow_rays && d_light && d_lobes),
+            who + ": NULL buffers (d_rays, d_surfaces, d_halton_index, d_shadow_rays, d_light and d_lobes are required; only d_next_rays may be NULL)");
+    REQUIRE((uintptr_t)d_rays % 16 == 0 && (uintptr_t)d_surfaces % 16 == 0 && (uintptr_t)d_shadow_rays % 16 == 0 && (uintptr_t)d_light % 16 == 0 && (uintptr_t)d_next_rays % 16 == 0 && (uintptr_t)d_lobes % 16 == 0,
+            who + ": d_rays, d_surfaces, d_shadow_rays, d_light, d_next_rays and d_lobes must be 16-byte aligned");
+    REQUIRE((uintptr_t)d_halton_index % 4 == 0, who + ": d_halton_index must be 4-byte aligned");
+    REQUIRE(max_bounces >= 1 && max_bounces <= 16, who + ": max_bounces must be in [1, 16] (the lobe choice uses Halton dimension 2 + 5 * max_bounces + bounce of a table of 100 primes)");
+    REQUIRE(bounce >= 0 && bounce < max_bounces, who + ": bounce must be in [0, max_bounces)");
+    bool done = false;
+    if (const int rc = scatter_prologue(who_c, scene, n, light_count, &done); rc || done) return rc;
+    return mrt::scatter_materials_device(scene->dev, (hipStream_t)hip_stream, d_rays, d_surfaces, d_halton_index, n, bounce, max_bounces, light_count > 0 ? light_count : scene->dev.light_count,
+                                         d_shadow_rays, d_light, d_next_rays, d_lobes, d_count);
+}
 int mrt_scene_scatter_materials_device(MRTScene scene, const void *d_rays, const void *d_surfaces, const void *d_halton_index, size_t n, int32_t bounce, int32_t max_bounces, int32_t light_count,
                                        void *d_shadow_rays, void *d_light, void *d_next_rays, void *d_lobes, void *hip_stream) {
     MRT_TRY
-    const char *who = "mrt_scene_scatter_materials_device";
-    REQUIRE(n == 0 || (d_rays && d_surfaces && d_halton_index && d_shadow_rays && d_light && d_lobes),
-            "mrt_scene_scatter_materials_device: NULL buffers (d_rays, d_surfaces, d_halton_index, d_shadow_rays, d_light and d_lobes are required; only d_next_rays may be NULL)");
-    REQUIRE((uintptr_t)d_rays % 16 == 0 && (uintptr_t)d_surfaces % 16 == 0 && (uintptr_t)d_shadow_rays % 16 == 0 && (uintptr_t)d_light % 16 == 0 && (uintptr_t)d_next_rays % 16 == 0 && (uintptr_t)d_lobes % 16 == 0,
-            "mrt_scene_scatter_materials_device: d_rays, d_surfaces, d_shadow_rays, d_light, d_next_rays and d_lobes must be 16-byte aligned");
-    REQUIRE((uintptr_t)d_halton_index % 4 == 0, "mrt_scene_scatter_materials_device: d_halton_index must be 4-byte aligned");
-    REQUIRE(max_bounces >= 1 && max_bounces <= 16, "mrt_scene_scatter_materials_device: max_bounces must be in [1, 16] (the lobe choice uses Halton dimension 2 + 5 * max_bounces + bounce of a table of 100 primes)");
-    REQUIRE(bounce >= 0 && bounce < max_bounces, "mrt_scene_scatter_materials_device: bounce must be in [0, max_bounces)");
-    bool done = false;
-    if (const int rc = scatter_prologue(who, scene, n, light_count, &done); rc || done) return rc;
-    return mrt::scatter_materials_device(scene->dev, (hipStream_t)hip_stream, d_rays, d_surfaces, d_halton_index, n, bounce, max_bounces, light_count > 0 ? light_count : scene->dev.light_count,
-                                         d_shadow_rays, d_light, d_next_rays, d_lobes);
+    return scatter_materials_entry("mrt_scene_scatter_materials_device", scene, d_rays, d_surfaces, d_halton_index, n, bounce, max_bounces, light_count, d_shadow_rays, d_light, d_next_rays, d_lobes, hip_stream,
+                                   nullptr, false);
+    MRT_CATCH
+}
+int mrt_scene_scatter_materials_device_counted(MRTScene scene, const void *d_rays, const void *d_surfaces, const void *d_halton_index, size_t n, int32_t bounce, int32_t max_bounces, int32_t light_count,
+                                               void *d_shadow_rays, void *d_light, void *d_next_rays, void *d_lobes, void *hip_stream, const void *d_count) {
+    MRT_TRY
+    return scatter_materials_entry("mrt_scene_scatter_materials_device_counted", scene, d_rays, d_surfaces, d_halton_index, n, bounce, max_bounces, light_count, d_shadow_rays, d_light, d_next_rays, d_lobes,
+                                   hip_stream, d_count, true);
+    MRT_CATCH
+}
+
+// Row queues on the caller's stream (queues.hip).  Plain arguments first, in the header's order, each message naming its argument; the context last.
+size_t mrt_compact_workspace_bytes(size_t n) { return mrt::compact_workspace_bytes(n); }
+int mrt_context_compact_rows_device(MRTContext ctx, const void *d_keep, size_t n, const void *d_count_in, const MRTRowColumn *columns, int32_t ncolumns, void *d_count_out, void *d_workspace,
+                                    size_t workspace_bytes, void *hip_stream) {
+    MRT_TRY
+    const std::string who = "mrt_context_compact_rows_device";
+    REQUIRE(n < (size_t(1) << 31), who + ": too many rows (n must be below 2^31)");
+    REQUIRE(n == 0 || d_keep, who + ": d_keep is NULL");
+    REQUIRE(n == 0 || d_count_out, who + ": d_count_out is NULL");
+    REQUIRE(n == 0 || d_workspace, who + ": d_workspace is NULL");
+    REQUIRE((uintptr_t)d_count_in % 4 == 0, who + ": d_count_in must be 4-byte aligned");
+    REQUIRE((uintptr_t)d_count_out % 4 == 0, who + ": d_count_out must be 4-byte aligned");
+    REQUIRE(!d_count_out || d_count_out != d_count_in, who + ": d_count_out must not be d_count_in (the kernels read the one after the other was written)");
+    REQUIRE(ncolumns >= 0 && ncolumns <= mrt::COMPACT_MAX_COLUMNS, who + ": ncolumns must be 0 .. 8");
+    REQUIRE(ncolumns == 0 || columns, who + ": columns is NULL with ncolumns > 0");
+    struct Range { uintptr_t lo, hi; const char *what; };
+    auto overlap = [](const Range &a, const Range &b) { return a.lo < b.hi && b.lo < a.hi; };
+    for (int c = 0; c < ncolumns; c++) {
+        const MRTRowColumn &col = columns[c];
+        const std::string name = who + ": columns[" + std::to_string(c) + "]";
+        REQUIRE(col.row_bytes != 0 && col.row_bytes <= 64 && col.row_bytes % 4 == 0, name + ".row_bytes must be a multiple of 4 in 4 .. 64");
+        const uintptr_t align = col.row_bytes % 16 == 0 ? 16 : 4;
+        REQUIRE(n == 0 || (col.src && col.dst), name + ": src or dst is NULL");
+        REQUIRE((uintptr_t)col.src % align == 0, name + ".src must be " + std::to_string(align) + "-byte aligned for rows of " + std::to_string(col.row_bytes) + " bytes");
+        REQUIRE((uintptr_t)col.dst % align == 0, name + ".dst must be " + std::to_string(align) + "-byte aligned for rows of " + std::to_string(col.row_bytes) + " bytes");
+    }
+    for (int c = 0; c < ncolumns && n; c++) {
+        const std::string name = who + ": columns[" + std::to_string(c) + "].dst";
+        const Range dst = {(uintptr_t)columns[c].dst, (uintptr_t)columns[c].dst + n * columns[c].row_bytes, ""};
+        const Range others[4] = {{(uintptr_t)columns[c].src, (uintptr_t)columns[c].src + n * columns[c].row_bytes, "its own src"}, {(uintptr_t)d_keep, (uintptr_t)d_keep + n, "d_keep"},
+                                 {(uintptr_t)d_count_in, (uintptr_t)d_count_in + (d_count_in ? 4 : 0), "d_count_in"}, {(uintptr_t)d_count_out, (uintptr_t)d_count_out + 4, "d_count_out"}};
+        for (const Range &o : others) REQUIRE(!overlap(dst, o), name + " overlaps " + o.what);
+        for (int k = 0; k < c; k++) {
+            const Range od = {(uintptr_t)columns[k].dst, (uintptr_t)columns[k].dst + n * columns[k].row_bytes, ""};
+            REQUIRE(!overlap(dst, od), name + " overlaps columns[" + std::to_string(k) + "].dst");
+        }
+    }
+    REQUIRE((uintptr_t)d_workspace % 16 == 0, who + ": d_workspace must be 16-byte aligned");
+    REQUIRE(n == 0 || workspace_bytes >= mrt::compact_workspace_bytes(n), who + ": workspace_bytes is below mrt_compact_workspace_bytes(n)");
+    REQUIRE(ctx, who + ": ctx is NULL");
+    if (n == 0 && !d_count_out) return MRT_OK;
+    if (int rc = bind_device(ctx)) return rc;
+    return mrt::compact_rows_device((hipStream_t)hip_stream, d_keep, n, d_count_in, columns, ncolumns, d_count_out, d_workspace);
     MRT_CATCH
 }
 

@@ -230,8 +230,9 @@ int unpack_tiles_into(float4 *image, int width, int height, const void *compact,
 int query_closest(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, MRTIntersection *out);
 int query_any(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, int32_t *out);
 // the stream-ordered forms on caller device buffers: two launches on `stream`, no allocation, copy or synchronisation (renderer.hip)
-int query_closest_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_out);
-int query_any_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_occluded);
+// d_count: null, or one uint32 on the device — both kernels then answer the rays below min(n, *d_count) and touch no other
+int query_closest_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_out, const void *d_count = nullptr);
+int query_any_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_occluded, const void *d_count = nullptr);
 // stages.hip: the primary rays of a renderer's image and their Halton indices on caller device buffers: one launch on `stream`, nothing of the renderer's is written
 int primary_rays_device(const Renderer &r, hipStream_t stream, uint32_t sample_index, void *d_rays, void *d_halton_index);
 int query_stats(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, int any, uint32_t *out4);

@@ -662,8 +662,9 @@ MRT_DEV MRTIntersection closest_record(const SceneView &s, bool two_level, bool 
 }
 constexpr uint32_t QUERY_STREAM_RAYS = 256;      // rays per wave of the static split, as k_query_stream
 template <bool TWO_LEVEL, bool ANY>
-__global__ void __launch_bounds__(64, TWO_LEVEL ? MRT_TWO_LEVEL_WAVES : MRT_WIDE_STREAM_WAVES) k_query_stream_device(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, void *__restrict__ out) {
+__global__ void __launch_bounds__(64, TWO_LEVEL ? MRT_TWO_LEVEL_WAVES : MRT_WIDE_STREAM_WAVES) k_query_stream_device(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, const uint32_t *__restrict__ count, void *__restrict__ out) {
     extern __shared__ uint32_t stk_dyn[];
+    if (count) n = min(n, *count);      // the caller's device-side ray count (null: every ray), read once as a uniform scalar load: the rays at and past it are not touched
     const uint32_t begin = blockIdx.x * QUERY_STREAM_RAYS;
     if (begin >= n) return;
     traverse_wide_stream<TWO_LEVEL>(s, OneRange{begin, min(n, begin + QUERY_STREAM_RAYS)}, stk_dyn,
@@ -679,8 +680,9 @@ __global__ void __launch_bounds__(64, TWO_LEVEL ? MRT_TWO_LEVEL_WAVES : MRT_WIDE
         });
 }
 template <bool WIDE, bool ANY>
-__global__ void __launch_bounds__(64) k_query_lane_device(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, void *__restrict__ out) {
+__global__ void __launch_bounds__(64) k_query_lane_device(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, const uint32_t *__restrict__ count, void *__restrict__ out) {
     extern __shared__ uint32_t stk[];      // WIDE: the scene's wide-tree depth x WIDE_STACK_LEVEL_BYTES, sized by the host
+    if (count) n = min(n, *count);      // (as k_query_stream_device)
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
     const bool mine = i < n && (s.num_wnodes == 0 || rays[i].min_distance != 0.0f);      // without the 8-wide layout no stream kernel ran: every ray is answered here
     if (__ballot(mine) == 0ull) return;      // nothing for this wave: a uniform branch to the end
@@ -1754,22 +1756,23 @@ int query_stream(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, 
 
 // The stream-ordered entries (mrt_scene_intersect_closest_device / _any_device): both launches on the caller's stream, nothing else.
 template <bool ANY>
-static int query_device_t(const DeviceScene &sc, hipStream_t stream, const MRTRay *d_rays, size_t n, void *d_out) {
+static int query_device_t(const DeviceScene &sc, hipStream_t stream, const MRTRay *d_rays, size_t n, void *d_out, const void *d_count) {
     const SceneView sv = sc.view();
+    const uint32_t *const cnt = static_cast<const uint32_t *>(d_count);      // (grids are sized by n, the capacity: a workgroup past the count leaves at once)
     const uint32_t n32 = (uint32_t)n;
     if (sc.num_wnodes) {
         const size_t lds = (size_t)sc.wide_depth * WIDE_STACK_LEVEL_BYTES + (sc.num_inst ? WIDE_WORLD_RAY_BYTES : 0);
-        if (sc.num_inst) hipLaunchKernelGGL((k_query_stream_device<true, ANY>), dim3(cdiv(n, QUERY_STREAM_RAYS)), dim3(64), lds, stream, sv, d_rays, n32, d_out);
-        else hipLaunchKernelGGL((k_query_stream_device<false, ANY>), dim3(cdiv(n, QUERY_STREAM_RAYS)), dim3(64), lds, stream, sv, d_rays, n32, d_out);
+        if (sc.num_inst) hipLaunchKernelGGL((k_query_stream_device<true, ANY>), dim3(cdiv(n, QUERY_STREAM_RAYS)), dim3(64), lds, stream, sv, d_rays, n32, cnt, d_out);
+        else hipLaunchKernelGGL((k_query_stream_device<false, ANY>), dim3(cdiv(n, QUERY_STREAM_RAYS)), dim3(64), lds, stream, sv, d_rays, n32, cnt, d_out);
         MRT_HIP(hipGetLastError());
     }
-    if (sc.num_wnodes) hipLaunchKernelGGL((k_query_lane_device<true, ANY>), dim3(cdiv(n, 64)), dim3(64), (size_t)sc.wide_depth * WIDE_STACK_LEVEL_BYTES, stream, sv, d_rays, n32, d_out);
-    else hipLaunchKernelGGL((k_query_lane_device<false, ANY>), dim3(cdiv(n, 64)), dim3(64), 0, stream, sv, d_rays, n32, d_out);
+    if (sc.num_wnodes) hipLaunchKernelGGL((k_query_lane_device<true, ANY>), dim3(cdiv(n, 64)), dim3(64), (size_t)sc.wide_depth * WIDE_STACK_LEVEL_BYTES, stream, sv, d_rays, n32, cnt, d_out);
+    else hipLaunchKernelGGL((k_query_lane_device<false, ANY>), dim3(cdiv(n, 64)), dim3(64), 0, stream, sv, d_rays, n32, cnt, d_out);
     MRT_HIP(hipGetLastError());
     return MRT_OK;
 }
-int query_closest_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_out) { return query_device_t<false>(sc, stream, static_cast<const MRTRay *>(d_rays), n, d_out); }
-int query_any_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_occluded) { return query_device_t<true>(sc, stream, static_cast<const MRTRay *>(d_rays), n, d_occluded); }
+int query_closest_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_out, const void *d_count) { return query_device_t<false>(sc, stream, static_cast<const MRTRay *>(d_rays), n, d_out, d_count); }
+int query_any_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_occluded, const void *d_count) { return query_device_t<true>(sc, stream, static_cast<const MRTRay *>(d_rays), n, d_occluded, d_count); }
 
 int probe_halton(hipStream_t stream, const int32_t *i, const int32_t *d, size_t n, float *out) {
     if (n == 0) return MRT_OK;

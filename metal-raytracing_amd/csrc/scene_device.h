@@ -428,15 +428,23 @@ void drop_blas_workspace(DeviceScene &sc);      // (the rejected count is kept)
 // surface.hip: hit records resolved to surface data on the caller's stream
 void surface_vertex_offsets(const std::vector<HostMesh> &meshes, std::vector<uint64_t> &offsets);      // the caller's vertex numbering: meshes + 1 entries
 int surface_prepare(const std::vector<HostMesh> &meshes, DeviceScene &sc);      // makes sc.surface_ws if it is not there (allocates, uploads the slot table, blocks)
-int resolve_hits_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, const void *d_hits, size_t n, void *d_surfaces);      // one launch, nothing else; needs sc.surface_ws
-int interpolate_device(const DeviceScene &sc, hipStream_t stream, const void *d_hits, size_t n, const void *d_attr, size_t attr_stride, uint32_t channels, void *d_out, size_t out_stride);
+// (d_count, here and in the stage entries below: null, or one uint32 on the device — the kernel then handles the rows below min(n, *d_count) and touches no other)
+int resolve_hits_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, const void *d_hits, size_t n, void *d_surfaces, const void *d_count = nullptr);      // one launch, nothing else; needs sc.surface_ws
+int interpolate_device(const DeviceScene &sc, hipStream_t stream, const void *d_hits, size_t n, const void *d_attr, size_t attr_stride, uint32_t channels, void *d_out, size_t out_stride,
+                       const void *d_count = nullptr);
 void drop_surface_workspace(DeviceScene &sc);      // (a commit: the table restates the mesh list of the commit before)
 int upload_lights(const MRTLight *lights, int count, hipStream_t stream, DeviceScene &out);
 // stages.hip: what follows a surface in the reference's kernel, on the caller's stream
 int scatter_device(const DeviceScene &sc, hipStream_t stream, const void *d_surfaces, const void *d_halton_index, size_t n, int bounce, int light_count, void *d_shadow_rays, void *d_light,
-                   void *d_next_rays);      // one launch, nothing else; light_count in [1, sc.light_count], bounce in [0, 18]
+                   void *d_next_rays, const void *d_count = nullptr);      // one launch, nothing else; light_count in [1, sc.light_count], bounce in [0, 18]
 // stages_materials.hip: the same step with the materials extension on
 int scatter_materials_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, const void *d_surfaces, const void *d_halton_index, size_t n, int bounce, int max_bounces,
-                             int light_count, void *d_shadow_rays, void *d_light, void *d_next_rays, void *d_lobes);      // one launch, nothing else; light_count in [1, sc.light_count], max_bounces in [1, 16], bounce in [0, max_bounces)
+                             int light_count, void *d_shadow_rays, void *d_light, void *d_next_rays, void *d_lobes, const void *d_count = nullptr);      // one launch, nothing else; light_count in [1, sc.light_count], max_bounces in [1, 16], bounce in [0, max_bounces)
+// queues.hip: stable compaction of the rows of up to eight columns on the caller's stream, the count left on the device
+constexpr uint32_t COMPACT_ROWS = 2048;               // rows per workgroup of the count and move kernels
+constexpr uint32_t COMPACT_SCAN_THREADS = 1024;       // per-workgroup totals the one scan workgroup takes at a step
+constexpr int COMPACT_MAX_COLUMNS = 8;
+size_t compact_workspace_bytes(size_t n);             // one uint32 per workgroup, rounded up to 16 bytes (at least 16)
+int compact_rows_device(hipStream_t stream, const void *d_keep, size_t n, const void *d_count_in, const MRTRowColumn *columns, int ncolumns, void *d_count_out, void *d_workspace);      // three launches, nothing else
 
 }  // namespace mrt

@@ -43,7 +43,8 @@ __global__ void __launch_bounds__(256) k_primary_rays(const PrimaryParams p, con
 // NEXT: the bounce ray is wanted (d_next_rays was given)
 template <bool NEXT>
 __global__ void __launch_bounds__(256) k_scatter(const LightDev *__restrict__ lights, const int lc, const int dim0, const float4 *__restrict__ surfaces, const int32_t *__restrict__ halton_index,
-                                                 const uint32_t n, float4 *__restrict__ shadow_rays, float4 *__restrict__ light, float4 *__restrict__ next_rays) {
+                                                 const uint32_t cap, const uint32_t *__restrict__ count, float4 *__restrict__ shadow_rays, float4 *__restrict__ light, float4 *__restrict__ next_rays) {
+    const uint32_t n = count ? min(cap, *count) : cap;          // the caller's device-side row count (null: every row), read once as a uniform scalar load
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -82,11 +83,12 @@ int primary_rays_device(const Renderer &r, hipStream_t stream, uint32_t sample_i
 }
 
 int scatter_device(const DeviceScene &sc, hipStream_t stream, const void *d_surfaces, const void *d_halton_index, size_t n, int bounce, int light_count, void *d_shadow_rays, void *d_light,
-                   void *d_next_rays) {
-    const dim3 grid((uint32_t)((n + 255) / 256));          // n < 2^31
+                   void *d_next_rays, const void *d_count) {
+    const dim3 grid((uint32_t)((n + 255) / 256));          // n < 2^31 (the capacity, whatever the count)
     const int dim0 = 2 + 5 * bounce;                         // dim0 + 4 < 100, the prime table's size: bounce <= 18
     hipLaunchKernelGGL(d_next_rays ? k_scatter<true> : k_scatter<false>, grid, dim3(256), 0, stream, sc.lights.p, light_count, dim0, static_cast<const float4 *>(d_surfaces),
-                       static_cast<const int32_t *>(d_halton_index), (uint32_t)n, static_cast<float4 *>(d_shadow_rays), static_cast<float4 *>(d_light), static_cast<float4 *>(d_next_rays));
+                       static_cast<const int32_t *>(d_halton_index), (uint32_t)n, static_cast<const uint32_t *>(d_count), static_cast<float4 *>(d_shadow_rays), static_cast<float4 *>(d_light),
+                       static_cast<float4 *>(d_next_rays));
     MRT_HIP(hipGetLastError());
     return MRT_OK;
 }

@@ -20,8 +20,9 @@ namespace {
 // NEXT: the continuation ray is wanted (d_next_rays was given); without it the two normalisations and the cosine-hemisphere sample are not computed
 template <bool NEXT>
 __global__ void __launch_bounds__(256) k_scatter_materials(const LightDev *__restrict__ lights, const float4 *__restrict__ materials, const uint32_t slots, const int lc, const int dim0, const int dim_lobe,
-                                                           const float4 *__restrict__ rays, const float4 *__restrict__ surfaces, const int32_t *__restrict__ halton_index, const uint32_t n,
+                                                           const float4 *__restrict__ rays, const float4 *__restrict__ surfaces, const int32_t *__restrict__ halton_index, const uint32_t cap, const uint32_t *__restrict__ count,
                                                            float4 *__restrict__ shadow_rays, float4 *__restrict__ light, float4 *__restrict__ next_rays, float4 *__restrict__ lobes) {
+    const uint32_t n = count ? min(cap, *count) : cap;          // the caller's device-side row count (null: every row), read once as a uniform scalar load
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -62,12 +63,12 @@ __global__ void __launch_bounds__(256) k_scatter_materials(const LightDev *__res
 }  // namespace
 
 int scatter_materials_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, const void *d_surfaces, const void *d_halton_index, size_t n, int bounce, int max_bounces,
-                             int light_count, void *d_shadow_rays, void *d_light, void *d_next_rays, void *d_lobes) {
-    const dim3 grid((uint32_t)((n + 255) / 256));          // n < 2^31
+                             int light_count, void *d_shadow_rays, void *d_light, void *d_next_rays, void *d_lobes, const void *d_count) {
+    const dim3 grid((uint32_t)((n + 255) / 256));          // n < 2^31 (the capacity, whatever the count)
     const int dim0 = 2 + 5 * bounce, dim_lobe = 2 + 5 * max_bounces + bounce;          // max_bounces <= 16, bounce < max_bounces: dim_lobe <= 97, below the prime table's 100
     const uint32_t slots = (uint32_t)(sc.materials.n / 3);          // instances x max_submeshes (three rows per resource slot)
     hipLaunchKernelGGL(d_next_rays ? k_scatter_materials<true> : k_scatter_materials<false>, grid, dim3(256), 0, stream, sc.lights.p, sc.materials.p, slots, light_count, dim0, dim_lobe,
-                       static_cast<const float4 *>(d_rays), static_cast<const float4 *>(d_surfaces), static_cast<const int32_t *>(d_halton_index), (uint32_t)n,
+                       static_cast<const float4 *>(d_rays), static_cast<const float4 *>(d_surfaces), static_cast<const int32_t *>(d_halton_index), (uint32_t)n, static_cast<const uint32_t *>(d_count),
                        static_cast<float4 *>(d_shadow_rays), static_cast<float4 *>(d_light), static_cast<float4 *>(d_next_rays), static_cast<float4 *>(d_lobes));
     MRT_HIP(hipGetLastError());
     return MRT_OK;

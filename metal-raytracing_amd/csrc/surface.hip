@@ -35,7 +35,10 @@ MRT_DEV bool surface_slot(const SurfaceView &s, const uint4 h0, const uint4 h1, 
     return h1.x < row.y;
 }
 
-__global__ void __launch_bounds__(256) k_resolve_hits(const SurfaceView s, const float4 *__restrict__ rays, const uint4 *__restrict__ hits, const uint32_t n, float4 *__restrict__ out) {
+// `count` (here and in k_interpolate): null, or the caller's device-side row count — read once, as a uniform scalar load; the rows at and past min(cap, *count) are not touched
+__global__ void __launch_bounds__(256) k_resolve_hits(const SurfaceView s, const float4 *__restrict__ rays, const uint4 *__restrict__ hits, const uint32_t cap, const uint32_t *__restrict__ count,
+                                                      float4 *__restrict__ out) {
+    const uint32_t n = count ? min(cap, *count) : cap;
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const uint4 h0 = hits[2 * (size_t)i], h1 = hits[2 * (size_t)i + 1];
@@ -67,8 +70,9 @@ __global__ void __launch_bounds__(256) k_resolve_hits(const SurfaceView s, const
 
 // VEC: attribute rows, output rows and both bases are 16-byte aligned and the channel count is a multiple of four — one 16-byte load per row, one 16-byte store
 template <bool VEC>
-__global__ void __launch_bounds__(256) k_interpolate(const SurfaceView s, const uint4 *__restrict__ hits, const uint64_t work, const uint32_t groups, const uint32_t channels,
-                                                     const char *__restrict__ attr, const size_t attr_stride, char *__restrict__ out, const size_t out_stride) {
+__global__ void __launch_bounds__(256) k_interpolate(const SurfaceView s, const uint4 *__restrict__ hits, const uint32_t cap, const uint32_t *__restrict__ count, const uint32_t groups,
+                                                     const uint32_t channels, const char *__restrict__ attr, const size_t attr_stride, char *__restrict__ out, const size_t out_stride) {
+    const uint64_t work = (uint64_t)(count ? min(cap, *count) : cap) * groups;
     const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (w >= work) return;
     const uint32_t i = (uint32_t)(w / groups), c0 = 4u * (uint32_t)(w % groups);
@@ -158,20 +162,22 @@ int surface_prepare(const std::vector<HostMesh> &meshes, DeviceScene &sc) {
 
 void drop_surface_workspace(DeviceScene &sc) { sc.surface_ws.reset(); }
 
-int resolve_hits_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, const void *d_hits, size_t n, void *d_surfaces) {
+int resolve_hits_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, const void *d_hits, size_t n, void *d_surfaces, const void *d_count) {
     hipLaunchKernelGGL(k_resolve_hits, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, surface_view(sc), static_cast<const float4 *>(d_rays), static_cast<const uint4 *>(d_hits),
-                       (uint32_t)n, static_cast<float4 *>(d_surfaces));
+                       (uint32_t)n, static_cast<const uint32_t *>(d_count), static_cast<float4 *>(d_surfaces));
     MRT_HIP(hipGetLastError());
     return MRT_OK;
 }
 
-int interpolate_device(const DeviceScene &sc, hipStream_t stream, const void *d_hits, size_t n, const void *d_attr, size_t attr_stride, uint32_t channels, void *d_out, size_t out_stride) {
+int interpolate_device(const DeviceScene &sc, hipStream_t stream, const void *d_hits, size_t n, const void *d_attr, size_t attr_stride, uint32_t channels, void *d_out, size_t out_stride,
+                       const void *d_count) {
     const uint32_t groups = (channels + 3) / 4;
-    const uint64_t work = (uint64_t)n * groups;          // n < 2^31, groups <= 16: 2^27 workgroups at the most
+    const uint64_t work = (uint64_t)n * groups;          // n < 2^31, groups <= 16: 2^27 workgroups at the most (the grid is sized by the capacity, whatever the count)
+    const uint32_t *const cnt = static_cast<const uint32_t *>(d_count);
     const bool vec = channels % 4 == 0 && attr_stride % 16 == 0 && out_stride % 16 == 0 && (uintptr_t)d_attr % 16 == 0 && (uintptr_t)d_out % 16 == 0;
     const dim3 grid((uint32_t)((work + 255) / 256));
-    if (vec) hipLaunchKernelGGL(k_interpolate<true>, grid, dim3(256), 0, stream, surface_view(sc), static_cast<const uint4 *>(d_hits), work, groups, channels, static_cast<const char *>(d_attr), attr_stride, static_cast<char *>(d_out), out_stride);
-    else hipLaunchKernelGGL(k_interpolate<false>, grid, dim3(256), 0, stream, surface_view(sc), static_cast<const uint4 *>(d_hits), work, groups, channels, static_cast<const char *>(d_attr), attr_stride, static_cast<char *>(d_out), out_stride);
+    if (vec) hipLaunchKernelGGL(k_interpolate<true>, grid, dim3(256), 0, stream, surface_view(sc), static_cast<const uint4 *>(d_hits), (uint32_t)n, cnt, groups, channels, static_cast<const char *>(d_attr), attr_stride, static_cast<char *>(d_out), out_stride);
+    else hipLaunchKernelGGL(k_interpolate<false>, grid, dim3(256), 0, stream, surface_view(sc), static_cast<const uint4 *>(d_hits), (uint32_t)n, cnt, groups, channels, static_cast<const char *>(d_attr), attr_stride, static_cast<char *>(d_out), out_stride);
     MRT_HIP(hipGetLastError());
     return MRT_OK;
 }

@@ -122,7 +122,16 @@ class DeviceScene:
         check(lib.mrt_debug_intersect_stream(self.handle, ptr(rays), rays.shape[0], 1 if any_hit else 0, ptr(out)))
         return out
 
-    def _device_query(self, fn, rays, out, stream, out_shape):
+    def _count_word(self, count, what="count"):
+        """the count= argument of the *_device methods — a one-element torch.int32 or torch.uint32 tensor on the context's device — as a pointer; it is never read here"""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        kinds = tuple(k for k in (torch.int32, getattr(torch, "uint32", None)) if k is not None)
+        if not isinstance(count, torch.Tensor) or count.device != dev or count.dtype not in kinds or count.numel() != 1:
+            raise ValueError(f"{what} must be a torch.int32 or torch.uint32 tensor with one element on {dev}")
+        return C.c_void_p(count.data_ptr())
+
+    def _device_query(self, fn, rays, out, stream, out_shape, count=None):
         import torch
         dev = torch.device("cuda", self.ctx.device)
         if not isinstance(rays, torch.Tensor) or rays.device != dev:
@@ -135,19 +144,23 @@ class DeviceScene:
         elif not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous torch.int32 tensor of shape {shape} on {dev}")
         n = rays.shape[0]
-        check(fn(self.handle, C.c_void_p(rays.data_ptr() if n else None), n, C.c_void_p(out.data_ptr() if n else None), C.c_void_p(self._stream_handle(stream))))
+        more = () if count is None else (self._count_word(count),)
+        check(fn(self.handle, C.c_void_p(rays.data_ptr() if n else None), n, C.c_void_p(out.data_ptr() if n else None), C.c_void_p(self._stream_handle(stream)), *more))
         return out
 
-    def intersect_closest_device(self, rays, out=None, stream=None):
+    def intersect_closest_device(self, rays, out=None, stream=None, count=None):
         """Closest hits of rays that live on the GPU, ordered on a stream: rays is a contiguous torch.float32 (n, 8) tensor on the context's device
         ([ox, oy, oz, tmin, dx, dy, dz, tmax]); returns torch.int32 (n, 8), one MRTIntersection per row (unpack_intersections gives the fields).  Nothing is
         allocated (but `out` when it is None), copied or synchronised.  stream: None = torch's current stream of that device; an integer handle (0 = the
-        null stream) or a torch.cuda.Stream.  Keep rays and out alive until the stream has passed the call."""
-        return self._device_query(lib.mrt_scene_intersect_closest_device, rays, out, stream, (8,))
+        null stream) or a torch.cuda.Stream.  Keep rays and out alive until the stream has passed the call.
+        count: None, or a one-element torch.int32 / uint32 tensor on that device — the length of the queue the rows hold, as compact_rows_device leaves it.  The rows
+        below min(n, count) are handled exactly as without it; no row from there on is read or written.  The word is read on the GPU when the kernels start, never here
+        (this holds for count= of every *_device method)."""
+        return self._device_query(lib.mrt_scene_intersect_closest_device if count is None else lib.mrt_scene_intersect_closest_device_counted, rays, out, stream, (8,), count)
 
-    def intersect_any_device(self, rays, out=None, stream=None):
+    def intersect_any_device(self, rays, out=None, stream=None, count=None):
         """Any-hit form of intersect_closest_device: torch.int32 (n,), 1 = occluded."""
-        return self._device_query(lib.mrt_scene_intersect_any_device, rays, out, stream, ())
+        return self._device_query(lib.mrt_scene_intersect_any_device if count is None else lib.mrt_scene_intersect_any_device_counted, rays, out, stream, (), count)
 
     def _hit_records(self, hits, what="hits"):
         """the (n, 8) torch.int32 tensor of MRTIntersection records intersect_closest_device returns, checked"""
@@ -159,7 +172,7 @@ class DeviceScene:
             raise ValueError(f"{what} must be a contiguous torch.int32 tensor of shape (n, 8): the records of intersect_closest_device")
         return dev
 
-    def resolve_hits_device(self, rays, hits, out=None, stream=None):
+    def resolve_hits_device(self, rays, hits, out=None, stream=None, count=None):
         """The step after intersect_closest_device, on the GPU and ordered on a stream: rays (n, 8) float32 and hits (n, 8) int32 as that method takes and returns them ->
         torch.float32 (n, 16), one MRTSurface per row: position | distance, shading normal | type, base colour | resource slot, instance / geometry / primitive ids
         (unpack_surfaces gives the fields).  The values are the ones the device holds now: vertices written by update_mesh_device / update_blas_device, poses written by
@@ -176,11 +189,12 @@ class DeviceScene:
             out = torch.empty((n, 16), dtype=torch.float32, device=dev)
         elif not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != (n, 16) or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous torch.float32 tensor of shape {(n, 16)} on {dev}")
-        check(lib.mrt_scene_resolve_hits_device(self.handle, C.c_void_p(rays.data_ptr() if n else None), C.c_void_p(hits.data_ptr() if n else None), n,
-                                                C.c_void_p(out.data_ptr() if n else None), C.c_void_p(self._stream_handle(stream))))
+        fn, more = (lib.mrt_scene_resolve_hits_device, ()) if count is None else (lib.mrt_scene_resolve_hits_device_counted, (self._count_word(count),))
+        check(fn(self.handle, C.c_void_p(rays.data_ptr() if n else None), C.c_void_p(hits.data_ptr() if n else None), n,
+                 C.c_void_p(out.data_ptr() if n else None), C.c_void_p(self._stream_handle(stream)), *more))
         return out
 
-    def interpolate_device(self, hits, attributes, out=None, stream=None):
+    def interpolate_device(self, hits, attributes, out=None, stream=None, count=None):
         """Per-vertex data of the caller's interpolated at the hits, on the GPU and ordered on a stream: attributes is a torch.float32 (V, C) tensor on the context's
         device, 1 <= C <= 64, rows contiguous and any multiple of 4 bytes apart (a slice of a wider tensor is fine; nothing is copied), one row per vertex in the
         numbering vertex_offsets() describes -> torch.float32 (n, C): (u * a1 + v * a2) + ((1 - u) - v) * a0 over the hit triangle's vertices, zeros for a miss.
@@ -201,12 +215,13 @@ class DeviceScene:
         elif (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != (n, ch) or out.stride(1) != 1
               or (n > 1 and out.stride(0) < ch)):
             raise ValueError(f"out must be a torch.float32 tensor of shape {(n, ch)} on {dev} with contiguous rows")
-        check(lib.mrt_scene_interpolate_device(self.handle, C.c_void_p(hits.data_ptr() if n else None), n, C.c_void_p(a.data_ptr() if n else None),
-                                               (a.stride(0) if a.shape[0] > 1 else ch) * 4, ch, C.c_void_p(out.data_ptr() if n else None), (out.stride(0) if n > 1 else ch) * 4,
-                                               C.c_void_p(self._stream_handle(stream))))
+        fn, more = (lib.mrt_scene_interpolate_device, ()) if count is None else (lib.mrt_scene_interpolate_device_counted, (self._count_word(count),))
+        check(fn(self.handle, C.c_void_p(hits.data_ptr() if n else None), n, C.c_void_p(a.data_ptr() if n else None),
+                 (a.stride(0) if a.shape[0] > 1 else ch) * 4, ch, C.c_void_p(out.data_ptr() if n else None), (out.stride(0) if n > 1 else ch) * 4,
+                 C.c_void_p(self._stream_handle(stream)), *more))
         return out
 
-    def scatter_device(self, surfaces, halton_index, bounce, light_count=0, next_rays=True, out=None, stream=None):
+    def scatter_device(self, surfaces, halton_index, bounce, light_count=0, next_rays=True, out=None, stream=None, count=None):
         """What follows a surface in the reference's kernel (its diffuse path; the materials extension is scatter_materials_device), on the GPU and ordered on a stream: surfaces
         (n, 16) float32 as resolve_hits_device returns them, halton_index (n,) int32 as Renderer.primary_rays_device returns it, bounce the path depth of these surfaces
         (0 .. 18), light_count Uniforms.lightCount (0 = every light of the scene) -> (shadow_rays (n, 8) float32, light (n, 4) float32, next_rays (n, 8) float32 or
@@ -231,10 +246,11 @@ class DeviceScene:
             if len(out) != len(shapes) or any(not isinstance(o, torch.Tensor) or o.device != dev or o.dtype != torch.float32 or tuple(o.shape) != sh or not o.is_contiguous() for o, sh in zip(out, shapes)):
                 raise ValueError(f"out must be {len(shapes)} contiguous torch.float32 tensors of shapes {shapes} on {dev}")
         p = [C.c_void_p(t.data_ptr() if n else None) for t in (surfaces, h) + out]
-        check(lib.mrt_scene_scatter_device(self.handle, p[0], p[1], n, int(bounce), int(light_count), p[2], p[3], p[4] if next_rays else None, C.c_void_p(self._stream_handle(stream))))
+        fn, more = (lib.mrt_scene_scatter_device, ()) if count is None else (lib.mrt_scene_scatter_device_counted, (self._count_word(count),))
+        check(fn(self.handle, p[0], p[1], n, int(bounce), int(light_count), p[2], p[3], p[4] if next_rays else None, C.c_void_p(self._stream_handle(stream)), *more))
         return (out[0], out[1], out[2] if next_rays else None)
 
-    def scatter_materials_device(self, rays, surfaces, halton_index, bounce, max_bounces, light_count=0, next_rays=True, out=None, stream=None):
+    def scatter_materials_device(self, rays, surfaces, halton_index, bounce, max_bounces, light_count=0, next_rays=True, out=None, stream=None, count=None):
         """scatter_device with the materials extension on — what follows a surface when Renderer's option materials = 1 — on the GPU and ordered on a stream: rays (n, 8)
         float32, the rays that hit these surfaces (their direction is read); surfaces, halton_index, light_count as scatter_device takes them; max_bounces the path
         length of the integrator (1 .. 16) and 0 <= bounce < max_bounces: the lobe choice reads Halton dimension 2 + 5 * max_bounces + bounce -> (shadow_rays (n, 8),
@@ -265,9 +281,56 @@ class DeviceScene:
             if len(out) != len(shapes) or any(not isinstance(o, torch.Tensor) or o.device != dev or o.dtype != torch.float32 or tuple(o.shape) != sh or not o.is_contiguous() for o, sh in zip(out, shapes)):
                 raise ValueError(f"out must be {len(shapes)} contiguous torch.float32 tensors of shapes {shapes} on {dev}")
         p = [C.c_void_p(t.data_ptr() if n else None) for t in (rays, surfaces, h) + out]
-        check(lib.mrt_scene_scatter_materials_device(self.handle, p[0], p[1], p[2], n, int(bounce), int(max_bounces), int(light_count), p[3], p[4], p[5] if next_rays else None, p[-1],
-                                                     C.c_void_p(self._stream_handle(stream))))
+        fn, more = (lib.mrt_scene_scatter_materials_device, ()) if count is None else (lib.mrt_scene_scatter_materials_device_counted, (self._count_word(count),))
+        check(fn(self.handle, p[0], p[1], p[2], n, int(bounce), int(max_bounces), int(light_count), p[3], p[4], p[5] if next_rays else None, p[-1],
+                 C.c_void_p(self._stream_handle(stream)), *more))
         return (out[0], out[1], out[2] if next_rays else None, out[-1])
+
+    def compact_rows_device(self, keep, columns, count=None, out=None, workspace=None, stream=None):
+        """A queue made of the rows that go on, on the GPU and ordered on a stream: keep is a torch.bool or torch.uint8 tensor of shape (n,), columns a sequence of at most
+        eight contiguous tensors with n rows each (a row — everything behind the first dimension — is a multiple of 4 bytes, at most 64) -> (outs, count_out).  With
+        m = min(n, count) (n when count is None), outs[c][j] is columns[c]'s j-th row among the rows i < m with keep[i] set, in their order — what
+        columns[c][:m][keep[:m]] gives — and count_out, a one-element torch.int32 tensor, is their number: hand it to the next stage as count=.  The rows of outs from
+        count_out on keep what they held.  out: the tensors to write (shapes and dtypes of columns; none may be one of them), allocated when None; workspace: a torch.uint8
+        tensor of at least compact_workspace_bytes(n) bytes, allocated when None; count: as every *_device method takes it.  Neither count is read on the host: nothing
+        is copied or synchronised, and with out and workspace given nothing is allocated but the four bytes of count_out.  stream: as intersect_closest_device takes it."""
+        import torch
+        from ._ffi import RowColumn
+        dev = torch.device("cuda", self.ctx.device)
+        if not isinstance(keep, torch.Tensor) or keep.device != dev or keep.dtype not in (torch.bool, torch.uint8) or keep.dim() != 1 or not keep.is_contiguous():
+            raise ValueError(f"keep must be a contiguous torch.bool or torch.uint8 tensor of shape (n,) on {dev}")
+        n = keep.shape[0]
+        columns = list(columns)
+        if len(columns) > 8:
+            raise ValueError("at most eight columns")
+        for c in columns:
+            if not isinstance(c, torch.Tensor) or c.device != dev or c.dim() < 1 or c.shape[0] != n or not c.is_contiguous():
+                raise ValueError(f"every column must be a contiguous torch tensor on {dev} with {n} rows")
+        if out is None:
+            out = [torch.empty_like(c) for c in columns]
+        else:
+            out = list(out)
+            if len(out) != len(columns) or any(not isinstance(o, torch.Tensor) or o.device != dev or o.dtype != c.dtype or o.shape != c.shape or not o.is_contiguous() for o, c in zip(out, columns)):
+                raise ValueError("out must hold one contiguous tensor per column, of that column's shape and dtype")
+        need = int(lib.mrt_compact_workspace_bytes(n))
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        elif not isinstance(workspace, torch.Tensor) or workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+            raise ValueError(f"workspace must be a contiguous torch.uint8 tensor on {dev} (compact_workspace_bytes(n) bytes)")
+        table = (RowColumn * max(1, len(columns)))()
+        for k, (c, o) in enumerate(zip(columns, out)):
+            table[k].src, table[k].dst = c.data_ptr() if n else None, o.data_ptr() if n else None
+            table[k].row_bytes = int(np.prod(c.shape[1:], dtype=np.int64)) * c.element_size()          # (the library refuses what is no multiple of 4 in 4 .. 64)
+        count_out = torch.empty(1, dtype=torch.int32, device=dev)
+        check(lib.mrt_context_compact_rows_device(self.ctx.handle, C.c_void_p(keep.data_ptr() if n else None), n, None if count is None else self._count_word(count), table, len(columns),
+                                                  C.c_void_p(count_out.data_ptr()), C.c_void_p(workspace.data_ptr() if workspace.numel() else None), workspace.numel(),
+                                                  C.c_void_p(self._stream_handle(stream))))
+        return out, count_out
+
+    @staticmethod
+    def compact_workspace_bytes(n):
+        """bytes of workspace compact_rows_device needs for n rows (never 0; it does not decrease with n)"""
+        return int(lib.mrt_compact_workspace_bytes(int(n)))
 
     def vertex_offsets(self):
         """The vertex numbering interpolate_device reads attributes in: (meshes + 1,) uint64 — each mesh's first row, the source meshes concatenated in mesh-id order and

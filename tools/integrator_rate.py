@@ -11,6 +11,13 @@ and, once (the materials leg; the Cornell box with a glass sphe
       32 + 16 + 32 + 32 B: 180 B (with whole 64-byte surface rows and 32-byte ray rows, as the lines are fetched: 212 B, reported beside it; the material and light rows are
       gathers from tables of a few lines and are not counted) — and one composed materials frame at 1920 x 1080, four bounces, beside Renderer with materials = 1 drawing one
       frame, timed as (b).
+and, per scene and for the materials leg (the queue legs):
+  (d) compact_rows_device alone at 2^22 rows on the columns of a path's state — rays 32 B, Halton index 4 B, pixel 4 B, throughput 16 B — keeping the surfaces of bounce 1's
+      dense rows and keeping a random 50 %, against its byte floor at the same copy bandwidth: 2 B of keep per row (it is read twice) plus 56 B read and 56 B written per
+      kept row;
+  (e) the composed 1080p frame ON QUEUES (tests/queues_compose.py: the wanted shadow rays and the surviving paths compacted at every bounce), in two forms — the counts read
+      by the host once per bounce and every tensor sliced to them; no host read at all, the counts handed on as count= and torch's ops over the capacity with the tail
+      masked — beside the dense composed frame and Renderer of (b) / (c), timed the same way in the same loop.  Both must report same_bits true.
 3 warm + 20 timed repetitions, the legs alternating, medians.
 Usage: python tools/integrator_rate.py [--scenes dragon,dragon4] [--materials 1] [--reps 20]      (prints one JSON line)"""
 import argparse
@@ -64,6 +71,49 @@ def compose_materials(torch, r, ds, sample_index, dev, miss, bounces):
     return acc
 
 
+def queue_legs(torch, m, ds, dev, rows, keeps, copy_gbs, timed, stream):
+    """(d): compact_rows_device alone on a path's state, one entry per keep mask of `keeps` (name -> (rows,) bool)"""
+    cols = [torch.empty((rows, 8), device=dev).normal_(), torch.zeros(rows, dtype=torch.int32, device=dev), torch.arange(rows, dtype=torch.int32, device=dev), torch.ones((rows, 4), device=dev)]
+    out = [torch.empty_like(c) for c in cols]
+    ws = torch.empty(ds.compact_workspace_bytes(rows), dtype=torch.uint8, device=dev)
+    res = {}
+    for name, keep in keeps.items():
+        ds.compact_rows_device(keep, cols, out=out, workspace=ws, stream=0)
+        torch.cuda.synchronize()
+        ms = timed([lambda: ds.compact_rows_device(keep, cols, out=out, workspace=ws, stream=stream)])[0]
+        share = float(keep.float().mean())
+        floor = (2.0 + 112.0 * share) * rows / copy_gbs / 1e6
+        res[name] = {"keep_share": share, "ms": ms, "floor_ms": floor, "over_floor": ms / floor}
+    return res
+
+
+def frame_legs(torch, r, dev, ts, reps, legs):
+    """(b) / (c) / (e) in one loop: each callable of `legs` (name -> fn() -> (n, 3) sample) composed on the side stream, then Renderer drawing frame 0; medians of host wall
+    and HIP-event time per leg, and whether each leg's sample has the renderer's bits"""
+    wall = {k: [] for k in legs}; ev = {k: [] for k in legs}; rw = []; own = []; acc = {}
+    for rep in range(3 + reps):
+        for k, fn in legs.items():
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0 = time.perf_counter()
+                e0.record(ts); acc[k] = fn(); e1.record(ts); ts.synchronize()
+                t1 = time.perf_counter()
+            if rep >= 3: wall[k].append((t1 - t0) * 1e3); ev[k].append(e0.elapsed_time(e1))
+        r.frameIndex = 0
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        r.draw(1, wait=True)
+        t3 = time.perf_counter()
+        if rep >= 3: rw.append((t3 - t2) * 1e3); own.append(float(r.stats.ms_gpu_last))
+    img = torch.from_numpy(r.accumulation()).to(dev).reshape(-1, 4)[:, 0:3].contiguous().view(torch.int32)
+    out = {"renderer_wall_ms": statistics.median(rw), "renderer_device_ms": statistics.median(own)}
+    for k in legs:
+        out[k] = {"wall_ms": statistics.median(wall[k]), "event_ms": statistics.median(ev[k]), "over_renderer_wall": statistics.median(wall[k]) / statistics.median(rw),
+                  "same_bits": bool(torch.equal(acc[k].view(torch.int32), img))}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default="dragon,dragon4")
@@ -97,6 +147,10 @@ def main():
     del src, dst
     miss = torch.tensor([[0.0, 0.0, 0.0, -1.0] + [0.0] * 12], device=dev)
     miss.view(torch.int32)[0, 11] = -1; miss.view(torch.int32)[0, 12:15] = -1          # the miss record of resolve_hits_device
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from queues_compose import compose_queued                       # the queued frame of the GPU tests (test infrastructure: the tool runs from the repository)
+    gen = torch.Generator(device=dev); gen.manual_seed(1)
+    half = torch.rand(rows, device=dev, generator=gen) < 0.5
     for name in [x for x in a.scenes.split(",") if x]:
         two_level = name == "dragon4"
         opts = {"instancing": 1} if two_level else None
@@ -120,6 +174,7 @@ def main():
         row["a"] = {"primary_ms": t[0], "primary_floor_ms": floor_p, "primary_over_floor": t[0] / floor_p,
                     "scatter_b0_ms": t[1], "scatter_b1_ms": t[2], "scatter_floor_ms": floor_s, "scatter_b0_over_floor": t[1] / floor_s, "scatter_b1_over_floor": t[2] / floor_s,
                     "surface_share_b0": float((surf0[:, 7].view(torch.int32) == 1).float().mean()), "surface_share_b1": float((surf1[:, 7].view(torch.int32) == 1).float().mean())}
+        row["d"] = queue_legs(torch, m, ds, dev, rows, {"bounce_1_surfaces": (surf1[:, 7].view(torch.int32) == 1).contiguous(), "random_half": half}, copy_gbs, timed, s)
         del prim, outs, surf0, surf1
         r.close()
         # (b) the composed frame beside the renderer's
@@ -145,6 +200,10 @@ def main():
         row["b"] = {"composed_wall_ms": statistics.median(wall["composed"]), "renderer_wall_ms": statistics.median(wall["renderer"]), "composed_event_ms": statistics.median(ev),
                     "renderer_device_ms": statistics.median(own), "composed_over_renderer_wall": statistics.median(wall["composed"]) / statistics.median(wall["renderer"]),
                     "same_bits": bool(torch.equal(acc.view(torch.int32), img.contiguous().view(torch.int32)))}
+        # (e) the same frame on queues, both forms, beside the dense one and the renderer in one loop
+        row["e"] = frame_legs(torch, r, dev, ts, a.reps, {"dense": lambda: compose(torch, r, ds, 0, dev, miss),
+                                                          "queued_host_counts": lambda: compose_queued(torch, r, ds, 0, dev, bounces=3, host_counts=True),
+                                                          "queued_no_host_read": lambda: compose_queued(torch, r, ds, 0, dev, bounces=3, host_counts=False)})
         r.close()
         res["scenes"][name] = row
     if a.materials:
@@ -165,6 +224,7 @@ def main():
         lobes = outs[3][:, 3].view(torch.int32)
         row["c"] = {"scatter_materials_b0_ms": t[0], "no_next_rays_ms": t[1], "floor_180B_ms": floor_c, "over_floor_180B": t[0] / floor_c, "floor_212B_ms": floor_l, "over_floor_212B": t[0] / floor_l,
                     "lobe_share": [float((lobes == k).float().mean()) for k in range(6)]}
+        row["d"] = queue_legs(torch, m, ds, dev, rows, {"bounce_0_paths_that_go_on": ((lobes >= 1) & (lobes <= 4)).contiguous(), "random_half": half}, copy_gbs, timed, s)
         del prim, outs, surf0, lobes
         r.close()
         r = m.Renderer((1920, 1080), cornell_with_materials(m, (1920, 1080)), ctx=ctx, max_bounces=bounces)
@@ -189,6 +249,9 @@ def main():
         row["frame"] = {"composed_wall_ms": statistics.median(wall["composed"]), "renderer_wall_ms": statistics.median(wall["renderer"]), "composed_event_ms": statistics.median(ev),
                         "renderer_device_ms": statistics.median(own), "composed_over_renderer_wall": statistics.median(wall["composed"]) / statistics.median(wall["renderer"]),
                         "same_bits": bool(torch.equal(acc.view(torch.int32), img.contiguous().view(torch.int32)))}
+        row["e"] = frame_legs(torch, r, dev, ts, a.reps, {"dense": lambda: compose_materials(torch, r, ds, 0, dev, miss, bounces),
+                                                          "queued_host_counts": lambda: compose_queued(torch, r, ds, 0, dev, bounces=bounces, materials=True, host_counts=True),
+                                                          "queued_no_host_read": lambda: compose_queued(torch, r, ds, 0, dev, bounces=bounces, materials=True, host_counts=False)})
         r.close()
         res["materials"] = row
     ctx.close()
