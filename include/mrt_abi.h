@@ -101,17 +101,20 @@ typedef struct {
 } MRTIntersection;                                                    /* 32 B                   */
 
 typedef struct {
-    uint64_t triangles;        /* T: triangles in the committed scene                          */
+    uint64_t triangles;        /* T: triangles in the committed scene (every instance's own)   */
     uint64_t vertices;         /* V                                                            */
-    uint64_t bvh_nodes;        /* nodes in the traversal layout                                */
-    uint64_t bvh_leaves;
+    uint64_t bvh_nodes;        /* nodes of the layout the rays walk: the 8-wide nodes; the binary (rope) nodes of a scene without the 8-wide
+                                  layout (wide_layout = 0); two-level scenes: the nodes of the rope TLAS (the BLASes' are in scene_bytes)   */
+    uint64_t bvh_leaves;       /* leaves of the binary tree after its SAH collapse, whichever layout was emitted from it (the 8-wide layout
+                                  groups the same references into leaf slots of its own); two-level scenes: summed over the BLASes         */
     uint64_t scene_bytes;      /* device bytes of nodes + triangle packets + shading tables    */
     float    build_ms;         /* device time of the last mrt_scene_commit                     */
     float    sah_cost;         /* SAH cost of the emitted tree (Ct=1, Ci=1); after a refit: the build's figure x wide_cost / wide_cost_built */
     int32_t  instances;
     int32_t  max_submeshes;    /* resource-table stride (Renderer.swift:128-139)               */
     int32_t  max_leaf_tris;
-    int32_t  max_depth;
+    int32_t  max_depth;        /* levels of the 8-wide tree (= wide_depth); without it: depth of the binary tree in edges from its root;
+                                  two-level scenes: levels of the rope TLAS                                                                */
     int32_t  wide_layout;      /* 1: the scene has the 8-wide layout and every ray walks it; 0: it could not be built (tree deeper than the
                                   traversal stack can be made, node index beyond 24 bits, scene option wide = 0) and every ray falls back to
                                   the binary rope walk — about a third of the rate                                                        */

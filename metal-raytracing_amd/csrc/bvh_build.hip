@@ -1015,6 +1015,7 @@ struct FlatBuild {
         out.stats = MRTSceneStats{};
         out.stats.triangles = T; out.stats.vertices = V; out.stats.instances = (int32_t)I; out.stats.max_submeshes = max_sub;
         out.stats.max_leaf_tris = opt.max_leaf;
+        out.stats.leaf_growth = 1.0f;          // 1 after a build, with or without the 8-wide layout (a refit puts stats_before back and chains on it)
     }
 
     int upload_tables() {

@@ -4,6 +4,9 @@ renders, bit for bit; its intersector must answer like brute force."""
 import numpy as np
 import pytest
 
+import bvh_audit
+import tree_stats_reference
+
 pytestmark = pytest.mark.gpu
 
 
@@ -132,6 +135,8 @@ def test_two_level_refit_gives_the_image_of_a_fresh_build_and_of_the_oracle(mrt,
         assert ds.refits == step + 1 and st.refits == step + 1, "the commit after update_mesh alone must refit the BLAS, not build"
         assert st.build_ms < st0.build_ms, (st.build_ms, st0.build_ms)
         assert st.wide_cost_built == st0.wide_cost_built and st.wide_cost > st.wide_cost_built, "a deformed mesh on the build's tree: the boxes loosen, and the statistics say so"
+        cost, _ = tree_stats_reference.scene_wide_cost(bvh_audit.layout_of(ds))          # ... and by how much: the recount from the layout the scene dumps (test_tree_stats.py has the other figures)
+        assert tree_stats_reference.ulps32(st.wide_cost, cost.emu) <= 2 and abs(float(st.wide_cost) - cost.exact) <= cost.bound, (st.wide_cost, cost)
         assert st.sah_cost > st0.sah_cost          # the build's figure scaled by each BLAS's own cost ratio (mean over the BLASes)
         assert st.leaf_growth > 1.2, st.leaf_growth          # the moved mesh's leaf boxes against the build's: the sharper signal
         costs.append(st.wide_cost)

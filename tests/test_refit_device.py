@@ -11,12 +11,14 @@ import numpy as np
 import pytest
 
 import bvh_audit as A
+import tree_stats_reference as T
 from test_fuzz_geometry import _material, _rays, _scene
 
 pytestmark = pytest.mark.gpu
 
 SIZE = (96, 64)
 SEED = 1
+F32 = np.float32
 FIELDS = ("type", "distance", "instance_id", "geometry_id", "primitive_id", "u", "v")
 LAYOUTS = {"wide": None, "wide+rope": {"rope": 1}, "rope": {"wide": 0}}
 FAN, FAN_COPIES, SOUP = 1, (1, 2, 3), 4          # mesh ids in _scene: the pole fan is not the first mesh (its vertices do not start at 0) and is flattened three times
@@ -145,6 +147,7 @@ def test_parity_with_the_host_path(mrt, orc, gpu_ctx, layout):
     assert a.stats.wide_layout == (0 if layout == "rope" else 1)
     d_rays = _t(r, gpu_ctx)
     before = a.intersect_closest(r)
+    sah_built = b.stats.sah_cost
     links = _links(b)
     assert (links is None) == (layout == "rope")
     for step in range(2):          # the second step chains leaf_growth on the first
@@ -171,6 +174,10 @@ def test_parity_with_the_host_path(mrt, orc, gpu_ctx, layout):
         assert (ra.stats.closest_rays, ra.stats.shadow_rays) == (rb.stats.closest_rays, rb.stats.shadow_rays)
         _same_stats(a, b)
         assert b.stats.refits == step + 1
+        if layout != "rope":          # ... and equal to the recount from the layout the scene dumps (tests/tree_stats_reference.py; test_tree_stats.py has the other figures)
+            cost, _ = T.scene_wide_cost(A.layout_of(b))
+            assert T.ulps32(b.stats.wide_cost, cost.emu) <= 2 and abs(float(b.stats.wide_cost) - cost.exact) <= cost.bound, (b.stats.wide_cost, cost)
+            assert F32(b.stats.sah_cost) == F32(sah_built) * (F32(b.stats.wide_cost) / F32(b.stats.wide_cost_built))
     assert b.device_updates_rejected == 0
     ra.close(); rb.close()
 
