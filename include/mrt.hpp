@@ -192,6 +192,24 @@ struct Scene {                                                       // Scene.sw
         check(mrt_scene_scatter_materials_device_counted(committed, deviceRays, deviceSurfaces, deviceHaltonIndex, n, bounce, maxBounces, lightCount, deviceShadowRays, deviceLight,
                                                          deviceNextRays, deviceLobes, hipStream, deviceCount));
     }
+    // The integrator's path state between the stages (mrt_context_*_paths_device, _deposit_light_device, _fold_sample_device): one kernel each on
+    // hipStream, no allocation, copy or wait.  deviceCount may be nullptr (all n rows); a pixel occurs at most once among the rows of a call.  advancePathsDevice takes
+    // exactly one of deviceSurfaces (the diffuse form) and deviceLobes (the materials form, which needs devicePixel and deviceRadiance); deviceKeepPath may be nullptr.
+    static void resetPathsDevice(MRTContext ctx, size_t n, void *deviceThroughput, void *devicePixel, void *deviceRadiance, size_t pixelCount, void *hipStream) {
+        check(mrt_context_reset_paths_device(ctx, n, deviceThroughput, devicePixel, deviceRadiance, pixelCount, hipStream));
+    }
+    static void advancePathsDevice(MRTContext ctx, size_t n, const void *deviceCount, const void *deviceSurfaces, const void *deviceLobes, const void *deviceLight, void *deviceThroughput,
+                                   const void *devicePixel, void *deviceRadiance, size_t pixelCount, void *deviceKeepShadow, void *deviceKeepPath, void *hipStream) {
+        check(mrt_context_advance_paths_device(ctx, n, deviceCount, deviceSurfaces, deviceLobes, deviceLight, deviceThroughput, devicePixel, deviceRadiance, pixelCount, deviceKeepShadow,
+                                               deviceKeepPath, hipStream));
+    }
+    static void depositLightDevice(MRTContext ctx, size_t n, const void *deviceCount, const void *deviceOccluded, const void *deviceLight, const void *deviceThroughput,
+                                   const void *devicePixel, void *deviceRadiance, size_t pixelCount, void *hipStream) {
+        check(mrt_context_deposit_light_device(ctx, n, deviceCount, deviceOccluded, deviceLight, deviceThroughput, devicePixel, deviceRadiance, pixelCount, hipStream));
+    }
+    static void foldSampleDevice(MRTContext ctx, size_t pixelCount, void *deviceSample, void *deviceAccum, uint32_t frameIndex, bool clearSample, void *hipStream) {
+        check(mrt_context_fold_sample_device(ctx, pixelCount, deviceSample, deviceAccum, frameIndex, clearSample ? 1 : 0, hipStream));
+    }
     // each mesh's first attribute row (an instance reports its source's) and, last, the number of rows: meshCount + 1 entries
     static std::vector<uint64_t> vertexOffsets(MRTScene scene, size_t meshCount) {
         std::vector<uint64_t> o(meshCount + 1); check(mrt_scene_vertex_offsets(scene, o.data(), o.size())); return o;

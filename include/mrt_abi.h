@@ -484,6 +484,44 @@ int mrt_scene_scatter_materials_device_counted(MRTScene scene, const void *d_ray
                                                int32_t light_count, void *d_shadow_rays, void *d_light, void *d_next_rays /* may be NULL */, void *d_lobes, void *hip_stream,
                                                const void *d_count);
 
+/* The integrator's path state on DEVICE buffers, ordered on a stream of the caller's: what lies between the stage entries above — throughput x colour,
+ * emission along the path, the keep masks the two compactions of a bounce take, radiance += light x throughput where the shadow ray got through, the running average.
+ * With them a frame on queues is library calls only, with no host read and no element-wise pass of the caller's.  None of the four reads a scene.
+ *   Common: each call enqueues ONE kernel on hip_stream (taken literally; 0 is HIP's null stream) and nothing else: no allocation, no copy from host memory, no wait.
+ *     Buffers are on the context's device and stay alive until the stream has passed the call.  Ray, throughput, light, radiance, MRTSurface and MRTScatterLobe rows are
+ *     16-byte aligned; index, count and occluded words 4-byte aligned.  d_count is one uint32 on the device and may be NULL: the kernels handle the rows i < m,
+ *     m = min(n, *d_count) (n when NULL); the word is read as unsigned, once, when the kernel starts, and no row from m on is read or written.  n == 0 is MRT_OK and
+ *     launches nothing.  d_radiance is npixels rows of 4 float32; only .rgb is ever changed.  A pixel word is read as unsigned and a row whose pixel is >= npixels
+ *     deposits nothing: nothing outside the image is touched, whatever a row holds.  The caller owes that a pixel occurs AT MOST ONCE among the rows < m of one call
+ *     (true of every queue the compaction above makes of distinct pixels): the deposit is a plain load, add and store, no atomics, and the image is the same from run to
+ *     run; where the caller breaks this, that pixel's sum is unspecified and nothing else is.  Arithmetic is float32, one rounding per * and per +, IEEE divide.
+ *     Plain arguments are checked first, the message names the argument, and a NULL context is refused last.  MRT_ERR_INVALID_ARGUMENT: n or npixels >= 2^31, a
+ *     required buffer that is NULL with n > 0, a misaligned buffer, and what each entry adds below.
+ *   mrt_context_reset_paths_device: the state before bounce 0 — throughput[i] = {1, 1, 1, 1} and pixel[i] = i for i < n, radiance[p] = {0, 0, 0, 0} for p < npixels where
+ *     d_radiance is given.
+ *   mrt_context_advance_paths_device: the step after scatter.  EXACTLY ONE of d_surfaces / d_lobes is given (both, or neither, is refused).
+ *     Diffuse form (d_surfaces, the rows of mrt_scene_resolve_hits_device; only their normal | type and base_color | slot groups are read): on = type == 1;
+ *     thr.rgb = thr.rgb * base_color for every row < m; keep_path = on; keep_shadow = on && light.w == 1.0f.  d_pixel and d_radiance are not read and may be NULL.
+ *     Materials form (d_lobes, the rows of mrt_scene_scatter_materials_device; d_pixel and d_radiance are required): where lobe != 0,
+ *     radiance[pixel].rgb = radiance[pixel].rgb + thr.rgb * emission with the throughput BEFORE its update; then thr.rgb = thr.rgb * weight for every row < m;
+ *     keep_path = 1 <= lobe <= 4; keep_shadow = light.w == 1.0f.
+ *     thr.w keeps its bits.  The mask bytes are written as 0 or 1 for every row < m; d_keep_path may be NULL (the last bounce: no second mask is written).
+ *   mrt_context_deposit_light_device: the step after the any-hit query on the compacted shadow queue — for the rows < m with occluded == 0,
+ *     radiance[pixel].rgb = radiance[pixel].rgb + light.rgb * thr.rgb.
+ *   mrt_context_fold_sample_device: the reference's running average of a frame's sample into the accumulation — frame_index == 0: accum.rgb = sample.rgb; otherwise
+ *     accum.rgb = (sample.rgb + accum.rgb * (float)frame_index) / (float)(frame_index + 1); accum.w = 1.0f, as the renderer writes it.  clear_sample != 0 leaves the sample
+ *     rows as zeros for the next frame, in the same pass.  frame_index == 2^32 - 1 and d_sample == d_accum are refused.  d_accum goes straight into
+ *     mrt_renderer_write_accum_from_device: the tonemap and the denoiser then apply to a composed image.                                                                 */
+int mrt_context_reset_paths_device(MRTContext ctx, size_t n, void *d_throughput /* n x 4 float32 */, void *d_pixel /* n x uint32 */, void *d_radiance /* may be NULL */,
+                                   size_t npixels, void *hip_stream);
+int mrt_context_advance_paths_device(MRTContext ctx, size_t n, const void *d_count /* may be NULL */, const void *d_surfaces /* n x MRTSurface or NULL */,
+                                     const void *d_lobes /* n x MRTScatterLobe or NULL */, const void *d_light /* n x 4 float32 */, void *d_throughput /* in and out */,
+                                     const void *d_pixel, void *d_radiance, size_t npixels, void *d_keep_shadow /* n x uint8 */, void *d_keep_path /* n x uint8, may be NULL */,
+                                     void *hip_stream);
+int mrt_context_deposit_light_device(MRTContext ctx, size_t n, const void *d_count /* may be NULL */, const void *d_occluded /* n x int32 */, const void *d_light,
+                                     const void *d_throughput, const void *d_pixel, void *d_radiance, size_t npixels, void *hip_stream);
+int mrt_context_fold_sample_device(MRTContext ctx, size_t npixels, void *d_sample, void *d_accum, uint32_t frame_index, int32_t clear_sample, void *hip_stream);
+
 /* ---------------------------------------------------------------- host-side geometry helpers
  * (no GPU needed) — the library's OBJ/MTL reader standing in for ModelIO (Model.swift:16-21,
  * SubMesh.swift:37-54) and the procedural dragon proxy (dragon.obj is absent upstream).        */

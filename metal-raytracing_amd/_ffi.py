@@ -189,6 +189,10 @@ SIGNATURES = {
     "mrt_scene_interpolate_device_counted": (C.c_int, [_P, _P, _SZ, _P, _SZ, _I32, _P, _SZ, _P, _P]),
     "mrt_scene_scatter_device_counted": (C.c_int, [_P, _P, _P, _SZ, _I32, _I32, _P, _P, _P, _P, _P]),
     "mrt_scene_scatter_materials_device_counted": (C.c_int, [_P, _P, _P, _P, _SZ, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "mrt_context_reset_paths_device": (C.c_int, [_P, _SZ, _P, _P, _P, _SZ, _P]),
+    "mrt_context_advance_paths_device": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P]),
+    "mrt_context_deposit_light_device": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "mrt_context_fold_sample_device": (C.c_int, [_P, _SZ, _P, _P, _U32, _I32, _P]),
     "mrt_obj_load": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
     "mrt_dragon_proxy": (C.c_int, [C.POINTER(_P)]),
     "mrt_dragon_proxy_irregular": (C.c_int, [C.POINTER(_P)]),

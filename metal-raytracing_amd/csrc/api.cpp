@@ -3,6 +3,7 @@
 // There is no CPU fallback: without a HIP device mrt_context_create fails (MRT_ERR_NO_DEVICE).
 #include "api_types.h"
 #include "abi_check.h"
+#include "paths.h"
 #include "../../include/mrt_debug.h"
 #include <algorithm>
 #include <cstring>
@@ -711,6 +712,75 @@ int mrt_context_compact_rows_device(MRTContext ctx, const void *d_keep, size_t n
     return mrt::compact_rows_device((hipStream_t)hip_stream, d_keep, n, d_count_in, columns, ncolumns, d_count_out, d_workspace);
     MRT_CATCH
 }
+
+// The integrator's path state on the caller's stream (paths.hip).  Plain arguments first, each message naming its argument; the context last.
+#define REQUIRE_ALIGNED(ptr, bytes) REQUIRE((uintptr_t)(ptr) % (bytes) == 0, who + ": " #ptr " must be " #bytes "-byte aligned")
+#define REQUIRE_GIVEN(ptr) REQUIRE(n == 0 || (ptr), who + ": " #ptr " is NULL")
+int mrt_context_reset_paths_device(MRTContext ctx, size_t n, void *d_throughput, void *d_pixel, void *d_radiance, size_t npixels, void *hip_stream) {
+    MRT_TRY
+    const std::string who = "mrt_context_reset_paths_device";
+    REQUIRE(n < (size_t(1) << 31), who + ": too many rows (n must be below 2^31)");
+    REQUIRE(npixels < (size_t(1) << 31), who + ": too many pixels (npixels must be below 2^31)");
+    REQUIRE_GIVEN(d_throughput); REQUIRE_GIVEN(d_pixel);
+    REQUIRE_ALIGNED(d_throughput, 16); REQUIRE_ALIGNED(d_pixel, 4); REQUIRE_ALIGNED(d_radiance, 16);
+    REQUIRE(ctx, who + ": ctx is NULL");
+    if (n == 0) return MRT_OK;
+    if (int rc = bind_device(ctx)) return rc;
+    return mrt::reset_paths_device((hipStream_t)hip_stream, n, d_throughput, d_pixel, d_radiance, npixels);
+    MRT_CATCH
+}
+int mrt_context_advance_paths_device(MRTContext ctx, size_t n, const void *d_count, const void *d_surfaces, const void *d_lobes, const void *d_light, void *d_throughput, const void *d_pixel,
+                                     void *d_radiance, size_t npixels, void *d_keep_shadow, void *d_keep_path, void *hip_stream) {
+    MRT_TRY
+    const std::string who = "mrt_context_advance_paths_device";
+    REQUIRE(n < (size_t(1) << 31), who + ": too many rows (n must be below 2^31)");
+    REQUIRE(npixels < (size_t(1) << 31), who + ": too many pixels (npixels must be below 2^31)");
+    REQUIRE(!(d_surfaces && d_lobes), who + ": both d_surfaces and d_lobes are given (exactly one: the diffuse form or the materials form)");
+    REQUIRE(n == 0 || d_surfaces || d_lobes, who + ": neither d_surfaces nor d_lobes is given (exactly one: the diffuse form or the materials form)");
+    REQUIRE_GIVEN(d_light); REQUIRE_GIVEN(d_throughput); REQUIRE_GIVEN(d_keep_shadow);
+    if (d_lobes) {
+        REQUIRE(n == 0 || d_pixel, who + ": d_pixel is NULL (the materials form deposits emission)");
+        REQUIRE(n == 0 || d_radiance, who + ": d_radiance is NULL (the materials form deposits emission)");
+    }
+    REQUIRE_ALIGNED(d_count, 4); REQUIRE_ALIGNED(d_surfaces, 16); REQUIRE_ALIGNED(d_lobes, 16); REQUIRE_ALIGNED(d_light, 16); REQUIRE_ALIGNED(d_throughput, 16);
+    REQUIRE_ALIGNED(d_pixel, 4); REQUIRE_ALIGNED(d_radiance, 16);
+    REQUIRE(ctx, who + ": ctx is NULL");
+    if (n == 0) return MRT_OK;
+    if (int rc = bind_device(ctx)) return rc;
+    return mrt::advance_paths_device((hipStream_t)hip_stream, n, d_count, d_surfaces, d_lobes, d_light, d_throughput, d_pixel, d_radiance, npixels, d_keep_shadow, d_keep_path);
+    MRT_CATCH
+}
+int mrt_context_deposit_light_device(MRTContext ctx, size_t n, const void *d_count, const void *d_occluded, const void *d_light, const void *d_throughput, const void *d_pixel, void *d_radiance,
+                                     size_t npixels, void *hip_stream) {
+    MRT_TRY
+    const std::string who = "mrt_context_deposit_light_device";
+    REQUIRE(n < (size_t(1) << 31), who + ": too many rows (n must be below 2^31)");
+    REQUIRE(npixels < (size_t(1) << 31), who + ": too many pixels (npixels must be below 2^31)");
+    REQUIRE_GIVEN(d_occluded); REQUIRE_GIVEN(d_light); REQUIRE_GIVEN(d_throughput); REQUIRE_GIVEN(d_pixel); REQUIRE_GIVEN(d_radiance);
+    REQUIRE_ALIGNED(d_count, 4); REQUIRE_ALIGNED(d_occluded, 4); REQUIRE_ALIGNED(d_light, 16); REQUIRE_ALIGNED(d_throughput, 16); REQUIRE_ALIGNED(d_pixel, 4); REQUIRE_ALIGNED(d_radiance, 16);
+    REQUIRE(ctx, who + ": ctx is NULL");
+    if (n == 0) return MRT_OK;
+    if (int rc = bind_device(ctx)) return rc;
+    return mrt::deposit_light_device((hipStream_t)hip_stream, n, d_count, d_occluded, d_light, d_throughput, d_pixel, d_radiance, npixels);
+    MRT_CATCH
+}
+int mrt_context_fold_sample_device(MRTContext ctx, size_t npixels, void *d_sample, void *d_accum, uint32_t frame_index, int32_t clear_sample, void *hip_stream) {
+    MRT_TRY
+    const std::string who = "mrt_context_fold_sample_device";
+    const size_t n = npixels;
+    REQUIRE(npixels < (size_t(1) << 31), who + ": too many pixels (npixels must be below 2^31)");
+    REQUIRE(frame_index != 0xFFFFFFFFu, who + ": frame_index must be below 2^32 - 1 (the fold divides by frame_index + 1)");
+    REQUIRE_GIVEN(d_sample); REQUIRE_GIVEN(d_accum);
+    REQUIRE_ALIGNED(d_sample, 16); REQUIRE_ALIGNED(d_accum, 16);
+    REQUIRE(!d_sample || d_sample != d_accum, who + ": d_sample must not be d_accum");
+    REQUIRE(ctx, who + ": ctx is NULL");
+    if (n == 0) return MRT_OK;
+    if (int rc = bind_device(ctx)) return rc;
+    return mrt::fold_sample_device((hipStream_t)hip_stream, npixels, d_sample, d_accum, frame_index, clear_sample != 0);
+    MRT_CATCH
+}
+#undef REQUIRE_ALIGNED
+#undef REQUIRE_GIVEN
 
 int mrt_debug_traversal_stats(MRTScene scene, const MRTRay *rays, size_t n, int32_t any_hit, uint32_t *out4) {
     MRT_TRY

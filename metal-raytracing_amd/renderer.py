@@ -332,6 +332,111 @@ class DeviceScene:
         """bytes of workspace compact_rows_device needs for n rows (never 0; it does not decrease with n)"""
         return int(lib.mrt_compact_workspace_bytes(int(n)))
 
+    def _rows(self, t, what, dtype, shape):
+        """a contiguous torch tensor of that dtype and shape on the context's device, checked (shape: a tuple, None for any number of rows) -> the tensor"""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype not in dtypes or t.dim() != len(shape) or not t.is_contiguous()
+                or any(s is not None and s != have for s, have in zip(shape, t.shape))):
+            names = " or ".join(str(d) for d in dtypes)
+            raise ValueError(f"{what} must be a contiguous {names} tensor of shape {tuple('n' if s is None else s for s in shape)} on {dev}")
+        return t
+
+    @staticmethod
+    def _index_kinds():
+        import torch
+        return tuple(k for k in (torch.int32, getattr(torch, "uint32", None)) if k is not None)
+
+    def reset_paths_device(self, n, radiance=True, out=None, stream=None):
+        """The path state before bounce 0, on the GPU and ordered on a stream -> (throughput (n, 4) float32 of ones, pixel (n,) int32 = 0 .. n - 1, radiance (n, 4)
+        float32 of zeros or None).  radiance=False writes (and returns) no image.  out: the tuple of tensors to write, (throughput, pixel, radiance) or (throughput, pixel);
+        a radiance tensor given there may have any number of rows (the image's pixels).  Nothing is allocated (but the outputs when out is None), copied or synchronised.
+        stream: as intersect_closest_device takes it."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        n = int(n)
+        if out is None:
+            out = (torch.empty((n, 4), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)) + ((torch.empty((n, 4), dtype=torch.float32, device=dev),) if radiance else ())
+        out = tuple(out)
+        if len(out) != (3 if radiance else 2):
+            raise ValueError(f"out must hold {3 if radiance else 2} tensors: throughput, pixel" + (", radiance" if radiance else ""))
+        thr = self._rows(out[0], "out[0] (throughput)", torch.float32, (n, 4))
+        pix = self._rows(out[1], "out[1] (pixel)", self._index_kinds(), (n,))
+        rad = self._rows(out[2], "out[2] (radiance)", torch.float32, (None, 4)) if radiance else None
+        npix = rad.shape[0] if radiance else 0
+        check(lib.mrt_context_reset_paths_device(self.ctx.handle, n, C.c_void_p(thr.data_ptr() if n else None), C.c_void_p(pix.data_ptr() if n else None),
+                                                 C.c_void_p(rad.data_ptr() if npix else None), npix, C.c_void_p(self._stream_handle(stream))))
+        return thr, pix, rad
+
+    def advance_paths_device(self, light, throughput, pixel=None, radiance=None, surfaces=None, lobes=None, count=None, keep_path=True, out=None, stream=None):
+        """The step after scatter, on the GPU and ordered on a stream: the throughput updated in place, emission deposited, the keep masks of the bounce's two
+        compactions written -> (keep_shadow, keep_path), torch.uint8 (n,) holding 0 or 1 (keep_path None with keep_path=False, the last bounce).  Exactly one of surfaces
+        and lobes.  surfaces (n, 16) float32, the rows of resolve_hits_device — the diffuse form: throughput.rgb *= base_color; keep_path = type == 1; keep_shadow =
+        keep_path and light[:, 3] == 1.  lobes (n, 8) float32, the rows of scatter_materials_device — the materials form, which needs pixel (n,) int32 and radiance
+        (pixels, 4) float32: radiance[pixel].rgb += throughput.rgb * emission where lobe != 0, with the throughput before its update; throughput.rgb *= weight; keep_path =
+        1 <= lobe <= 4; keep_shadow = light[:, 3] == 1.  A pixel may occur at most once among the rows in use; a row whose pixel is outside the image deposits nothing.
+        count: as every *_device method takes it — rows from min(n, count) on are neither read nor written, masks included.  out: the masks to write, (keep_shadow,
+        keep_path) or (keep_shadow,).  Nothing is allocated (but the masks when out is None), copied or synchronised.  stream: as intersect_closest_device takes it."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        if (surfaces is None) == (lobes is None):
+            raise ValueError("exactly one of surfaces (the diffuse form) and lobes (the materials form) must be given")
+        light = self._rows(light, "light", torch.float32, (None, 4))
+        n = light.shape[0]
+        thr = self._rows(throughput, "throughput", torch.float32, (n, 4))
+        if surfaces is not None: self._rows(surfaces, "surfaces", torch.float32, (n, 16))
+        else: self._rows(lobes, "lobes", torch.float32, (n, 8))
+        if lobes is not None and (pixel is None or radiance is None):
+            raise ValueError("the materials form needs pixel and radiance: it deposits emission")
+        if pixel is not None: self._rows(pixel, "pixel", self._index_kinds(), (n,))
+        if radiance is not None: self._rows(radiance, "radiance", torch.float32, (None, 4))
+        npix = 0 if radiance is None else radiance.shape[0]
+        want = 2 if keep_path else 1
+        if out is None:
+            out = tuple(torch.empty((n,), dtype=torch.uint8, device=dev) for _ in range(want))
+        out = tuple(out)
+        if len(out) != want:
+            raise ValueError(f"out must hold {want} torch.uint8 tensors of shape {(n,)}")
+        for k, o in enumerate(out): self._rows(o, f"out[{k}]", torch.uint8, (n,))
+
+        def p(t, live=n):
+            return C.c_void_p(t.data_ptr() if t is not None and live else None)
+
+        check(lib.mrt_context_advance_paths_device(self.ctx.handle, n, None if count is None else self._count_word(count), p(surfaces), p(lobes), p(light), p(thr), p(pixel),
+                                                   p(radiance, n and npix), npix, p(out[0]), p(out[1]) if keep_path else None, C.c_void_p(self._stream_handle(stream))))
+        return out[0], (out[1] if keep_path else None)
+
+    def deposit_light_device(self, occluded, light, throughput, pixel, radiance, count=None, stream=None):
+        """The step after intersect_any_device on the compacted shadow queue, on the GPU and ordered on a stream: radiance[pixel].rgb += light.rgb * throughput.rgb for
+        the rows in use with occluded == 0.  occluded (n,) int32, light and throughput (n, 4) float32, pixel (n,) int32, radiance (pixels, 4) float32 (its fourth
+        component keeps its bits).  A pixel may occur at most once among the rows in use (plain load, add, store: no atomics); a row whose pixel is outside the image
+        deposits nothing.  count: as every *_device method takes it.  Nothing is allocated, copied or synchronised.  stream: as intersect_closest_device takes it."""
+        import torch
+        occ = self._rows(occluded, "occluded", torch.int32, (None,))
+        n = occ.shape[0]
+        self._rows(light, "light", torch.float32, (n, 4)); self._rows(throughput, "throughput", torch.float32, (n, 4))
+        self._rows(pixel, "pixel", self._index_kinds(), (n,)); self._rows(radiance, "radiance", torch.float32, (None, 4))
+        npix = radiance.shape[0]
+        if n and not npix:
+            return                                                                                     # an image without pixels: no row can deposit
+        p = [C.c_void_p(t.data_ptr() if n else None) for t in (occ, light, throughput, pixel, radiance)]
+        check(lib.mrt_context_deposit_light_device(self.ctx.handle, n, None if count is None else self._count_word(count), *p, npix, C.c_void_p(self._stream_handle(stream))))
+
+    def fold_sample_device(self, sample, accum, frame_index, clear_sample=False, stream=None):
+        """The reference's running average on the GPU, ordered on a stream: sample and accum (pixels, 4) float32; frame_index 0: accum.rgb = sample.rgb, otherwise
+        accum.rgb = (sample.rgb + accum.rgb * frame_index) / (frame_index + 1); accum[:, 3] = 1.  clear_sample=True leaves sample as zeros for the next frame, in the same
+        pass.  accum is what Renderer.write_accum_from(accum.data_ptr(), nbytes) takes.  Nothing is allocated, copied or synchronised.  stream: as intersect_closest_device takes it."""
+        import torch
+        s = self._rows(sample, "sample", torch.float32, (None, 4))
+        npix = s.shape[0]
+        a = self._rows(accum, "accum", torch.float32, (npix, 4))
+        frame_index = int(frame_index)
+        if not 0 <= frame_index < 2 ** 32 - 1:
+            raise ValueError("frame_index must be in [0, 2^32 - 1)")
+        check(lib.mrt_context_fold_sample_device(self.ctx.handle, npix, C.c_void_p(s.data_ptr() if npix else None), C.c_void_p(a.data_ptr() if npix else None), frame_index,
+                                                 1 if clear_sample else 0, C.c_void_p(self._stream_handle(stream))))
+
     def vertex_offsets(self):
         """The vertex numbering interpolate_device reads attributes in: (meshes + 1,) uint64 — each mesh's first row, the source meshes concatenated in mesh-id order and
         an instance reporting its source's; the last entry is the number of rows."""

@@ -18,6 +18,13 @@ and, per scene and for the materials leg (the queue legs):
   (e) the composed 1080p frame ON QUEUES (tests/queues_compose.py: the wanted shadow rays and the surviving paths compacted at every bounce), in two forms — the counts read
       by the host once per bounce and every tensor sliced to them; no host read at all, the counts handed on as count= and torch's ops over the capacity with the tail
       masked — beside the dense composed frame and Renderer of (b) / (c), timed the same way in the same loop.  Both must report same_bits true.
+and, per scene and for the materials leg (the path-state legs):
+  (f) each path-state stage alone at 2^22 rows against its byte floor at the same copy bandwidth — advance_paths_device, diffuse form: 32 B of surface, 16 B of light and
+      16 B of throughput read, 16 B + 2 B of masks written per row (the materials form, in the materials leg: 32 B of lobe and the 2 x 16 B of the radiance row in place of
+      the surface); deposit_light_device: 4 + 16 + 16 + 4 B read per row and 2 x 16 B of radiance per lit row; fold_sample_device: 2 x 16 B read and 16 B written per
+      pixel, 16 B more with clear_sample;
+  (g) the frame on queues composed with the path-state stages (tests/paths_compose.py: no torch op between the stages, count= throughout, fold_sample_device at the end) in
+      the loop of (e), beside its legs; same_bits against Renderer, and its medians over those of (e)'s no-host-read form.
 3 warm + 20 timed repetitions, the legs alternating, medians.
 Usage: python tools/integrator_rate.py [--scenes dragon,dragon4] [--materials 1] [--reps 20]      (prints one JSON line)"""
 import argparse
@@ -87,6 +94,38 @@ def queue_legs(torch, m, ds, dev, rows, keeps, copy_gbs, timed, stream):
     return res
 
 
+def path_legs(torch, ds, dev, rows, surfaces, lobes, light, copy_gbs, timed, stream):
+    """(f): the path-state stages alone on `rows` rows — advance in the form the rows given allow (surfaces or lobes), deposit on the light rows with a random half of the
+    shadow rays occluded, fold with and without clear_sample"""
+    thr, pix, rad = ds.reset_paths_device(rows, stream=0)
+    masks = (torch.empty(rows, dtype=torch.uint8, device=dev), torch.empty(rows, dtype=torch.uint8, device=dev))
+    gen = torch.Generator(device=dev); gen.manual_seed(2)
+    occluded = (torch.rand(rows, device=dev, generator=gen) < 0.5).to(torch.int32)
+    accum = torch.zeros((rows, 4), device=dev)
+    form = {"surfaces": surfaces} if lobes is None else {"lobes": lobes, "pixel": pix, "radiance": rad}
+    fns = [lambda: ds.advance_paths_device(light, thr, out=masks, stream=stream, **form), lambda: ds.advance_paths_device(light, thr, keep_path=False, out=masks[:1], stream=stream, **form),
+           lambda: ds.deposit_light_device(occluded, light, thr, pix, rad, stream=stream), lambda: ds.fold_sample_device(rad, accum, 1, stream=stream),
+           lambda: ds.fold_sample_device(rad, accum, 1, clear_sample=True, stream=stream)]
+    for fn in fns: fn()
+    torch.cuda.synchronize()
+    t = timed(fns)
+    lit = float((occluded == 0).float().mean())
+    per_row = {"advance": (114.0 if lobes is not None else 82.0), "advance_last_bounce": (113.0 if lobes is not None else 81.0), "deposit": 40.0 + 32.0 * lit, "fold": 48.0, "fold_clear": 64.0}
+    res = {"form": "materials" if lobes is not None else "diffuse", "lit_share": lit}
+    for (k, b), ms in zip(per_row.items(), t):
+        floor = b * rows / copy_gbs / 1e6
+        res[k] = {"ms": ms, "bytes_per_row": b, "floor_ms": floor, "over_floor": ms / floor}
+    return res
+
+
+def fused_over_queued(e):
+    """(g) out of the loop of (e): the fused leg and its medians over the no-host-read form's"""
+    g = e.pop("fused_path_state")
+    q = e["queued_no_host_read"]
+    g["wall_over_queued_no_host_read"] = g["wall_ms"] / q["wall_ms"]; g["event_over_queued_no_host_read"] = g["event_ms"] / q["event_ms"]
+    return g
+
+
 def frame_legs(torch, r, dev, ts, reps, legs):
     """(b) / (c) / (e) in one loop: each callable of `legs` (name -> fn() -> (n, 3) sample) composed on the side stream, then Renderer drawing frame 0; medians of host wall
     and HIP-event time per leg, and whether each leg's sample has the renderer's bits"""
@@ -110,7 +149,7 @@ def frame_legs(torch, r, dev, ts, reps, legs):
     out = {"renderer_wall_ms": statistics.median(rw), "renderer_device_ms": statistics.median(own)}
     for k in legs:
         out[k] = {"wall_ms": statistics.median(wall[k]), "event_ms": statistics.median(ev[k]), "over_renderer_wall": statistics.median(wall[k]) / statistics.median(rw),
-                  "same_bits": bool(torch.equal(acc[k].view(torch.int32), img))}
+                  "same_bits": bool(torch.equal(acc[k][:, 0:3].contiguous().view(torch.int32), img))}
     return out
 
 
@@ -149,6 +188,12 @@ def main():
     miss.view(torch.int32)[0, 11] = -1; miss.view(torch.int32)[0, 12:15] = -1          # the miss record of resolve_hits_device
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from queues_compose import compose_queued                       # the queued frame of the GPU tests (test infrastructure: the tool runs from the repository)
+    from paths_compose import compose_fused                         # and the same frame with the path state kept by the library
+
+    def fused(r, ds, bounces, materials, accum):
+        rad = compose_fused(torch, r, ds, 0, dev, bounces=bounces, materials=materials)
+        ds.fold_sample_device(rad, accum, 0)
+        return accum
     gen = torch.Generator(device=dev); gen.manual_seed(1)
     half = torch.rand(rows, device=dev, generator=gen) < 0.5
     for name in [x for x in a.scenes.split(",") if x]:
@@ -175,6 +220,7 @@ def main():
                     "scatter_b0_ms": t[1], "scatter_b1_ms": t[2], "scatter_floor_ms": floor_s, "scatter_b0_over_floor": t[1] / floor_s, "scatter_b1_over_floor": t[2] / floor_s,
                     "surface_share_b0": float((surf0[:, 7].view(torch.int32) == 1).float().mean()), "surface_share_b1": float((surf1[:, 7].view(torch.int32) == 1).float().mean())}
         row["d"] = queue_legs(torch, m, ds, dev, rows, {"bounce_1_surfaces": (surf1[:, 7].view(torch.int32) == 1).contiguous(), "random_half": half}, copy_gbs, timed, s)
+        row["f"] = path_legs(torch, ds, dev, rows, surf0, None, outs[1], copy_gbs, timed, s)
         del prim, outs, surf0, surf1
         r.close()
         # (b) the composed frame beside the renderer's
@@ -200,10 +246,13 @@ def main():
         row["b"] = {"composed_wall_ms": statistics.median(wall["composed"]), "renderer_wall_ms": statistics.median(wall["renderer"]), "composed_event_ms": statistics.median(ev),
                     "renderer_device_ms": statistics.median(own), "composed_over_renderer_wall": statistics.median(wall["composed"]) / statistics.median(wall["renderer"]),
                     "same_bits": bool(torch.equal(acc.view(torch.int32), img.contiguous().view(torch.int32)))}
-        # (e) the same frame on queues, both forms, beside the dense one and the renderer in one loop
+        # (e) the same frame on queues, both forms, beside the dense one and the renderer in one loop; (g) the fused form in the same loop
+        accum = torch.empty((1920 * 1080, 4), device=dev)
         row["e"] = frame_legs(torch, r, dev, ts, a.reps, {"dense": lambda: compose(torch, r, ds, 0, dev, miss),
                                                           "queued_host_counts": lambda: compose_queued(torch, r, ds, 0, dev, bounces=3, host_counts=True),
-                                                          "queued_no_host_read": lambda: compose_queued(torch, r, ds, 0, dev, bounces=3, host_counts=False)})
+                                                          "queued_no_host_read": lambda: compose_queued(torch, r, ds, 0, dev, bounces=3, host_counts=False),
+                                                          "fused_path_state": lambda: fused(r, ds, 3, False, accum)})
+        row["g"] = fused_over_queued(row["e"])
         r.close()
         res["scenes"][name] = row
     if a.materials:
@@ -225,6 +274,7 @@ def main():
         row["c"] = {"scatter_materials_b0_ms": t[0], "no_next_rays_ms": t[1], "floor_180B_ms": floor_c, "over_floor_180B": t[0] / floor_c, "floor_212B_ms": floor_l, "over_floor_212B": t[0] / floor_l,
                     "lobe_share": [float((lobes == k).float().mean()) for k in range(6)]}
         row["d"] = queue_legs(torch, m, ds, dev, rows, {"bounce_0_paths_that_go_on": ((lobes >= 1) & (lobes <= 4)).contiguous(), "random_half": half}, copy_gbs, timed, s)
+        row["f"] = path_legs(torch, ds, dev, rows, None, outs[3], outs[1], copy_gbs, timed, s)
         del prim, outs, surf0, lobes
         r.close()
         r = m.Renderer((1920, 1080), cornell_with_materials(m, (1920, 1080)), ctx=ctx, max_bounces=bounces)
@@ -249,9 +299,12 @@ def main():
         row["frame"] = {"composed_wall_ms": statistics.median(wall["composed"]), "renderer_wall_ms": statistics.median(wall["renderer"]), "composed_event_ms": statistics.median(ev),
                         "renderer_device_ms": statistics.median(own), "composed_over_renderer_wall": statistics.median(wall["composed"]) / statistics.median(wall["renderer"]),
                         "same_bits": bool(torch.equal(acc.view(torch.int32), img.contiguous().view(torch.int32)))}
+        accum = torch.empty((1920 * 1080, 4), device=dev)
         row["e"] = frame_legs(torch, r, dev, ts, a.reps, {"dense": lambda: compose_materials(torch, r, ds, 0, dev, miss, bounces),
                                                           "queued_host_counts": lambda: compose_queued(torch, r, ds, 0, dev, bounces=bounces, materials=True, host_counts=True),
-                                                          "queued_no_host_read": lambda: compose_queued(torch, r, ds, 0, dev, bounces=bounces, materials=True, host_counts=False)})
+                                                          "queued_no_host_read": lambda: compose_queued(torch, r, ds, 0, dev, bounces=bounces, materials=True, host_counts=False),
+                                                          "fused_path_state": lambda: fused(r, ds, bounces, True, accum)})
+        row["g"] = fused_over_queued(row["e"])
         r.close()
         res["materials"] = row
     ctx.close()
