@@ -210,6 +210,21 @@ struct Scene {                                                       // Scene.sw
     static void foldSampleDevice(MRTContext ctx, size_t pixelCount, void *deviceSample, void *deviceAccum, uint32_t frameIndex, bool clearSample, void *hipStream) {
         check(mrt_context_fold_sample_device(ctx, pixelCount, deviceSample, deviceAccum, frameIndex, clearSample ? 1 : 0, hipStream));
     }
+    // From a composed frame to an image a host can show (mrt_context_fold_guides_device, _denoise_device, _tonemap_device): the guide buffers folded from
+    // the frame's bounce-0 MRTSurface rows (frameIndex 0 replaces them), Renderer::denoise's filter of any device image (params nullptr = the defaults; the workspace of
+    // denoiseWorkspaceBytes(width, height) bytes is the caller's) and the tonemap into width x height RGBA8, top row first.  On hipStream; no allocation, copy or wait.
+    static void foldGuidesDevice(MRTContext ctx, size_t pixelCount, const void *deviceSurfaces, void *deviceNormalDepth, void *deviceAlbedo, void *deviceIds, uint32_t frameIndex,
+                                 void *hipStream) {
+        check(mrt_context_fold_guides_device(ctx, pixelCount, deviceSurfaces, deviceNormalDepth, deviceAlbedo, deviceIds, frameIndex, hipStream));
+    }
+    static size_t denoiseWorkspaceBytes(int width, int height) { size_t n = 0; check(mrt_denoise_workspace_bytes(width, height, &n)); return n; }
+    static void denoiseDevice(MRTContext ctx, int width, int height, const void *deviceImage, const void *deviceNormalDepth, const void *deviceAlbedo, void *deviceWorkspace,
+                              size_t workspaceBytes, void *deviceOut, const MRTDenoiseParams *params, void *hipStream) {
+        check(mrt_context_denoise_device(ctx, width, height, deviceImage, deviceNormalDepth, deviceAlbedo, deviceWorkspace, workspaceBytes, deviceOut, params, hipStream));
+    }
+    static void tonemapDevice(MRTContext ctx, int width, int height, const void *deviceImage, void *deviceRgba8, void *hipStream) {
+        check(mrt_context_tonemap_device(ctx, width, height, deviceImage, deviceRgba8, hipStream));
+    }
     // each mesh's first attribute row (an instance reports its source's) and, last, the number of rows: meshCount + 1 entries
     static std::vector<uint64_t> vertexOffsets(MRTScene scene, size_t meshCount) {
         std::vector<uint64_t> o(meshCount + 1); check(mrt_scene_vertex_offsets(scene, o.data(), o.size())); return o;
@@ -335,6 +350,16 @@ class Renderer {                                                     // Renderer
         std::vector<float> a((size_t)w_ * h_ * 4); check(mrt_renderer_read_denoised(r_, a.data(), a.size() * 4)); return a;
     }
     std::vector<uint8_t> denoisedTonemapped() { std::vector<uint8_t> a((size_t)w_ * h_ * 4); check(mrt_renderer_read_denoised_tonemapped_rgba8(r_, a.data(), a.size())); return a; }
+    // the same three steps for an image the caller holds on the device, on a stream (Scene::foldGuidesDevice / denoiseDevice / tonemapDevice): images of this renderer's size
+    void foldGuidesDevice(const void *deviceSurfaces, void *deviceNormalDepth, void *deviceAlbedo, void *deviceIds, uint32_t frameIndex, void *hipStream) {
+        Scene::foldGuidesDevice(ctx_, (size_t)w_ * h_, deviceSurfaces, deviceNormalDepth, deviceAlbedo, deviceIds, frameIndex, hipStream);
+    }
+    size_t denoiseWorkspaceBytes() const { return Scene::denoiseWorkspaceBytes(w_, h_); }
+    void denoiseDevice(const void *deviceImage, const void *deviceNormalDepth, const void *deviceAlbedo, void *deviceWorkspace, size_t workspaceBytes, void *deviceOut,
+                       const MRTDenoiseParams *params, void *hipStream) {
+        Scene::denoiseDevice(ctx_, w_, h_, deviceImage, deviceNormalDepth, deviceAlbedo, deviceWorkspace, workspaceBytes, deviceOut, params, hipStream);
+    }
+    void tonemapDevice(const void *deviceImage, void *deviceRgba8, void *hipStream) { Scene::tonemapDevice(ctx_, w_, h_, deviceImage, deviceRgba8, hipStream); }
     MRTRenderStats stats() { MRTRenderStats s; check(mrt_renderer_stats(r_, &s)); return s; }
     MRTSceneStats sceneStats() { MRTSceneStats s; check(mrt_scene_stats(scene_, &s)); return s; }
     int width() const { return w_; }

@@ -663,6 +663,36 @@ int mrt_renderer_copy_denoised_to_device(MRTRenderer r, void *device_ptr, size_t
 /* mrt_renderer_read_tonemapped_rgba8 of the denoised image: what a host puts on screen.        */
 int mrt_renderer_read_denoised_tonemapped_rgba8(MRTRenderer r, uint8_t *rgba, size_t nbytes);
 
+/* Guide buffers, denoiser and tonemap as stages on DEVICE buffers, ordered on a stream of the caller's: the three steps above for an image the CALLER
+ * holds — a frame composed from the stage entries, a torch tensor, the image mrt_group_gathered_device_ptr assembles — with no renderer in the loop.  None reads a scene.
+ *   Common (the rules of the path-state entries): buffers are on the context's device and stay alive until the stream has passed the call; hip_stream is taken literally
+ *     (0 is HIP's null stream); after the call nothing is allocated, nothing is copied from host memory and nothing waits.  Plain arguments are checked first, the message
+ *     names the argument, and a NULL context is refused last.  Rows of 16 bytes are 16-byte aligned.  Arithmetic is float32, one rounding per operation, IEEE divide.
+ *     Images are laid out like the accumulation buffer: width*height entries, row 0 = bottom.
+ *   mrt_context_fold_guides_device: one frame folded into the three guide buffers from the frame's bounce-0 surface rows — d_surfaces is npixels x MRTSurface as
+ *     mrt_scene_resolve_hits_device wrote them for the rays of mrt_renderer_primary_rays_device, row p = pixel p.  The outputs are laid out exactly as
+ *     MRT_GUIDE_NORMAL_DEPTH / _ALBEDO / _IDS.  Per pixel: on = type == 1; n_new = on ? {normal, distance} : 0; a_new = on ? {base_color, 1} : 0;
+ *     ids = on ? {1, instance_id, geometry_id, primitive_id} : {0, -1, -1, -1} — a row that is not on contributes these whatever its other words hold.
+ *     frame_index == 0 replaces the averages (the old contents are not read: any bits are a valid start); otherwise (new + old * (float)frame_index) /
+ *     (float)(frame_index + 1) per component, all four of both buffers.  The ids are always this frame's.  One kernel per call; npixels == 0 is MRT_OK and launches
+ *     nothing.  Folding frames 0 .. f - 1 of a renderer's primary rays gives that renderer's guides after f frames, bit for bit.
+ *     MRT_ERR_INVALID_ARGUMENT: npixels >= 2^31, frame_index == 2^32 - 1, a NULL or misaligned buffer with npixels > 0, two of the four buffers being the same pointer.
+ *   mrt_context_denoise_device: exactly the filter mrt_renderer_denoise defines (the comment block above; params == NULL = the same defaults) with d_image in place of the
+ *     accumulation buffer, d_workspace (mrt_denoise_workspace_bytes: two images, 2 * width * height * 16) in place of the two scratch images and d_out in place of the
+ *     denoised buffer.  d_image.w is ignored; the output alpha is 1; the inputs are not modified.  MRT_ERR_INVALID_ARGUMENT: parameters out of range (as
+ *     mrt_renderer_denoise), width or height <= 0, width * height >= 2^30, a NULL or misaligned buffer, workspace_bytes too small, d_out or the workspace overlapping an
+ *     input or each other (byte ranges).
+ *   mrt_context_tonemap_device: mrt_renderer_read_tonemapped_rgba8's image of d_image left on the device — Reinhard c / (1 + c), saturate,
+ *     (unsigned char)(v * 255 + 0.5), alpha 255, rows flipped so the top row comes first.  d_rgba8 is width * height * 4 bytes, 4-byte aligned.  One kernel.
+ *     MRT_ERR_INVALID_ARGUMENT: the sizes as above, a NULL or misaligned buffer, d_rgba8 overlapping d_image.
+ * Guides and the filter for a device group: apply these entries to the gathered image on the root's context.                                                           */
+int mrt_context_fold_guides_device(MRTContext ctx, size_t npixels, const void *d_surfaces, void *d_normal_depth, void *d_albedo, void *d_ids, uint32_t frame_index,
+                                   void *hip_stream);
+int mrt_denoise_workspace_bytes(int32_t width, int32_t height, size_t *bytes);
+int mrt_context_denoise_device(MRTContext ctx, int32_t width, int32_t height, const void *d_image, const void *d_normal_depth, const void *d_albedo, void *d_workspace,
+                               size_t workspace_bytes, void *d_out, const MRTDenoiseParams *params, void *hip_stream);
+int mrt_context_tonemap_device(MRTContext ctx, int32_t width, int32_t height, const void *d_image, void *d_rgba8, void *hip_stream);
+
 /* ---------------------------------------------------------------- device group (multi-GPU, one process)
  * The reference creates ONE device and ONE queue (MTLCreateSystemDefaultDevice + makeCommandQueue, Renderer.swift:46-59); this is that
  * seam widened to the n GPUs of a node.  The scene and its BVH are replicated on every device; the image is sharded by 8x8 screen tile

@@ -235,6 +235,10 @@ SIGNATURES = {
     "mrt_renderer_read_denoised": (C.c_int, [_P, _P, _SZ]),
     "mrt_renderer_copy_denoised_to_device": (C.c_int, [_P, _P, _SZ]),
     "mrt_renderer_read_denoised_tonemapped_rgba8": (C.c_int, [_P, _P, _SZ]),
+    "mrt_context_fold_guides_device": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _U32, _P]),
+    "mrt_denoise_workspace_bytes": (C.c_int, [_I32, _I32, C.POINTER(_SZ)]),
+    "mrt_context_denoise_device": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _SZ, _P, C.POINTER(DenoiseParams), _P]),
+    "mrt_context_tonemap_device": (C.c_int, [_P, _I32, _I32, _P, _P, _P]),
     "mrt_renderer_stats": (C.c_int, [_P, C.POINTER(RenderStats)]),
     "mrt_renderer_reset_stats": (C.c_int, [_P]),
     "mrt_renderer_kernel_times": (C.c_int, [_P, C.POINTER(KernelTimes)]),

@@ -4,6 +4,7 @@
 #include "api_types.h"
 #include "abi_check.h"
 #include "paths.h"
+#include "image.h"
 #include "../../include/mrt_debug.h"
 #include <algorithm>
 #include <cstring>
@@ -779,6 +780,87 @@ int mrt_context_fold_sample_device(MRTContext ctx, size_t npixels, void *d_sampl
     return mrt::fold_sample_device((hipStream_t)hip_stream, npixels, d_sample, d_accum, frame_index, clear_sample != 0);
     MRT_CATCH
 }
+
+// From a composed frame to an image a host can show, on the caller's stream (image.hip).  The same order: plain arguments, each message naming its
+// argument; the context last.
+namespace {
+struct ByteRange { uintptr_t lo, hi; const char *what; };
+inline ByteRange byte_range(const void *p, size_t bytes, const char *what) { return {(uintptr_t)p, (uintptr_t)p + bytes, what}; }
+inline bool ranges_overlap(const ByteRange &a, const ByteRange &b) { return a.lo < b.hi && b.lo < a.hi; }
+}  // namespace
+#define REQUIRE_IMAGE_SIZE() \
+    REQUIRE(width > 0, who + ": width must be above 0"); REQUIRE(height > 0, who + ": height must be above 0"); \
+    REQUIRE((uint64_t)width * (uint64_t)height < (uint64_t(1) << 30), who + ": too many pixels (width * height must be below 2^30)")
+int mrt_context_fold_guides_device(MRTContext ctx, size_t npixels, const void *d_surfaces, void *d_normal_depth, void *d_albedo, void *d_ids, uint32_t frame_index, void *hip_stream) {
+    MRT_TRY
+    const std::string who = "mrt_context_fold_guides_device";
+    const size_t n = npixels;
+    REQUIRE(npixels < (size_t(1) << 31), who + ": too many pixels (npixels must be below 2^31)");
+    REQUIRE(frame_index != 0xFFFFFFFFu, who + ": frame_index must be below 2^32 - 1 (the fold divides by frame_index + 1)");
+    REQUIRE_GIVEN(d_surfaces); REQUIRE_GIVEN(d_normal_depth); REQUIRE_GIVEN(d_albedo); REQUIRE_GIVEN(d_ids);
+    REQUIRE_ALIGNED(d_surfaces, 16); REQUIRE_ALIGNED(d_normal_depth, 16); REQUIRE_ALIGNED(d_albedo, 16); REQUIRE_ALIGNED(d_ids, 16);
+    const ByteRange bufs[4] = {byte_range(d_surfaces, 0, "d_surfaces"), byte_range(d_normal_depth, 0, "d_normal_depth"), byte_range(d_albedo, 0, "d_albedo"), byte_range(d_ids, 0, "d_ids")};
+    for (int a = 0; a < 4; a++)
+        for (int b = a + 1; b < 4; b++) REQUIRE(!bufs[a].lo || bufs[a].lo != bufs[b].lo, who + ": " + bufs[a].what + " must not be " + bufs[b].what);
+    REQUIRE(ctx, who + ": ctx is NULL");
+    if (n == 0) return MRT_OK;
+    if (int rc = bind_device(ctx)) return rc;
+    return mrt::fold_guides_device((hipStream_t)hip_stream, npixels, d_surfaces, d_normal_depth, d_albedo, d_ids, frame_index);
+    MRT_CATCH
+}
+int mrt_denoise_workspace_bytes(int32_t width, int32_t height, size_t *bytes) {
+    MRT_TRY
+    const std::string who = "mrt_denoise_workspace_bytes";
+    REQUIRE_IMAGE_SIZE();
+    REQUIRE(bytes, who + ": bytes is NULL");
+    *bytes = mrt::denoise_workspace_bytes(width, height);
+    return MRT_OK;
+    MRT_CATCH
+}
+int mrt_context_denoise_device(MRTContext ctx, int32_t width, int32_t height, const void *d_image, const void *d_normal_depth, const void *d_albedo, void *d_workspace, size_t workspace_bytes,
+                               void *d_out, const MRTDenoiseParams *params, void *hip_stream) {
+    MRT_TRY
+    const std::string who = "mrt_context_denoise_device";
+    REQUIRE_IMAGE_SIZE();
+    MRTDenoiseParams p{};
+    if (params) p = *params;
+    else { p.iterations = MRT_DENOISE_DEFAULT_ITERATIONS; p.sigma_color = MRT_DENOISE_DEFAULT_SIGMA_COLOR; p.sigma_normal = MRT_DENOISE_DEFAULT_SIGMA_NORMAL; p.sigma_depth = MRT_DENOISE_DEFAULT_SIGMA_DEPTH; p.demodulate = 1; }
+    // Renderer::enqueue_denoise's checks and words
+    REQUIRE(p.iterations >= 1 && p.iterations <= 8, who + ": denoise: iterations must be in [1,8]");
+    const float big = 3.0e38f;
+    REQUIRE((p.sigma_color > 0.0f && p.sigma_color < big) && (p.sigma_normal > 0.0f && p.sigma_normal < big) && (p.sigma_depth > 0.0f && p.sigma_depth < big),
+            who + ": denoise: sigma_color, sigma_normal and sigma_depth must be finite and > 0");
+    REQUIRE(p.demodulate == 0 || p.demodulate == 1, who + ": denoise: demodulate must be 0 or 1");
+    const size_t n = (size_t)width * (size_t)height, image_bytes = n * 16, need = mrt::denoise_workspace_bytes(width, height);
+    REQUIRE_GIVEN(d_image); REQUIRE_GIVEN(d_normal_depth); REQUIRE_GIVEN(d_albedo); REQUIRE_GIVEN(d_workspace); REQUIRE_GIVEN(d_out);
+    REQUIRE_ALIGNED(d_image, 16); REQUIRE_ALIGNED(d_normal_depth, 16); REQUIRE_ALIGNED(d_albedo, 16); REQUIRE_ALIGNED(d_workspace, 16); REQUIRE_ALIGNED(d_out, 16);
+    REQUIRE(workspace_bytes >= need, who + ": workspace_bytes is below mrt_denoise_workspace_bytes(width, height)");
+    const ByteRange inputs[3] = {byte_range(d_image, image_bytes, "d_image"), byte_range(d_normal_depth, image_bytes, "d_normal_depth"), byte_range(d_albedo, image_bytes, "d_albedo")};
+    const ByteRange work = byte_range(d_workspace, need, "d_workspace"), out = byte_range(d_out, image_bytes, "d_out");
+    for (const ByteRange &in : inputs) {
+        REQUIRE(!ranges_overlap(out, in), who + ": d_out overlaps " + in.what);
+        REQUIRE(!ranges_overlap(work, in), who + ": d_workspace overlaps " + in.what);
+    }
+    REQUIRE(!ranges_overlap(out, work), who + ": d_out overlaps d_workspace");
+    REQUIRE(ctx, who + ": ctx is NULL");
+    if (int rc = bind_device(ctx)) return rc;
+    return mrt::denoise_image_device((hipStream_t)hip_stream, width, height, d_image, d_normal_depth, d_albedo, d_workspace, d_out, p);
+    MRT_CATCH
+}
+int mrt_context_tonemap_device(MRTContext ctx, int32_t width, int32_t height, const void *d_image, void *d_rgba8, void *hip_stream) {
+    MRT_TRY
+    const std::string who = "mrt_context_tonemap_device";
+    REQUIRE_IMAGE_SIZE();
+    const size_t n = (size_t)width * (size_t)height;
+    REQUIRE_GIVEN(d_image); REQUIRE_GIVEN(d_rgba8);
+    REQUIRE_ALIGNED(d_image, 16); REQUIRE_ALIGNED(d_rgba8, 4);
+    REQUIRE(!ranges_overlap(byte_range(d_rgba8, n * 4, ""), byte_range(d_image, n * 16, "")), who + ": d_rgba8 overlaps d_image");
+    REQUIRE(ctx, who + ": ctx is NULL");
+    if (int rc = bind_device(ctx)) return rc;
+    return mrt::tonemap_image_device((hipStream_t)hip_stream, width, height, d_image, d_rgba8);
+    MRT_CATCH
+}
+#undef REQUIRE_IMAGE_SIZE
 #undef REQUIRE_ALIGNED
 #undef REQUIRE_GIVEN
 

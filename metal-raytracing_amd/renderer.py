@@ -437,6 +437,94 @@ class DeviceScene:
         check(lib.mrt_context_fold_sample_device(self.ctx.handle, npix, C.c_void_p(s.data_ptr() if npix else None), C.c_void_p(a.data_ptr() if npix else None), frame_index,
                                                  1 if clear_sample else 0, C.c_void_p(self._stream_handle(stream))))
 
+    def fold_guides_device(self, surfaces, frame_index, out=None, stream=None):
+        """One frame folded into the first-hit guide buffers from its bounce-0 surface rows, on the GPU and ordered on a stream: surfaces (pixels, 16) float32, the rows
+        resolve_hits_device wrote for the rays of Renderer.primary_rays_device (row p = pixel p) -> (normal_depth (pixels, 4) float32, albedo (pixels, 4) float32, ids
+        (pixels, 4) int32), laid out as Renderer.guides() returns them.  A surface (type == 1) contributes normal | distance, base colour | 1 and {1, instance, geometry,
+        primitive}; any other row zeros and {0, -1, -1, -1}, whatever else it holds.  frame_index 0 replaces the averages (what they held is not read), otherwise
+        (new + old * frame_index) / (frame_index + 1); the ids are this frame's.  out: the triple to update in place — this is how the averages are carried from frame to
+        frame; allocated when None.  Folding frames 0 .. f - 1 gives the guides of Renderer(guides = 1) after draw(f), bit for bit.  Nothing is allocated (but the outputs
+        when out is None), copied or synchronised.  stream: as intersect_closest_device takes it."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        s = self._rows(surfaces, "surfaces", torch.float32, (None, 16))
+        npix = s.shape[0]
+        frame_index = int(frame_index)
+        if not 0 <= frame_index < 2 ** 32 - 1:
+            raise ValueError("frame_index must be in [0, 2^32 - 1)")
+        if out is None:
+            out = (torch.empty((npix, 4), dtype=torch.float32, device=dev), torch.empty((npix, 4), dtype=torch.float32, device=dev), torch.empty((npix, 4), dtype=torch.int32, device=dev))
+        out = tuple(out)
+        if len(out) != 3:
+            raise ValueError("out must hold 3 tensors: normal_depth, albedo, ids")
+        nd = self._rows(out[0], "out[0] (normal_depth)", torch.float32, (npix, 4))
+        al = self._rows(out[1], "out[1] (albedo)", torch.float32, (npix, 4))
+        ids = self._rows(out[2], "out[2] (ids)", torch.int32, (npix, 4))
+        p = [C.c_void_p(t.data_ptr() if npix else None) for t in (s, nd, al, ids)]
+        check(lib.mrt_context_fold_guides_device(self.ctx.handle, npix, *p, frame_index, C.c_void_p(self._stream_handle(stream))))
+        return nd, al, ids
+
+    @staticmethod
+    def denoise_workspace_bytes(size):
+        """bytes of workspace denoise_device needs for an image of size (width, height): two images of 16 bytes per pixel"""
+        n = C.c_size_t(0)
+        check(lib.mrt_denoise_workspace_bytes(int(size[0]), int(size[1]), C.byref(n)))
+        return int(n.value)
+
+    def denoise_device(self, image, normal_depth, albedo, size, iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None, demodulate=None, out=None, workspace=None,
+                       stream=None):
+        """Renderer.denoise's filter of an image the caller holds, on the GPU and ordered on a stream: image, normal_depth and albedo are float32 tensors of width x height
+        x 4 elements — (h, w, 4) or (h * w, 4), row 0 = bottom — size = (width, height) -> the denoised image, float32 of image's shape, alpha 1.  image[..., 3] is
+        ignored and no input is modified.  The parameters and their defaults are Renderer.denoise's.  out: the tensor to write (image's shape; it may not overlap an
+        input); workspace: a torch.uint8 tensor of at least denoise_workspace_bytes(size) bytes; both are allocated with torch when None.  Otherwise nothing is allocated,
+        copied or synchronised.  stream: as intersect_closest_device takes it."""
+        import torch
+        from ._ffi import DENOISE_DEFAULTS, DenoiseParams
+        dev = torch.device("cuda", self.ctx.device)
+        w, h = int(size[0]), int(size[1])
+        need = self.denoise_workspace_bytes((w, h))                                                     # (refuses a size that is not positive or too large)
+        shapes = ((h, w, 4), (h * w, 4))
+
+        def img(t, what):
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or tuple(t.shape) not in shapes or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous torch.float32 tensor of shape {shapes[0]} or {shapes[1]} on {dev}")
+            return t
+
+        img(image, "image"); img(normal_depth, "normal_depth"); img(albedo, "albedo")
+        if out is None:
+            out = torch.empty_like(image)
+        elif tuple(img(out, "out").shape) != tuple(image.shape):
+            raise ValueError("out must have image's shape")
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        elif not isinstance(workspace, torch.Tensor) or workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+            raise ValueError(f"workspace must be a contiguous torch.uint8 tensor on {dev} (denoise_workspace_bytes(size) bytes)")
+        given = dict(iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_depth=sigma_depth, demodulate=demodulate)
+        v = {k: (DENOISE_DEFAULTS[k] if x is None else x) for k, x in given.items()}
+        p = DenoiseParams(int(v["iterations"]), float(v["sigma_color"]), float(v["sigma_normal"]), float(v["sigma_depth"]), int(v["demodulate"]))
+        check(lib.mrt_context_denoise_device(self.ctx.handle, w, h, C.c_void_p(image.data_ptr()), C.c_void_p(normal_depth.data_ptr()), C.c_void_p(albedo.data_ptr()),
+                                             C.c_void_p(workspace.data_ptr() if workspace.numel() else None), workspace.numel(), C.c_void_p(out.data_ptr()), C.byref(p),
+                                             C.c_void_p(self._stream_handle(stream))))
+        return out
+
+    def tonemap_device(self, image, size, out=None, stream=None):
+        """Renderer.tonemapped() of an image the caller holds, left on the GPU and ordered on a stream: image a float32 tensor of shape (h, w, 4) or (h * w, 4), row 0 =
+        bottom, size = (width, height) -> torch.uint8 (h, w, 4), top row first: Reinhard, saturate, round to 8 bits, alpha 255.  out: the tensor to write, allocated
+        when None.  Nothing else is allocated, copied or synchronised.  stream: as intersect_closest_device takes it."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        w, h = int(size[0]), int(size[1])
+        self.denoise_workspace_bytes((w, h))                                                            # (refuses a size that is not positive or too large)
+        shapes = ((h, w, 4), (h * w, 4))
+        if not isinstance(image, torch.Tensor) or image.device != dev or image.dtype != torch.float32 or tuple(image.shape) not in shapes or not image.is_contiguous():
+            raise ValueError(f"image must be a contiguous torch.float32 tensor of shape {shapes[0]} or {shapes[1]} on {dev}")
+        if out is None:
+            out = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
+        else:
+            self._rows(out, "out", torch.uint8, (h, w, 4))
+        check(lib.mrt_context_tonemap_device(self.ctx.handle, w, h, C.c_void_p(image.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(self._stream_handle(stream))))
+        return out
+
     def vertex_offsets(self):
         """The vertex numbering interpolate_device reads attributes in: (meshes + 1,) uint64 — each mesh's first row, the source meshes concatenated in mesh-id order and
         an instance reporting its source's; the last entry is the number of rows."""

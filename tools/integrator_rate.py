@@ -25,8 +25,14 @@ and, per scene and for the materials leg (the path-state legs):
       pixel, 16 B more with clear_sample;
   (g) the frame on queues composed with the path-state stages (tests/paths_compose.py: no torch op between the stages, count= throughout, fold_sample_device at the end) in
       the loop of (e), beside its legs; same_bits against Renderer, and its medians over those of (e)'s no-host-read form.
+and, per scene (the image legs), at 1920 x 1080:
+  (h) each image stage alone, HIP events — fold_guides_device at frame 0 and at a later frame against its byte floors at the same copy bandwidth (112 and 144 B per pixel:
+      the 64-byte surface row, the two old averages except at frame 0, three 16-byte entries written), tonemap_device against 20 B per pixel, and denoise_device beside
+      Renderer.denoise on the same image and guides (the same kernels: the expectation is equality);
+  (i) the fused frame of (g) with and without the guide fold of its bounce-0 rows, beside Renderer drawing the frame with guides = 0 and with guides = 1 (which walks the
+      primary rays a second time), the four alternating in one loop: what guides cost a composed frame and what they cost the renderer.
 3 warm + 20 timed repetitions, the legs alternating, medians.
-Usage: python tools/integrator_rate.py [--scenes dragon,dragon4] [--materials 1] [--reps 20]      (prints one JSON line)"""
+Usage: python tools/integrator_rate.py [--scenes dragon,dragon4] [--materials 1] [--reps 20] [--legs all|image]      (prints one JSON line; --legs image: (h) and (i) alone)"""
 import argparse
 import json
 import os
@@ -126,6 +132,97 @@ def fused_over_queued(e):
     return g
 
 
+class FoldAtBounceZero:
+    """a DeviceScene whose resolve_hits_device also folds the rows into the guide buffers where they are a frame's bounce-0 rows (the dense call, without count=): the
+    fused frame of paths_compose.compose_fused with the guide fold in it, call for call"""
+
+    def __init__(self, ds, frame_index, guides):
+        self._ds, self._frame, self.guides = ds, frame_index, guides
+
+    def __getattr__(self, name):
+        return getattr(self._ds, name)
+
+    def resolve_hits_device(self, rays, hits, **kw):
+        surf = self._ds.resolve_hits_device(rays, hits, **kw)
+        if "count" not in kw: self.guides = self._ds.fold_guides_device(surf, self._frame, out=self.guides)
+        return surf
+
+
+def image_legs(torch, m, ctx, r, ds, dev, ts, reps, copy_gbs, timed, compose_fused):
+    """(h) and (i) on a 1920 x 1080 renderer"""
+    w, h = r.size
+    n = w * h
+    s = ts.cuda_stream
+    r.set_option("guides", 1)
+    r.frameIndex = 0
+    r.draw(4, wait=True)
+    g = r.guides()
+    image = torch.from_numpy(r.accumulation()).to(dev); nd = torch.from_numpy(g["normal_depth"]).to(dev); al = torch.from_numpy(g["albedo"]).to(dev)
+    rays, _ = r.primary_rays_device(sample_index=4, stream=0)
+    surf = ds.resolve_hits_device(rays, ds.intersect_closest_device(rays, stream=0), stream=0)
+    guides = (nd.reshape(-1, 4).clone(), al.reshape(-1, 4).clone(), torch.empty((n, 4), dtype=torch.int32, device=dev))
+    den = torch.empty_like(image); rgba = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
+    work = torch.empty(ds.denoise_workspace_bytes((w, h)), dtype=torch.uint8, device=dev)
+    theirs = torch.cuda.ExternalStream(ctx.stream, device=dev)                     # the renderer's stream: its filter is enqueued there
+    torch.cuda.synchronize()
+    t = timed([lambda: ds.fold_guides_device(surf, 0, out=guides, stream=s), lambda: ds.fold_guides_device(surf, 4, out=guides, stream=s),
+               lambda: ds.tonemap_device(image, (w, h), out=rgba, stream=s)])
+    mine, own = [], []
+    for rep in range(3 + reps):                                                    # the two filters alternating with nothing between them: each finds what the other left in the caches
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(ts); ds.denoise_device(image, nd, al, (w, h), out=den, workspace=work, stream=s); e1.record(ts); ts.synchronize()
+        if rep >= 3: mine.append(e0.elapsed_time(e1))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(theirs); r.denoise(read=False); e1.record(theirs); theirs.synchronize()
+        if rep >= 3: own.append(e0.elapsed_time(e1))
+    t.append(statistics.median(mine))
+    same = bool(torch.equal(den.view(torch.int32), torch.from_numpy(r.denoised()).to(dev).view(torch.int32)))
+    res = {"surface_share": float((surf[:, 7].view(torch.int32) == 1).float().mean())}
+    for k, ms, b in (("fold_frame_0", t[0], 112.0), ("fold_later_frame", t[1], 144.0), ("tonemap", t[2], 20.0)):
+        floor = b * n / copy_gbs / 1e6
+        res[k] = {"ms": ms, "bytes_per_pixel": b, "floor_ms": floor, "over_floor": ms / floor}
+    res["denoise"] = {"device_ms": t[3], "renderer_ms": statistics.median(own), "device_over_renderer": t[3] / statistics.median(own), "same_bits": same}
+    # (i)
+    accum = torch.empty((n, 4), device=dev)
+    folded = FoldAtBounceZero(ds, 0, (torch.empty((n, 4), device=dev), torch.empty((n, 4), device=dev), torch.empty((n, 4), dtype=torch.int32, device=dev)))
+
+    def fused(scene):
+        rad = compose_fused(torch, r, scene, 0, dev, bounces=3)
+        ds.fold_sample_device(rad, accum, 0)
+        return accum
+
+    legs = {"fused": lambda: fused(ds), "fused_with_guide_fold": lambda: fused(folded)}
+    wall = {k: [] for k in legs}; ev = {k: [] for k in legs}; rw = {0: [], 1: []}; rd = {0: [], 1: []}
+    for rep in range(3 + reps):
+        for k, fn in legs.items():
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0 = time.perf_counter()
+                e0.record(ts); fn(); e1.record(ts); ts.synchronize()
+                t1 = time.perf_counter()
+            if rep >= 3: wall[k].append((t1 - t0) * 1e3); ev[k].append(e0.elapsed_time(e1))
+        for on in (0, 1):
+            r.set_option("guides", on)
+            r.frameIndex = 0
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            r.draw(1, wait=True)
+            t3 = time.perf_counter()
+            if rep >= 3: rw[on].append((t3 - t2) * 1e3); rd[on].append(float(r.stats.ms_gpu_last))
+    gr = r.guides()                                                                # (the last draw had guides = 1, frame 0)
+    med = statistics.median
+    frame = {k: {"wall_ms": med(wall[k]), "event_ms": med(ev[k])} for k in legs}
+    frame["guide_fold_cost_event_ms"] = med(ev["fused_with_guide_fold"]) - med(ev["fused"]); frame["guide_fold_cost_wall_ms"] = med(wall["fused_with_guide_fold"]) - med(wall["fused"])
+    frame["renderer"] = {"wall_ms": med(rw[0]), "device_ms": med(rd[0])}; frame["renderer_guides"] = {"wall_ms": med(rw[1]), "device_ms": med(rd[1])}
+    frame["renderer_guides_cost_wall_ms"] = med(rw[1]) - med(rw[0]); frame["renderer_guides_cost_device_ms"] = med(rd[1]) - med(rd[0])
+    frame["same_bits"] = bool(torch.equal(accum.view(torch.int32), torch.from_numpy(r.accumulation()).to(dev).reshape(-1, 4).view(torch.int32))
+                              and all(torch.equal(a.view(torch.int32), torch.from_numpy(gr[k]).to(dev).reshape(-1, 4).view(torch.int32))
+                                      for a, k in zip(folded.guides, ("normal_depth", "albedo", "ids"))))
+    r.set_option("guides", 0)
+    return {"h": res, "i": frame}
+
+
 def frame_legs(torch, r, dev, ts, reps, legs):
     """(b) / (c) / (e) in one loop: each callable of `legs` (name -> fn() -> (n, 3) sample) composed on the side stream, then Renderer drawing frame 0; medians of host wall
     and HIP-event time per leg, and whether each leg's sample has the renderer's bits"""
@@ -159,7 +256,9 @@ def main():
     ap.add_argument("--materials", type=int, default=1, help="(c): the materials leg")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--side", type=int, default=2048, help="(a): the image is side x side pixels")
+    ap.add_argument("--legs", choices=("all", "image"), default="all", help="image: (h) and (i) alone, per scene (no materials leg)")
     a = ap.parse_args()
+    if a.legs == "image": a.materials = 0
     import torch
     import metal_raytracing_amd as m
     ctx = m.Context(0)
@@ -200,6 +299,13 @@ def main():
         two_level = name == "dragon4"
         opts = {"instancing": 1} if two_level else None
         row = {"instancing": int(two_level)}
+        if a.legs == "image":
+            r = m.Renderer((1920, 1080), m.SCENES[name]((1920, 1080)), ctx=ctx, scene_options=opts)
+            row["triangles"] = int(r.device_scene.stats.triangles)
+            row.update(image_legs(torch, m, ctx, r, r.device_scene, dev, ts, a.reps, copy_gbs, timed, compose_fused))
+            r.close()
+            res["scenes"][name] = row
+            continue
         # (a) the stages alone
         sc = m.SCENES[name]((a.side, a.side))
         r = m.Renderer((a.side, a.side), sc, ctx=ctx, scene_options=opts)
@@ -253,6 +359,7 @@ def main():
                                                           "queued_no_host_read": lambda: compose_queued(torch, r, ds, 0, dev, bounces=3, host_counts=False),
                                                           "fused_path_state": lambda: fused(r, ds, 3, False, accum)})
         row["g"] = fused_over_queued(row["e"])
+        row.update(image_legs(torch, m, ctx, r, ds, dev, ts, a.reps, copy_gbs, timed, compose_fused))
         r.close()
         res["scenes"][name] = row
     if a.materials:
