@@ -25,30 +25,17 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line) {
 
 static int bind_device(MRTContext ctx) { MRT_HIP(hipSetDevice(ctx->device)); return MRT_OK; }
 
-// HostMesh copies brought up to date (download_stale_meshes).  A mesh updated on the device and never refitted there is a vertex change like mrt_scene_update_mesh's: where nothing
-// else changed since the commit, the next commit refits instead of building.
+// HostMesh copies brought up to date.  What the three families of device updates left for the next commit — vertices nobody refitted (§10d flattened, §10f per BLAS), instances
+// moved (§10e) — is reported to scene->changes, which decides what that makes of the commit (scene_changes.h).
 static int sync_host_meshes(MRTScene scene) {
-    bool pending = false;
-    int rc = mrt::download_stale_meshes(scene->meshes, scene->dev, &pending);
-    if (!rc && pending && scene->committed) scene->only_vertices_changed = true;
+    bool flat_vertices = false, blas_vertices = false, moved = false;
+    int rc = mrt::download_stale_meshes(scene->meshes, scene->dev, &flat_vertices);
     // a two-level scene whose BLASes were refitted on the device (mrt_scene_refit_blas_device): their root boxes — update_tlas builds the TLAS from them — and statistics first,
-    // then the vertices of the meshes updated there
+    // then the vertices of the meshes updated there, then the matrices of the instances moved there
     if (!rc) rc = mrt::resolve_blas_refits(scene->dev, scene->opt, scene->ctx->stream);
-    bool blas_pending = false;
-    if (!rc) rc = mrt::download_stale_blas_meshes(scene->meshes, scene->dev, &blas_pending);
-    if (!rc && blas_pending) {          // a mesh updated by mrt_scene_update_blas_device that no refit followed: a vertex change, whatever else waits for the commit
-        if (scene->committed) scene->only_vertices_changed = true;
-        else if (scene->only_transforms_changed) { scene->only_vertices_changed = false; scene->only_transforms_changed = false; }      // mrt_scene_set_instance_transform since: vertices AND transforms, a full build
-    }
-    // instances moved on the device (mrt_scene_set_instance_transforms_device): their HostMesh::xf read back — a transform change like mrt_scene_set_instance_transform's
-    bool moved = false;
+    if (!rc) rc = mrt::download_stale_blas_meshes(scene->meshes, scene->dev, &blas_vertices);
     if (!rc) rc = mrt::download_moved_transforms(scene->meshes, scene->dev, &moved);
-    if (!rc && moved) {
-        // vertices AND transforms changed: a full build.  A scene still `committed` can be here too — its vertex change was found two lines up (poses and an unrefitted
-        // update, both on the device) —, and neither flag set with `committed` set is a full build for mrt_scene_commit
-        if (scene->only_vertices_changed) { scene->only_vertices_changed = false; scene->only_transforms_changed = false; }
-        else if (scene->committed) scene->only_transforms_changed = true;
-    }
+    scene->changes.device_changes_found(flat_vertices, blas_vertices, moved);          // (also where a later read-back failed: the workspaces have forgotten what they reported)
     return rc;
 }
 
@@ -148,7 +135,7 @@ static bool all_finite(const float *p, size_t stride_bytes, size_t n, int comps)
     }
     return bad == 0;
 }
-static void mark_changed(MRTScene scene) { scene->committed = false; scene->only_transforms_changed = false; scene->only_vertices_changed = false; }      // a mesh, a submesh or an option changed: the next commit builds
+static void mark_changed(MRTScene scene) { scene->changes.host_changed(mrt::Pending::rebuild); }      // a mesh, a submesh or an option changed: the next commit builds
 static void grow_stage(MRTScene scene, size_t bytes) {          // the pinned staging area of the commit's uploads (see mrt_mesh_add_submesh)
     scene->stage_need += bytes;
     if (scene->stage_need > scene->dev.stage.cap && bind_device(scene->ctx) == MRT_OK) { if (scene->dev.stage.reserve(std::max(scene->stage_need, 2 * scene->dev.stage.cap)) != hipSuccess) (void)hipGetLastError(); }
@@ -254,7 +241,7 @@ int mrt_scene_set_lights(MRTScene scene, const MRTLight *lights, int32_t count) 
     MRT_TRY
     REQUIRE(scene && count >= 0 && (count == 0 || lights), "mrt_scene_set_lights: bad argument");
     scene->lights.assign(lights, lights + count);
-    if (scene->committed) { int rc = bind_device(scene->ctx); if (rc) return rc; return mrt::upload_lights(scene->lights.data(), count, scene->ctx->stream, scene->dev); }
+    if (scene->changes.committed()) { int rc = bind_device(scene->ctx); if (rc) return rc; return mrt::upload_lights(scene->lights.data(), count, scene->ctx->stream, scene->dev); }
     return MRT_OK;
     MRT_CATCH
 }
@@ -292,19 +279,21 @@ int mrt_scene_commit(MRTScene scene) {
     // meshes' host copies, which everything below reads, are brought up to date
     rc = mrt::resolve_device_refits(scene->dev, scene->opt, scene->ctx->stream); if (rc) return rc;
     rc = sync_host_meshes(scene); if (rc) return rc;
-    if (scene->only_transforms_changed && scene->opt.instancing && scene->dev.num_inst == scene->meshes.size())
-        rc = mrt::update_tlas(scene->meshes, scene->ctx->stream, scene->dev);         // instance rows + TLAS; the BLASes stay (the refit of an animated scene)
-    else if (scene->only_vertices_changed && scene->opt.instancing && scene->opt.refit && (rc = mrt::refit_two_level(scene->meshes, scene->opt, scene->ctx->stream, scene->dev)) != MRT_ERR_UNSUPPORTED) {}      // the changed meshes' BLASes refitted in place + the TLAS
-    else rc = mrt::build_scene(scene->meshes, scene->opt, scene->ctx->stream, scene->dev, scene->only_transforms_changed && !scene->opt.instancing, scene->only_vertices_changed && !scene->opt.instancing);
-    if (rc) return rc;
-    scene->only_transforms_changed = false; scene->only_vertices_changed = false;
-    for (auto &m : scene->meshes) m.dirty = false;
-    if (scene->dev.refit_ws) {          // a refit kept the tree and with it the workspace of the stream-ordered refit: its chained leaf_growth goes on from this commit's, its dirty marks are spent
-        MRT_HIP(hipMemcpy(scene->dev.refit_ws->leaf_growth.p, &scene->dev.stats.leaf_growth, 4, hipMemcpyHostToDevice));
-        MRT_HIP(hipMemset(scene->dev.refit_ws->inst_dirty.p, 0, scene->dev.refit_ws->inst_dirty.bytes()));
+    switch (scene->changes.recipe(scene->opt.instancing, scene->opt.refit, scene->dev.num_inst == scene->meshes.size())) {
+    case mrt::CommitRecipe::tlas_only: rc = mrt::update_tlas(scene->meshes, scene->ctx->stream, scene->dev); break;          // instance rows + TLAS; the BLASes stay (the refit of an animated scene)
+    case mrt::CommitRecipe::refit_blas_else_build:          // the changed meshes' BLASes refitted in place + the TLAS
+        rc = mrt::refit_two_level(scene->meshes, scene->opt, scene->ctx->stream, scene->dev);
+        if (rc == MRT_ERR_UNSUPPORTED) rc = mrt::build_scene(scene->meshes, scene->opt, scene->ctx->stream, scene->dev);
+        break;
+    case mrt::CommitRecipe::build_keep_geometry: rc = mrt::build_scene(scene->meshes, scene->opt, scene->ctx->stream, scene->dev, true, false); break;
+    case mrt::CommitRecipe::build_refit: rc = mrt::build_scene(scene->meshes, scene->opt, scene->ctx->stream, scene->dev, false, true); break;
+    case mrt::CommitRecipe::build: rc = mrt::build_scene(scene->meshes, scene->opt, scene->ctx->stream, scene->dev); break;
     }
+    if (rc) return rc;
+    for (auto &m : scene->meshes) m.dirty = false;
+    rc = mrt::refit_workspace_after_commit(scene->dev); if (rc) return rc;
     rc = mrt::upload_lights(scene->lights.data(), (int)scene->lights.size(), scene->ctx->stream, scene->dev); if (rc) return rc;
-    scene->committed = true;
+    scene->changes.commit_done();
     return MRT_OK;
     MRT_CATCH
 }
@@ -315,13 +304,10 @@ int mrt_scene_update_mesh(MRTScene scene, int32_t mesh_id, const float *position
     mrt::HostMesh &m = scene->meshes[(size_t)mesh_id];
     REQUIRE(all_finite(positions, pos_stride, nverts, 3) && all_finite(normals, nrm_stride, nverts, 3), "mrt_scene_update_mesh: a position or a normal is NaN or infinite (the mesh keeps what it had)");
     copy_vertex_rows(m, positions, pos_stride, normals, nrm_stride, nverts);
-    if (scene->dev.refit_ws && (size_t)mesh_id < scene->dev.refit_ws->host_stale.size()) scene->dev.refit_ws->host_stale[(size_t)mesh_id] = 0;      // (replaced on the device before: this copy is the newer one now)
-    if (scene->dev.blas_ws && (size_t)mesh_id < scene->dev.blas_ws->blas_of_mesh.size() && scene->dev.blas_ws->blas_of_mesh[(size_t)mesh_id] >= 0) scene->dev.blas_ws->host_stale[(size_t)scene->dev.blas_ws->blas_of_mesh[(size_t)mesh_id]] = 0;
+    mrt::host_vertices_are_newer(scene->dev, (size_t)mesh_id);          // (replaced on the device before: this copy is the newer one now)
     // a committed scene in which nothing else changes until the next commit keeps its tree: that commit refits (flattened scenes with the 8-wide layout; others build again)
     m.dirty = true;
-    if (scene->committed) scene->only_vertices_changed = true;                         // the first change since the commit
-    else if (!scene->only_vertices_changed) scene->only_transforms_changed = false;    // something else changed already (a transform, a mesh, an option): the next commit builds
-    scene->committed = false;
+    scene->changes.host_changed(mrt::Pending::vertices);
     return MRT_OK;
     MRT_CATCH
 }
@@ -332,19 +318,17 @@ int mrt_scene_set_instance_transform(MRTScene scene, int32_t mesh_id, const floa
     REQUIRE(all_finite(xf, 64, 1, 16), "mrt_scene_set_instance_transform: the transform holds a NaN or an infinity (the instance keeps what it had)");
     float *m = scene->meshes[mesh_id].xf;
     memcpy(m, xf, 64);
-    if (scene->dev.inst_ws && (size_t)mesh_id < scene->dev.inst_ws->moved.size()) scene->dev.inst_ws->moved[(size_t)mesh_id] = 0;      // (moved on the device before: this matrix is the newer one now)
+    mrt::host_transform_is_newer(scene->dev, (size_t)mesh_id);          // (moved on the device before: this matrix is the newer one now)
     m[3] = m[7] = m[11] = 0.0f; m[15] = 1.0f;
     // flattened scene: the world-space BVH is rebuilt by the next mrt_scene_commit (22 ms for 885 K triangles);
     // two-level scene: the next commit rewrites the instance rows and rebuilds the TLAS only
-    if (scene->committed) scene->only_transforms_changed = true;
-    if (scene->only_vertices_changed) { scene->only_vertices_changed = false; scene->only_transforms_changed = false; }      // vertices AND transforms changed: a full build
-    scene->committed = false;
+    scene->changes.host_changed(mrt::Pending::transforms);
     return MRT_OK;
     MRT_CATCH
 }
 int mrt_scene_stats(MRTScene scene, MRTSceneStats *out) {
     REQUIRE(scene && out, "mrt_scene_stats: bad argument");
-    if (!scene->committed) { mrt::set_error("mrt_scene_stats: scene not committed"); return MRT_ERR_STATE; }
+    if (!scene->changes.committed()) { mrt::set_error("mrt_scene_stats: scene not committed"); return MRT_ERR_STATE; }
     // refits enqueued by mrt_scene_refit_device or by mrt_scene_refit_blas_device: wait for the last one and read what it left (the only place this blocks)
     const bool unresolved[2] = {scene->dev.refit_ws && scene->dev.refit_ws->unresolved, scene->dev.blas_ws && scene->dev.blas_ws->unresolved};
     for (int k = 0; k < 2; k++) if (unresolved[k]) {
@@ -365,7 +349,7 @@ int mrt_scene_instance_transform(MRTScene scene, int32_t mesh_id, float out[12])
 int mrt_scene_intersect_closest(MRTScene scene, const MRTRay *rays, size_t n, MRTIntersection *out) {
     MRT_TRY
     REQUIRE(scene && (n == 0 || (rays && out)), "mrt_scene_intersect_closest: bad argument");
-    if (!scene->committed) { mrt::set_error("mrt_scene_intersect_closest: scene not committed"); return MRT_ERR_STATE; }
+    if (!scene->changes.committed()) { mrt::set_error("mrt_scene_intersect_closest: scene not committed"); return MRT_ERR_STATE; }
     int rc = bind_device(scene->ctx); if (rc) return rc;
     return mrt::query_closest(scene->dev, scene->ctx->stream, rays, n, out);
     MRT_CATCH
@@ -373,7 +357,7 @@ int mrt_scene_intersect_closest(MRTScene scene, const MRTRay *rays, size_t n, MR
 int mrt_scene_intersect_any(MRTScene scene, const MRTRay *rays, size_t n, int32_t *occluded) {
     MRT_TRY
     REQUIRE(scene && (n == 0 || (rays && occluded)), "mrt_scene_intersect_any: bad argument");
-    if (!scene->committed) { mrt::set_error("mrt_scene_intersect_any: scene not committed"); return MRT_ERR_STATE; }
+    if (!scene->changes.committed()) { mrt::set_error("mrt_scene_intersect_any: scene not committed"); return MRT_ERR_STATE; }
     int rc = bind_device(scene->ctx); if (rc) return rc;
     return mrt::query_any(scene->dev, scene->ctx->stream, rays, n, occluded);
     MRT_CATCH
@@ -390,7 +374,7 @@ static int intersect_device(const char *who, MRTScene scene, const void *d_rays,
     if (int rc = check_count_word(who, d_count, counted)) return rc;
     if (!(scene && (n == 0 || (d_rays && d_out)))) { mrt::set_error(std::string(who) + ": bad argument"); return MRT_ERR_INVALID_ARGUMENT; }
     if (n >= (size_t(1) << 31)) { mrt::set_error(std::string(who) + ": too many rays (n must be below 2^31)"); return MRT_ERR_INVALID_ARGUMENT; }
-    if (!scene->committed) { mrt::set_error(std::string(who) + ": scene not committed"); return MRT_ERR_STATE; }
+    if (!scene->changes.committed()) { mrt::set_error(std::string(who) + ": scene not committed"); return MRT_ERR_STATE; }
     if (n == 0) return MRT_OK;
     int rc = bind_device(scene->ctx); if (rc) return rc;
     return any ? mrt::query_any_device(scene->dev, (hipStream_t)hip_stream, d_rays, n, d_out, d_count) : mrt::query_closest_device(scene->dev, (hipStream_t)hip_stream, d_rays, n, d_out, d_count);
@@ -419,8 +403,8 @@ int mrt_scene_intersect_any_device(MRTScene scene, const void *d_rays, size_t n,
 // The three families of stream-ordered updates (§10d - §10f) look at the scene before anything else: it exists, it is committed, nothing the host changed waits for a commit.  The family's *_supported call and bind_device follow at the call site.
 static int device_entry_prologue(const char *who, MRTScene scene) {
     if (!scene) { mrt::set_error(std::string(who) + ": scene is NULL"); return MRT_ERR_INVALID_ARGUMENT; }
-    if (!scene->committed) {
-        mrt::set_error(std::string(who) + (scene->only_vertices_changed || scene->only_transforms_changed ? ": host-side changes are pending (mrt_scene_commit first)" : ": scene not committed"));
+    if (!scene->changes.committed()) {
+        mrt::set_error(std::string(who) + (scene->changes.host_changes_pending() ? ": host-side changes are pending (mrt_scene_commit first)" : ": scene not committed"));
         return MRT_ERR_STATE;
     }
     return MRT_OK;
@@ -538,7 +522,7 @@ int mrt_scene_device_updates_rejected(MRTScene scene, uint64_t *count) {
 static int surface_prologue(const char *who, MRTScene scene, size_t n) {
     if (n >= (size_t(1) << 31)) { mrt::set_error(std::string(who) + ": too many hits (n must be below 2^31)"); return MRT_ERR_INVALID_ARGUMENT; }
     if (!scene) { mrt::set_error(std::string(who) + ": scene is NULL"); return MRT_ERR_INVALID_ARGUMENT; }
-    if (!scene->committed) { mrt::set_error(std::string(who) + ": scene not committed"); return MRT_ERR_STATE; }
+    if (!scene->changes.committed()) { mrt::set_error(std::string(who) + ": scene not committed"); return MRT_ERR_STATE; }
     return MRT_OK;
 }
 static int resolve_hits_entry(const char *who, MRTScene scene, const void *d_rays, const void *d_hits, size_t n, void *d_surfaces, void *hip_stream, const void *d_count, bool counted) {
@@ -867,7 +851,7 @@ int mrt_context_tonemap_device(MRTContext ctx, int32_t width, int32_t height, co
 int mrt_debug_traversal_stats(MRTScene scene, const MRTRay *rays, size_t n, int32_t any_hit, uint32_t *out4) {
     MRT_TRY
     REQUIRE(scene && (n == 0 || (rays && out4)), "mrt_debug_traversal_stats: bad argument");
-    if (!scene->committed) { mrt::set_error("mrt_debug_traversal_stats: scene not committed"); return MRT_ERR_STATE; }
+    if (!scene->changes.committed()) { mrt::set_error("mrt_debug_traversal_stats: scene not committed"); return MRT_ERR_STATE; }
     if (scene->dev.num_inst) { mrt::set_error("mrt_debug_traversal_stats: not available for two-level scenes"); return MRT_ERR_UNSUPPORTED; }
     int rc = bind_device(scene->ctx); if (rc) return rc;
     return mrt::query_stats(scene->dev, scene->ctx->stream, rays, n, any_hit, out4);
@@ -877,7 +861,7 @@ int mrt_debug_traversal_stats(MRTScene scene, const MRTRay *rays, size_t n, int3
 int mrt_debug_stream_stats(MRTScene scene, const MRTRay *rays, size_t n, int32_t any_hit, uint32_t per_wave, uint32_t *out8, size_t nwaves) {
     MRT_TRY
     REQUIRE(scene && rays && out8 && per_wave >= 64 && nwaves * (size_t)per_wave >= n, "mrt_debug_stream_stats: bad argument");
-    if (!scene->committed) { mrt::set_error("mrt_debug_stream_stats: scene not committed"); return MRT_ERR_STATE; }
+    if (!scene->changes.committed()) { mrt::set_error("mrt_debug_stream_stats: scene not committed"); return MRT_ERR_STATE; }
     int rc = bind_device(scene->ctx); if (rc) return rc;
     return mrt::query_stream_stats(scene->dev, scene->ctx->stream, rays, n, any_hit, per_wave, out8, nwaves);
     MRT_CATCH
@@ -886,7 +870,7 @@ int mrt_debug_stream_stats(MRTScene scene, const MRTRay *rays, size_t n, int32_t
 int mrt_debug_intersect_stream(MRTScene scene, const MRTRay *rays, size_t n, int32_t any_hit, MRTIntersection *out) {
     MRT_TRY
     REQUIRE(scene && rays && out, "mrt_debug_intersect_stream: bad argument");
-    if (!scene->committed) { mrt::set_error("mrt_debug_intersect_stream: scene not committed"); return MRT_ERR_STATE; }
+    if (!scene->changes.committed()) { mrt::set_error("mrt_debug_intersect_stream: scene not committed"); return MRT_ERR_STATE; }
     int rc = bind_device(scene->ctx); if (rc) return rc;
     return mrt::query_stream(scene->dev, scene->ctx->stream, rays, n, any_hit ? 1 : 0, out);
     MRT_CATCH
@@ -986,7 +970,7 @@ int mrt_renderer_create(MRTContext ctx, MRTScene scene, int32_t width, int32_t h
     REQUIRE(width > 0 && height > 0 && (int64_t)width * height < (1ll << 30), "mrt_renderer_create: bad size");
     REQUIRE(max_bounces >= 1 && max_bounces <= 19, "mrt_renderer_create: max_bounces must be in [1,19] (Halton prime table holds 100 primes)");
     REQUIRE(scene->ctx == ctx, "mrt_renderer_create: scene belongs to another context");
-    if (!scene->committed) { mrt::set_error("mrt_renderer_create: scene not committed"); return MRT_ERR_STATE; }
+    if (!scene->changes.committed()) { mrt::set_error("mrt_renderer_create: scene not committed"); return MRT_ERR_STATE; }
     int rc = bind_device(ctx); if (rc) return rc;
     std::unique_ptr<MRTRenderer_> r(new MRTRenderer_());
     r->ctx = ctx; r->scene = scene;
@@ -1175,7 +1159,7 @@ int mrt_renderer_render(MRTRenderer r, int32_t n_frames) {
     MRT_TRY
     RENDERER_PROLOGUE("mrt_renderer_render")
     REQUIRE(n_frames >= 0, "mrt_renderer_render: n_frames < 0");
-    if (!r->scene->committed) { mrt::set_error("mrt_renderer_render: scene was modified and not re-committed"); return MRT_ERR_STATE; }
+    if (!r->scene->changes.committed()) { mrt::set_error("mrt_renderer_render: scene was modified and not re-committed"); return MRT_ERR_STATE; }
     if (n_frames == 0) return MRT_OK;
     return r->r.render(n_frames);
     MRT_CATCH
@@ -1333,7 +1317,7 @@ int mrt_debug_seeds(MRTContext ctx, uint32_t seed, int32_t width, int32_t height
 int mrt_debug_wide_histogram(MRTScene scene, uint32_t *out12) {
     MRT_TRY
     REQUIRE(scene && out12, "mrt_debug_wide_histogram: bad argument");
-    if (!scene->committed) { mrt::set_error("mrt_debug_wide_histogram: scene not committed"); return MRT_ERR_STATE; }
+    if (!scene->changes.committed()) { mrt::set_error("mrt_debug_wide_histogram: scene not committed"); return MRT_ERR_STATE; }
     int rc = bind_device(scene->ctx); if (rc) return rc;
     return mrt::wide_histogram(scene->dev, scene->ctx->stream, out12);
     MRT_CATCH
@@ -1342,7 +1326,7 @@ int mrt_debug_wide_histogram(MRTScene scene, uint32_t *out12) {
 int mrt_debug_read_wnodes(MRTScene scene, void *out, size_t nbytes, uint64_t *num_nodes) {
     MRT_TRY
     REQUIRE(scene && num_nodes, "mrt_debug_read_wnodes: bad argument");
-    if (!scene->committed) { mrt::set_error("mrt_debug_read_wnodes: scene not committed"); return MRT_ERR_STATE; }
+    if (!scene->changes.committed()) { mrt::set_error("mrt_debug_read_wnodes: scene not committed"); return MRT_ERR_STATE; }
     *num_nodes = scene->dev.num_wnodes;
     const size_t have = (size_t)scene->dev.num_wnodes * mrt::WNODE_STRIDE * 16;
     if (out == nullptr) return MRT_OK;
@@ -1357,7 +1341,7 @@ int mrt_debug_read_layout(MRTScene scene, int32_t part, void *out, size_t nbytes
     MRT_TRY
     REQUIRE(scene && count, "mrt_debug_read_layout: bad argument");
     REQUIRE(part >= 0 && part <= 9, "mrt_debug_read_layout: part must be 0 .. 9");
-    if (!scene->committed) { mrt::set_error("mrt_debug_read_layout: scene not committed"); return MRT_ERR_STATE; }
+    if (!scene->changes.committed()) { mrt::set_error("mrt_debug_read_layout: scene not committed"); return MRT_ERR_STATE; }
     const mrt::DeviceScene &d = scene->dev;
     const size_t npk = d.wpackets.p ? d.wpackets.n / mrt::WPK : 0, ninst = d.num_inst, nwt = (d.num_inst && d.wtlas_index.p) ? d.wtlas_index.n : 0;
     uint32_t header[8] = {d.num_wnodes, d.num_inst ? d.tlas_wcap : 0u, d.num_inst, (uint32_t)d.wide_depth, (uint32_t)npk, (uint32_t)d.blas_wdepth, (uint32_t)nwt, mrt::WPK};
@@ -1401,14 +1385,14 @@ int mrt_debug_commit_times(MRTScene scene, double *out6) {
 int mrt_debug_validate(MRTScene scene) {
     MRT_TRY
     REQUIRE(scene, "mrt_debug_validate: scene is NULL");
-    if (!scene->committed) { mrt::set_error("mrt_debug_validate: scene not committed"); return MRT_ERR_STATE; }
+    if (!scene->changes.committed()) { mrt::set_error("mrt_debug_validate: scene not committed"); return MRT_ERR_STATE; }
     int rc = bind_device(scene->ctx); if (rc) return rc;
     return mrt::validate_layout(scene->dev, scene->ctx->stream, false);
     MRT_CATCH
 }
 int mrt_debug_validate_patched(MRTScene scene, uint32_t node, uint32_t word, uint32_t value) {
     MRT_TRY
-    REQUIRE(scene && scene->committed && node < scene->dev.num_wnodes && word < 4 * mrt::WNODE_STRIDE, "mrt_debug_validate_patched: bad argument");
+    REQUIRE(scene && scene->changes.committed() && node < scene->dev.num_wnodes && word < 4 * mrt::WNODE_STRIDE, "mrt_debug_validate_patched: bad argument");
     int rc = bind_device(scene->ctx); if (rc) return rc;
     mrt::DevBuf<float4> copy; MRT_HIP(copy.alloc(scene->dev.wnodes.n));
     MRT_HIP(hipMemcpy(copy.p, scene->dev.wnodes.p, scene->dev.wnodes.bytes(), hipMemcpyDeviceToDevice));
@@ -1419,7 +1403,7 @@ int mrt_debug_validate_patched(MRTScene scene, uint32_t node, uint32_t word, uin
 #ifdef MRT_DIAGNOSTICS
 int mrt_debug_poke_wnode(MRTScene scene, uint32_t node, uint32_t word, uint32_t value, uint32_t *old_value) {
     MRT_TRY
-    REQUIRE(scene && scene->committed && node < scene->dev.num_wnodes && word < 4 * mrt::WNODE_STRIDE, "mrt_debug_poke_wnode: bad argument");
+    REQUIRE(scene && scene->changes.committed() && node < scene->dev.num_wnodes && word < 4 * mrt::WNODE_STRIDE, "mrt_debug_poke_wnode: bad argument");
     int rc = bind_device(scene->ctx); if (rc) return rc;
     uint32_t *p = reinterpret_cast<uint32_t *>(scene->dev.wnodes.p + (size_t)mrt::WNODE_STRIDE * node) + word;
     if (old_value) MRT_HIP(hipMemcpy(old_value, p, 4, hipMemcpyDeviceToHost));

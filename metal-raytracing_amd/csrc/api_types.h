@@ -1,6 +1,7 @@
 // api_types.h — what the opaque handles of include/mrt_abi.h point at (shared by api.cpp and group.hip).
 #pragma once
 #include "renderer.h"
+#include "scene_changes.h"
 
 struct MRTContext_ {
     int device = 0;
@@ -15,9 +16,7 @@ struct MRTScene_ {
     std::vector<MRTLight> lights;
     mrt::BuildOptions opt;
     mrt::DeviceScene dev;
-    bool committed = false;
-    bool only_vertices_changed = false;     // since the last commit: nothing but mrt_scene_update_mesh calls — a flattened scene with the 8-wide layout refits its tree (scene option refit)
-    bool only_transforms_changed = false;   // since the last commit: a two-level scene rebuilds its TLAS only, a flattened one rebuilds from the geometry already on the device
+    mrt::SceneChanges changes;              // committed or not, and what changed since the last commit: scene_changes.h decides what the next commit does
     int renderers = 0;                      // renderers made on this scene and not yet destroyed: mrt_scene_destroy refuses while any is left (they hold a pointer to `dev`)
     size_t stage_need = 0;                  // bytes the upload staging of the meshes added so far will take (mrt_mesh_add_submesh grows the pinned area)
 };

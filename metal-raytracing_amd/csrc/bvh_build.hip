@@ -1348,7 +1348,7 @@ struct FlatBuild {
 
 }  // namespace
 
-int build_scene(const std::vector<HostMesh> &meshes_in, const BuildOptions &opt, hipStream_t stream, DeviceScene &out, bool only_transforms_changed, bool only_vertices_changed) {
+int build_scene(const std::vector<HostMesh> &meshes_in, const BuildOptions &opt, hipStream_t stream, DeviceScene &out, bool geometry_unchanged, bool refit) {
     out.validate = opt.validate != 0;
     drop_instance_workspace(out);          // (a build: the TLAS the workspace was made for is gone)
     if (opt.instancing) { drop_refit_workspace(out); return build_two_level(meshes_in, opt, stream, out); }
@@ -1356,7 +1356,7 @@ int build_scene(const std::vector<HostMesh> &meshes_in, const BuildOptions &opt,
     // an instance (mrt_scene_add_instance) takes its geometry from its source mesh; flattening gives every instance its own world-space copy
     std::vector<MeshRef> refs;
     for (auto &m : meshes_in) refs.push_back(MeshRef{m.source >= 0 ? &meshes_in[(size_t)m.source] : &m, m.xf});
-    if (int rc = build_flat(refs, opt, stream, out, nullptr, only_transforms_changed, only_vertices_changed && opt.refit)) return rc;
+    if (int rc = build_flat(refs, opt, stream, out, nullptr, geometry_unchanged, refit && opt.refit)) return rc;
     const auto tv = std::chrono::steady_clock::now();
     const int rc = out.validate ? validate_layout(out, stream, false) : MRT_OK;
     out.commit_ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tv).count();

@@ -450,6 +450,16 @@ void drop_refit_workspace(DeviceScene &sc) {
     if (sc.refit_ws) retire_gate(sc, sc.refit_ws->gate);
     sc.refit_ws.reset();
 }
+int refit_workspace_after_commit(DeviceScene &sc) {
+    if (!sc.refit_ws) return MRT_OK;
+    MRT_HIP(hipMemcpy(sc.refit_ws->leaf_growth.p, &sc.stats.leaf_growth, 4, hipMemcpyHostToDevice));
+    MRT_HIP(hipMemset(sc.refit_ws->inst_dirty.p, 0, sc.refit_ws->inst_dirty.bytes()));
+    return MRT_OK;
+}
+void host_vertices_are_newer(DeviceScene &sc, size_t mesh) {
+    if (sc.refit_ws && mesh < sc.refit_ws->host_stale.size()) sc.refit_ws->host_stale[mesh] = 0;
+    if (sc.blas_ws && mesh < sc.blas_ws->blas_of_mesh.size() && sc.blas_ws->blas_of_mesh[mesh] >= 0) sc.blas_ws->host_stale[(size_t)sc.blas_ws->blas_of_mesh[mesh]] = 0;
+}
 
 int device_updates_rejected(DeviceScene &sc, uint64_t *count) {
     *count = sc.rejected_before;

@@ -369,7 +369,7 @@ struct DeviceScene {
 // bvh_build.hip
 void pack_material(const MRTMaterial &m, float4 *out3);
 int layout_limits(uint64_t triangles, uint64_t nodes);    // MRT_OK, or MRT_ERR_UNSUPPORTED when the traversal layouts cannot address such a scene
-int build_scene(const std::vector<HostMesh> &meshes, const BuildOptions &opt, hipStream_t stream, DeviceScene &out, bool only_transforms_changed = false, bool only_vertices_changed = false);      // only_transforms_changed: same meshes, submeshes and options as the commit before (flattened scenes keep their geometry on the device)
+int build_scene(const std::vector<HostMesh> &meshes, const BuildOptions &opt, hipStream_t stream, DeviceScene &out, bool geometry_unchanged = false, bool refit = false);      // flattened scenes, as build_flat: geometry_unchanged: only transforms changed since the commit before (the geometry on the device is kept); refit: only vertices did
 // bvh_host_sah.cpp (builder = 2): binned-SAH topology over n reference boxes, built on the host
 void host_sah_topology(const float4 *lo, const float4 *hi, uint32_t n, std::vector<uint32_t> &order, std::vector<uint32_t> &left, std::vector<uint32_t> &right, std::vector<uint32_t> &parent);
 struct MeshRef { const HostMesh *g; const float *xf; };         // geometry + object->world matrix (column-major 4x4)
@@ -403,6 +403,8 @@ int resolve_device_refits(DeviceScene &sc, const BuildOptions &opt, hipStream_t 
 int download_stale_meshes(std::vector<HostMesh> &meshes, DeviceScene &sc, bool *pending_found = nullptr);      // blocks; the HostMesh copies of meshes updated on the device, read back from g_pos / normals; pending_found: a mesh was updated on the device and not refitted since (it is marked dirty)
 int device_updates_rejected(DeviceScene &sc, uint64_t *count);      // blocks
 void drop_refit_workspace(DeviceScene &sc);      // (a build: the tree the workspace was made for is gone)
+int refit_workspace_after_commit(DeviceScene &sc);      // a commit that kept sc.refit_ws (a refit): its chained leaf_growth goes on from the commit's, its dirty marks are spent; blocks
+void host_vertices_are_newer(DeviceScene &sc, size_t mesh);      // mrt_scene_update_mesh after an update on the device (either form): the next sync leaves the mesh's host copy alone
 // tlas_refit.hip: instance moves from device buffers, ordered on the caller's stream
 int instances_device_supported(const DeviceScene &sc, const BuildOptions &opt, const char *who);      // MRT_OK, or MRT_ERR_UNSUPPORTED + message: a flattened scene, a scene without an instance
 int instances_device_prepare(DeviceScene &sc);      // makes sc.inst_ws if it is not there (allocates, uploads the level tables, blocks)
@@ -416,6 +418,7 @@ constexpr uint32_t TLAS_RESORT_MAX = 65536;           // instances mrt_scene_reb
 int tlas_rebuild_supported(const DeviceScene &sc, const char *who);      // MRT_OK, or MRT_ERR_UNSUPPORTED + message: more than TLAS_RESORT_MAX instances in the TLAS
 int device_rebuild_tlas(DeviceScene &sc, hipStream_t stream);      // needs sc.inst_ws (instances_device_prepare); ends with device_refit_instances
 int tlas_host_build(const float *lo4, const float *hi4, uint32_t n, uint32_t *rope_order, uint32_t *rope_links, uint32_t *wide_order, uint32_t *wide_pos, uint32_t *counts);      // two_level.hip: mrt_debug_tlas_host_build
+void host_transform_is_newer(DeviceScene &sc, size_t mesh);      // mrt_scene_set_instance_transform after a move on the device: the next sync leaves HostMesh::xf alone
 void drop_instance_workspace(DeviceScene &sc);      // (update_tlas: the TLAS the workspace was made for is gone; the rejected count is kept)
 // bvh_refit.hip: meshes of two-level scenes deformed from device buffers, ordered on the caller's stream
 int blas_device_supported(const DeviceScene &sc, const BuildOptions &opt, size_t meshes, const char *who);      // MRT_OK, or MRT_ERR_UNSUPPORTED + message: a flattened scene, refit = 0, a scene refit_two_level would not take

@@ -262,6 +262,7 @@ void drop_instance_workspace(DeviceScene &sc) {
     if (sc.inst_ws) retire_gate(sc, sc.inst_ws->gate);
     sc.inst_ws.reset();
 }
+void host_transform_is_newer(DeviceScene &sc, size_t mesh) { if (sc.inst_ws && mesh < sc.inst_ws->moved.size()) sc.inst_ws->moved[mesh] = 0; }
 
 int instances_device_prepare(DeviceScene &sc) {
     if (sc.inst_ws) return MRT_OK;

@@ -493,3 +493,112 @@ def test_refusals(mrt, orc, gpu_ctx):
     assert raw(h, mesh=0) == 0 and lib.mrt_scene_refit_blas_device(h, None) == 0, last()          # the mesh beside it deforms
     torch.cuda.synchronize()
     assert lib.mrt_scene_destroy(h) == 0
+
+
+# ------------------------------------------------------------------------------------------------ what a commit makes of changes of several kinds (csrc/scene_changes.h)
+# The sequences in which the three booleans that came before the one value ended in a TLAS-only commit over stale BLASes (tests/test_scene_changes_cpu.py lists them), on
+# the scene of 9 instances.  Each needs the host to learn of a device-side change between two changes without a commit: mrt_group_renderer_create does that to its template.
+N_SEQ = 9
+FROM = 5          # the instances FROM .. 8 take their poses of step 1, the others keep those of step 0
+
+
+def _found_by_a_sync(mrt, ds):
+    """what mrt_group_renderer_create does to its template scene: the host copies brought up to date (mrt_scene_sync_host_meshes); the group and its renderer go again"""
+    lib = mrt.lib
+    ids = (C.c_int32 * 1)(0)
+    g, r = C.c_void_p(), C.c_void_p()
+    assert lib.mrt_group_create(ids, 1, C.byref(g)) == 0, lib.mrt_last_error()
+    assert lib.mrt_group_renderer_create(g, ds.handle, 16, 16, 1, 3, C.byref(r)) == 0, lib.mrt_last_error()
+    assert lib.mrt_group_renderer_destroy(r) == 0 and lib.mrt_group_destroy(g) == 0, lib.mrt_last_error()
+
+
+def _dev_move(ds, gpu_ctx, step, first=0):
+    t = _t(_poses(N_SEQ, step)[first:], gpu_ctx)
+    ds.set_instance_transforms_device(first, t)
+    return t
+
+
+def _from_scratch(mrt, gpu_ctx, opts, pose_key, box_step):
+    """a scene with the final vertices and poses that is built, not updated: an option set before the commit makes it build everything"""
+    ds = mrt.DeviceScene(gpu_ctx, _case(mrt, N_SEQ)[0], opts)
+    xf = _start(N_SEQ)
+    for step, first in pose_key: xf[first:] = _poses(N_SEQ, step)[first:]
+    for k in range(N_SEQ): ds.set_instance_transform(k, xf[k])
+    ds.update_mesh(BOX, *_deformed(mrt, BOX, box_step))
+    assert mrt.lib.mrt_scene_set_option(ds.handle, b"validate", 1.0) == 0
+    ds.commit()
+    assert ds.stats.refits == 0
+    return ds
+
+
+def _row_1(mrt, ds, gpu_ctx, keep):
+    keep.append(_dev_move(ds, gpu_ctx, 0)); _found_by_a_sync(mrt, ds)
+    ds.update_mesh(BOX, *_deformed(mrt, BOX, 0))
+    return ((0, 0),)
+
+
+def _row_2(mrt, ds, gpu_ctx, keep):
+    keep.append(_dev_move(ds, gpu_ctx, 0)); _found_by_a_sync(mrt, ds)
+    keep.append(_dev_update(mrt, ds, gpu_ctx, BOX, 0)); _found_by_a_sync(mrt, ds)
+    return ((0, 0),)
+
+
+def _row_3(mrt, ds, gpu_ctx, keep):
+    keep.append(_dev_update(mrt, ds, gpu_ctx, BOX, 0)); keep.append(_dev_move(ds, gpu_ctx, 0)); _found_by_a_sync(mrt, ds)
+    for k in range(FROM, N_SEQ): ds.set_instance_transform(k, _poses(N_SEQ, 1)[k])
+    return ((0, 0), (1, FROM))
+
+
+def _row_4(mrt, ds, gpu_ctx, keep):
+    keep.append(_dev_update(mrt, ds, gpu_ctx, BOX, 0)); keep.append(_dev_move(ds, gpu_ctx, 0)); _found_by_a_sync(mrt, ds)
+    keep.append(_dev_move(ds, gpu_ctx, 1, FROM)); _found_by_a_sync(mrt, ds)
+    return ((0, 0), (1, FROM))
+
+
+@pytest.mark.parametrize("row", [_row_1, _row_2, _row_3, _row_4], ids=["moves found, then update_mesh", "moves found, then an unrefitted update found", "both found, then set_instance_transform", "both found, then moves found again"])
+def test_a_commit_after_changes_of_both_kinds_builds_the_blases_too(mrt, orc, gpu_ctx, row):
+    import torch
+    r = np.array(_case(mrt, N_SEQ)[2])
+    ds = mrt.DeviceScene(gpu_ctx, _case(mrt, N_SEQ)[0], TWO)
+    keep = []
+    pose_key = row(mrt, ds, gpu_ctx, keep)
+    ds.commit()
+    torch.cuda.synchronize()
+    assert ds.stats.refits == 0 and ds.refits == 0          # vertices and transforms: the recipe is a build, and a build counts no refit
+    ref = _oracle(mrt, orc, N_SEQ, pose_key, (0, None))
+    assert float((ref["distance"] >= 0).mean()) >= 0.08
+    _changed(ref, _oracle(mrt, orc, N_SEQ, pose_key, (None, None)), "the deformed box against the box as it was: ")          # (what a TLAS-only commit would answer)
+    scratch = _from_scratch(mrt, gpu_ctx, TWO, pose_key, 0)
+    hits = ds.intersect_closest(r)
+    _same_records(hits, scratch.intersect_closest(r), "against the scene built from scratch: ")
+    _same_records(hits, ref, "against the oracle: ")
+    A.audit(A.layout_of(ds)).check()
+    assert ds.device_updates_rejected == 0
+    del keep
+    ds.close(); scratch.close()
+
+
+def test_a_flattened_scene_waiting_with_transforms_keeps_the_vertices_the_device_wrote(mrt, orc, gpu_ctx):
+    """the one exception to the join: update_mesh_device without a refit, then set_instance_transform, then commit — built from the geometry on the device, where the update wrote"""
+    import torch
+    sc, meshes, rays = _case(mrt, N_SEQ)
+    r = np.array(rays)
+    ds = mrt.DeviceScene(gpu_ctx, sc)
+    tp, tq = (_td(x, gpu_ctx) for x in _deformed(mrt, BOX, 0))
+    ds.update_mesh_device(BOX, tp, tq)
+    for k in range(FROM, N_SEQ): ds.set_instance_transform(k, _poses(N_SEQ, 1)[k])
+    ds.commit()
+    torch.cuda.synchronize()
+    assert ds.stats.refits == 0 and ds.refits == 0          # build_keep_geometry is a build
+    xf = _start(N_SEQ); xf[FROM:] = _poses(N_SEQ, 1)[FROM:]
+    geo = _deformed(mrt, BOX, 0)
+    moved = [(*(geo if k % 2 == BOX else (p, nr)), np.ascontiguousarray(xf[k]), subs, src) for k, (p, nr, _, subs, src) in enumerate(meshes)]
+    ref = orc.OracleScene(moved, sc.lights).intersect_closest(r, brute=True)
+    assert float((ref["distance"] >= 0).mean()) >= 0.08
+    scratch = _from_scratch(mrt, gpu_ctx, {}, ((1, FROM),), 0)
+    hits = ds.intersect_closest(r)
+    _same_records(hits, scratch.intersect_closest(r), "against the scene built from scratch: ")
+    _same_records(hits, ref, "against the oracle: ")
+    assert ds.device_updates_rejected == 0
+    del tp, tq
+    ds.close(); scratch.close()
