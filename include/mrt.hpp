@@ -113,6 +113,14 @@ struct Scene {                                                       // Scene.sw
     // Nothing is allocated, copied or synchronised; keep the buffers alive until the stream has passed the call.
     static void intersectClosestDevice(MRTScene committed, const void *deviceRays, size_t n, void *deviceOut, void *hipStream) { check(mrt_scene_intersect_closest_device(committed, deviceRays, n, deviceOut, hipStream)); }
     static void intersectAnyDevice(MRTScene committed, const void *deviceRays, size_t n, void *deviceOccluded, void *hipStream) { check(mrt_scene_intersect_any_device(committed, deviceRays, n, deviceOccluded, hipStream)); }
+    // All hits in order (mrt_scene_intersect_all_device): per ray the maxHits (1 .. MRT_MAX_HITS) smallest hits under (distance, triangle id), ascending, each triangle once ->
+    // n x maxHits x MRTIntersection (16-byte aligned; misses pad a row) and n x int32 counts.  Flattened scenes; truncation is not reported (ask for one more).
+    static void intersectAllDevice(MRTScene committed, const void *deviceRays, size_t n, int32_t maxHits, void *deviceOut, void *deviceHitCounts, void *hipStream) {
+        check(mrt_scene_intersect_all_device(committed, deviceRays, n, maxHits, deviceOut, deviceHitCounts, hipStream));
+    }
+    static void intersectAllDeviceCounted(MRTScene committed, const void *deviceRays, size_t n, int32_t maxHits, void *deviceOut, void *deviceHitCounts, void *hipStream, const void *deviceCount) {
+        check(mrt_scene_intersect_all_device_counted(committed, deviceRays, n, maxHits, deviceOut, deviceHitCounts, hipStream, deviceCount));
+    }
     // Stream-ordered deformation of a committed flattened MRTScene (mrt_scene_update_mesh_device / mrt_scene_refit_device): strided float3 positions and normals in device
     // memory replace one mesh's vertices, then the resident tree is refitted, all on hipStream; updatesRejected() blocks and counts the updates refused for a NaN or an infinity.
     static void updateMeshDevice(MRTScene committed, int32_t meshId, const void *devicePositions, size_t positionStrideBytes, const void *deviceNormals, size_t normalStrideBytes, size_t vertexCount, void *hipStream) {

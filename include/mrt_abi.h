@@ -255,6 +255,29 @@ int mrt_scene_intersect_any(MRTScene scene, const MRTRay *rays, size_t n, int32_
  * MRT_ERR_STATE: the scene is not committed.  MRT_ERR_INVALID_ARGUMENT: NULL scene, NULL buffers with n > 0, n >= 2^31.  n == 0: MRT_OK, nothing is launched. */
 int mrt_scene_intersect_closest_device(MRTScene scene, const void *d_rays, size_t n, void *d_out, void *hip_stream);
 int mrt_scene_intersect_any_device(MRTScene scene, const void *d_rays, size_t n, void *d_occluded, void *hip_stream);
+/* ALL hits in order, on DEVICE buffers and ordered on a stream of the caller's: what lies between the first hit and the end of the ray — the surfaces a
+ * shadow ray crosses, the returns of a range sensor, thickness, crossing parity.  d_rays is n x MRTRay, d_out n x max_hits x MRTIntersection (16-byte aligned),
+ * d_hit_counts n x int32.  The call enqueues ONE kernel on hip_stream (taken literally, as above: 0 is HIP's null stream) and returns: it allocates nothing, copies nothing
+ * and synchronises nothing; the caller owes what the two entries above ask for.
+ *   A hit is a triangle whose test passes with min_distance <= t <= max_distance, both ends inclusive, as in the entries above.  Ray i's result is the max_hits SMALLEST hits
+ *   under the key (distance, the library's global triangle id), ascending — the ascending id is the tie rule of the closest hit — written to d_out[i * max_hits + 0 .. count - 1]
+ *   in that order; the other max_hits - count records of the row are the miss record {0, -1.0f, -1, -1, -1, 0, 0, 0}, so all max_hits records of a row are always written.
+ *   d_hit_counts[i] = count, 0 .. max_hits.  Every triangle is listed at most once, also where the build split it into several references (scene option presplit).
+ *   Truncation is NOT reported: once the list is full the walk prunes at its last distance and never learns whether more hits exist.  A caller who has to know asks for
+ *   one more than it needs.
+ *   By construction: record 0 has the bits mrt_scene_intersect_closest_device returns for the same ray; count > 0 exactly where mrt_scene_intersect_any_device says
+ *   occluded; the result depends on neither the layout, the builder, nor a refit having happened.  Each record is what mrt_scene_resolve_hits_device takes: the rows
+ *   reshaped to (n * max_hits) records beside each ray repeated max_hits times resolve to surfaces, the padding to miss surfaces.
+ *   Domain: the closest entry's (finite origin and direction, 0 <= min_distance <= max_distance, +inf allowed); outside it the result is unspecified and the call still
+ *   terminates.  One ray per lane, no lane refill (DESIGN.md §10o has the rates).
+ *   Scenes: committed flattened scenes in every layout (8-wide, 8-wide + rope, wide = 0) and the empty scene (all counts 0).  A two-level scene (instancing = 1) is
+ *   refused, MRT_ERR_UNSUPPORTED: the walk across both levels is not written yet.
+ *   Plain arguments are checked first and a NULL scene is refused last.  MRT_ERR_INVALID_ARGUMENT: max_hits outside 1 .. MRT_MAX_HITS; n >= 2^31; n * max_hits >= 2^31;
+ *   NULL buffers with n > 0; d_out not 16-byte, d_rays or d_hit_counts not 4-byte aligned; NULL scene.  MRT_ERR_STATE: the scene is not committed.  n == 0: MRT_OK, nothing
+ *   is launched.  _counted (declared with its six twins below): rows at and past *d_count are touched in neither output.                                                */
+#define MRT_MAX_HITS 16
+int mrt_scene_intersect_all_device(MRTScene scene, const void *d_rays, size_t n, int32_t max_hits, void *d_out /* n x max_hits x MRTIntersection */,
+                                   void *d_hit_counts /* n x int32 */, void *hip_stream);
 /* Deforming geometry from DEVICE buffers, ordered on a stream of the caller's: the other half of the loop "move vertices -> refit -> query or draw" on one stream.
  * mrt_scene_update_mesh_device replaces the vertices of one mesh of a COMMITTED flattened scene with vertex_count strided float3 positions and normals read from
  * device memory (strides >= 12, multiples of 4: a row of a torch view of 16 or 32 bytes is fine; 4-byte aligned pointers), in every flattened instance of that mesh;
@@ -475,6 +498,7 @@ int mrt_context_compact_rows_device(MRTContext ctx, const void *d_keep /* n x ui
                                     void *hip_stream);
 int mrt_scene_intersect_closest_device_counted(MRTScene scene, const void *d_rays, size_t n, void *d_out, void *hip_stream, const void *d_count);
 int mrt_scene_intersect_any_device_counted(MRTScene scene, const void *d_rays, size_t n, void *d_occluded, void *hip_stream, const void *d_count);
+int mrt_scene_intersect_all_device_counted(MRTScene scene, const void *d_rays, size_t n, int32_t max_hits, void *d_out, void *d_hit_counts, void *hip_stream, const void *d_count);
 int mrt_scene_resolve_hits_device_counted(MRTScene scene, const void *d_rays, const void *d_hits, size_t n, void *d_surfaces, void *hip_stream, const void *d_count);
 int mrt_scene_interpolate_device_counted(MRTScene scene, const void *d_hits, size_t n, const void *d_attributes, size_t attr_stride_bytes, int32_t channels,
                                          void *d_out, size_t out_stride_bytes, void *hip_stream, const void *d_count);

@@ -168,6 +168,8 @@ SIGNATURES = {
     "mrt_scene_intersect_any": (C.c_int, [_P, _P, _SZ, _P]),
     "mrt_scene_intersect_closest_device": (C.c_int, [_P, _P, _SZ, _P, _P]),
     "mrt_scene_intersect_any_device": (C.c_int, [_P, _P, _SZ, _P, _P]),
+    "mrt_scene_intersect_all_device": (C.c_int, [_P, _P, _SZ, _I32, _P, _P, _P]),
+    "mrt_scene_intersect_all_device_counted": (C.c_int, [_P, _P, _SZ, _I32, _P, _P, _P, _P]),
     "mrt_scene_update_mesh_device": (C.c_int, [_P, _I32, _P, _SZ, _P, _SZ, _SZ, _P]),
     "mrt_scene_refit_device": (C.c_int, [_P, _P]),
     "mrt_scene_device_updates_rejected": (C.c_int, [_P, C.POINTER(C.c_uint64)]),

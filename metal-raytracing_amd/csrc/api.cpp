@@ -399,6 +399,36 @@ int mrt_scene_intersect_any_device(MRTScene scene, const void *d_rays, size_t n,
     return intersect_device("mrt_scene_intersect_any_device", scene, d_rays, n, d_occluded, hip_stream, true);
     MRT_CATCH
 }
+// All hits in order (multihit.hip).  Plain arguments first, as the surface and stage entries check theirs, so that every one of these refusals needs no device; the scene last.
+static int intersect_all_entry(const char *who_c, MRTScene scene, const void *d_rays, size_t n, int32_t max_hits, void *d_out, void *d_hit_counts, void *hip_stream, const void *d_count, bool counted) {
+    const std::string who(who_c);
+    if (int rc = check_count_word(who_c, d_count, counted)) return rc;
+    REQUIRE(max_hits >= 1 && max_hits <= MRT_MAX_HITS, who + ": max_hits must be 1 .. " + std::to_string(MRT_MAX_HITS));
+    REQUIRE(n < (size_t(1) << 31), who + ": too many rays (n must be below 2^31)");
+    REQUIRE(n * (size_t)max_hits < (size_t(1) << 31), who + ": too many records (n * max_hits must be below 2^31)");
+    REQUIRE(n == 0 || (d_rays && d_out && d_hit_counts), who + ": NULL buffers");
+    REQUIRE((uintptr_t)d_rays % 4 == 0 && (uintptr_t)d_hit_counts % 4 == 0, who + ": rays and hit counts must be 4-byte aligned");
+    REQUIRE((uintptr_t)d_out % 16 == 0, who + ": the records must be 16-byte aligned");
+    if (!scene) { mrt::set_error(who + ": scene is NULL"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (!scene->changes.committed()) { mrt::set_error(who + ": scene not committed"); return MRT_ERR_STATE; }
+    if (scene->opt.instancing || scene->dev.num_inst) {
+        mrt::set_error(who + ": two-level scenes (scene option instancing = 1) are not served: the walk across both levels is not written yet; flattened scenes in every layout are");
+        return MRT_ERR_UNSUPPORTED;
+    }
+    if (n == 0) return MRT_OK;
+    if (int rc = bind_device(scene->ctx)) return rc;
+    return mrt::intersect_all_device(scene->dev, (hipStream_t)hip_stream, d_rays, n, max_hits, d_out, d_hit_counts, d_count);
+}
+int mrt_scene_intersect_all_device(MRTScene scene, const void *d_rays, size_t n, int32_t max_hits, void *d_out, void *d_hit_counts, void *hip_stream) {
+    MRT_TRY
+    return intersect_all_entry("mrt_scene_intersect_all_device", scene, d_rays, n, max_hits, d_out, d_hit_counts, hip_stream, nullptr, false);
+    MRT_CATCH
+}
+int mrt_scene_intersect_all_device_counted(MRTScene scene, const void *d_rays, size_t n, int32_t max_hits, void *d_out, void *d_hit_counts, void *hip_stream, const void *d_count) {
+    MRT_TRY
+    return intersect_all_entry("mrt_scene_intersect_all_device_counted", scene, d_rays, n, max_hits, d_out, d_hit_counts, hip_stream, d_count, true);
+    MRT_CATCH
+}
 
 // The three families of stream-ordered updates (§10d - §10f) look at the scene before anything else: it exists, it is committed, nothing the host changed waits for a commit.  The family's *_supported call and bind_device follow at the call site.
 static int device_entry_prologue(const char *who, MRTScene scene) {

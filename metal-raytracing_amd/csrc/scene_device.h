@@ -437,6 +437,8 @@ int interpolate_device(const DeviceScene &sc, hipStream_t stream, const void *d_
                        const void *d_count = nullptr);
 void drop_surface_workspace(DeviceScene &sc);      // (a commit: the table restates the mesh list of the commit before)
 int upload_lights(const MRTLight *lights, int count, hipStream_t stream, DeviceScene &out);
+// multihit.hip: per ray the max_hits smallest hits under (distance, triangle id), on the caller's stream
+int intersect_all_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, int max_hits, void *d_out, void *d_hit_counts, const void *d_count = nullptr);      // one launch, nothing else; flattened scenes, max_hits in [1, MRT_MAX_HITS]
 // stages.hip: what follows a surface in the reference's kernel, on the caller's stream
 int scatter_device(const DeviceScene &sc, hipStream_t stream, const void *d_surfaces, const void *d_halton_index, size_t n, int bounce, int light_count, void *d_shadow_rays, void *d_light,
                    void *d_next_rays, const void *d_count = nullptr);      // one launch, nothing else; light_count in [1, sc.light_count], bounce in [0, 18]

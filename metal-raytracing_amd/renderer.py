@@ -162,6 +162,36 @@ class DeviceScene:
         """Any-hit form of intersect_closest_device: torch.int32 (n,), 1 = occluded."""
         return self._device_query(lib.mrt_scene_intersect_any_device if count is None else lib.mrt_scene_intersect_any_device_counted, rays, out, stream, (), count)
 
+    def intersect_all_device(self, rays, max_hits, out=None, counts_out=None, stream=None, count=None):
+        """ALL hits of rays that live on the GPU, in order and ordered on a stream: rays as intersect_closest_device takes them, max_hits 1 .. 16 -> (hits, hit_counts):
+        hits torch.int32 (n, max_hits, 8), per ray the max_hits smallest hits under (distance, triangle id), ascending, each triangle once, then miss records (every record
+        of a row is written); hit_counts torch.int32 (n,), the number of hit records, 0 .. max_hits.  Row [i, 0] has the bits of intersect_closest_device, and
+        hit_counts > 0 is intersect_any_device.  Truncation is not reported: ask for one more than needed to learn whether there are more.  Flattened scenes in every
+        layout; a two-level scene raises MRTError (unsupported).  Nothing is allocated (but the outputs that are None), copied or synchronised.  stream, count: as
+        intersect_closest_device takes them; rows at and past count are touched in neither output.
+        What follows: resolve_hits_device(rays.repeat_interleave(max_hits, 0), hits.view(-1, 8)) gives one MRTSurface per record (miss rows for the padding), whose
+        resource_slot column leads to the slot's material — the product of its `dissolve` over a shadow ray's records is what the ray lets through."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        if not isinstance(rays, torch.Tensor) or rays.device != dev:
+            raise ValueError(f"rays must be a torch tensor on {dev}")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("rays must be a contiguous torch.float32 tensor of shape (n, 8): [ox, oy, oz, tmin, dx, dy, dz, tmax]")
+        if isinstance(max_hits, bool) or not isinstance(max_hits, int) or not 1 <= max_hits <= 16:
+            raise ValueError("max_hits must be an integer 1 .. 16")
+        n = rays.shape[0]
+        outs = []
+        for what, t, shape in (("out", out, (n, max_hits, 8)), ("counts_out", counts_out, (n,))):
+            if t is None:
+                t = torch.empty(shape, dtype=torch.int32, device=dev)
+            elif not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous torch.int32 tensor of shape {shape} on {dev}")
+            outs.append(t)
+        fn, more = (lib.mrt_scene_intersect_all_device, ()) if count is None else (lib.mrt_scene_intersect_all_device_counted, (self._count_word(count),))
+        check(fn(self.handle, C.c_void_p(rays.data_ptr() if n else None), n, max_hits, C.c_void_p(outs[0].data_ptr() if n else None), C.c_void_p(outs[1].data_ptr() if n else None),
+                 C.c_void_p(self._stream_handle(stream)), *more))
+        return outs[0], outs[1]
+
     def _hit_records(self, hits, what="hits"):
         """the (n, 8) torch.int32 tensor of MRTIntersection records intersect_closest_device returns, checked"""
         import torch

@@ -5,6 +5,11 @@ primary rays through pixel centres), 2^22 rays built on the device with torch fr
   (b) the entry on a copy whose rays all have min_distance = 1e-30: the whole batch takes the one-ray-per-lane walk of the host entries;
   (c) the wall time of the host entry (host arrays in and out) for the same rays.
 (a) and (b) alternate in one process; device time from HIP events on the stream, 3 warm + 20 timed repetitions, median.
+All-hits leg (DeviceScene.intersect_all_device; flattened scenes), the forms alternating in one process the same way:
+  (1) all-hits with K = 1 against (b) on the min_distance = 1e-30 rays: the same walk with one candidate in registers — what the list costs when it is not needed;
+  (2) all-hits with K = 4 and K = 8 against K successive intersect_closest_device calls, each with min_distance one float past the previous distance (torch ops on
+      the same stream in between, no compaction: a ray that has missed walks and misses again) — what a caller does without the entry, and it loses ties;
+  (3) all-hits with K = 1 against (a) on the min_distance = 0 rays: what the missing lane refill costs.
 Usage: python tools/query_rate.py [--rays 4194304] [--scenes dragon,dragon4]      (prints one JSON line)"""
 import argparse
 import json
@@ -97,8 +102,30 @@ def main():
                 fn(h[:4096])
                 t0 = time.perf_counter(); fn(h); wall.append((time.perf_counter() - t0) * 1e3)
             mr = lambda ms: a.rays / ms / 1e3
+            if not two_level:
+                cnt = torch.empty((a.rays,), dtype=torch.int32, device=dev)
+                outs = {K: torch.empty((a.rays, K, 8), dtype=torch.int32, device=dev) for K in (1, 4, 8)}
+                work = rays.clone()
+
+                def successive(K):
+                    work.copy_(rays)
+                    for k in range(K):
+                        ds.intersect_closest_device(work, out=oc, stream=s)
+                        if k + 1 < K:          # one float past the hit; a ray that missed keeps its window
+                            work[:, 3] = torch.where(oc[:, 0] == 1, (oc[:, 1] + 1).view(torch.float32), work[:, 3])
+                torch.cuda.synchronize()
+                u = timed([lambda: ds.intersect_closest_device(lane, out=oc, stream=s), lambda: ds.intersect_all_device(lane, 1, out=outs[1], counts_out=cnt, stream=s),
+                           lambda: ds.intersect_closest_device(rays, out=oc, stream=s), lambda: ds.intersect_all_device(rays, 1, out=outs[1], counts_out=cnt, stream=s),
+                           lambda: ds.intersect_all_device(rays, 4, out=outs[4], counts_out=cnt, stream=s), lambda: successive(4),
+                           lambda: ds.intersect_all_device(rays, 8, out=outs[8], counts_out=cnt, stream=s), lambda: successive(8)])
+                mean_hits = float(cnt.float().mean())          # of the K = 8 call
+                all_hits = {"b_lane_ms": u[0], "all1_lane_ms": u[1], "all1_over_b": u[1] / u[0], "a_stream_ms": u[2], "all1_ms": u[3], "all1_over_a": u[3] / u[2],
+                            "all4_ms": u[4], "closest_x4_ms": u[5], "x4_over_all4": u[5] / u[4], "all8_ms": u[6], "closest_x8_ms": u[7], "x8_over_all8": u[7] / u[6],
+                            "all1_Mrays": mr(u[3]), "all4_Mrays": mr(u[4]), "all8_Mrays": mr(u[6]), "mean_hits_at_8": mean_hits}
+                del outs, work
             row[dist] = {"hit_share": hit_share,
                          "closest": {"a_stream_ms": t[0], "b_lane_ms": t[1], "c_host_wall_ms": wall[0], "a_Mrays": mr(t[0]), "b_Mrays": mr(t[1]), "c_Mrays": mr(wall[0]), "a_over_b": t[1] / t[0], "a_over_c": wall[0] / t[0]},
+                         **({} if two_level else {"all_hits": all_hits}),
                          "any": {"a_stream_ms": t[2], "b_lane_ms": t[3], "c_host_wall_ms": wall[1], "a_Mrays": mr(t[2]), "b_Mrays": mr(t[3]), "c_Mrays": mr(wall[1]), "a_over_b": t[3] / t[2], "a_over_c": wall[1] / t[2]}}
         res["scenes"][name] = row
         ds.close()
