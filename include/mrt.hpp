@@ -121,6 +121,24 @@ struct Scene {                                                       // Scene.sw
     static void intersectAllDeviceCounted(MRTScene committed, const void *deviceRays, size_t n, int32_t maxHits, void *deviceOut, void *deviceHitCounts, void *hipStream, const void *deviceCount) {
         check(mrt_scene_intersect_all_device_counted(committed, deviceRays, n, maxHits, deviceOut, deviceHitCounts, hipStream, deviceCount));
     }
+    // Visibility masks (mrt_scene_set_mesh_masks; the reference's ShaderTypes.h:23-30): one 32-bit mask per mesh id, 0xFFFFFFFF until set; a ray with mask r sees mesh m iff
+    // masks[m] & r.  Takes effect at once, commit or not; no build, refit or commit follows.  Draws ignore masks: the masked queries below honour them.
+    static void setMeshMasks(MRTScene scene, int32_t firstMeshId, const std::vector<uint32_t> &masks) { check(mrt_scene_set_mesh_masks(scene, firstMeshId, (int32_t)masks.size(), masks.data())); }
+    static std::vector<uint32_t> meshMasks(MRTScene scene, int32_t firstMeshId, int32_t count) {
+        std::vector<uint32_t> m((size_t)count); check(mrt_scene_get_mesh_masks(scene, firstMeshId, count, m.data())); return m;
+    }
+    // The three queries above for rays that may not see everything: deviceRayMasks is nullptr (rayMask holds for every ray) or n x uint32 on the device (rayMask is ignored);
+    // deviceCount is nullptr or the row count on the device.  One launch, one ray per lane; the records are those of a scene holding the visible meshes only.
+    static void intersectClosestMaskedDevice(MRTScene committed, const void *deviceRays, const void *deviceRayMasks, uint32_t rayMask, size_t n, void *deviceOut, void *hipStream, const void *deviceCount = nullptr) {
+        check(mrt_scene_intersect_closest_masked_device(committed, deviceRays, deviceRayMasks, rayMask, n, deviceOut, hipStream, deviceCount));
+    }
+    static void intersectAnyMaskedDevice(MRTScene committed, const void *deviceRays, const void *deviceRayMasks, uint32_t rayMask, size_t n, void *deviceOccluded, void *hipStream, const void *deviceCount = nullptr) {
+        check(mrt_scene_intersect_any_masked_device(committed, deviceRays, deviceRayMasks, rayMask, n, deviceOccluded, hipStream, deviceCount));
+    }
+    static void intersectAllMaskedDevice(MRTScene committed, const void *deviceRays, const void *deviceRayMasks, uint32_t rayMask, size_t n, int32_t maxHits, void *deviceOut, void *deviceHitCounts,
+                                         void *hipStream, const void *deviceCount = nullptr) {
+        check(mrt_scene_intersect_all_masked_device(committed, deviceRays, deviceRayMasks, rayMask, n, maxHits, deviceOut, deviceHitCounts, hipStream, deviceCount));
+    }
     // Stream-ordered deformation of a committed flattened MRTScene (mrt_scene_update_mesh_device / mrt_scene_refit_device): strided float3 positions and normals in device
     // memory replace one mesh's vertices, then the resident tree is refitted, all on hipStream; updatesRejected() blocks and counts the updates refused for a NaN or an infinity.
     static void updateMeshDevice(MRTScene committed, int32_t meshId, const void *devicePositions, size_t positionStrideBytes, const void *deviceNormals, size_t normalStrideBytes, size_t vertexCount, void *hipStream) {
@@ -316,6 +334,19 @@ class Renderer {                                                     // Renderer
     void *stream() const { void *s = nullptr; check(mrt_context_get_stream(ctx_, &s)); return s; }
     void intersectClosestDevice(const void *deviceRays, size_t n, void *deviceOut, void *hipStream) { Scene::intersectClosestDevice(scene_, deviceRays, n, deviceOut, hipStream); }
     void intersectAnyDevice(const void *deviceRays, size_t n, void *deviceOccluded, void *hipStream) { Scene::intersectAnyDevice(scene_, deviceRays, n, deviceOccluded, hipStream); }
+    // visibility masks per mesh id and the masked queries (Scene::setMeshMasks / intersectClosestMaskedDevice ...); draw() ignores masks
+    void setMeshMasks(int32_t firstMeshId, const std::vector<uint32_t> &masks) { Scene::setMeshMasks(scene_, firstMeshId, masks); }
+    std::vector<uint32_t> meshMasks(int32_t firstMeshId, int32_t count) const { return Scene::meshMasks(scene_, firstMeshId, count); }
+    void intersectClosestMaskedDevice(const void *deviceRays, const void *deviceRayMasks, uint32_t rayMask, size_t n, void *deviceOut, void *hipStream, const void *deviceCount = nullptr) {
+        Scene::intersectClosestMaskedDevice(scene_, deviceRays, deviceRayMasks, rayMask, n, deviceOut, hipStream, deviceCount);
+    }
+    void intersectAnyMaskedDevice(const void *deviceRays, const void *deviceRayMasks, uint32_t rayMask, size_t n, void *deviceOccluded, void *hipStream, const void *deviceCount = nullptr) {
+        Scene::intersectAnyMaskedDevice(scene_, deviceRays, deviceRayMasks, rayMask, n, deviceOccluded, hipStream, deviceCount);
+    }
+    void intersectAllMaskedDevice(const void *deviceRays, const void *deviceRayMasks, uint32_t rayMask, size_t n, int32_t maxHits, void *deviceOut, void *deviceHitCounts, void *hipStream,
+                                  const void *deviceCount = nullptr) {
+        Scene::intersectAllMaskedDevice(scene_, deviceRays, deviceRayMasks, rayMask, n, maxHits, deviceOut, deviceHitCounts, hipStream, deviceCount);
+    }
     // hit records resolved to surface data, and the caller's per-vertex data interpolated at the hits (Scene::resolveHitsDevice / interpolateDevice / vertexOffsets)
     void resolveHitsDevice(const void *deviceRays, const void *deviceHits, size_t n, void *deviceSurfaces, void *hipStream) { Scene::resolveHitsDevice(scene_, deviceRays, deviceHits, n, deviceSurfaces, hipStream); }
     void interpolateDevice(const void *deviceHits, size_t n, const void *deviceAttributes, size_t attributeStrideBytes, int32_t channels, void *deviceOut, size_t outStrideBytes, void *hipStream) {

@@ -278,6 +278,41 @@ int mrt_scene_intersect_any_device(MRTScene scene, const void *d_rays, size_t n,
 #define MRT_MAX_HITS 16
 int mrt_scene_intersect_all_device(MRTScene scene, const void *d_rays, size_t n, int32_t max_hits, void *d_out /* n x max_hits x MRTIntersection */,
                                    void *d_hit_counts /* n x int32 */, void *hip_stream);
+/* Visibility masks: which geometry a ray may see.  Metal's intersector takes a mask with every intersect call and every instance carries one; the
+ * reference declares the bits (ShaderTypes.h:23-30), sets descriptor.mask = 0xFF (Renderer.swift:196), carries a mask per submesh, and leaves its masked intersect
+ * calls commented out (Raytracing.metal:243,363-365): primary rays see the light's own geometry, shadow and bounce rays do not.  The constants below are the reference's.
+ *   Every mesh id — the id MRTIntersection.instance_id reports; a mesh and each instance made by mrt_scene_add_instance have their own — carries one 32-bit mask,
+ *   0xFFFFFFFF until it is set.  A triangle of mesh m is VISIBLE to a ray with mask r iff (mask[m] & r) != 0; a ray mask of 0 sees nothing.
+ *   mrt_scene_set_mesh_masks writes the masks of the mesh ids first_mesh_id .. + count - 1, before or after a commit.  On a committed scene it writes the device table
+ *   and blocks until that is done, as a commit does (no masked query of this scene may be in flight); the tree does not depend on masks, so the call needs no commit
+ *   after it and costs no build, refit or TLAS update.  Masks survive every commit and every stream-ordered update, refit and TLAS rebuild; a mesh added later has
+ *   0xFFFFFFFF.  mrt_scene_get_mesh_masks reads them back.  MRT_ERR_INVALID_ARGUMENT: NULL scene, NULL masks with count > 0, a range outside the scene's meshes.
+ *   Draws (mrt_renderer_render) IGNORE masks: an integrator composed from the query and stage entries honours them by calling the masked entries below.          */
+#define MRT_GEOMETRY_MASK_TRIANGLE 1u          /* ShaderTypes.h:23-30 */
+#define MRT_GEOMETRY_MASK_LIGHT 2u
+#define MRT_RAY_MASK_PRIMARY 3u
+#define MRT_RAY_MASK_SHADOW 1u
+#define MRT_RAY_MASK_SECONDARY 1u
+int mrt_scene_set_mesh_masks(MRTScene scene, int32_t first_mesh_id, int32_t count, const uint32_t *masks);
+int mrt_scene_get_mesh_masks(MRTScene scene, int32_t first_mesh_id, int32_t count, uint32_t *masks);
+/* The three device queries with a visibility mask per call or per ray: ONE kernel on hip_stream (taken literally, as above), no allocation, no copy, no wait.
+ *   d_ray_masks: NULL — ray_mask holds for every ray — or n x uint32 in device memory, 4-byte aligned, one per ray — ray_mask is then ignored.
+ *   d_count: NULL, or one uint32 on the device with the meaning it has in the _counted entries: rows at and past it are neither read nor written.
+ *   The result of ray i is, in every field and bit, what the unmasked entry of the same name returns for ray i on a scene that holds only the meshes visible to it,
+ *   with the ids of the full scene: ties at equal distance go to the lowest global triangle id AMONG THE VISIBLE triangles; a triangle the ray may not see neither ends
+ *   an any-hit walk, nor lowers a closest walk's bound, nor takes a slot of an all-hits list.  With every mask all-ones the entries return the unmasked entries' bits.
+ *   One ray per lane, whatever min_distance is (no lane refill: DESIGN.md §10p has the rates).  In a two-level scene an instance the ray may not see is skipped before
+ *   its BLAS is entered: the mask tested is the INSTANCE's, not its source mesh's.
+ *   Scenes: closest and any — committed flattened scenes in every layout, two-level scenes, empty scenes; all — flattened scenes only (two-level: MRT_ERR_UNSUPPORTED,
+ *   as mrt_scene_intersect_all_device).  Plain arguments are checked before the scene is looked at: MRT_ERR_INVALID_ARGUMENT for max_hits outside 1 .. MRT_MAX_HITS,
+ *   n >= 2^31, n * max_hits >= 2^31, NULL buffers with n > 0, the all-hits records (its d_out) not 16-byte aligned, any other buffer not 4-byte aligned, NULL scene;
+ *   MRT_ERR_STATE: the scene is not committed.  Every refusal leaves the outputs untouched.  n == 0: MRT_OK, nothing is launched.                                */
+int mrt_scene_intersect_closest_masked_device(MRTScene scene, const void *d_rays, const void *d_ray_masks, uint32_t ray_mask, size_t n, void *d_out, void *hip_stream,
+                                              const void *d_count);
+int mrt_scene_intersect_any_masked_device(MRTScene scene, const void *d_rays, const void *d_ray_masks, uint32_t ray_mask, size_t n, void *d_occluded, void *hip_stream,
+                                          const void *d_count);
+int mrt_scene_intersect_all_masked_device(MRTScene scene, const void *d_rays, const void *d_ray_masks, uint32_t ray_mask, size_t n, int32_t max_hits, void *d_out,
+                                          void *d_hit_counts, void *hip_stream, const void *d_count);
 /* Deforming geometry from DEVICE buffers, ordered on a stream of the caller's: the other half of the loop "move vertices -> refit -> query or draw" on one stream.
  * mrt_scene_update_mesh_device replaces the vertices of one mesh of a COMMITTED flattened scene with vertex_count strided float3 positions and normals read from
  * device memory (strides >= 12, multiples of 4: a row of a torch view of 16 or 32 bytes is fine; 4-byte aligned pointers), in every flattened instance of that mesh;

@@ -133,6 +133,8 @@ class DenoiseParams(C.Structure):  # MRTDenoiseParams (include/mrt_abi.h; no cou
 
 
 GUIDE_NORMAL_DEPTH, GUIDE_ALBEDO, GUIDE_IDS = 0, 1, 2
+GEOMETRY_MASK_TRIANGLE, GEOMETRY_MASK_LIGHT = 1, 2                    # MRT_GEOMETRY_MASK_* / MRT_RAY_MASK_* (ShaderTypes.h:23-30): DeviceScene.set_mesh_masks and mask= of the queries
+RAY_MASK_PRIMARY, RAY_MASK_SHADOW, RAY_MASK_SECONDARY = 3, 1, 1
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_color": 4.0, "sigma_normal": 0.25, "sigma_depth": 0.25, "demodulate": 1}      # MRT_DENOISE_DEFAULT_*
 
 assert C.sizeof(Camera) == 64 and C.sizeof(Light) == 128 and C.sizeof(Uniforms) == 96 and C.sizeof(Material) == 64
@@ -170,6 +172,11 @@ SIGNATURES = {
     "mrt_scene_intersect_any_device": (C.c_int, [_P, _P, _SZ, _P, _P]),
     "mrt_scene_intersect_all_device": (C.c_int, [_P, _P, _SZ, _I32, _P, _P, _P]),
     "mrt_scene_intersect_all_device_counted": (C.c_int, [_P, _P, _SZ, _I32, _P, _P, _P, _P]),
+    "mrt_scene_set_mesh_masks": (C.c_int, [_P, _I32, _I32, _P]),
+    "mrt_scene_get_mesh_masks": (C.c_int, [_P, _I32, _I32, _P]),
+    "mrt_scene_intersect_closest_masked_device": (C.c_int, [_P, _P, _P, _U32, _SZ, _P, _P, _P]),
+    "mrt_scene_intersect_any_masked_device": (C.c_int, [_P, _P, _P, _U32, _SZ, _P, _P, _P]),
+    "mrt_scene_intersect_all_masked_device": (C.c_int, [_P, _P, _P, _U32, _SZ, _I32, _P, _P, _P, _P]),
     "mrt_scene_update_mesh_device": (C.c_int, [_P, _I32, _P, _SZ, _P, _SZ, _SZ, _P]),
     "mrt_scene_refit_device": (C.c_int, [_P, _P]),
     "mrt_scene_device_updates_rejected": (C.c_int, [_P, C.POINTER(C.c_uint64)]),

@@ -51,6 +51,26 @@ int mrt_scene_sync_host_meshes(MRTScene scene) {
     return rc;
 }
 
+// Visibility masks.  The host list is the truth and is as long as the mesh list once someone has asked for it; the device table restates it.  No build, refit or
+// update touches the table, and DevBuf::alloc keeps an allocation of the same size, so a commit uploads it only when the mesh count changed or masks were set while the scene was
+// not committed (`force`: mrt_scene_set_mesh_masks on a committed scene).  Blocks, as a commit does.
+static std::vector<uint32_t> &mesh_masks_of(MRTScene scene) {
+    if (scene->mesh_masks.size() != scene->meshes.size()) scene->mesh_masks.resize(scene->meshes.size(), 0xFFFFFFFFu);
+    return scene->mesh_masks;
+}
+static int upload_mesh_masks(MRTScene scene, bool force) {
+    const std::vector<uint32_t> &m = mesh_masks_of(scene);
+    mrt::DevBuf<uint32_t> &table = scene->dev.mesh_masks;
+    if (!force && !scene->masks_stale && table.p && scene->masks_uploaded == m.size()) return MRT_OK;          // (the entries written, not the allocation: an empty scene's table is one word nobody wrote)
+    MRT_HIP(table.alloc(m.size()));
+    if (!m.empty()) {
+        MRT_HIP(hipMemcpyAsync(table.p, m.data(), m.size() * sizeof(uint32_t), hipMemcpyHostToDevice, scene->ctx->stream));
+        MRT_HIP(hipStreamSynchronize(scene->ctx->stream));
+    }
+    scene->masks_stale = false; scene->masks_uploaded = m.size();
+    return MRT_OK;
+}
+
 extern "C" {
 
 const char *mrt_last_error(void) { return mrt::g_err.c_str(); }
@@ -293,6 +313,7 @@ int mrt_scene_commit(MRTScene scene) {
     for (auto &m : scene->meshes) m.dirty = false;
     rc = mrt::refit_workspace_after_commit(scene->dev); if (rc) return rc;
     rc = mrt::upload_lights(scene->lights.data(), (int)scene->lights.size(), scene->ctx->stream, scene->dev); if (rc) return rc;
+    rc = upload_mesh_masks(scene, false); if (rc) return rc;
     scene->changes.commit_done();
     return MRT_OK;
     MRT_CATCH
@@ -427,6 +448,71 @@ int mrt_scene_intersect_all_device(MRTScene scene, const void *d_rays, size_t n,
 int mrt_scene_intersect_all_device_counted(MRTScene scene, const void *d_rays, size_t n, int32_t max_hits, void *d_out, void *d_hit_counts, void *hip_stream, const void *d_count) {
     MRT_TRY
     return intersect_all_entry("mrt_scene_intersect_all_device_counted", scene, d_rays, n, max_hits, d_out, d_hit_counts, hip_stream, d_count, true);
+    MRT_CATCH
+}
+
+// Visibility masks (masked.hip).  Setting masks is no change in the sense of scene_changes.h: the tree does not depend on them.
+static int check_mask_range(const char *who_c, MRTScene scene, int32_t first, int32_t count, const void *masks) {
+    const std::string who(who_c);
+    REQUIRE(scene, who + ": scene is NULL");
+    REQUIRE(first >= 0 && count >= 0 && (size_t)first + (size_t)count <= scene->meshes.size(), who + ": mesh ids out of range");
+    REQUIRE(count == 0 || masks, who + ": masks is NULL");
+    return MRT_OK;
+}
+int mrt_scene_set_mesh_masks(MRTScene scene, int32_t first_mesh_id, int32_t count, const uint32_t *masks) {
+    MRT_TRY
+    if (int rc = check_mask_range("mrt_scene_set_mesh_masks", scene, first_mesh_id, count, masks)) return rc;
+    if (count == 0) return MRT_OK;
+    std::copy(masks, masks + count, mesh_masks_of(scene).begin() + first_mesh_id);
+    if (!scene->changes.committed()) { scene->masks_stale = true; return MRT_OK; }          // the commit that has to come uploads the table
+    if (int rc = bind_device(scene->ctx)) return rc;
+    return upload_mesh_masks(scene, true);
+    MRT_CATCH
+}
+int mrt_scene_get_mesh_masks(MRTScene scene, int32_t first_mesh_id, int32_t count, uint32_t *masks) {
+    MRT_TRY
+    if (int rc = check_mask_range("mrt_scene_get_mesh_masks", scene, first_mesh_id, count, masks)) return rc;
+    const std::vector<uint32_t> &m = mesh_masks_of(scene);
+    std::copy(m.begin() + first_mesh_id, m.begin() + first_mesh_id + count, masks);
+    return MRT_OK;
+    MRT_CATCH
+}
+// The masked queries: plain arguments first, as intersect_all_entry checks its own, then the scene.  max_hits / d_hit_counts: MASKED_ALL only.
+static int intersect_masked_entry(const char *who_c, mrt::MaskedQuery query, MRTScene scene, const void *d_rays, const void *d_ray_masks, uint32_t ray_mask, size_t n, int32_t max_hits, void *d_out,
+                                  void *d_hit_counts, void *hip_stream, const void *d_count) {
+    const std::string who(who_c);
+    const bool all = query == mrt::MASKED_ALL, records = query != mrt::MASKED_ANY;
+    REQUIRE((uintptr_t)d_count % 4 == 0, who + ": d_count must be 4-byte aligned");
+    if (all) REQUIRE(max_hits >= 1 && max_hits <= MRT_MAX_HITS, who + ": max_hits must be 1 .. " + std::to_string(MRT_MAX_HITS));
+    REQUIRE(n < (size_t(1) << 31), who + ": too many rays (n must be below 2^31)");
+    if (all) REQUIRE(n * (size_t)max_hits < (size_t(1) << 31), who + ": too many records (n * max_hits must be below 2^31)");
+    REQUIRE(n == 0 || (d_rays && d_out && (!all || d_hit_counts)), who + ": NULL buffers");
+    REQUIRE((uintptr_t)d_rays % 4 == 0 && (uintptr_t)d_ray_masks % 4 == 0 && (uintptr_t)d_hit_counts % 4 == 0, who + ": rays, ray masks and hit counts must be 4-byte aligned");
+    REQUIRE((uintptr_t)d_out % (all ? 16 : 4) == 0, all ? who + ": the records must be 16-byte aligned" : who + (records ? ": d_out must be 4-byte aligned" : ": d_occluded must be 4-byte aligned"));          // (as the unmasked twins: the list is written in 16-byte stores, a closest record in words)
+    if (!scene) { mrt::set_error(who + ": scene is NULL"); return MRT_ERR_INVALID_ARGUMENT; }
+    if (!scene->changes.committed()) { mrt::set_error(who + ": scene not committed"); return MRT_ERR_STATE; }
+    if (all && (scene->opt.instancing || scene->dev.num_inst)) {
+        mrt::set_error(who + ": two-level scenes (scene option instancing = 1) are not served: the walk across both levels is not written yet; flattened scenes in every layout are");
+        return MRT_ERR_UNSUPPORTED;
+    }
+    if (n == 0) return MRT_OK;
+    if (int rc = bind_device(scene->ctx)) return rc;
+    return mrt::intersect_masked_device(scene->dev, (hipStream_t)hip_stream, query, d_rays, d_ray_masks, ray_mask, n, max_hits, d_out, d_hit_counts, d_count);
+}
+int mrt_scene_intersect_closest_masked_device(MRTScene scene, const void *d_rays, const void *d_ray_masks, uint32_t ray_mask, size_t n, void *d_out, void *hip_stream, const void *d_count) {
+    MRT_TRY
+    return intersect_masked_entry("mrt_scene_intersect_closest_masked_device", mrt::MASKED_CLOSEST, scene, d_rays, d_ray_masks, ray_mask, n, 1, d_out, nullptr, hip_stream, d_count);
+    MRT_CATCH
+}
+int mrt_scene_intersect_any_masked_device(MRTScene scene, const void *d_rays, const void *d_ray_masks, uint32_t ray_mask, size_t n, void *d_occluded, void *hip_stream, const void *d_count) {
+    MRT_TRY
+    return intersect_masked_entry("mrt_scene_intersect_any_masked_device", mrt::MASKED_ANY, scene, d_rays, d_ray_masks, ray_mask, n, 1, d_occluded, nullptr, hip_stream, d_count);
+    MRT_CATCH
+}
+int mrt_scene_intersect_all_masked_device(MRTScene scene, const void *d_rays, const void *d_ray_masks, uint32_t ray_mask, size_t n, int32_t max_hits, void *d_out, void *d_hit_counts, void *hip_stream,
+                                          const void *d_count) {
+    MRT_TRY
+    return intersect_masked_entry("mrt_scene_intersect_all_masked_device", mrt::MASKED_ALL, scene, d_rays, d_ray_masks, ray_mask, n, max_hits, d_out, d_hit_counts, hip_stream, d_count);
     MRT_CATCH
 }
 

@@ -19,6 +19,9 @@ struct MRTScene_ {
     mrt::SceneChanges changes;              // committed or not, and what changed since the last commit: scene_changes.h decides what the next commit does
     int renderers = 0;                      // renderers made on this scene and not yet destroyed: mrt_scene_destroy refuses while any is left (they hold a pointer to `dev`)
     size_t stage_need = 0;                  // bytes the upload staging of the meshes added so far will take (mrt_mesh_add_submesh grows the pinned area)
+    std::vector<uint32_t> mesh_masks;       // visibility mask per mesh id (mrt_scene_set_mesh_masks); shorter than `meshes` until someone asks: the missing entries are 0xFFFFFFFF
+    bool masks_stale = false;               // masks set while the scene was not committed: the next commit uploads the table (otherwise only a commit that changes the mesh count does)
+    size_t masks_uploaded = SIZE_MAX;       // entries of mesh_masks the device table holds (SIZE_MAX: never written; 0 after the commit of an empty scene, whose one-word allocation holds nothing)
 };
 struct MRTRenderer_ {
     MRTContext ctx = nullptr;

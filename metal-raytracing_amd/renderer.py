@@ -83,6 +83,24 @@ class DeviceScene:
             raise MRTError(1, f"update_mesh: {nrm.shape[0]} normals for {pos.shape[0]} positions (one normal per vertex)")
         check(lib.mrt_scene_update_mesh(self.handle, int(mesh_id), ptr(pos), 12, ptr(nrm), 12, pos.shape[0]))
 
+    def set_mesh_masks(self, masks, first_mesh_id=0):
+        """Visibility masks of the mesh ids first_mesh_id .. (the ids Intersection.instance_id reports; an instance has its own): 32-bit integers, 0xFFFFFFFF until set.  A ray
+        with mask r (mask= of the intersect_*_device methods) sees the triangles of mesh m iff masks[m] & r.  Takes effect at once on a committed scene (it blocks, as a commit
+        does) and needs no commit: the tree does not depend on masks, and nothing is built or refitted.  Masks survive every commit, update and refit.  DRAWS IGNORE MASKS: a
+        Renderer traces every mesh; an integrator composed from the query and stage methods honours masks by passing mask= to its query calls."""
+        m = np.asarray(masks)
+        if m.ndim != 1 or m.dtype.kind not in "iu" or (m.size and (int(m.min()) < 0 or int(m.max()) > 0xFFFFFFFF)):
+            raise ValueError("masks must be a 1-D sequence of integers 0 .. 0xFFFFFFFF")
+        m = np.ascontiguousarray(m, np.uint32)
+        check(lib.mrt_scene_set_mesh_masks(self.handle, int(first_mesh_id), m.shape[0], ptr(m)))
+
+    def mesh_masks(self):
+        """the visibility mask of every mesh id of the COMMITTED scene, numpy uint32 (meshes,): the count is the last commit's (stats.instances), so a mesh added through the C ABI
+        since then appears after the next commit (set_mesh_masks can address it before)"""
+        m = np.zeros(int(self.stats.instances), np.uint32)
+        check(lib.mrt_scene_get_mesh_masks(self.handle, 0, m.shape[0], ptr(m)))
+        return m
+
     @property
     def refits(self):
         v = C.c_uint32()
@@ -131,7 +149,21 @@ class DeviceScene:
             raise ValueError(f"{what} must be a torch.int32 or torch.uint32 tensor with one element on {dev}")
         return C.c_void_p(count.data_ptr())
 
-    def _device_query(self, fn, rays, out, stream, out_shape, count=None):
+    def _mask_args(self, mask, n):
+        """the mask= argument of the three query methods as (d_ray_masks, ray_mask): a Python int is the mask of every ray; a contiguous torch.int32 / uint32 (n,) tensor on the
+        context's device holds one mask per ray.  Anything else is a ValueError, before the library is called."""
+        import torch
+        if isinstance(mask, int) and not isinstance(mask, bool):
+            if not 0 <= mask <= 0xFFFFFFFF:
+                raise ValueError("mask must fit 32 bits: 0 .. 0xFFFFFFFF")
+            return C.c_void_p(None), mask
+        dev = torch.device("cuda", self.ctx.device)
+        kinds = tuple(k for k in (torch.int32, getattr(torch, "uint32", None)) if k is not None)
+        if not isinstance(mask, torch.Tensor) or mask.device != dev or mask.dtype not in kinds or tuple(mask.shape) != (n,) or not mask.is_contiguous():
+            raise ValueError(f"mask must be None, an int, or a contiguous torch.int32 / torch.uint32 tensor of shape ({n},) on {dev}: one mask per ray")
+        return C.c_void_p(mask.data_ptr() if n else None), 0
+
+    def _device_query(self, fn, rays, out, stream, out_shape, count=None, mask=None, masked_fn=None):
         import torch
         dev = torch.device("cuda", self.ctx.device)
         if not isinstance(rays, torch.Tensor) or rays.device != dev:
@@ -144,31 +176,43 @@ class DeviceScene:
         elif not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous torch.int32 tensor of shape {shape} on {dev}")
         n = rays.shape[0]
+        if mask is not None:
+            masks, word = self._mask_args(mask, n)
+            check(masked_fn(self.handle, C.c_void_p(rays.data_ptr() if n else None), masks, word, n, C.c_void_p(out.data_ptr() if n else None), C.c_void_p(self._stream_handle(stream)),
+                            None if count is None else self._count_word(count)))
+            return out
         more = () if count is None else (self._count_word(count),)
         check(fn(self.handle, C.c_void_p(rays.data_ptr() if n else None), n, C.c_void_p(out.data_ptr() if n else None), C.c_void_p(self._stream_handle(stream)), *more))
         return out
 
-    def intersect_closest_device(self, rays, out=None, stream=None, count=None):
+    def intersect_closest_device(self, rays, out=None, stream=None, count=None, mask=None):
         """Closest hits of rays that live on the GPU, ordered on a stream: rays is a contiguous torch.float32 (n, 8) tensor on the context's device
         ([ox, oy, oz, tmin, dx, dy, dz, tmax]); returns torch.int32 (n, 8), one MRTIntersection per row (unpack_intersections gives the fields).  Nothing is
         allocated (but `out` when it is None), copied or synchronised.  stream: None = torch's current stream of that device; an integer handle (0 = the
         null stream) or a torch.cuda.Stream.  Keep rays and out alive until the stream has passed the call.
         count: None, or a one-element torch.int32 / uint32 tensor on that device — the length of the queue the rows hold, as compact_rows_device leaves it.  The rows
         below min(n, count) are handled exactly as without it; no row from there on is read or written.  The word is read on the GPU when the kernels start, never here
-        (this holds for count= of every *_device method)."""
-        return self._device_query(lib.mrt_scene_intersect_closest_device if count is None else lib.mrt_scene_intersect_closest_device_counted, rays, out, stream, (8,), count)
+        (this holds for count= of every *_device method).
+        mask: None — this call, every mesh visible — or which geometry the rays may see (set_mesh_masks): an int is the mask of every ray, a contiguous torch.int32 / uint32
+        (n,) tensor on that device one mask per ray.  A triangle of mesh m is visible to a ray with mask r iff mesh_masks()[m] & r; the record is the one this method returns
+        on a scene that holds the visible meshes only, with this scene's ids.  One ray per lane, one launch (mrt_scene_intersect_closest_masked_device; this holds for
+        mask= of intersect_any_device and intersect_all_device too)."""
+        return self._device_query(lib.mrt_scene_intersect_closest_device if count is None else lib.mrt_scene_intersect_closest_device_counted, rays, out, stream, (8,), count,
+                                  mask, lib.mrt_scene_intersect_closest_masked_device)
 
-    def intersect_any_device(self, rays, out=None, stream=None, count=None):
-        """Any-hit form of intersect_closest_device: torch.int32 (n,), 1 = occluded."""
-        return self._device_query(lib.mrt_scene_intersect_any_device if count is None else lib.mrt_scene_intersect_any_device_counted, rays, out, stream, (), count)
+    def intersect_any_device(self, rays, out=None, stream=None, count=None, mask=None):
+        """Any-hit form of intersect_closest_device: torch.int32 (n,), 1 = occluded (mask: by a triangle the ray may see)."""
+        return self._device_query(lib.mrt_scene_intersect_any_device if count is None else lib.mrt_scene_intersect_any_device_counted, rays, out, stream, (), count,
+                                  mask, lib.mrt_scene_intersect_any_masked_device)
 
-    def intersect_all_device(self, rays, max_hits, out=None, counts_out=None, stream=None, count=None):
+    def intersect_all_device(self, rays, max_hits, out=None, counts_out=None, stream=None, count=None, mask=None):
         """ALL hits of rays that live on the GPU, in order and ordered on a stream: rays as intersect_closest_device takes them, max_hits 1 .. 16 -> (hits, hit_counts):
         hits torch.int32 (n, max_hits, 8), per ray the max_hits smallest hits under (distance, triangle id), ascending, each triangle once, then miss records (every record
         of a row is written); hit_counts torch.int32 (n,), the number of hit records, 0 .. max_hits.  Row [i, 0] has the bits of intersect_closest_device, and
         hit_counts > 0 is intersect_any_device.  Truncation is not reported: ask for one more than needed to learn whether there are more.  Flattened scenes in every
         layout; a two-level scene raises MRTError (unsupported).  Nothing is allocated (but the outputs that are None), copied or synchronised.  stream, count: as
-        intersect_closest_device takes them; rows at and past count are touched in neither output.
+        intersect_closest_device takes them; rows at and past count are touched in neither output.  mask: as intersect_closest_device takes it — an invisible triangle
+        takes no slot of the list.
         What follows: resolve_hits_device(rays.repeat_interleave(max_hits, 0), hits.view(-1, 8)) gives one MRTSurface per record (miss rows for the padding), whose
         resource_slot column leads to the slot's material — the product of its `dissolve` over a shadow ray's records is what the ray lets through."""
         import torch
@@ -187,6 +231,12 @@ class DeviceScene:
             elif not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
                 raise ValueError(f"{what} must be a contiguous torch.int32 tensor of shape {shape} on {dev}")
             outs.append(t)
+        if mask is not None:
+            masks, word = self._mask_args(mask, n)
+            check(lib.mrt_scene_intersect_all_masked_device(self.handle, C.c_void_p(rays.data_ptr() if n else None), masks, word, n, max_hits, C.c_void_p(outs[0].data_ptr() if n else None),
+                                                            C.c_void_p(outs[1].data_ptr() if n else None), C.c_void_p(self._stream_handle(stream)),
+                                                            None if count is None else self._count_word(count)))
+            return outs[0], outs[1]
         fn, more = (lib.mrt_scene_intersect_all_device, ()) if count is None else (lib.mrt_scene_intersect_all_device_counted, (self._count_word(count),))
         check(fn(self.handle, C.c_void_p(rays.data_ptr() if n else None), n, max_hits, C.c_void_p(outs[0].data_ptr() if n else None), C.c_void_p(outs[1].data_ptr() if n else None),
                  C.c_void_p(self._stream_handle(stream)), *more))
@@ -732,7 +782,8 @@ def unpack_lobes(t):
 
 
 class Renderer:
-    """Renderer.swift:12-357."""
+    """Renderer.swift:12-357.  Draws ignore visibility masks (DeviceScene.set_mesh_masks): every mesh is traced by every ray class; an integrator composed from the query
+    and stage methods honours them by passing mask= to its query calls (a renderer option is the follow-up of §11)."""
 
     @property
     def maxFramesInFlight(self):

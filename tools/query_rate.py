@@ -10,7 +10,12 @@ All-hits leg (DeviceScene.intersect_all_device; flattened scene
   (2) all-hits with K = 4 and K = 8 against K successive intersect_closest_device calls, each with min_distance one float past the previous distance (torch ops on
       the same stream in between, no compaction: a ray that has missed walks and misses again) — what a caller does without the entry, and it loses ties;
   (3) all-hits with K = 1 against (a) on the min_distance = 0 rays: what the missing lane refill costs.
-Usage: python tools/query_rate.py [--rays 4194304] [--scenes dragon,dragon4]      (prints one JSON line)"""
+Masked leg (mask= of the three methods), the forms alternating in one process the same way; the unmasked entry in the same job is the yardstick:
+  (i)  flattened scenes: closest and any with every mask all-ones against (b) on the min_distance = 1e-30 rays — the like-for-like one-ray-per-lane walk: what the filter
+       costs — and against (a) on the min_distance = 0 rays: what the missing lane refill costs; all-hits K = 4 masked against unmasked;
+  (ii) two-level scenes (dragon x 4): dragon j carries the bit 1 << j, every other mesh the bit 0x10; a ray mask that sees ONE dragon of the four (0x11) against one that
+       sees all four (0x1F) against the unmasked entry in both of its forms — are skipped instances nearly free?
+Usage: python tools/query_rate.py [--rays 4194304] [--scenes dragon,dragon4] [--legs queries,all_hits,masked]      (prints one JSON line)"""
 import argparse
 import json
 import os
@@ -62,6 +67,7 @@ def main():
     ap.add_argument("--rays", type=int, default=1 << 22)
     ap.add_argument("--scenes", default="dragon,dragon4")
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--legs", default="queries,all_hits,masked")
     a = ap.parse_args()
     import torch
     import metal_raytracing_amd as m
@@ -81,6 +87,7 @@ def main():
                     if rep >= 3: ms[k].append(e0.elapsed_time(e1))
         return [statistics.median(x) for x in ms]
 
+    legs = set(a.legs.split(","))
     for name in a.scenes.split(","):
         two_level = name == "dragon4"
         sc = m.SCENES[name]((1920, 1080))
@@ -93,6 +100,36 @@ def main():
             oc = torch.empty((a.rays, 8), dtype=torch.int32, device=dev); oa = torch.empty((a.rays,), dtype=torch.int32, device=dev)
             torch.cuda.synchronize()
             s = ts.cuda_stream
+            mr = lambda ms: a.rays / ms / 1e3
+            row[dist] = {}
+            if "masked" in legs:
+                ALL = 0xFFFFFFFF
+                if two_level:
+                    names = [mo.name for mo in sc.models for _ in mo.meshes]
+                    dragons = [i for i, nm in enumerate(names) if nm == "dragon"]
+                    masks = [0x10] * len(names)
+                    for j, i in enumerate(dragons): masks[i] = 1 << j
+                    ds.set_mesh_masks(masks)
+                    one, four = 0x11, 0x10 | ((1 << len(dragons)) - 1)
+                    v = timed([lambda: ds.intersect_closest_device(rays, out=oc, stream=s), lambda: ds.intersect_closest_device(lane, out=oc, stream=s),
+                               lambda: ds.intersect_closest_device(rays, out=oc, stream=s, mask=four), lambda: ds.intersect_closest_device(rays, out=oc, stream=s, mask=one),
+                               lambda: ds.intersect_any_device(lane, out=oa, stream=s), lambda: ds.intersect_any_device(rays, out=oa, stream=s, mask=four),
+                               lambda: ds.intersect_any_device(rays, out=oa, stream=s, mask=one)])
+                    row[dist]["masked"] = {"dragons": len(dragons), "closest_a_stream_ms": v[0], "closest_b_lane_ms": v[1], "closest_sees_four_ms": v[2], "closest_sees_one_ms": v[3],
+                                           "four_over_b": v[2] / v[1], "one_over_four": v[3] / v[2], "any_b_lane_ms": v[4], "any_sees_four_ms": v[5], "any_sees_one_ms": v[6],
+                                           "any_one_over_four": v[6] / v[5], "sees_four_Mrays": mr(v[2]), "sees_one_Mrays": mr(v[3])}
+                    ds.set_mesh_masks([ALL] * len(names))
+                else:
+                    cnt = torch.empty((a.rays,), dtype=torch.int32, device=dev); o4 = torch.empty((a.rays, 4, 8), dtype=torch.int32, device=dev)
+                    v = timed([lambda: ds.intersect_closest_device(lane, out=oc, stream=s), lambda: ds.intersect_closest_device(lane, out=oc, stream=s, mask=ALL),
+                               lambda: ds.intersect_closest_device(rays, out=oc, stream=s), lambda: ds.intersect_closest_device(rays, out=oc, stream=s, mask=ALL),
+                               lambda: ds.intersect_any_device(lane, out=oa, stream=s), lambda: ds.intersect_any_device(lane, out=oa, stream=s, mask=ALL),
+                               lambda: ds.intersect_all_device(rays, 4, out=o4, counts_out=cnt, stream=s), lambda: ds.intersect_all_device(rays, 4, out=o4, counts_out=cnt, stream=s, mask=ALL)])
+                    row[dist]["masked"] = {"closest_b_lane_ms": v[0], "closest_masked_lane_ms": v[1], "masked_over_b": v[1] / v[0], "closest_a_stream_ms": v[2], "closest_masked_ms": v[3],
+                                           "masked_over_a": v[3] / v[2], "any_b_lane_ms": v[4], "any_masked_lane_ms": v[5], "any_masked_over_b": v[5] / v[4],
+                                           "all4_ms": v[6], "all4_masked_ms": v[7], "all4_masked_over_all4": v[7] / v[6], "closest_masked_Mrays": mr(v[3])}
+                    del o4, cnt
+            if not legs & {"queries", "all_hits"}: continue
             t = timed([lambda: ds.intersect_closest_device(rays, out=oc, stream=s), lambda: ds.intersect_closest_device(lane, out=oc, stream=s),
                        lambda: ds.intersect_any_device(rays, out=oa, stream=s), lambda: ds.intersect_any_device(lane, out=oa, stream=s)])
             hit_share = float((oc[:, 0] == 1).float().mean())
@@ -101,8 +138,7 @@ def main():
             for fn in (ds.intersect_closest, ds.intersect_any):
                 fn(h[:4096])
                 t0 = time.perf_counter(); fn(h); wall.append((time.perf_counter() - t0) * 1e3)
-            mr = lambda ms: a.rays / ms / 1e3
-            if not two_level:
+            if not two_level and "all_hits" in legs:
                 cnt = torch.empty((a.rays,), dtype=torch.int32, device=dev)
                 outs = {K: torch.empty((a.rays, K, 8), dtype=torch.int32, device=dev) for K in (1, 4, 8)}
                 work = rays.clone()
@@ -123,10 +159,10 @@ def main():
                             "all4_ms": u[4], "closest_x4_ms": u[5], "x4_over_all4": u[5] / u[4], "all8_ms": u[6], "closest_x8_ms": u[7], "x8_over_all8": u[7] / u[6],
                             "all1_Mrays": mr(u[3]), "all4_Mrays": mr(u[4]), "all8_Mrays": mr(u[6]), "mean_hits_at_8": mean_hits}
                 del outs, work
-            row[dist] = {"hit_share": hit_share,
+            row[dist].update({"hit_share": hit_share,
                          "closest": {"a_stream_ms": t[0], "b_lane_ms": t[1], "c_host_wall_ms": wall[0], "a_Mrays": mr(t[0]), "b_Mrays": mr(t[1]), "c_Mrays": mr(wall[0]), "a_over_b": t[1] / t[0], "a_over_c": wall[0] / t[0]},
-                         **({} if two_level else {"all_hits": all_hits}),
-                         "any": {"a_stream_ms": t[2], "b_lane_ms": t[3], "c_host_wall_ms": wall[1], "a_Mrays": mr(t[2]), "b_Mrays": mr(t[3]), "c_Mrays": mr(wall[1]), "a_over_b": t[3] / t[2], "a_over_c": wall[1] / t[2]}}
+                         **({} if two_level or "all_hits" not in legs else {"all_hits": all_hits}),
+                         "any": {"a_stream_ms": t[2], "b_lane_ms": t[3], "c_host_wall_ms": wall[1], "a_Mrays": mr(t[2]), "b_Mrays": mr(t[3]), "c_Mrays": mr(wall[1]), "a_over_b": t[3] / t[2], "a_over_c": wall[1] / t[2]}})
         res["scenes"][name] = row
         ds.close()
     ctx.close()
