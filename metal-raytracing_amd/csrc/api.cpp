@@ -420,7 +420,7 @@ int mrt_scene_intersect_any_device(MRTScene scene, const void *d_rays, size_t n,
     return intersect_device("mrt_scene_intersect_any_device", scene, d_rays, n, d_occluded, hip_stream, true);
     MRT_CATCH
 }
-// All hits in order (multihit.hip).  Plain arguments first, as the surface and stage entries check theirs, so that every one of these refusals needs no device; the scene last.
+// All hits in order (multihit.hip, its walk and list in lane_walk.h).  Plain arguments first, as the surface and stage entries check theirs, so that every one of these refusals needs no device; the scene last.
 static int intersect_all_entry(const char *who_c, MRTScene scene, const void *d_rays, size_t n, int32_t max_hits, void *d_out, void *d_hit_counts, void *hip_stream, const void *d_count, bool counted) {
     const std::string who(who_c);
     if (int rc = check_count_word(who_c, d_count, counted)) return rc;
@@ -451,7 +451,7 @@ int mrt_scene_intersect_all_device_counted(MRTScene scene, const void *d_rays, s
     MRT_CATCH
 }
 
-// Visibility masks (masked.hip).  Setting masks is no change in the sense of scene_changes.h: the tree does not depend on them.
+// Visibility masks (masked.hip, its walks and filter in lane_walk.h).  Setting masks is no change in the sense of scene_changes.h: the tree does not depend on them.
 static int check_mask_range(const char *who_c, MRTScene scene, int32_t first, int32_t count, const void *masks) {
     const std::string who(who_c);
     REQUIRE(scene, who + ": scene is NULL");

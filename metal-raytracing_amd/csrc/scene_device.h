@@ -363,7 +363,7 @@ struct DeviceScene {
     DevBuf<double> cost_words;                                   // wide_tree_cost's 8 + 24 bytes for refit_two_level (made once, kept: no hipMalloc / hipFree pair per commit)
     std::unique_ptr<SurfaceWorkspace> surface_ws;                // the surface entries' slot table (null until the first mrt_scene_resolve_hits_device / _interpolate_device after a commit)
     uint64_t rejected_before = 0;                                // device updates refused in the lifetimes of earlier workspaces of this scene
-    DevBuf<uint32_t> mesh_masks;                                 // visibility mask per mesh id (masked.hip): a buffer of its own, written by mrt_scene_set_mesh_masks and by a commit whose mesh count changed, read by the masked queries alone — no build, refit or view() knows it
+    DevBuf<uint32_t> mesh_masks;                                 // visibility mask per mesh id: a buffer of its own, written by mrt_scene_set_mesh_masks and by a commit whose mesh count changed, read by the masked queries alone (masked.hip, through lane_walk.h's Visibility) — no build, refit or view() knows it
     SceneView view() const;
 };
 
@@ -438,9 +438,9 @@ int interpolate_device(const DeviceScene &sc, hipStream_t stream, const void *d_
                        const void *d_count = nullptr);
 void drop_surface_workspace(DeviceScene &sc);      // (a commit: the table restates the mesh list of the commit before)
 int upload_lights(const MRTLight *lights, int count, hipStream_t stream, DeviceScene &out);
-// multihit.hip: per ray the max_hits smallest hits under (distance, triangle id), on the caller's stream
+// multihit.hip: per ray the max_hits smallest hits under (distance, triangle id), on the caller's stream (the walks and the list: lane_walk.h, §10q)
 int intersect_all_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, int max_hits, void *d_out, void *d_hit_counts, const void *d_count = nullptr);      // one launch, nothing else; flattened scenes, max_hits in [1, MRT_MAX_HITS]
-// masked.hip: the three device queries with a visibility mask per call or per ray
+// masked.hip: the three device queries with a visibility mask per call or per ray (the walks, the sinks and the filter: lane_walk.h, §10q)
 enum MaskedQuery { MASKED_CLOSEST = 0, MASKED_ANY = 1, MASKED_ALL = 2 };
 int intersect_masked_device(const DeviceScene &sc, hipStream_t stream, MaskedQuery query, const void *d_rays, const void *d_ray_masks, uint32_t ray_mask, size_t n, int max_hits, void *d_out,
                             void *d_hit_counts, const void *d_count);      // one launch, nothing else; needs sc.mesh_masks; MASKED_ALL: flattened scenes, max_hits in [1, MRT_MAX_HITS]

@@ -222,3 +222,5 @@ def test_multihit_kernels_use_no_scratch(tmp_path):
     for name in seen:
         v = re.search(rf"\.set {re.escape(name)}\.num_vgpr, (\d+)", txt)
         assert v and int(v.group(1)) <= 128, (name, v and v.group(1))          # at most 128: four waves per SIMD stay possible (LDS bounds the kernels at three for K = 16)
+        ceiling = 78 if "ILb1E" in name else 72          # what the kernels needed when they held their own copies of the walks: a register regression fails here, not on a GPU
+        assert int(v.group(1)) <= ceiling, (name, v.group(1), ceiling)

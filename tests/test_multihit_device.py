@@ -3,6 +3,7 @@ record and every count must have the bits of tests/multihit_reference.py — eve
 tests/test_multihit_cpu.py — in every layout and for every builder, before and after a refit; record 0 must be intersect_closest_device's record and count > 0
 intersect_any_device's answer.  The reference of a scene is computed once for K = 16: the answer for a smaller K is its first K entries, by the definition."""
 import functools
+import gc
 
 import numpy as np
 import pytest
@@ -381,6 +382,7 @@ def test_nothing_is_allocated(mrt, gpu_ctx, layout):
         word = torch.tensor([len(rays)], dtype=torch.int32, device=dev)
         ds.intersect_all_device(d, 16, out=out, counts_out=cnt); ds.intersect_all_device(d, 16, out=out, counts_out=cnt, count=word)          # the warm calls
         torch.cuda.synchronize()
+        gc.collect()          # tensors that earlier tests left in reference cycles are freed now, not by a collection in the middle of the loop (as tests/test_masked_device.py does)
         before = (torch.cuda.memory_allocated(dev), torch.cuda.mem_get_info(dev)[0])
         for k in range(20):
             ds.intersect_all_device(d, 16, out=out, counts_out=cnt, count=word if k % 2 else None)
