@@ -251,6 +251,16 @@ struct Scene {                                                       // Scene.sw
     static void tonemapDevice(MRTContext ctx, int width, int height, const void *deviceImage, void *deviceRgba8, void *hipStream) {
         check(mrt_context_tonemap_device(ctx, width, height, deviceImage, deviceRgba8, hipStream));
     }
+    // Temporal reprojection of the accumulated image (mrt_context_reproject_device): foldSampleDevice's running average kept up while the camera or an
+    // instance moves.  This frame's bounce-0 MRTSurface rows and radiance sample, the PREVIOUS frame's own guide entries (foldGuidesDevice with frameIndex 0) and history
+    // {rgb, length} -> deviceOut {rgb, length}, the next frame's history.  devicePrevPosition (where each visible point was a frame ago) may be nullptr: the geometry
+    // did not move.  params nullptr = the defaults.  deviceOut overlaps no input.  One kernel on hipStream; no allocation, copy or wait.
+    static void reprojectDevice(MRTContext ctx, int width, int height, const Camera &camera, const Camera &prevCamera, const void *deviceSurfaces, const void *devicePrevPosition,
+                                const void *devicePrevNormalDepth, const void *devicePrevIds, const void *devicePrevHistory, const void *deviceSample, void *deviceOut,
+                                const MRTReprojectParams *params, void *hipStream) {
+        check(mrt_context_reproject_device(ctx, width, height, &camera, &prevCamera, deviceSurfaces, devicePrevPosition, devicePrevNormalDepth, devicePrevIds, devicePrevHistory,
+                                           deviceSample, deviceOut, params, hipStream));
+    }
     // each mesh's first attribute row (an instance reports its source's) and, last, the number of rows: meshCount + 1 entries
     static std::vector<uint64_t> vertexOffsets(MRTScene scene, size_t meshCount) {
         std::vector<uint64_t> o(meshCount + 1); check(mrt_scene_vertex_offsets(scene, o.data(), o.size())); return o;
@@ -399,6 +409,12 @@ class Renderer {                                                     // Renderer
         Scene::denoiseDevice(ctx_, w_, h_, deviceImage, deviceNormalDepth, deviceAlbedo, deviceWorkspace, workspaceBytes, deviceOut, params, hipStream);
     }
     void tonemapDevice(const void *deviceImage, void *deviceRgba8, void *hipStream) { Scene::tonemapDevice(ctx_, w_, h_, deviceImage, deviceRgba8, hipStream); }
+    // the accumulation carried across a camera or instance move (Scene::reprojectDevice): images of this renderer's size; the cameras are the caller's to keep
+    void reprojectDevice(const Camera &camera, const Camera &prevCamera, const void *deviceSurfaces, const void *devicePrevPosition, const void *devicePrevNormalDepth,
+                         const void *devicePrevIds, const void *devicePrevHistory, const void *deviceSample, void *deviceOut, const MRTReprojectParams *params, void *hipStream) {
+        Scene::reprojectDevice(ctx_, w_, h_, camera, prevCamera, deviceSurfaces, devicePrevPosition, devicePrevNormalDepth, devicePrevIds, devicePrevHistory, deviceSample, deviceOut,
+                               params, hipStream);
+    }
     MRTRenderStats stats() { MRTRenderStats s; check(mrt_renderer_stats(r_, &s)); return s; }
     MRTSceneStats sceneStats() { MRTSceneStats s; check(mrt_scene_stats(scene_, &s)); return s; }
     int width() const { return w_; }

@@ -752,6 +752,61 @@ int mrt_context_denoise_device(MRTContext ctx, int32_t width, int32_t height, co
                                size_t workspace_bytes, void *d_out, const MRTDenoiseParams *params, void *hip_stream);
 int mrt_context_tonemap_device(MRTContext ctx, int32_t width, int32_t height, const void *d_image, void *d_rgba8, void *hip_stream);
 
+/* Temporal reprojection of the accumulated image on DEVICE buffers, ordered on a stream of the caller's: mrt_context_fold_sample_device averages pixel p
+ * onto pixel p and so has to restart whenever a camera or an instance moves; this entry finds where each visible surface point was in the previous frame, fetches the
+ * history there if it is the same surface, and keeps averaging — the temporal step of SVGF-style pipelines (Schied et al. 2017), without moments.  The common rules of
+ * the image stages above hold: buffers of the context's device, hip_stream taken literally, ONE launch, nothing allocated, copied from host memory or waited for; plain
+ * arguments checked first, each message naming its argument, a NULL context refused last; every refusal leaves d_out untouched.  Reads no scene.
+ *   width, height     images are laid out like the accumulation buffer: pixel p = y * width + x, row 0 = bottom; npixels = width * height
+ *   camera            this frame's camera and prev_camera the previous frame's, in HOST memory (copied into the launch)
+ *   d_surfaces        npixels x MRTSurface, row p = pixel p: this frame's bounce-0 rows (mrt_scene_resolve_hits_device for mrt_renderer_primary_rays_device's rays)
+ *   d_prev_position   npixels x 16 bytes, xyz used: the world position, IN THE PREVIOUS FRAME, of the surface point seen at p now.  NULL = the geometry did not move:
+ *                     the row's own position is used.  The caller makes it (rigid instances: the two poses applied to the row's position; deformation:
+ *                     mrt_scene_interpolate_device over the previous vertices); no entry here produces it.
+ *   d_prev_normal_depth, d_prev_ids   float4 {n.xyz, t} and int4 {on, instance, geometry, primitive}: the PREVIOUS frame's own guide entries, not averaged — what
+ *                     mrt_context_fold_guides_device(prev surfaces, frame_index = 0) wrote
+ *   d_prev_history    float4: rgb = the accumulated colour, w = the history length in frames.  A zero-filled buffer is a valid "no history" start.
+ *   d_sample          float4: this frame's radiance, w ignored
+ *   d_out             float4: rgb = the new accumulated colour, w = the new history length — the next frame's d_prev_history
+ *   params            NULL = the defaults below
+ * The definition, per pixel (x, y): float32, one rounding per operation, no fused multiply-add, IEEE divide, no square root.  dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z;
+ * cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x).
+ *   project(C, q) inverts the ray generation (px = x + jitter; direction = normalize(((px / width) 2 - 1) right + ((py / height) 2 - 1) up + forward)) for any
+ *     non-degenerate basis: nx = cross(up, forward), ny = cross(forward, right), nz = cross(right, up), det = dot(right, nx); v = q - C.position; a = dot(v, nx) / det,
+ *     b = dot(v, ny) / det, c = dot(v, nz) / det.  It fails unless c > 0 (a NaN fails).  Otherwise px = ((a / c + 1) * 0.5) * (float)width, py = ((b / c + 1) * 0.5) *
+ *     (float)height, d2 = dot(v, v).
+ *   1. cur = d_surfaces[p].  cur.type != 1: out = {sample.rgb, 1}.
+ *   2. P1 = project(camera, cur.position); P0 = project(prev_camera, prev_position).  Either fails or gives a px or py that is not finite: out = {sample.rgb, 1}.
+ *   3. fx = (float)x + (P0.px - P1.px), fy = (float)y + (P0.py - P1.py) — the motion-vector form: the sub-pixel jitter of the primary ray cancels and a still world
+ *      gives fx == x exactly.  x0 = floor(fx), ax = fx - x0; y0 = floor(fy), ay = fy - y0.
+ *   4. Four taps (i, j) in the order (0,0), (1,0), (0,1), (1,1) at column x0 + i, row y0 + j with weight w = (i ? ax : 1 - ax) * (j ? ay : 1 - ay).  A tap of weight 0
+ *      is not read.  A tap is inside iff its float column lies in [0, width - 1] and its float row in [0, height - 1], decided before any conversion to an integer.  A
+ *      tap is VALID iff it is inside, ids.on == 1, ids.instance == cur.instance_id, ids.geometry == cur.geometry_id (the primitive is not compared: a point may cross
+ *      a triangle edge), dot(prev_n, cur.normal) >= min_cos_normal, fabs(t_prev * t_prev - P0.d2) <= depth_tolerance * P0.d2, and history.w >= 1.  Valid taps add
+ *      sw += w; sc += w * history.rgb; sl += w * history.w.  The words of a tap that is not valid are selected away, never computed with: a NaN there does not reach
+ *      the output.
+ *   5. sw > 0: hist = sc / sw, len = min(sl / sw + 1, max_history) (min(a, b) = a < b ? a : b), out = {(sample.rgb + hist * (len - 1)) / len, len}.  Otherwise
+ *      out = {sample.rgb, 1}.
+ * By construction: equal cameras and d_prev_position == NULL over frames 0 .. f - 1 give mrt_context_fold_sample_device's accumulation bit for bit in rgb as long as
+ * max_history > f and every on-surface pixel's previous ids equal this frame's ((s + a f) / (f + 1), the same expression); a clamped max_history = M gives the
+ * exponential average (s + a (M - 1)) / M; a zero d_prev_history gives the sample.
+ * Not provided: the Renderer's own draws do not reproject; there is no variance or moments buffer; the previous normal is not rotated with a rotating instance (fast
+ * rotation loses history: conservative); a pixel that misses restarts at its sample; nothing here produces d_prev_position.
+ * MRT_ERR_INVALID_ARGUMENT: width or height <= 0 or >= 2^24, width * height >= 2^30, a NULL camera, a NULL or not 16-byte aligned buffer (d_prev_position may be NULL),
+ * d_out overlapping any input (byte ranges), max_history < 1 or not finite, min_cos_normal or depth_tolerance NaN, depth_tolerance < 0.                              */
+typedef struct {
+    float   max_history;      /* >= 1, finite: the history length is clamped to it (the exponential average's window)            */
+    float   min_cos_normal;   /* a tap's normal . this pixel's normal must reach it                                             */
+    float   depth_tolerance;  /* >= 0, on SQUARED distance relative to the reprojected point's: 0.1 is about 5 % in distance     */
+    int32_t _pad;
+} MRTReprojectParams;         /* 16 B; NULL = defaults                                                                           */
+#define MRT_REPROJECT_DEFAULT_MAX_HISTORY     32.0f    /* chosen on the CPU restatement against a converged image */
+#define MRT_REPROJECT_DEFAULT_MIN_COS_NORMAL  0.9f
+#define MRT_REPROJECT_DEFAULT_DEPTH_TOLERANCE 0.1f
+int mrt_context_reproject_device(MRTContext ctx, int32_t width, int32_t height, const MRTCamera *camera, const MRTCamera *prev_camera, const void *d_surfaces,
+                                 const void *d_prev_position, const void *d_prev_normal_depth, const void *d_prev_ids, const void *d_prev_history, const void *d_sample,
+                                 void *d_out, const MRTReprojectParams *params, void *hip_stream);
+
 /* ---------------------------------------------------------------- device group (multi-GPU, one process)
  * The reference creates ONE device and ONE queue (MTLCreateSystemDefaultDevice + makeCommandQueue, Renderer.swift:46-59); this is that
  * seam widened to the n GPUs of a node.  The scene and its BVH are replicated on every device; the image is sharded by 8x8 screen tile

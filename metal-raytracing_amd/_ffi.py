@@ -135,11 +135,18 @@ class DenoiseParams(C.Structure):  # MRTDenoiseParams (include/mrt_abi.h; no cou
 GUIDE_NORMAL_DEPTH, GUIDE_ALBEDO, GUIDE_IDS = 0, 1, 2
 GEOMETRY_MASK_TRIANGLE, GEOMETRY_MASK_LIGHT = 1, 2                    # MRT_GEOMETRY_MASK_* / MRT_RAY_MASK_* (ShaderTypes.h:23-30): DeviceScene.set_mesh_masks and mask= of the queries
 RAY_MASK_PRIMARY, RAY_MASK_SHADOW, RAY_MASK_SECONDARY = 3, 1, 1
+
+
+class ReprojectParams(C.Structure):  # MRTReprojectParams (include/mrt_abi.h; no counterpart in ShaderTypes.h)
+    _fields_ = [("max_history", C.c_float), ("min_cos_normal", C.c_float), ("depth_tolerance", C.c_float), ("_pad", C.c_int32)]
+
+
+REPROJECT_DEFAULTS = {"max_history": 32.0, "min_cos_normal": 0.9, "depth_tolerance": 0.1}      # MRT_REPROJECT_DEFAULT_*
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_color": 4.0, "sigma_normal": 0.25, "sigma_depth": 0.25, "demodulate": 1}      # MRT_DENOISE_DEFAULT_*
 
 assert C.sizeof(Camera) == 64 and C.sizeof(Light) == 128 and C.sizeof(Uniforms) == 96 and C.sizeof(Material) == 64
 assert C.sizeof(Ray) == 32 and C.sizeof(Intersection) == 32 and C.sizeof(DenoiseParams) == 32 and C.sizeof(Surface) == 64 and C.sizeof(ScatterLobe) == 32
-assert C.sizeof(RowColumn) == 24
+assert C.sizeof(RowColumn) == 24 and C.sizeof(ReprojectParams) == 16
 
 # ---------------------------------------------------------------- function table: every symbol include/mrt_abi.h declares
 _P, _I32, _U32, _F, _SZ = C.c_void_p, C.c_int32, C.c_uint32, C.c_float, C.c_size_t
@@ -248,6 +255,7 @@ SIGNATURES = {
     "mrt_denoise_workspace_bytes": (C.c_int, [_I32, _I32, C.POINTER(_SZ)]),
     "mrt_context_denoise_device": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _SZ, _P, C.POINTER(DenoiseParams), _P]),
     "mrt_context_tonemap_device": (C.c_int, [_P, _I32, _I32, _P, _P, _P]),
+    "mrt_context_reproject_device": (C.c_int, [_P, _I32, _I32, C.POINTER(Camera), C.POINTER(Camera), _P, _P, _P, _P, _P, _P, _P, C.POINTER(ReprojectParams), _P]),
     "mrt_renderer_stats": (C.c_int, [_P, C.POINTER(RenderStats)]),
     "mrt_renderer_reset_stats": (C.c_int, [_P]),
     "mrt_renderer_kernel_times": (C.c_int, [_P, C.POINTER(KernelTimes)]),

@@ -42,4 +42,6 @@ MRT_AT(MRTRowColumn, src, 0); MRT_AT(MRTRowColumn, dst, 8); MRT_AT(MRTRowColumn,
 static_assert(sizeof(MRTDenoiseParams) == 32, "MRTDenoiseParams is 32 bytes");
 MRT_AT(MRTDenoiseParams, iterations, 0); MRT_AT(MRTDenoiseParams, sigma_color, 4); MRT_AT(MRTDenoiseParams, sigma_normal, 8);
 MRT_AT(MRTDenoiseParams, sigma_depth, 12); MRT_AT(MRTDenoiseParams, demodulate, 16);
+static_assert(sizeof(MRTReprojectParams) == 16, "MRTReprojectParams is 16 bytes");
+MRT_AT(MRTReprojectParams, max_history, 0); MRT_AT(MRTReprojectParams, min_cos_normal, 4); MRT_AT(MRTReprojectParams, depth_tolerance, 8);
 #undef MRT_AT

@@ -5,6 +5,7 @@
 #include "abi_check.h"
 #include "paths.h"
 #include "image.h"
+#include "temporal.h"
 #include "../../include/mrt_debug.h"
 #include <algorithm>
 #include <cstring>
@@ -958,6 +959,36 @@ int mrt_context_tonemap_device(MRTContext ctx, int32_t width, int32_t height, co
     REQUIRE(ctx, who + ": ctx is NULL");
     if (int rc = bind_device(ctx)) return rc;
     return mrt::tonemap_image_device((hipStream_t)hip_stream, width, height, d_image, d_rgba8);
+    MRT_CATCH
+}
+// Temporal reprojection of the accumulated image (temporal.hip).  The same order again.
+int mrt_context_reproject_device(MRTContext ctx, int32_t width, int32_t height, const MRTCamera *camera, const MRTCamera *prev_camera, const void *d_surfaces,
+                                 const void *d_prev_position, const void *d_prev_normal_depth, const void *d_prev_ids, const void *d_prev_history, const void *d_sample,
+                                 void *d_out, const MRTReprojectParams *params, void *hip_stream) {
+    MRT_TRY
+    const std::string who = "mrt_context_reproject_device";
+    REQUIRE_IMAGE_SIZE();
+    REQUIRE(width < (1 << 24), who + ": width must be below 2^24 (a column is a float)"); REQUIRE(height < (1 << 24), who + ": height must be below 2^24 (a row is a float)");
+    REQUIRE(camera, who + ": camera is NULL"); REQUIRE(prev_camera, who + ": prev_camera is NULL");
+    MRTReprojectParams p{};
+    if (params) p = *params;
+    else { p.max_history = MRT_REPROJECT_DEFAULT_MAX_HISTORY; p.min_cos_normal = MRT_REPROJECT_DEFAULT_MIN_COS_NORMAL; p.depth_tolerance = MRT_REPROJECT_DEFAULT_DEPTH_TOLERANCE; }
+    REQUIRE(p.max_history >= 1.0f && p.max_history < 3.0e38f, who + ": max_history must be finite and at least 1");
+    REQUIRE(p.min_cos_normal == p.min_cos_normal, who + ": min_cos_normal is NaN");
+    REQUIRE(p.depth_tolerance >= 0.0f, who + ": depth_tolerance must be at least 0 and not NaN");
+    const size_t n = (size_t)width * (size_t)height, image_bytes = n * 16;
+    REQUIRE_GIVEN(d_surfaces); REQUIRE_GIVEN(d_prev_normal_depth); REQUIRE_GIVEN(d_prev_ids); REQUIRE_GIVEN(d_prev_history); REQUIRE_GIVEN(d_sample); REQUIRE_GIVEN(d_out);
+    REQUIRE_ALIGNED(d_surfaces, 16); REQUIRE_ALIGNED(d_prev_position, 16); REQUIRE_ALIGNED(d_prev_normal_depth, 16); REQUIRE_ALIGNED(d_prev_ids, 16);
+    REQUIRE_ALIGNED(d_prev_history, 16); REQUIRE_ALIGNED(d_sample, 16); REQUIRE_ALIGNED(d_out, 16);
+    const ByteRange inputs[6] = {byte_range(d_surfaces, n * sizeof(MRTSurface), "d_surfaces"), byte_range(d_prev_position, d_prev_position ? image_bytes : 0, "d_prev_position"),
+                                 byte_range(d_prev_normal_depth, image_bytes, "d_prev_normal_depth"), byte_range(d_prev_ids, image_bytes, "d_prev_ids"),
+                                 byte_range(d_prev_history, image_bytes, "d_prev_history"), byte_range(d_sample, image_bytes, "d_sample")};
+    const ByteRange out = byte_range(d_out, image_bytes, "d_out");
+    for (const ByteRange &in : inputs) REQUIRE(!ranges_overlap(out, in), who + ": d_out overlaps " + in.what);
+    REQUIRE(ctx, who + ": ctx is NULL");
+    if (int rc = bind_device(ctx)) return rc;
+    return mrt::reproject_device((hipStream_t)hip_stream, width, height, *camera, *prev_camera, d_surfaces, d_prev_position, d_prev_normal_depth, d_prev_ids, d_prev_history, d_sample,
+                                 d_out, p);
     MRT_CATCH
 }
 #undef REQUIRE_IMAGE_SIZE

@@ -605,6 +605,42 @@ class DeviceScene:
         check(lib.mrt_context_tonemap_device(self.ctx.handle, w, h, C.c_void_p(image.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(self._stream_handle(stream))))
         return out
 
+    def reproject_device(self, surfaces, sample, prev_normal_depth, prev_ids, prev_history, size, camera, prev_camera, prev_position=None, max_history=None, min_cos_normal=None,
+                         depth_tolerance=None, out=None, stream=None):
+        """Temporal reprojection of the accumulated image, on the GPU and ordered on a stream: what fold_sample_device does for a still world, kept up while the camera or
+        an instance moves.  surfaces (pixels, 16) float32, this frame's bounce-0 rows of resolve_hits_device (row p = pixel p = y * width + x, row 0 = bottom); sample
+        (pixels, 4) float32, this frame's radiance (w ignored); prev_normal_depth (pixels, 4) float32 and prev_ids (pixels, 4) int32, the PREVIOUS frame's own guide
+        entries — what fold_guides_device(previous surfaces, 0) returned, not averaged; prev_history (pixels, 4) float32, rgb = accumulated colour, w = history length in
+        frames (zeros: no history); size = (width, height); camera and prev_camera the two frames' Camera -> out (pixels, 4) float32: rgb = the new accumulated colour, w
+        = the new length — the next frame's prev_history.  prev_position (pixels, 4) float32, xyz used: where, in the previous frame, the surface point seen at p now was
+        (None: the geometry did not move); the caller makes it, from the instance's two poses or interpolate_device over the previous vertices.  Each surface pixel is
+        projected into both cameras, up to four bilinear taps of the history are fetched at pixel + (previous - current) and kept where instance, geometry, normal
+        (dot >= min_cos_normal, 0.9), squared distance (relative depth_tolerance, 0.1) and a length >= 1 agree, and out = (sample + history * (len - 1)) / len with len
+        = min(length + 1, max_history (32)); a pixel that misses, projects nowhere or keeps no tap restarts at {sample, 1}.  The definition is include/mrt_abi.h's.  out
+        may not overlap an input; it is allocated when None.  Otherwise nothing is allocated, copied or synchronised.  stream: as intersect_closest_device takes it."""
+        import torch
+        from ._ffi import REPROJECT_DEFAULTS, ReprojectParams
+        dev = torch.device("cuda", self.ctx.device)
+        w, h = int(size[0]), int(size[1])
+        self.denoise_workspace_bytes((w, h))                                                            # (refuses a size that is not positive or too large)
+        n = w * h
+        self._rows(surfaces, "surfaces", torch.float32, (n, 16)); self._rows(sample, "sample", torch.float32, (n, 4))
+        self._rows(prev_normal_depth, "prev_normal_depth", torch.float32, (n, 4)); self._rows(prev_ids, "prev_ids", torch.int32, (n, 4))
+        self._rows(prev_history, "prev_history", torch.float32, (n, 4))
+        if prev_position is not None: self._rows(prev_position, "prev_position", torch.float32, (n, 4))
+        if not isinstance(camera, Camera) or not isinstance(prev_camera, Camera):
+            raise ValueError("camera and prev_camera must be Camera structures")
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        else:
+            self._rows(out, "out", torch.float32, (n, 4))
+        given = dict(max_history=max_history, min_cos_normal=min_cos_normal, depth_tolerance=depth_tolerance)
+        v = {k: float(REPROJECT_DEFAULTS[k] if x is None else x) for k, x in given.items()}
+        par = ReprojectParams(v["max_history"], v["min_cos_normal"], v["depth_tolerance"], 0)
+        p = [C.c_void_p(None if t is None else t.data_ptr()) for t in (surfaces, prev_position, prev_normal_depth, prev_ids, prev_history, sample, out)]
+        check(lib.mrt_context_reproject_device(self.ctx.handle, w, h, C.byref(camera), C.byref(prev_camera), *p, C.byref(par), C.c_void_p(self._stream_handle(stream))))
+        return out
+
     def vertex_offsets(self):
         """The vertex numbering interpolate_device reads attributes in: (meshes + 1,) uint64 — each mesh's first row, the source meshes concatenated in mesh-id order and
         an instance reporting its source's; the last entry is the number of rows."""

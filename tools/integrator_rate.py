@@ -31,8 +31,16 @@ and, per scene (the image legs), at 1920 x 1080:
       Renderer.denoise on the same image and guides (the same kernels: the expectation is equality);
   (i) the fused frame of (g) with and without the guide fold of its bounce-0 rows, beside Renderer drawing the frame with guides = 0 and with guides = 1 (which walks the
       primary rays a second time), the four alternating in one loop: what guides cost a composed frame and what they cost the renderer.
+and, per scene (the temporal legs), at 1920 x 1080:
+  (j) reproject_device alone, HIP events, in three cases — a still world (equal cameras, no previous positions), a camera turned by a third of a pixel and by three pixels
+      (previous positions given) — against its byte floor at the same copy bandwidth: per pixel the 64-byte surface row, 16 B of sample and 16 B written, and per
+      surface pixel 48 B of the previous frame's ids, normal | depth and history (a moved frame's four taps are its neighbours' too: the lines are the same), 16 B more
+      with previous positions;
+  (k) the fused frame of (g) ending in reproject_device and the fold of the frame's own guide entries (fold_guides_device at frame index 0, the next frame's previous
+      entries) beside the same frame ending in fold_sample_device, alternating in one loop.
 3 warm + 20 timed repetitions, the legs alternating, medians.
-Usage: python tools/integrator_rate.py [--scenes dragon,dragon4] [--materials 1] [--reps 20] [--legs all|image]      (prints one JSON line; --legs image: (h) and (i) alone)"""
+Usage: python tools/integrator_rate.py [--scenes dragon,dragon4] [--materials 1] [--reps 20] [--legs all|image|temporal]
+(prints one JSON line; --legs image: (h) and (i) alone; --legs temporal: (j) and (k) alone)"""
 import argparse
 import json
 import os
@@ -223,6 +231,88 @@ def image_legs(torch, m, ctx, r, ds, dev, ts, reps, copy_gbs, timed, compose_fus
     return {"h": res, "i": frame}
 
 
+class KeepBounceZero:
+    """a DeviceScene that keeps the rows of the dense resolve_hits_device call — a frame's bounce-0 rows — for the stage after the frame"""
+
+    def __init__(self, ds):
+        self._ds, self.rows = ds, None
+
+    def __getattr__(self, name):
+        return getattr(self._ds, name)
+
+    def resolve_hits_device(self, rays, hits, **kw):
+        surf = self._ds.resolve_hits_device(rays, hits, **kw)
+        if "count" not in kw: self.rows = surf
+        return surf
+
+
+def temporal_legs(torch, m, r, ds, dev, ts, reps, copy_gbs, timed, compose_fused):
+    """(j) and (k) on a 1920 x 1080 renderer"""
+    w, h = r.size
+    n = w * h
+    s = ts.cuda_stream
+    base = m.Camera.from_buffer_copy(r.scene.camera)
+
+    def turned(pixels):
+        c = m.Camera.from_buffer_copy(base)
+        for k in "xyz": setattr(c.forward, k, getattr(base.forward, k) + 2.0 * pixels / w * getattr(base.right, k))          # every pixel moves by about `pixels` columns
+        return c
+
+    def rows_of(camera, sample_index):
+        r.set_camera(camera)
+        rays, _ = r.primary_rays_device(sample_index=sample_index, stream=0)
+        return ds.resolve_hits_device(rays, ds.intersect_closest_device(rays, stream=0), stream=0)
+
+    prev_rows = rows_of(base, 0)
+    nd, _, ids = ds.fold_guides_device(prev_rows, 0, stream=0)
+    hist = torch.rand((n, 4), device=dev); hist[:, 3] = 5.0
+    sample = torch.rand((n, 4), device=dev)
+    out = torch.empty((n, 4), device=dev)
+    cases = {"still": (base, rows_of(base, 1), False), "third_of_a_pixel": (turned(1.0 / 3.0), None, True), "three_pixels": (turned(3.0), None, True)}
+    res = {}
+    fns = []
+    for name, (cam, rows, moved) in cases.items():
+        rows = rows_of(cam, 1) if rows is None else rows
+        pos = rows[:, 0:4].contiguous() if moved else None                              # (the scene stands still: a point's previous position is its own)
+        share = float((rows[:, 7].view(torch.int32) == 1).float().mean())
+        res[name] = {"surface_share": share, "bytes_per_pixel": 96.0 + (48.0 + (16.0 if moved else 0.0)) * share}
+        fns.append(lambda cam=cam, rows=rows, pos=pos: ds.reproject_device(rows, sample, nd, ids, hist, (w, h), cam, base, prev_position=pos, out=out, stream=s))
+    r.set_camera(base)
+    torch.cuda.synchronize()
+    for (name, row), ms, fn in zip(res.items(), timed(fns), fns):
+        fn(); torch.cuda.synchronize()
+        floor = row["bytes_per_pixel"] * n / copy_gbs / 1e6
+        row.update(ms=ms, floor_ms=floor, over_floor=ms / floor, kept_share=float((out[:, 3] > 1.0).float().mean()))
+    # (k)
+    accum = torch.empty((n, 4), device=dev)
+    keeper = KeepBounceZero(ds)
+    guides = (torch.empty((n, 4), device=dev), torch.empty((n, 4), device=dev), torch.empty((n, 4), dtype=torch.int32, device=dev))
+
+    def folded():
+        ds.fold_sample_device(compose_fused(torch, r, ds, 1, dev, bounces=3), accum, 1)
+
+    def reprojected():
+        rad = compose_fused(torch, r, keeper, 1, dev, bounces=3)
+        ds.reproject_device(keeper.rows, rad, nd, ids, hist, (w, h), base, base, out=out)
+        ds.fold_guides_device(keeper.rows, 0, out=guides)
+
+    legs = {"fused_fold_sample": folded, "fused_reproject": reprojected}
+    wall = {k: [] for k in legs}; ev = {k: [] for k in legs}
+    for rep in range(3 + reps):
+        for k, fn in legs.items():
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0 = time.perf_counter()
+                e0.record(ts); fn(); e1.record(ts); ts.synchronize()
+                t1 = time.perf_counter()
+            if rep >= 3: wall[k].append((t1 - t0) * 1e3); ev[k].append(e0.elapsed_time(e1))
+    med = statistics.median
+    frame = {k: {"wall_ms": med(wall[k]), "event_ms": med(ev[k])} for k in legs}
+    frame["reproject_cost_event_ms"] = med(ev["fused_reproject"]) - med(ev["fused_fold_sample"]); frame["reproject_cost_wall_ms"] = med(wall["fused_reproject"]) - med(wall["fused_fold_sample"])
+    return {"j": res, "k": frame}
+
+
 def frame_legs(torch, r, dev, ts, reps, legs):
     """(b) / (c) / (e) in one loop: each callable of `legs` (name -> fn() -> (n, 3) sample) composed on the side stream, then Renderer drawing frame 0; medians of host wall
     and HIP-event time per leg, and whether each leg's sample has the renderer's bits"""
@@ -256,9 +346,9 @@ def main():
     ap.add_argument("--materials", type=int, default=1, help="(c): the materials leg")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--side", type=int, default=2048, help="(a): the image is side x side pixels")
-    ap.add_argument("--legs", choices=("all", "image"), default="all", help="image: (h) and (i) alone, per scene (no materials leg)")
+    ap.add_argument("--legs", choices=("all", "image", "temporal"), default="all", help="image: (h) and (i) alone, per scene (no materials leg); temporal: (j) and (k) alone")
     a = ap.parse_args()
-    if a.legs == "image": a.materials = 0
+    if a.legs != "all": a.materials = 0
     import torch
     import metal_raytracing_amd as m
     ctx = m.Context(0)
@@ -299,10 +389,11 @@ def main():
         two_level = name == "dragon4"
         opts = {"instancing": 1} if two_level else None
         row = {"instancing": int(two_level)}
-        if a.legs == "image":
+        if a.legs != "all":
             r = m.Renderer((1920, 1080), m.SCENES[name]((1920, 1080)), ctx=ctx, scene_options=opts)
             row["triangles"] = int(r.device_scene.stats.triangles)
-            row.update(image_legs(torch, m, ctx, r, r.device_scene, dev, ts, a.reps, copy_gbs, timed, compose_fused))
+            if a.legs == "image": row.update(image_legs(torch, m, ctx, r, r.device_scene, dev, ts, a.reps, copy_gbs, timed, compose_fused))
+            else: row.update(temporal_legs(torch, m, r, r.device_scene, dev, ts, a.reps, copy_gbs, timed, compose_fused))
             r.close()
             res["scenes"][name] = row
             continue
@@ -360,6 +451,7 @@ def main():
                                                           "fused_path_state": lambda: fused(r, ds, 3, False, accum)})
         row["g"] = fused_over_queued(row["e"])
         row.update(image_legs(torch, m, ctx, r, ds, dev, ts, a.reps, copy_gbs, timed, compose_fused))
+        row.update(temporal_legs(torch, m, r, ds, dev, ts, a.reps, copy_gbs, timed, compose_fused))
         r.close()
         res["scenes"][name] = row
     if a.materials:
