@@ -526,6 +526,18 @@ __global__ void k_tonemap(const float4 *__restrict__ accum, int w, int h, uchar4
 }
 
 // ------------------------------------------------------------------ query kernels (C-ABI intersect_*)
+// the record of a closest-hit query: ids by hit_ids, u = U / |det|, v = V / |det|; a miss is {0, -1.0f, -1, -1, -1, 0, 0}
+MRT_DEV MRTIntersection closest_record(const SceneView &s, bool two_level, bool hit, const TravHit &h) {
+    MRTIntersection o;
+    o._pad = 0; o.type = 0; o.distance = -1.0f; o.instance_id = o.geometry_id = o.primitive_id = -1; o.u = o.v = 0.0f;
+    if (hit) {
+        uint32_t inst, geom, prim;
+        hit_ids(s, two_level, h.gid, inst, geom, prim);
+        o.type = 1; o.distance = h.t; o.instance_id = (int32_t)inst; o.geometry_id = (int32_t)geom; o.primitive_id = (int32_t)prim;
+        o.u = h.U / h.ad; o.v = h.V / h.ad;
+    }
+    return o;
+}
 template <bool WIDE>
 __global__ void __launch_bounds__(64) k_query_closest(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, MRTIntersection *__restrict__ out) {
     extern __shared__ uint32_t stk[];      // WIDE: the scene's wide-tree depth x WIDE_STACK_LEVEL_BYTES, sized by the host
@@ -536,17 +548,7 @@ __global__ void __launch_bounds__(64) k_query_closest(SceneView s, const MRTRay 
     const f3 ro = mk3(r.origin[0], r.origin[1], r.origin[2]), rd = mk3(r.direction[0], r.direction[1], r.direction[2]);
     bool hit = s.num_inst ? traverse_instanced<false>(s, ro, rd, r.min_distance, r.max_distance, h)
              : WIDE ? traverse_wide<false>(s, ro, rd, r.min_distance, r.max_distance, h, stk) : traverse<false>(s, ro, rd, r.min_distance, r.max_distance, h);
-    MRTIntersection o;
-    o._pad = 0;
-    if (hit) {
-        uint32_t inst, geom;
-        if (s.num_inst) { inst = instance_of_gid(s, h.gid); const InstanceDev &I = s.inst[inst]; geom = s.tri_shade[I.ts_base + (h.gid - I.gid_base)].w & 0xFFFFu; }
-        else { const uint4 ts = s.tri_shade[h.gid]; inst = ts.w >> 16; geom = ts.w & 0xFFFFu; }
-        o.type = 1; o.distance = h.t; o.instance_id = (int32_t)inst; o.geometry_id = (int32_t)geom;
-        o.primitive_id = (int32_t)(h.gid - s.geom_base[inst * (uint32_t)s.max_sub + geom]);
-        o.u = h.U / h.ad; o.v = h.V / h.ad;
-    } else { o.type = 0; o.distance = -1.0f; o.instance_id = o.geometry_id = o.primitive_id = -1; o.u = o.v = 0.0f; }
-    out[i] = o;
+    out[i] = closest_record(s, s.num_inst != 0, hit, h);
 }
 template <bool WIDE>
 __global__ void __launch_bounds__(64) k_query_any(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, int32_t *__restrict__ out) {
@@ -625,16 +627,8 @@ __global__ void __launch_bounds__(64) k_query_stream(SceneView s, const MRTRay *
             A = make_float4(r.origin[0], r.origin[1], r.origin[2], r.max_distance); B = make_float4(r.direction[0], r.direction[1], r.direction[2], 0.0f);
         },
         [&](uint32_t i, bool is_any, bool hit, const TravHit &h) {
-            MRTIntersection o;
-            o._pad = 0; o.type = hit ? 1 : 0; o.distance = -1.0f; o.instance_id = o.geometry_id = o.primitive_id = -1; o.u = o.v = 0.0f;
-            if (hit && !is_any) {
-                uint32_t inst, geom;
-                if (TWO_LEVEL) { inst = instance_of_gid(s, h.gid); const InstanceDev &I = s.inst[inst]; geom = s.tri_shade[I.ts_base + (h.gid - I.gid_base)].w & 0xFFFFu; }
-                else { const uint4 ts = s.tri_shade[h.gid]; inst = ts.w >> 16; geom = ts.w & 0xFFFFu; }
-                o.distance = h.t; o.instance_id = (int32_t)inst; o.geometry_id = (int32_t)geom;
-                o.primitive_id = (int32_t)(h.gid - s.geom_base[inst * (uint32_t)s.max_sub + geom]);
-                o.u = h.U / h.ad; o.v = h.V / h.ad;
-            }
+            MRTIntersection o = closest_record(s, TWO_LEVEL, hit && !is_any, h);
+            o.type = hit ? 1 : 0;
             out[i] = o;
         });
 }
@@ -647,19 +641,6 @@ __global__ void __launch_bounds__(64) k_query_stream(SceneView s, const MRTRay *
 //                           partial-tile slot (tmax < 0 -> miss: one refill slot, no node visit) and its result is not written.
 //   k_query_lane_device     the other rays — and all rays of a scene without the 8-wide layout — one per lane with the walks of mrt_scene_intersect_closest / _any,
 //                           which carry tmin.  A lane whose ray the stream kernel answered leaves after reading min_distance.
-MRT_DEV MRTIntersection closest_record(const SceneView &s, bool two_level, bool hit, const TravHit &h) {
-    MRTIntersection o;
-    o._pad = 0; o.type = 0; o.distance = -1.0f; o.instance_id = o.geometry_id = o.primitive_id = -1; o.u = o.v = 0.0f;
-    if (hit) {
-        uint32_t inst, geom;
-        if (two_level) { inst = instance_of_gid(s, h.gid); const InstanceDev &I = s.inst[inst]; geom = s.tri_shade[I.ts_base + (h.gid - I.gid_base)].w & 0xFFFFu; }
-        else { const uint4 ts = s.tri_shade[h.gid]; inst = ts.w >> 16; geom = ts.w & 0xFFFFu; }
-        o.type = 1; o.distance = h.t; o.instance_id = (int32_t)inst; o.geometry_id = (int32_t)geom;
-        o.primitive_id = (int32_t)(h.gid - s.geom_base[inst * (uint32_t)s.max_sub + geom]);
-        o.u = h.U / h.ad; o.v = h.V / h.ad;
-    }
-    return o;
-}
 constexpr uint32_t QUERY_STREAM_RAYS = 256;      // rays per wave of the static split, as k_query_stream
 template <bool TWO_LEVEL, bool ANY>
 __global__ void __launch_bounds__(64, TWO_LEVEL ? MRT_TWO_LEVEL_WAVES : MRT_WIDE_STREAM_WAVES) k_query_stream_device(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, const uint32_t *__restrict__ count, void *__restrict__ out) {

@@ -250,11 +250,12 @@ MRT_DEV void leave_instance(const uint32_t *stack, uint32_t lane, const f3 wo, c
     t_base = tl_pack >> 8; t_mask = tl_pack & 0xFFu;
 }
 
-// stack: depth x WIDE_STACK_LEVEL_BYTES of LDS for the wave (depth = the scene's wide-tree depth, <= WIDE_STACK)
-template <bool ANY, bool STATS = false, bool RUNTIME_ANY = false>
-MRT_DEV bool traverse_wide(const SceneView &s, f3 o, f3 d, float tmin, float tmax, TravHit &h, uint32_t *stack /* depth x WIDE_STACK_LEVEL_BYTES in LDS */, TravCounters *tc = nullptr, bool any_rt = false, uint32_t root = 0 /* the node the walk starts at: a BLAS root of a two-level scene, with the ray in that instance's object space */) {
-    h.t = tmax; h.U = 0.0f; h.V = 0.0f; h.ad = 1.0f; h.gid = 0xFFFFFFFFu;
-    if (s.num_wnodes == 0) return false;
+// One ray per lane on the 8-wide layout, with tmin.  stack: depth x WIDE_STACK_LEVEL_BYTES of LDS for the wave (depth = the scene's wide-tree depth, <= WIDE_STACK).
+// root: the node the walk starts at — a BLAS root of a two-level scene, with the ray in that instance's object space.  Filter and sink as walk_rope (traverse.h); a
+// candidate's packet counts from s.wpackets.  STATS: the counters of k_query_stats (diagnostics).
+template <bool STATS = false, class Filter, class Sink>
+MRT_DEV void walk_wide(const SceneView &s, const Filter &vis, const f3 o, const f3 d, const float tmin, Sink &k, uint32_t *stack, uint32_t root = 0, TravCounters *tc = nullptr) {
+    if (s.num_wnodes == 0) return;
     const uint32_t lane = threadIdx.x & 63;
     const float ix = safe_inv(d.x), iy = safe_inv(d.y), iz = safe_inv(d.z);
     const bool nx = d.x < 0.0f, ny = d.y < 0.0f, nz = d.z < 0.0f;
@@ -276,24 +277,23 @@ MRT_DEV bool traverse_wide(const SceneView &s, f3 o, f3 d, float tmin, float tma
         }
         if (STATS) { if (do_tri) tc->tris++; else tc->steps++; if ((int)lane == __ffsll((long long)__ballot(1)) - 1) tc->wave_iters++; }
         if (do_tri) {
-            const uint32_t k = (uint32_t)__ffs((int)t_mask) - 1u;
+            uint32_t pk = t_base + (uint32_t)__ffs((int)t_mask) - 1u;
             t_mask &= t_mask - 1u;
-            const float4 *__restrict__ pk = s.wpackets + WPK * (size_t)(t_base + k);
-            const float4 r0 = pk[0], r1 = pk[1], r2 = pk[2];
+            float4 r0, r1, r2;
+            MRT_LOAD_PACKET(s, pk, r0, r1, r2);
             float t, U, V, ad;
-            if (tri_test(r0, r1, r2, o, d, tmin, h.t, t, U, V, ad)) {
-                if (ANY || (RUNTIME_ANY && any_rt)) return true;
+            if (tri_test(r0, r1, r2, o, d, tmin, k.lim, t, U, V, ad)) {
                 const uint32_t gid = __float_as_uint(r0.w);
-                if (t < h.t || gid < h.gid) { h.t = t; h.U = U; h.V = V; h.ad = ad; h.gid = gid; }
+                if (vis.triangle(gid) && k.take(t, U, V, ad, pk, gid)) return;
             }
         } else {
-            const float4 *__restrict__ nd = s.wnodes + WNODE_STRIDE * (size_t)pending;
-            const float4 n0 = nd[0], n1 = nd[1], n2 = nd[2], n3 = nd[3], n4 = nd[4];
+            float4 n0, n1, n2, n3, n4;
+            MRT_LOAD_NODE(s, pending, n0, n1, n2, n3, n4);
             have_pending = false;
             uint32_t node_hits, tri_hits;
-            wide_node_test(n0, n1, n2, n3, n4, o, ix, iy, iz, nx, ny, nz, oct, tmin, h.t, node_hits, tri_hits);
-            if (STATS && tri_hits) tc->leaves++;
+            wide_node_test(n0, n1, n2, n3, n4, o, ix, iy, iz, nx, ny, nz, oct, tmin, k.lim, node_hits, tri_hits);
             if (STATS) {
+                if (tri_hits) tc->leaves++;
                 if ((node_hits | tri_hits) == 0u) tc->empty++;
                 // the node's own box (its quantisation grid, p .. p + 255 * 2^e, which encloses every child) against the ray's current limit: a visit that a
                 // distance kept with the stack entry would have skipped
@@ -301,14 +301,20 @@ MRT_DEV bool traverse_wide(const SceneView &s, f3 o, f3 d, float tmin, float tma
                 const float gx = __builtin_ldexpf(255.0f, (int)(int8_t)(ew & 0xFFu)), gy = __builtin_ldexpf(255.0f, (int)(int8_t)((ew >> 8) & 0xFFu)), gz = __builtin_ldexpf(255.0f, (int)(int8_t)((ew >> 16) & 0xFFu));
                 const float x0 = (n0.x - o.x) * ix, x1 = (n0.x + gx - o.x) * ix, y0 = (n0.y - o.y) * iy, y1 = (n0.y + gy - o.y) * iy, z0 = (n0.z - o.z) * iz, z1 = (n0.z + gz - o.z) * iz;
                 const float tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), tmin));
-                if (tn > h.t) tc->stale++;
+                if (tn > k.lim) tc->stale++;
             }
             if ((g_mask >> 8) != 0) { wstack_push(stack, sp, lane, g_base, g_mask); sp++; }     // siblings still to visit
             g_base = __float_as_uint(n1.x); g_mask = (node_hits << 8) | (__float_as_uint(n0.w) >> 24);
             t_base = __float_as_uint(n1.y); t_mask = tri_hits;
         }
     }
-    return h.gid != 0xFFFFFFFFu;
+}
+
+template <bool ANY, bool STATS = false, bool RUNTIME_ANY = false>
+MRT_DEV bool traverse_wide(const SceneView &s, f3 o, f3 d, float tmin, float tmax, TravHit &h, uint32_t *stack /* depth x WIDE_STACK_LEVEL_BYTES in LDS */, TravCounters *tc = nullptr, bool any_rt = false, uint32_t root = 0 /* as walk_wide's */) {
+    auto k = trav_sink<ANY, RUNTIME_ANY>(tmax, any_rt);
+    walk_wide<STATS>(s, SeesAll{}, o, d, tmin, k, stack, root, tc);
+    return trav_result(k, tmax, h);
 }
 
 // One ray per lane on the 8-wide layout, closest hit, the stream loop's iteration (node and triangle fetched in one round trip, scaled box test) without

@@ -11,6 +11,16 @@ import oracle as O
 G = os.path.join(ROOT, "tests", "golden")
 os.makedirs(G, exist_ok=True)
 
+# 0. `--traversal-stats [OUT.npz]` (needs the GPU, writes nothing else): the counters of tests/test_traversal_stats.py as the loaded library reports them.  The committed
+#    file is the record of the library BEFORE the lane walks were shared: run with MRT_LIB_PATH pointing at that commit's build.
+if "--traversal-stats" in sys.argv:
+    import test_traversal_stats as TS
+    out = ([a for a in sys.argv[1:] if a.endswith(".npz")] or [TS.GOLDEN])[0]
+    rows = TS.stats_rows(m, m.Context(0))
+    np.savez_compressed(out, **{k: v for k, v in rows.items() if not k.endswith("_primitive")})
+    print("golden written:", out, "from", m.LIB_PATH)
+    sys.exit(0)
+
 # 1. Halton table slice: i in a spread of indices, d in 0..21
 ii = np.array([0, 1, 2, 3, 5, 10, 1000, 123456, 1048575, 1048576 + 63], np.int32)
 tab = np.array([[O.halton(int(i), d) for d in range(22)] for i in ii], np.float32)
