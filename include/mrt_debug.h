@@ -69,6 +69,14 @@ int mrt_debug_host_sah(const float *lo4, const float *hi4, uint32_t n, uint32_t 
  * TLAS's leaf-child order; wide_pos[n]: per entry of wide_order, its position in the binary median order; counts68 = {rope nodes, rope depths, 8-wide nodes, 8-wide
  * levels, rope nodes per depth [32], 8-wide nodes per level [32]}.  What mrt_scene_rebuild_tlas_device rests on — the links depend on n alone — is checked with it. */
 int mrt_debug_tlas_host_build(const float *lo4, const float *hi4, uint32_t n, uint32_t *rope_order, uint32_t *rope_links, uint32_t *wide_order, uint32_t *wide_pos, uint32_t *counts68);
+/* The one encoder of the 8-wide node (csrc/wide_encode.h: build, both refits and the host TLAS build call it) on eight caller boxes (8 x float4 lo, 8 x float4 hi), as a
+ * refit calls it.  No device needed.  occupied_mask (1 .. 255): the slots that have a child; imask, a subset of it: the bits word 0 carries.  The node box is the union of
+ * the occupied children.  out_words20: the 80-byte node, word 1 (child_base, tri_base, meta) left zero.                                                              */
+int mrt_debug_wide_encode(const float *child_lo4, const float *child_hi4, uint32_t occupied_mask, uint32_t imask, uint32_t *out_words20);
+/* The instance arithmetic of a two-level scene (csrc/instance_math.h: the host's update_tlas and the device's instance moves call it) on one column-major 4x4 and one
+ * object-space box.  No device needed.  rows12: the world->object rows [A^-1 | -A^-1 t]; world_box6: the padded world box {lo.xyz, hi.xyz}.  MRT_ERR_INVALID_ARGUMENT
+ * for a matrix that is not taken (a determinant of zero, an infinite one); nothing is written then.                                                              */
+int mrt_debug_instance_box(const float *xf16, const float *obj_lo3, const float *obj_hi3, float *rows12, float *world_box6);
 /* The size check mrt_scene_commit applies (host only, no device needed): MRT_OK, or MRT_ERR_UNSUPPORTED when a scene of
  * `triangles` triangles whose BVH keeps `nodes` nodes (0 = unknown) cannot be addressed by the traversal layouts.      */
 int mrt_debug_layout_limits(uint64_t triangles, uint64_t nodes);

@@ -291,6 +291,8 @@ SIGNATURES = {
     "mrt_debug_segment_sizing": (C.c_int, [C.c_uint32, C.c_int32, C.POINTER(C.c_uint64)]),
     "mrt_debug_host_sah": (C.c_int, [_P, _P, _U32, _P, _P, _P, _P]),
     "mrt_debug_tlas_host_build": (C.c_int, [_P, _P, _U32, _P, _P, _P, _P, _P]),
+    "mrt_debug_wide_encode": (C.c_int, [_P, _P, _U32, _U32, _P]),
+    "mrt_debug_instance_box": (C.c_int, [_P, _P, _P, _P, _P]),
     "mrt_debug_validate": (C.c_int, [_P]),
     "mrt_debug_validate_patched": (C.c_int, [_P, _U32, _U32, _U32]),
 }

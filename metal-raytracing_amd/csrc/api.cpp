@@ -1577,6 +1577,21 @@ int mrt_debug_tlas_host_build(const float *lo4, const float *hi4, uint32_t n, ui
     return mrt::tlas_host_build(lo4, hi4, n, rope_order, rope_links, wide_order, wide_pos, counts68);
     MRT_CATCH
 }
+// the shared 8-wide encoder and the shared instance arithmetic on caller values (no device needed): what pins them without a GPU (tests/test_wide_encode_cpu.py)
+int mrt_debug_wide_encode(const float *child_lo4, const float *child_hi4, uint32_t occupied_mask, uint32_t imask, uint32_t *out_words20) {
+    MRT_TRY
+    REQUIRE(child_lo4 && child_hi4 && out_words20 && occupied_mask >= 1 && occupied_mask <= 255 && (imask & ~occupied_mask) == 0, "mrt_debug_wide_encode: bad argument");
+    mrt::wide_encode_host(child_lo4, child_hi4, occupied_mask, imask, out_words20);
+    return MRT_OK;
+    MRT_CATCH
+}
+int mrt_debug_instance_box(const float *xf16, const float *obj_lo3, const float *obj_hi3, float *rows12, float *world_box6) {
+    MRT_TRY
+    REQUIRE(xf16 && obj_lo3 && obj_hi3 && rows12 && world_box6, "mrt_debug_instance_box: bad argument");
+    if (!mrt::instance_box_host(xf16, obj_lo3, obj_hi3, rows12, world_box6)) { mrt::set_error("mrt_debug_instance_box: the matrix is not invertible"); return MRT_ERR_INVALID_ARGUMENT; }
+    return MRT_OK;
+    MRT_CATCH
+}
 int mrt_debug_layout_limits(uint64_t triangles, uint64_t nodes) {
     MRT_TRY
     return mrt::layout_limits(triangles, nodes);

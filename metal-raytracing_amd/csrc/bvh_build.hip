@@ -17,6 +17,7 @@
 //   emit      preorder node numbering, 8-octant escape ("rope") links, leaf-contiguous triangle packets
 // The host driver (FlatBuild, build_flat) is at the end of the file.  The refit of the finished layouts for deformed geometry is bvh_refit.hip's; what both use is in build_common.h.
 #include "build_common.h"
+#include "wide_encode.h"
 #include <chrono>
 #include <thread>
 #include <atomic>
@@ -723,50 +724,20 @@ __global__ void k_wide_level(TreeArrays t, WideDP dp, const uint32_t *__restrict
     if (!active) return;
     if ((uint64_t)next_base + base_i + tot_i > (uint64_t)max_w) { lv[WIDE_LV_ERROR] = 1u; return; }      // (wave-uniform) the node array would overflow: the host reports it
     const uint32_t my_i = base_i + xi - ninner, my_t = base_t + xt - ntris;
-    // slot assignment: preferred slot = side of the node centre per axis; greedy nearest free slot (Hamming)
-    int slot_of[8]; bool used[8] = {false, false, false, false, false, false, false, false};
-    const float cx = nlo.x + nhi.x, cy = nlo.y + nhi.y, cz = nlo.z + nhi.z;      // 2 x centre
-    for (int k = 0; k < nch; k++) {
-        uint32_t c = ch[k];
-        float4 lo = t.lo[c], hi = t.hi[c];
-        int pref = ((lo.x + hi.x) > cx ? 1 : 0) | ((lo.y + hi.y) > cy ? 2 : 0) | ((lo.z + hi.z) > cz ? 4 : 0);
-        int bs = -1, bd = 99;
-        for (int sl = 0; sl < 8; sl++) if (!used[sl]) { int dd = __popc((unsigned)(sl ^ pref)); if (dd < bd) { bd = dd; bs = sl; } }
-        used[bs] = true; slot_of[k] = bs;
-    }
-    int child_in_slot[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-    for (int k = 0; k < nch; k++) child_in_slot[slot_of[k]] = k;
-    // quantisation grid: p = lo, step 2^e >= extent / 255 per axis
-    float ext[3] = {nhi.x - nlo.x, nhi.y - nlo.y, nhi.z - nlo.z};
-    uint32_t eb[3]; float inv_step[3], step[3];
-    for (int a = 0; a < 3; a++) {
-        float sdiv = ext[a] / 255.0f;
-        uint32_t bits = __float_as_uint(sdiv);
-        uint32_t e = (bits >> 23) + ((bits & 0x7FFFFFu) ? 1u : 0u);
-        if (e < 1u) e = 1u; if (e > 254u) e = 254u;
-        eb[a] = e;
-        step[a] = __uint_as_float(e << 23);
-        inv_step[a] = __uint_as_float((254u - e) << 23);        // 2^-(e-127)
-    }
-    const float pl[3] = {nlo.x, nlo.y, nlo.z};
+    // slot assignment, quantisation grid and planes: the encoder of wide_encode.h, shared with the refits and the host TLAS build
+    const float pl[3] = {nlo.x, nlo.y, nlo.z}, ph[3] = {nhi.x, nhi.y, nhi.z};
+    const auto box_of = [&](uint32_t c, float lo[3], float hi[3]) { const float4 a = t.lo[c], b = t.hi[c]; lo[0] = a.x; lo[1] = a.y; lo[2] = a.z; hi[0] = b.x; hi[1] = b.y; hi[2] = b.z; };
+    int child_in_slot[8];
+    wide_assign_slots(pl, ph, nch, [&](int k, float lo[3], float hi[3]) { box_of(ch[k], lo, hi); }, child_in_slot);
+    const WideGrid g = wide_grid(pl, ph);
     uint32_t q[6][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}};     // qlo x,y,z then qhi x,y,z; 2 dwords (8 bytes) each
     uint32_t meta[2] = {0, 0}, imask = 0, rank_i = 0, off_t = 0;
     for (int sl = 0; sl < 8; sl++) {
         int k = child_in_slot[sl];
-        uint32_t ql[3] = {255, 255, 255}, qh[3] = {0, 0, 0};
+        float cl[3] = {0, 0, 0}, chh[3] = {0, 0, 0};
         if (k >= 0) {
             uint32_t c = ch[k];
-            float4 lo = t.lo[c], hi = t.hi[c];
-            const float cl[3] = {lo.x, lo.y, lo.z}, chh[3] = {hi.x, hi.y, hi.z};
-            for (int a = 0; a < 3; a++) {
-                float fl = floorf((cl[a] - pl[a]) * inv_step[a]);
-                float fh = ceilf((chh[a] - pl[a]) * inv_step[a]);
-                fl = fminf(fmaxf(fl, 0.0f), 255.0f); fh = fminf(fmaxf(fh, 0.0f), 255.0f);
-                // make sure the decoded planes still enclose the child after rounding of (c - p)
-                if (pl[a] + fl * step[a] > cl[a] && fl > 0.0f) fl -= 1.0f;
-                if (pl[a] + fh * step[a] < chh[a] && fh < 255.0f) fh += 1.0f;
-                ql[a] = (uint32_t)fl; qh[a] = (uint32_t)fh;
-            }
+            box_of(c, cl, chh);
             if (isleaf[k]) {
                 uint32_t cnt = t.ntri[c];
                 uint32_t m = (cnt << 5) | off_t;
@@ -781,15 +752,11 @@ __global__ void k_wide_level(TreeArrays t, WideDP dp, const uint32_t *__restrict
                 rank_i++;
             }
         }
-        for (int a = 0; a < 3; a++) { q[a][sl >> 2] |= ql[a] << (8 * (sl & 3)); q[3 + a][sl >> 2] |= qh[a] << (8 * (sl & 3)); }
+        wide_slot_planes(g, pl, sl, k >= 0, cl, chh, q);
     }
     const size_t w = WNODE_STRIDE * (size_t)(base_in + i);
-    // exponents are stored unbiased (int8, e - 127): the traversal scales 1/direction with v_ldexp_f32
-    wnodes[w + 0] = make_float4(nlo.x, nlo.y, nlo.z, __uint_as_float(((eb[0] - 127u) & 0xFFu) | (((eb[1] - 127u) & 0xFFu) << 8) | (((eb[2] - 127u) & 0xFFu) << 16) | (imask << 24)));
+    wide_write_node(wnodes + w, pl, g, imask, q);
     wnodes[w + 1] = make_float4(__uint_as_float(next_base + my_i), __uint_as_float(my_t), __uint_as_float(meta[0]), __uint_as_float(meta[1]));
-    wnodes[w + 2] = make_float4(__uint_as_float(q[0][0]), __uint_as_float(q[0][1]), __uint_as_float(q[1][0]), __uint_as_float(q[1][1]));
-    wnodes[w + 3] = make_float4(__uint_as_float(q[2][0]), __uint_as_float(q[2][1]), __uint_as_float(q[3][0]), __uint_as_float(q[3][1]));
-    wnodes[w + 4] = make_float4(__uint_as_float(q[4][0]), __uint_as_float(q[4][1]), __uint_as_float(q[5][0]), __uint_as_float(q[5][1]));
 }
 
 }  // namespace

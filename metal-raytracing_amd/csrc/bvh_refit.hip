@@ -7,6 +7,7 @@
 //     mrt_scene_update_blas_device / mrt_scene_refit_blas_device (device_refit_blas)
 // The device entries' update calls share one vertex ingest (enqueue_vertex_ingest) and, with the instance moves of tlas_refit.hip, one gate (UpdateGate, retire_gate).
 #include "build_common.h"
+#include "wide_encode.h"
 
 namespace mrt {
 namespace {
@@ -15,7 +16,8 @@ namespace {
 // The reference rebuilds nothing per frame (Renderer.swift:184-214 runs once); Metal's refit of a primitive acceleration structure is what this stands for.
 // The tree keeps its shape: every packet takes its triangle's new vertices (k_flatten's records, by the id the packet carries), then the levels are walked bottom-up —
 // one thread per node: the boxes of its leaf children from their triangles' padded boxes (k_flatten's, the build's own leaves; a pre-split triangle's references all get
-// the whole triangle's box), those of its internal children from the level below, the node's grid and the children's planes by k_wide_level's rules.
+// the whole triangle's box), those of its internal children from the level below, the node's grid and the children's planes by the encoder k_wide_level
+// built them with (wide_encode.h wide_encode_node).
 __global__ void k_refit_wide_packets(const float4 *__restrict__ tri_world, float4 *__restrict__ wpackets, uint32_t n) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
@@ -90,31 +92,7 @@ __global__ void k_refit_wide_level(float4 *__restrict__ wnodes, const float4 *__
         if (threadIdx.x == 0 && s_g[1] > 0.0) { atomicAdd(&growth[0], s_g[0]); atomicAdd(&growth[1], s_g[1]); }
     }
     if (!any) { nbox[2 * (size_t)(first + i)] = make_float4(n0.x, n0.y, n0.z, 0.0f); nbox[2 * (size_t)(first + i) + 1] = make_float4(n0.x, n0.y, n0.z, 0.0f); return; }      // (a node without children: nothing to move)
-    // the node's grid: p = lo, step 2^e >= extent / 255 per axis; a child's planes rounded outwards and checked against their decoded positions (as k_wide_level)
-    uint32_t eb[3]; float inv_step[3], step[3];
-    for (int a = 0; a < 3; a++) {
-        const float sdiv = (nh[a] - nl[a]) / 255.0f;
-        const uint32_t bits = __float_as_uint(sdiv);
-        uint32_t e = (bits >> 23) + ((bits & 0x7FFFFFu) ? 1u : 0u);
-        if (e < 1u) e = 1u; if (e > 254u) e = 254u;
-        eb[a] = e; step[a] = __uint_as_float(e << 23); inv_step[a] = __uint_as_float((254u - e) << 23);
-    }
-    uint32_t q[6][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}};
-    for (int sl = 0; sl < 8; sl++) {
-        uint32_t ql[3] = {255, 255, 255}, qh[3] = {0, 0, 0};
-        if (occ[sl]) for (int a = 0; a < 3; a++) {
-            float fl = floorf((clo[sl][a] - nl[a]) * inv_step[a]), fh = ceilf((chi[sl][a] - nl[a]) * inv_step[a]);
-            fl = fminf(fmaxf(fl, 0.0f), 255.0f); fh = fminf(fmaxf(fh, 0.0f), 255.0f);
-            if (nl[a] + fl * step[a] > clo[sl][a] && fl > 0.0f) fl -= 1.0f;
-            if (nl[a] + fh * step[a] < chi[sl][a] && fh < 255.0f) fh += 1.0f;
-            ql[a] = (uint32_t)fl; qh[a] = (uint32_t)fh;
-        }
-        for (int a = 0; a < 3; a++) { q[a][sl >> 2] |= ql[a] << (8 * (sl & 3)); q[3 + a][sl >> 2] |= qh[a] << (8 * (sl & 3)); }
-    }
-    wnodes[w + 0] = make_float4(nl[0], nl[1], nl[2], __uint_as_float(((eb[0] - 127u) & 0xFFu) | (((eb[1] - 127u) & 0xFFu) << 8) | (((eb[2] - 127u) & 0xFFu) << 16) | (imask << 24)));
-    wnodes[w + 2] = make_float4(__uint_as_float(q[0][0]), __uint_as_float(q[0][1]), __uint_as_float(q[1][0]), __uint_as_float(q[1][1]));
-    wnodes[w + 3] = make_float4(__uint_as_float(q[2][0]), __uint_as_float(q[2][1]), __uint_as_float(q[3][0]), __uint_as_float(q[3][1]));
-    wnodes[w + 4] = make_float4(__uint_as_float(q[4][0]), __uint_as_float(q[4][1]), __uint_as_float(q[5][0]), __uint_as_float(q[5][1]));
+    wide_encode_node(wnodes + w, nl, nh, clo, chi, occ, imask);        // the node's grid and the children's planes: k_wide_level's encoder
     nbox[2 * (size_t)(first + i)] = make_float4(nl[0], nl[1], nl[2], 0.0f); nbox[2 * (size_t)(first + i) + 1] = make_float4(nh[0], nh[1], nh[2], 0.0f);
 }
 

@@ -419,6 +419,8 @@ constexpr uint32_t TLAS_RESORT_MAX = 65536;           // instances mrt_scene_reb
 int tlas_rebuild_supported(const DeviceScene &sc, const char *who);      // MRT_OK, or MRT_ERR_UNSUPPORTED + message: more than TLAS_RESORT_MAX instances in the TLAS
 int device_rebuild_tlas(DeviceScene &sc, hipStream_t stream);      // needs sc.inst_ws (instances_device_prepare); ends with device_refit_instances
 int tlas_host_build(const float *lo4, const float *hi4, uint32_t n, uint32_t *rope_order, uint32_t *rope_links, uint32_t *wide_order, uint32_t *wide_pos, uint32_t *counts);      // two_level.hip: mrt_debug_tlas_host_build
+void wide_encode_host(const float *child_lo4, const float *child_hi4, uint32_t occupied_mask, uint32_t imask, uint32_t *out_words20);      // two_level.hip: mrt_debug_wide_encode (wide_encode.h on the host)
+bool instance_box_host(const float *xf16, const float *obj_lo3, const float *obj_hi3, float *rows12, float *world_box6);      // two_level.hip: mrt_debug_instance_box (instance_math.h on the host)
 void host_transform_is_newer(DeviceScene &sc, size_t mesh);      // mrt_scene_set_instance_transform after a move on the device: the next sync leaves HostMesh::xf alone
 void drop_instance_workspace(DeviceScene &sc);      // (update_tlas: the TLAS the workspace was made for is gone; the rejected count is kept)
 // bvh_refit.hip: meshes of two-level scenes deformed from device buffers, ordered on the caller's stream

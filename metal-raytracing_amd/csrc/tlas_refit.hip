@@ -1,13 +1,15 @@
 // tlas_refit.hip — instances of a two-level scene moved from device buffers, ordered on the caller's stream, for gfx950.
 //
 //   mrt_scene_set_instance_transforms_device   k_inst_check + k_inst_write: new object->world matrices from device memory; per instance its columns (inst_cols), its
-//                                              world->object rows (InstanceDev::w2o) and its padded world box (inst_box) rewritten in place — the device restatement of
-//                                              invert_affine and instance_box of two_level.hip, in double, in their operation order: the host's bits.
+//                                              world->object rows (InstanceDev::w2o) and its padded world box (inst_box) rewritten in place — by cofactors_of, rows_of
+//                                              and instance_box of instance_math.h, the functions update_tlas (two_level.hip) calls on the host: the host's bits.
 //   mrt_scene_refit_instances_device           k_tlas_rope_level per depth, k_tlas_wide_level per level, bottom-up: the boxes of both TLAS forms follow the instances'
 //                                              world boxes.  The topology is the last commit's (update_tlas); a commit builds the tree again.
 //   mrt_scene_refit_blas_device (bvh_refit.hip)  k_blas_instance_boxes between its BLAS refits and the TLAS refit above: the instances of a refitted BLAS take its new root box.
 // The launch boundary is the only grid-wide ordering used here: one launch per depth / level, each over at most a few thousand nodes.
 #include "scene_device.h"
+#include "instance_math.h"
+#include "wide_encode.h"
 #include <algorithm>
 
 namespace mrt {
@@ -15,87 +17,7 @@ namespace {
 
 inline uint32_t blocks_of(size_t n, size_t per) { return (uint32_t)((n + per - 1) / per); }
 
-// std::min / std::max as two_level.hip's host code evaluates them (the second argument only where it compares strictly beyond the first)
-template <class T> __device__ __forceinline__ T h_min(T a, T b) { return b < a ? b : a; }
-template <class T> __device__ __forceinline__ T h_max(T a, T b) { return a < b ? b : a; }
-
-struct DBox { float lo[3], hi[3]; };
-
 __device__ __forceinline__ uint32_t not_finite(uint32_t bits) { return ((bits & 0x7F800000u) + 0x00800000u) >> 31; }      // exponent all ones
-
-// invert_affine (two_level.hip): the determinant first — what decides whether the matrix is taken at all —, then the rows
-struct Cofactors { double c[3][3], det; };
-__device__ __forceinline__ Cofactors cofactors_of(const float *xf) {
-    const double a00 = xf[0], a10 = xf[1], a20 = xf[2], a01 = xf[4], a11 = xf[5], a21 = xf[6], a02 = xf[8], a12 = xf[9], a22 = xf[10];
-    Cofactors k;
-    k.c[0][0] = a11 * a22 - a12 * a21; k.c[0][1] = a02 * a21 - a01 * a22; k.c[0][2] = a01 * a12 - a02 * a11;
-    k.c[1][0] = a12 * a20 - a10 * a22; k.c[1][1] = a00 * a22 - a02 * a20; k.c[1][2] = a02 * a10 - a00 * a12;
-    k.c[2][0] = a10 * a21 - a11 * a20; k.c[2][1] = a01 * a20 - a00 * a21; k.c[2][2] = a00 * a11 - a01 * a10;
-    k.det = a00 * k.c[0][0] + a01 * k.c[1][0] + a02 * k.c[2][0];
-    return k;
-}
-__device__ __forceinline__ bool invertible(double det) { return fabs(det) > 0.0 && isfinite(det); }
-__device__ __forceinline__ void rows_of(const float *xf, const Cofactors &k, float rows[3][4]) {
-    const double tx = xf[12], ty = xf[13], tz = xf[14];
-    for (int r = 0; r < 3; r++) {
-        const double i0 = k.c[r][0] / k.det, i1 = k.c[r][1] / k.det, i2 = k.c[r][2] / k.det;
-        rows[r][0] = (float)i0; rows[r][1] = (float)i1; rows[r][2] = (float)i2;
-        rows[r][3] = (float)(-(i0 * tx + i1 * ty + i2 * tz));
-    }
-}
-
-// The corner loop and the float padding at the end of instance_box: the box [lo, hi] through the object->world matrix and, with `mi`, through the exact inverse of the float32 rows too.
-__device__ DBox corners_box(const float *xf, const double lo[3], const double hi[3], const double (*mi)[4]) {
-    DBox b;
-    for (int k = 0; k < 3; k++) { b.lo[k] = 3.0e38f; b.hi[k] = -3.0e38f; }
-    for (int c = 0; c < 8; c++) {
-        const double p[3] = {(c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2]};
-        for (int k = 0; k < 3; k++) {
-            const double w = (double)xf[k] * p[0] + (double)xf[4 + k] * p[1] + (double)xf[8 + k] * p[2] + (double)xf[12 + k];
-            b.lo[k] = h_min(b.lo[k], (float)w); b.hi[k] = h_max(b.hi[k], (float)w);
-            if (mi) {
-                const double v = mi[k][0] * p[0] + mi[k][1] * p[1] + mi[k][2] * p[2] + mi[k][3];
-                b.lo[k] = h_min(b.lo[k], nextafterf((float)v, -3.0e38f)); b.hi[k] = h_max(b.hi[k], nextafterf((float)v, 3.0e38f));
-            }
-        }
-    }
-    for (int k = 0; k < 3; k++) {
-        const float m = h_max(fabsf(b.lo[k]), fabsf(b.hi[k])), e = 4e-5f * m + 4e-6f;
-        b.lo[k] -= e; b.hi[k] += e;
-    }
-    return b;
-}
-
-// instance_box (two_level.hip) with the rows: the eight-round fixed point of the growth delta, then the corners through both maps
-__device__ DBox instance_box_dev(const float *xf, const float lo_in[3], const float hi_in[3], const float rows[3][4]) {
-    double lo[3] = {lo_in[0], lo_in[1], lo_in[2]}, hi[3] = {hi_in[0], hi_in[1], hi_in[2]};
-    const double g4 = 4.0 * 0x1p-24 / (1.0 - 4.0 * 0x1p-24);
-    DBox cur = corners_box(xf, lo, hi, nullptr);
-    for (int it = 0; it < 8; it++) {
-        double X[3];
-        for (int j = 0; j < 3; j++) X[j] = 1.1 * h_max(fabs((double)cur.lo[j]), fabs((double)cur.hi[j]));
-        double glo[3], ghi[3];
-        for (int k = 0; k < 3; k++) {
-            const double dk = 1.1 * g4 * (fabs((double)rows[k][0]) * X[0] + fabs((double)rows[k][1]) * X[1] + fabs((double)rows[k][2]) * X[2] + fabs((double)rows[k][3]));
-            lo[k] = (double)lo_in[k] - dk; hi[k] = (double)hi_in[k] + dk;
-            glo[k] = (double)nextafterf((float)lo[k], -3.0e38f); ghi[k] = (double)nextafterf((float)hi[k], 3.0e38f);
-        }
-        const DBox next = corners_box(xf, glo, ghi, nullptr);
-        bool grew = false;
-        for (int k = 0; k < 3; k++) grew = grew || next.lo[k] < cur.lo[k] || next.hi[k] > cur.hi[k];
-        cur = next;
-        if (!grew && it > 0) break;
-    }
-    double mi[3][4];
-    {
-        const double a[3][3] = {{rows[0][0], rows[0][1], rows[0][2]}, {rows[1][0], rows[1][1], rows[1][2]}, {rows[2][0], rows[2][1], rows[2][2]}};
-        const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) + a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
-        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++)
-            mi[r][c] = (a[(c + 1) % 3][(r + 1) % 3] * a[(c + 2) % 3][(r + 2) % 3] - a[(c + 1) % 3][(r + 2) % 3] * a[(c + 2) % 3][(r + 1) % 3]) / det;
-        for (int r = 0; r < 3; r++) mi[r][3] = -(mi[r][0] * rows[0][3] + mi[r][1] * rows[1][3] + mi[r][2] * rows[2][3]);
-    }
-    return corners_box(xf, lo, hi, mi);
-}
 
 // ------------------------------------------------------------------ matrices from device memory
 // What mrt_scene_set_instance_transform and update_tlas refuse on the host — a NaN or an infinity anywhere in the 16 floats, a matrix invert_affine does not take — is known here
@@ -126,7 +48,7 @@ __global__ void k_inst_write(const uint8_t *__restrict__ src, size_t stride, uin
     rows_of(xf, cofactors_of(xf), rows);
     const float4 blo = inst_box[4 * i], bhi = inst_box[4 * i + 1];          // the root box of its BLAS, object space: resident since the commit
     const float lo_in[3] = {blo.x, blo.y, blo.z}, hi_in[3] = {bhi.x, bhi.y, bhi.z};
-    const DBox b = instance_box_dev(xf, lo_in, hi_in, rows);
+    const Box b = instance_box(xf, lo_in, hi_in, rows);
     for (int c = 0; c < 4; c++) inst_cols[4 * i + c] = make_float4(xf[c * 4 + 0], xf[c * 4 + 1], xf[c * 4 + 2], 0.0f);
     for (int r = 0; r < 3; r++) inst[i].w2o[r] = make_float4(rows[r][0], rows[r][1], rows[r][2], rows[r][3]);
     inst_box[4 * i + 2] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.0f); inst_box[4 * i + 3] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.0f);
@@ -134,7 +56,7 @@ __global__ void k_inst_write(const uint8_t *__restrict__ src, size_t stride, uin
 
 // ------------------------------------------------------------------ a BLAS refitted on the stream (mrt_scene_refit_blas_device)
 // Its root box changed, so what update_tlas would compute on the host for each of its instances changes with it: the object box is the BLAS's new root box (the refit's
-// nbox[2 * root], as refit_blas reads it back), the padded world box is instance_box_dev of it under the instance's CURRENT columns and world->object rows — a pose set by
+// nbox[2 * root], as refit_blas reads it back), the padded world box is instance_box (instance_math.h) of it under the instance's CURRENT columns and world->object rows — a pose set by
 // k_inst_write is honoured.  An instance outside the TLAS of the last commit (no triangles, a singular matrix then) has the empty box update_tlas gave it, lo > hi, and keeps it.
 __global__ void k_blas_instance_boxes(const float4 *__restrict__ nbox, uint32_t root, const uint32_t *__restrict__ inst_list, uint32_t count, const float4 *__restrict__ inst_cols,
                                       const InstanceDev *__restrict__ inst, float4 *__restrict__ inst_box) {
@@ -147,7 +69,7 @@ __global__ void k_blas_instance_boxes(const float4 *__restrict__ nbox, uint32_t 
     for (int c = 0; c < 4; c++) { const float4 q = inst_cols[4 * i + c]; xf[c * 4 + 0] = q.x; xf[c * 4 + 1] = q.y; xf[c * 4 + 2] = q.z; xf[c * 4 + 3] = c == 3 ? 1.0f : 0.0f; }
     for (int r = 0; r < 3; r++) { const float4 q = inst[i].w2o[r]; rows[r][0] = q.x; rows[r][1] = q.y; rows[r][2] = q.z; rows[r][3] = q.w; }
     const float lo_in[3] = {blo.x, blo.y, blo.z}, hi_in[3] = {bhi.x, bhi.y, bhi.z};
-    const DBox b = instance_box_dev(xf, lo_in, hi_in, rows);
+    const Box b = instance_box(xf, lo_in, hi_in, rows);
     inst_box[4 * i] = make_float4(blo.x, blo.y, blo.z, 0.0f); inst_box[4 * i + 1] = make_float4(bhi.x, bhi.y, bhi.z, 0.0f);
     inst_box[4 * i + 2] = make_float4(b.lo[0], b.lo[1], b.lo[2], 0.0f); inst_box[4 * i + 3] = make_float4(b.hi[0], b.hi[1], b.hi[2], 0.0f);
 }
@@ -182,8 +104,10 @@ __global__ void k_tlas_rope_level(float4 *__restrict__ nodes, const uint32_t *__
 }
 
 // ------------------------------------------------------------------ the 8-wide TLAS (wnodes[0, tlas_wcap), wtlas_index): one launch per level, deepest first
-// One thread per node: the box of a leaf child is its instance's world box, that of an internal child the box the level below left in nbox; the node's origin, its power-of-two
-// grid and the children's planes by WideTlasBuilder's rules.  Slot assignment, imask, meta, child_base and tri_base stay.
+// One thread per node: the box of a leaf child is its instance's world box, that of an internal child the box the level below left in nbox; the node's origin,
+// its power-of-two grid and the children's planes by wide_encode_node, the encoder WideTlasBuilder built them with (wide_encode.h).  Slot assignment, imask, meta, child_base and tri_base stay.
+// (The slot loop is k_refit_wide_level's but for the box of a leaf child.  It stays written out in both: as one template over that box each kernel took more registers,
+// docs/HISTORY.md §20.)
 __global__ void k_tlas_wide_level(float4 *__restrict__ wnodes, const uint32_t *__restrict__ wtlas_index, const float4 *__restrict__ inst_box, float4 *__restrict__ nbox, uint32_t first, uint32_t count) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= count) return;
@@ -212,31 +136,7 @@ __global__ void k_tlas_wide_level(float4 *__restrict__ wnodes, const uint32_t *_
         any = any || occ[sl];
     }
     if (!any) { nbox[2 * node] = make_float4(n0.x, n0.y, n0.z, 0.0f); nbox[2 * node + 1] = make_float4(n0.x, n0.y, n0.z, 0.0f); return; }      // (a node without children: nothing to move)
-    uint32_t eb[3]; float inv_step[3], step[3];
-    for (int k = 0; k < 3; k++) {
-        const float sdiv = (nh[k] - nl[k]) / 255.0f;
-        const uint32_t bits = __float_as_uint(sdiv);
-        uint32_t e = (bits >> 23) + ((bits & 0x7FFFFFu) ? 1u : 0u);
-        if (e < 1u) e = 1u;
-        if (e > 254u) e = 254u;
-        eb[k] = e; step[k] = __uint_as_float(e << 23); inv_step[k] = __uint_as_float((254u - e) << 23);
-    }
-    uint32_t q[6][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}};
-    for (int sl = 0; sl < 8; sl++) {
-        uint32_t ql[3] = {255, 255, 255}, qh[3] = {0, 0, 0};
-        if (occ[sl]) for (int k = 0; k < 3; k++) {
-            float fl = floorf((clo[sl][k] - nl[k]) * inv_step[k]), fh = ceilf((chi[sl][k] - nl[k]) * inv_step[k]);
-            fl = fminf(fmaxf(fl, 0.0f), 255.0f); fh = fminf(fmaxf(fh, 0.0f), 255.0f);
-            if (nl[k] + fl * step[k] > clo[sl][k] && fl > 0.0f) fl -= 1.0f;
-            if (nl[k] + fh * step[k] < chi[sl][k] && fh < 255.0f) fh += 1.0f;
-            ql[k] = (uint32_t)fl; qh[k] = (uint32_t)fh;
-        }
-        for (int k = 0; k < 3; k++) { q[k][sl >> 2] |= ql[k] << (8 * (sl & 3)); q[3 + k][sl >> 2] |= qh[k] << (8 * (sl & 3)); }
-    }
-    wnodes[w + 0] = make_float4(nl[0], nl[1], nl[2], __uint_as_float(((eb[0] - 127u) & 0xFFu) | (((eb[1] - 127u) & 0xFFu) << 8) | (((eb[2] - 127u) & 0xFFu) << 16) | (imask << 24)));
-    wnodes[w + 2] = make_float4(__uint_as_float(q[0][0]), __uint_as_float(q[0][1]), __uint_as_float(q[1][0]), __uint_as_float(q[1][1]));
-    wnodes[w + 3] = make_float4(__uint_as_float(q[2][0]), __uint_as_float(q[2][1]), __uint_as_float(q[3][0]), __uint_as_float(q[3][1]));
-    wnodes[w + 4] = make_float4(__uint_as_float(q[4][0]), __uint_as_float(q[4][1]), __uint_as_float(q[5][0]), __uint_as_float(q[5][1]));
+    wide_encode_node(wnodes + w, nl, nh, clo, chi, occ, imask);
     nbox[2 * node] = make_float4(nl[0], nl[1], nl[2], 0.0f); nbox[2 * node + 1] = make_float4(nh[0], nh[1], nh[2], 0.0f);
 }
 

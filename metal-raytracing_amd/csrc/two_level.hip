@@ -18,6 +18,8 @@
 //          same node format, host-built, rewritten in place by update_tlas).  The stream traversal of traverse_wide.h walks both levels
 //          with one loop and one LDS stack; the rope layout stays for the query kernels and as the A/B path (wide_bounce = 0).
 #include "scene_device.h"
+#include "instance_math.h"
+#include "wide_encode.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -27,78 +29,25 @@
 namespace mrt {
 namespace {
 
-// inverse of the affine map p -> A p + t given as a column-major 4x4 (last row 0 0 0 1): rows of [A^-1 | -A^-1 t], evaluated in double with
-// this exact operation order (the CPU oracle restates it: the instance rows must agree bit for bit) and rounded to float once.
-bool invert_affine(const float *xf, float rows[3][4]) {
-    const double a00 = xf[0], a10 = xf[1], a20 = xf[2], a01 = xf[4], a11 = xf[5], a21 = xf[6], a02 = xf[8], a12 = xf[9], a22 = xf[10];
-    const double tx = xf[12], ty = xf[13], tz = xf[14];
-    const double c00 = a11 * a22 - a12 * a21, c01 = a02 * a21 - a01 * a22, c02 = a01 * a12 - a02 * a11;
-    const double c10 = a12 * a20 - a10 * a22, c11 = a00 * a22 - a02 * a20, c12 = a02 * a10 - a00 * a12;
-    const double c20 = a10 * a21 - a11 * a20, c21 = a01 * a20 - a00 * a21, c22 = a00 * a11 - a01 * a10;
-    const double det = a00 * c00 + a01 * c10 + a02 * c20;
-    if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return false;
-    const double i[3][3] = {{c00 / det, c01 / det, c02 / det}, {c10 / det, c11 / det, c12 / det}, {c20 / det, c21 / det, c22 / det}};
-    for (int r = 0; r < 3; r++) {
-        rows[r][0] = (float)i[r][0]; rows[r][1] = (float)i[r][1]; rows[r][2] = (float)i[r][2];
-        rows[r][3] = (float)(-(i[r][0] * tx + i[r][1] * ty + i[r][2] * tz));
-    }
-    return true;
-}
-
-struct Box { float lo[3], hi[3]; };
-
-// world box of an instance: the corners of its BLAS root box through the object->world matrix; padded like the leaf boxes of
-// bvh_build.hip (1e-5 |coord| + 1e-6) plus the rounding of the ray's trip into object space.  That rounding is bounded per object axis k by
-// delta_k = gamma_4 (sum_j |R_kj| max|X_j| + |w_k|) for the float32 w2o rows (R | w) and world points X in the box: the root box is grown by delta
-// before its corners are mapped (an instance translated 1e4 from the origin needs ~5e-3, far more than the 4e-5 relative pad gives).  The bound covers
-// world points inside the box; the drift of the object-space DIRECTION, which grows with t and with the distance of the ray origin, is not bounded here.
-// Its constants: X and delta taken 10 % larger than computed, at most eight rounds of the fixed point.
-Box instance_box(const float *xf, const float *lo_in, const float *hi_in, const float rows[3][4]) {
-    double lo[3] = {lo_in[0], lo_in[1], lo_in[2]}, hi[3] = {hi_in[0], hi_in[1], hi_in[2]};
-    if (rows) {          // X depends on the box delta grows: iterate (a contraction unless cond(R) gamma_4 nears 1: a few rounds, then 10 % to spare)
-        const double g4 = 4.0 * 0x1p-24 / (1.0 - 4.0 * 0x1p-24);
-        Box cur = instance_box(xf, lo_in, hi_in, nullptr);
-        for (int it = 0; it < 8; it++) {
-            double X[3];
-            for (int j = 0; j < 3; j++) X[j] = 1.1 * std::max(std::fabs((double)cur.lo[j]), std::fabs((double)cur.hi[j]));
-            float glo[3], ghi[3];
-            for (int k = 0; k < 3; k++) {
-                const double dk = 1.1 * g4 * (std::fabs((double)rows[k][0]) * X[0] + std::fabs((double)rows[k][1]) * X[1] + std::fabs((double)rows[k][2]) * X[2] + std::fabs((double)rows[k][3]));
-                lo[k] = (double)lo_in[k] - dk; hi[k] = (double)hi_in[k] + dk;
-                glo[k] = std::nextafter((float)lo[k], -3.0e38f); ghi[k] = std::nextafter((float)hi[k], 3.0e38f);
-            }
-            const Box next = instance_box(xf, glo, ghi, nullptr);
-            bool grew = false;
-            for (int k = 0; k < 3; k++) grew = grew || next.lo[k] < cur.lo[k] || next.hi[k] > cur.hi[k];
-            cur = next;
-            if (!grew && it > 0) break;
-        }
-    }
-    // (with the rows: the corners also through the exact inverse of the float32 rows, the map the traversal's object-space ray really inverts)
-    double mi[3][4] = {};
-    if (rows) {
-        const double a[3][3] = {{rows[0][0], rows[0][1], rows[0][2]}, {rows[1][0], rows[1][1], rows[1][2]}, {rows[2][0], rows[2][1], rows[2][2]}};
-        const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) + a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
-        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++)
-            mi[r][c] = (a[(c + 1) % 3][(r + 1) % 3] * a[(c + 2) % 3][(r + 2) % 3] - a[(c + 1) % 3][(r + 2) % 3] * a[(c + 2) % 3][(r + 1) % 3]) / det;
-        for (int r = 0; r < 3; r++) mi[r][3] = -(mi[r][0] * rows[0][3] + mi[r][1] * rows[1][3] + mi[r][2] * rows[2][3]);
-    }
+// The one step both host TLAS builders are made of (tlas_rebuild.hip rests on their agreeing): the union box of boxes[ids[first .. first + count)) and, when the range is
+// larger than a leaf, its split at count / 2 — the half of the smaller centres on the widest axis of the centres 0.5f * (lo + hi) (axis 0, then 1 or 2 if strictly wider)
+// goes in front, under the strict order (lo + hi on that axis, id).
+Box median_split(std::vector<uint32_t> &ids, uint32_t first, uint32_t count, const std::vector<Box> &boxes, uint32_t leaf) {
     Box b; for (int k = 0; k < 3; k++) { b.lo[k] = 3.0e38f; b.hi[k] = -3.0e38f; }
-    for (int c = 0; c < 8; c++) {
-        const double p[3] = {(c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2]};
+    float clo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, chi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    for (uint32_t i = first; i < first + count; i++) {
+        const Box &q = boxes[ids[i]];
         for (int k = 0; k < 3; k++) {
-            const double w = (double)xf[k] * p[0] + (double)xf[4 + k] * p[1] + (double)xf[8 + k] * p[2] + (double)xf[12 + k];
-            b.lo[k] = std::min(b.lo[k], (float)w); b.hi[k] = std::max(b.hi[k], (float)w);
-            if (rows) {
-                const double v = mi[k][0] * p[0] + mi[k][1] * p[1] + mi[k][2] * p[2] + mi[k][3];
-                b.lo[k] = std::min(b.lo[k], std::nextafter((float)v, -3.0e38f)); b.hi[k] = std::max(b.hi[k], std::nextafter((float)v, 3.0e38f));
-            }
+            b.lo[k] = std::min(b.lo[k], q.lo[k]); b.hi[k] = std::max(b.hi[k], q.hi[k]);
+            const float c = 0.5f * (q.lo[k] + q.hi[k]); clo[k] = std::min(clo[k], c); chi[k] = std::max(chi[k], c);
         }
     }
-    for (int k = 0; k < 3; k++) {
-        const float m = std::max(std::fabs(b.lo[k]), std::fabs(b.hi[k])), e = 4e-5f * m + 4e-6f;
-        b.lo[k] -= e; b.hi[k] += e;
-    }
+    if (count <= leaf) return b;
+    int ax = 0; if (chi[1] - clo[1] > chi[ax] - clo[ax]) ax = 1; if (chi[2] - clo[2] > chi[ax] - clo[ax]) ax = 2;
+    std::nth_element(ids.begin() + first, ids.begin() + first + count / 2, ids.begin() + first + count, [&](uint32_t x, uint32_t y) {
+        const float cx = boxes[x].lo[ax] + boxes[x].hi[ax], cy = boxes[y].lo[ax] + boxes[y].hi[ax];
+        return cx < cy || (cx == cy && x < y);
+    });
     return b;
 }
 
@@ -115,26 +64,13 @@ struct TlasBuilder {
     // builds the subtree over order[first, first + count) and returns its node index; `esc` = node to continue with afterwards
     uint32_t build(uint32_t first, uint32_t count, uint32_t esc, int d) {
         depth = std::max(depth, d);
-        Box b; for (int k = 0; k < 3; k++) { b.lo[k] = 3.0e38f; b.hi[k] = -3.0e38f; }
-        float clo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, chi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-        for (uint32_t i = first; i < first + count; i++) {
-            const Box &q = boxes[order[i]];
-            for (int k = 0; k < 3; k++) {
-                b.lo[k] = std::min(b.lo[k], q.lo[k]); b.hi[k] = std::max(b.hi[k], q.hi[k]);
-                const float c = 0.5f * (q.lo[k] + q.hi[k]); clo[k] = std::min(clo[k], c); chi[k] = std::max(chi[k], c);
-            }
-        }
+        const Box b = median_split(order, first, count, boxes, 2);
         const uint32_t me = (uint32_t)(nodes.size() / 4);
         nodes.resize(nodes.size() + 4); node_depth.push_back((uint32_t)d);
         uint32_t a, bb;
         if (count <= 2) { a = NODE_LEAF | first; bb = count; }
         else {
-            int ax = 0; if (chi[1] - clo[1] > chi[ax] - clo[ax]) ax = 1; if (chi[2] - clo[2] > chi[ax] - clo[ax]) ax = 2;
             const uint32_t half = count / 2;
-            std::nth_element(order.begin() + first, order.begin() + first + half, order.begin() + first + count, [&](uint32_t x, uint32_t y) {
-                const float cx = boxes[x].lo[ax] + boxes[x].hi[ax], cy = boxes[y].lo[ax] + boxes[y].hi[ax];
-                return cx < cy || (cx == cy && x < y);
-            });
             // preorder: the left subtree starts at me + 1; the right subtree's index is known once the left one is built
             const uint32_t left = me + 1;
             // the left subtree escapes to the right sibling, whose index = me + 1 + size(left subtree): build left with a placeholder, patch after
@@ -162,8 +98,8 @@ struct TlasBuilder {
 
 // 8-wide TLAS in the node format of scene_device.h: a median-split binary tree over the instance boxes (leaves = ONE instance), collapsed
 // greedily (largest surface area first) into nodes of up to eight children, BFS-numbered so that a node's internal children are contiguous;
-// child slots by octant of the child centre, boxes quantised outwards to 8 bits on the node's power-of-two grid — the host restatement of
-// k_wide_level.  A leaf child's "packet" tri_base + offset is an entry of `order` (instance ids).
+// child slots by octant of the child centre, boxes quantised outwards to 8 bits on the node's power-of-two grid — both by the encoder
+// k_wide_level uses (wide_encode.h).  A leaf child's "packet" tri_base + offset is an entry of `order` (instance ids).
 struct WideTlasBuilder {
     const std::vector<Box> &boxes;
     struct BNode { Box b; int left = -1, right = -1, inst = -1; uint32_t first = 0; };      // first: where its range of the median order begins (a leaf: its position there)
@@ -176,29 +112,14 @@ struct WideTlasBuilder {
     explicit WideTlasBuilder(const std::vector<Box> &b) : boxes(b) {}
     static float area(const Box &q) { const float x = q.hi[0] - q.lo[0], y = q.hi[1] - q.lo[1], z = q.hi[2] - q.lo[2]; return x * y + y * z + z * x; }
     int binary(std::vector<uint32_t> &ids, uint32_t first, uint32_t count) {
-        BNode n; for (int k = 0; k < 3; k++) { n.b.lo[k] = 3.0e38f; n.b.hi[k] = -3.0e38f; }
-        float clo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, chi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-        for (uint32_t i = first; i < first + count; i++) {
-            const Box &q = boxes[ids[i]];
-            for (int k = 0; k < 3; k++) {
-                n.b.lo[k] = std::min(n.b.lo[k], q.lo[k]); n.b.hi[k] = std::max(n.b.hi[k], q.hi[k]);
-                const float c = 0.5f * (q.lo[k] + q.hi[k]); clo[k] = std::min(clo[k], c); chi[k] = std::max(chi[k], c);
-            }
-        }
-        n.first = first;
+        BNode n; n.b = median_split(ids, first, count, boxes, 1); n.first = first;
         const int me = (int)bn.size(); bn.push_back(n);
         if (count == 1) { bn[me].inst = (int)ids[first]; return me; }
-        int ax = 0; if (chi[1] - clo[1] > chi[ax] - clo[ax]) ax = 1; if (chi[2] - clo[2] > chi[ax] - clo[ax]) ax = 2;
         const uint32_t half = count / 2;
-        std::nth_element(ids.begin() + first, ids.begin() + first + half, ids.begin() + first + count, [&](uint32_t x, uint32_t y) {
-            const float cx = boxes[x].lo[ax] + boxes[x].hi[ax], cy = boxes[y].lo[ax] + boxes[y].hi[ax];
-            return cx < cy || (cx == cy && x < y);
-        });
         const int l = binary(ids, first, half), r = binary(ids, first + half, count - half);
         bn[me].left = l; bn[me].right = r;
         return me;
     }
-    static float4 f4u(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { float f[4]; uint32_t u[4] = {a, b, c, d}; memcpy(f, u, 16); return make_float4(f[0], f[1], f[2], f[3]); }
     void build(std::vector<uint32_t> ids) {
         if (ids.empty()) return;
         const int root = binary(ids, 0, (uint32_t)ids.size());
@@ -223,50 +144,24 @@ struct WideTlasBuilder {
                         ch[best] = bn[(size_t)c].left; ch[nch++] = bn[(size_t)c].right;
                     }
                 }
-                int child_in_slot[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-                const float cx = f.b.lo[0] + f.b.hi[0], cy = f.b.lo[1] + f.b.hi[1], cz = f.b.lo[2] + f.b.hi[2];
-                for (int k = 0; k < nch; k++) {
-                    const Box &q = bn[(size_t)ch[k]].b;
-                    const int pref = ((q.lo[0] + q.hi[0]) > cx ? 1 : 0) | ((q.lo[1] + q.hi[1]) > cy ? 2 : 0) | ((q.lo[2] + q.hi[2]) > cz ? 4 : 0);
-                    int bs = -1, bd = 99;
-                    for (int sl = 0; sl < 8; sl++) if (child_in_slot[sl] < 0) { const int dd = __builtin_popcount((unsigned)(sl ^ pref)); if (dd < bd) { bd = dd; bs = sl; } }
-                    child_in_slot[bs] = k;
-                }
-                uint32_t eb[3]; float step[3], inv_step[3];
-                for (int a = 0; a < 3; a++) {
-                    const float sdiv = (f.b.hi[a] - f.b.lo[a]) / 255.0f;
-                    uint32_t bits; memcpy(&bits, &sdiv, 4);
-                    uint32_t e = (bits >> 23) + ((bits & 0x7FFFFFu) ? 1u : 0u);
-                    e = std::min(254u, std::max(1u, e));
-                    eb[a] = e;
-                    const uint32_t sb = e << 23, ib = (254u - e) << 23; memcpy(&step[a], &sb, 4); memcpy(&inv_step[a], &ib, 4);
-                }
+                int child_in_slot[8];
+                wide_assign_slots(f.b.lo, f.b.hi, nch, [&](int k, float lo[3], float hi[3]) { const Box &q = bn[(size_t)ch[k]].b; for (int a = 0; a < 3; a++) { lo[a] = q.lo[a]; hi[a] = q.hi[a]; } }, child_in_slot);
+                const WideGrid g = wide_grid(f.b.lo, f.b.hi);
                 uint32_t q[6][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}}, meta[2] = {0, 0}, imask = 0, off_t = 0;
                 const uint32_t my_i = next_base + (uint32_t)next.size(), my_t = (uint32_t)order.size();
                 for (int sl = 0; sl < 8; sl++) {
                     const int k = child_in_slot[sl];
-                    uint32_t ql[3] = {255, 255, 255}, qh[3] = {0, 0, 0};
+                    const Box &cb = bn[(size_t)ch[k >= 0 ? k : 0]].b;          // (read only for a slot that has a child)
+                    wide_slot_planes(g, f.b.lo, sl, k >= 0, cb.lo, cb.hi, q);
                     if (k >= 0) {
                         const BNode &c = bn[(size_t)ch[k]];
-                        for (int a = 0; a < 3; a++) {
-                            float fl = std::floor((c.b.lo[a] - f.b.lo[a]) * inv_step[a]), fh = std::ceil((c.b.hi[a] - f.b.lo[a]) * inv_step[a]);
-                            fl = std::min(std::max(fl, 0.0f), 255.0f); fh = std::min(std::max(fh, 0.0f), 255.0f);
-                            if (f.b.lo[a] + fl * step[a] > c.b.lo[a] && fl > 0.0f) fl -= 1.0f;
-                            if (f.b.lo[a] + fh * step[a] < c.b.hi[a] && fh < 255.0f) fh += 1.0f;
-                            ql[a] = (uint32_t)fl; qh[a] = (uint32_t)fh;
-                        }
                         if (c.inst >= 0) { meta[sl >> 2] |= ((1u << 5) | off_t) << (8 * (sl & 3)); order.push_back((uint32_t)c.inst); pos.push_back(c.first); off_t++; }
                         else { imask |= 1u << sl; next.push_back(ch[k]); }
                     }
-                    for (int a = 0; a < 3; a++) { q[a][sl >> 2] |= ql[a] << (8 * (sl & 3)); q[3 + a][sl >> 2] |= qh[a] << (8 * (sl & 3)); }
                 }
                 const size_t w = 5 * (size_t)(base + i);
-                float ew; const uint32_t ewb = ((eb[0] - 127u) & 0xFFu) | (((eb[1] - 127u) & 0xFFu) << 8) | (((eb[2] - 127u) & 0xFFu) << 16) | (imask << 24); memcpy(&ew, &ewb, 4);
-                nodes[w + 0] = make_float4(f.b.lo[0], f.b.lo[1], f.b.lo[2], ew);
-                nodes[w + 1] = f4u(my_i, my_t, meta[0], meta[1]);
-                nodes[w + 2] = f4u(q[0][0], q[0][1], q[1][0], q[1][1]);
-                nodes[w + 3] = f4u(q[2][0], q[2][1], q[3][0], q[3][1]);
-                nodes[w + 4] = f4u(q[4][0], q[4][1], q[5][0], q[5][1]);
+                wide_write_node(&nodes[w], f.b.lo, g, imask, q);
+                nodes[w + 1] = wide_f4u(my_i, my_t, meta[0], meta[1]);
             }
             base = next_base;
             level.swap(next);
@@ -422,7 +317,9 @@ int update_tlas(const std::vector<HostMesh> &meshes, hipStream_t stream, DeviceS
     std::vector<Box> boxes(I);
     std::vector<uint32_t> live;
     std::vector<float4> h_cols(std::max<size_t>(I * 4, 4));
-    std::vector<float4> h_box(4 * std::max<size_t>(I, 1), make_float4(0, 0, 0, 0));      // + the instance's world box (padded, as the TLAS has it): what the flat TLAS pass queues pairs on      // per instance, the box of its BLAS in OBJECT space (the flat TLAS pass tests the transformed ray against it); lo > hi: no ray enters
+    // per instance, the box of its BLAS in OBJECT space (the flat TLAS pass tests the transformed ray against it; lo > hi: no ray enters) and the instance's world box
+    // (padded, as the TLAS has it): what the flat TLAS pass queues pairs on
+    std::vector<float4> h_box(4 * std::max<size_t>(I, 1), make_float4(0, 0, 0, 0));
     for (size_t i = 0; i < I; i++) {
         InstanceDev &d = out.h_inst[i];
         const float *xf = meshes[i].xf;
@@ -512,11 +409,39 @@ int tlas_host_build(const float *lo4, const float *hi4, uint32_t n, uint32_t *ro
     return MRT_OK;
 }
 
+// mrt_debug_wide_encode: the encoder of wide_encode.h on eight caller boxes, as a refit calls it — the node box is the union of the occupied children; word 1 is left zero.
+void wide_encode_host(const float *child_lo4, const float *child_hi4, uint32_t occupied_mask, uint32_t imask, uint32_t *out_words20) {
+    float clo[8][3], chi[8][3], nl[3] = {3.0e38f, 3.0e38f, 3.0e38f}, nh[3] = {-3.0e38f, -3.0e38f, -3.0e38f}; bool occ[8];
+    for (int sl = 0; sl < 8; sl++) {
+        occ[sl] = ((occupied_mask >> sl) & 1u) != 0u;
+        for (int a = 0; a < 3; a++) {
+            clo[sl][a] = child_lo4[4 * sl + a]; chi[sl][a] = child_hi4[4 * sl + a];
+            if (occ[sl]) { nl[a] = fminf(nl[a], clo[sl][a]); nh[a] = fmaxf(nh[a], chi[sl][a]); }
+        }
+    }
+    float4 w[5];
+    memset(w, 0, sizeof w);
+    wide_encode_node(w, nl, nh, clo, chi, occ, imask);
+    memcpy(out_words20, w, sizeof w);
+}
+
+// mrt_debug_instance_box: invert_affine and instance_box of instance_math.h as update_tlas calls them; false for a matrix that is not taken (nothing written then)
+bool instance_box_host(const float *xf16, const float *obj_lo3, const float *obj_hi3, float *rows12, float *world_box6) {
+    float rows[3][4];
+    if (!invert_affine(xf16, rows)) return false;
+    const Box b = instance_box(xf16, obj_lo3, obj_hi3, rows);
+    memcpy(rows12, rows, sizeof rows);
+    for (int k = 0; k < 3; k++) { world_box6[k] = b.lo[k]; world_box6[3 + k] = b.hi[k]; }
+    return true;
+}
+
 int build_two_level(const std::vector<HostMesh> &meshes, const BuildOptions &opt_in, hipStream_t stream, DeviceScene &out) {
     const size_t I = meshes.size();
     drop_blas_workspace(out);          // (made for the BLASes this call replaces)
-    BuildOptions opt = opt_in; opt.instancing = 0; opt.rope = 1;      // the BLASes keep both layouts: the stackless two-level walk serves the query API and is the fallback of the render kernels
-    opt.presplit = 0.0f;                                                // one packet per triangle in a BLAS: the instance rows address packets by triangle count (ntri)                      // a BLAS is a flat scene of one mesh: rope layout (queries, A/B path) + 8-wide layout (render kernels)
+    // a BLAS is a flat scene of one mesh and keeps both layouts: the rope layout, whose stackless two-level walk serves the query API and is the fallback of the render
+    // kernels (the A/B path), and the 8-wide layout of the render kernels
+    BuildOptions opt = opt_in; opt.instancing = 0; opt.rope = 1;
+    opt.presplit = 0.0f;                                                // one packet per triangle in a BLAS: the instance rows address packets by triangle count (ntri)
     // distinct geometries, in order of first use
     std::vector<int> blas_of(I, -1); std::vector<size_t> blas_src;
     std::map<size_t, int> seen;
