@@ -84,7 +84,8 @@ typedef struct {                                                      /* ShaderT
 
 /* One ray / one intersector result, as `metal::raytracing::ray` and
  * `intersector<triangle_data, instancing>::result_type` present them (Raytracing.metal:214-221,
- * :230-247).  Used by the query entry points (parity tests, brute-force cross-checks).         */
+ * :230-247).  Used by the query entry points (parity tests, brute-force cross-checks).
+ * Direction components may be +0, -0 or denormal: the answer is the triangle test's either way. */
 typedef struct {
     float origin[3];    float min_distance;
     float direction[3]; float max_distance;

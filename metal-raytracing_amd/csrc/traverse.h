@@ -106,7 +106,7 @@ MRT_DEV void walk_rope(const SceneView &s, const Filter &vis, const f3 o, const 
     if (s.num_nodes == 0) return;
     const float ix = safe_inv(d.x), iy = safe_inv(d.y), iz = safe_inv(d.z);
     const float nox = -(o.x * ix), noy = -(o.y * iy), noz = -(o.z * iz);
-    const uint32_t oct = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
+    const uint32_t oct = (ix < 0.0f ? 1u : 0u) | (iy < 0.0f ? 2u : 0u) | (iz < 0.0f ? 4u : 0u);      // the reciprocal's sign: -0 counts as negative, as it does in 1 / d
     const uint32_t esc_off = 32u + ((oct >> 2) << 4), esc_lane = oct & 3u;
     // nodes and packets live in one allocation: one wave-uniform base + a 32-bit byte offset per lane
     const char *__restrict__ base = reinterpret_cast<const char *>(s.nodes);

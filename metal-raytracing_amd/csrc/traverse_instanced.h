@@ -52,7 +52,7 @@ MRT_DEV void walk_instanced(const SceneView &s, const Filter &vis, const f3 o, c
                 oo = to_object_point(I, o); dd = to_object_dir(I, d);
                 jx = box_inv(dd.x); jy = box_inv(dd.y); jz = box_inv(dd.z);
                 mox = -(oo.x * jx); moy = -(oo.y * jy); moz = -(oo.z * jz);
-                oct = (dd.x < 0.0f ? 1u : 0u) | (dd.y < 0.0f ? 2u : 0u) | (dd.z < 0.0f ? 4u : 0u);
+                oct = (jx < 0.0f ? 1u : 0u) | (jy < 0.0f ? 2u : 0u) | (jz < 0.0f ? 4u : 0u);
                 node_base = I.node_base; packet_base = I.packet_base; gid_base = I.gid_base;
                 bc = 0; in_blas = true;
                 continue;

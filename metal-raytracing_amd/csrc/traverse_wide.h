@@ -130,9 +130,11 @@ MRT_DEV void wide_node_test(const float4 n0, const float4 n1, const float4 n2, c
 // k_megakernel (megakernel.h) are built from them.  All of them inline away; their shapes (values in, small struct or references to plain locals out) are the ones that leave
 // the flattened kernels' assembly exactly as it was (tools/isa_diff.py; docs/HISTORY.md §18 lists the shapes that do not).
 // what the box tests need of a ray's direction: 1 / d per axis, the sign per axis, the octant (child slots are visited in slot ^ octant order)
+// The sign is the RECIPROCAL's: box_inv gives d = -0 the reciprocal -1e20, and wide_node_test takes no min / max over a slab's two planes — it trusts the near / far choice,
+// so a sign read from `d < 0` (false for -0) would swap the planes and miss every box (docs/HISTORY.md §21).
 struct RayBox { float ix, iy, iz; bool nx, ny, nz; uint32_t oct; };
 MRT_DEV RayBox ray_box(const f3 d) {
-    RayBox b; b.ix = box_inv(d.x); b.iy = box_inv(d.y); b.iz = box_inv(d.z); b.nx = d.x < 0.0f; b.ny = d.y < 0.0f; b.nz = d.z < 0.0f;
+    RayBox b; b.ix = box_inv(d.x); b.iy = box_inv(d.y); b.iz = box_inv(d.z); b.nx = b.ix < 0.0f; b.ny = b.iy < 0.0f; b.nz = b.iz < 0.0f;
     b.oct = (b.nx ? 1u : 0u) | (b.ny ? 2u : 0u) | (b.nz ? 4u : 0u);
     return b;
 }
@@ -258,7 +260,7 @@ MRT_DEV void walk_wide(const SceneView &s, const Filter &vis, const f3 o, const 
     if (s.num_wnodes == 0) return;
     const uint32_t lane = threadIdx.x & 63;
     const float ix = safe_inv(d.x), iy = safe_inv(d.y), iz = safe_inv(d.z);
-    const bool nx = d.x < 0.0f, ny = d.y < 0.0f, nz = d.z < 0.0f;
+    const bool nx = ix < 0.0f, ny = iy < 0.0f, nz = iz < 0.0f;      // the reciprocal's sign (ray_box)
     const uint32_t oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
     uint32_t sp = 0;
     uint32_t g_base = 0, g_mask = 0;      // node group: (permuted hit bits << 8) | imask
