@@ -110,8 +110,6 @@ __device__ __forceinline__ void refit_st_wt(__amdgpu_buffer_rsrc_t r, uint32_t i
 }
 
 // ------------------------------------------------------------------ host helpers
-static inline uint32_t cdiv(size_t a, size_t b) { return (uint32_t)((a + b - 1) / b); }
-
 struct EventPair {           // destroyed on every return path
     hipEvent_t a = nullptr, b = nullptr;
     ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }

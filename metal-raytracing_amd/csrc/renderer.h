@@ -229,7 +229,7 @@ uint32_t shard_tiles(int width, int height, int rank, int world);               
 int unpack_tiles_into(float4 *image, int width, int height, const void *compact, size_t nbytes, int rank, int world, hipStream_t st);
 int query_closest(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, MRTIntersection *out);
 int query_any(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, int32_t *out);
-// the stream-ordered forms on caller device buffers: two launches on `stream`, no allocation, copy or synchronisation (renderer.hip)
+// the stream-ordered forms on caller device buffers: two launches on `stream`, no allocation, copy or synchronisation (query.hip, as the host-pointer entries and the diagnostics below)
 // d_count: null, or one uint32 on the device — both kernels then answer the rays below min(n, *d_count) and touch no other
 int query_closest_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_out, const void *d_count = nullptr);
 int query_any_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_occluded, const void *d_count = nullptr);

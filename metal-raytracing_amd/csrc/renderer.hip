@@ -22,8 +22,10 @@
 //
 // Record layout (all 16-byte lanes, one dwordx4 per lane per access, fully coalesced):
 //   rayA = {origin.xyz, tmax}   rayB = {direction.xyz, pixel}   thr = {throughput.rgb, -}   (path rays)
-//   hit  = {t, U/|det|, V/|det|, gid}                                                        (16 B)
+//   hit  = {t, U/|det|, V/|det|, gid}                                                        (16 B; traverse.h hit_record)
 //   shadow rays reuse rayA/rayB with tmax = lightDistance - 1e-3; con = {Lc*throughput, -}
+// The wide traversal launches read a bounce's combined queue [bounce rays | shadow rays] through MixedQueue (traverse_wide.h).  The scene queries of the
+// C ABI (mrt_scene_intersect_*, mrt_debug_*) are query.hip; the device-function probes at the end of this file stay here: they use k_seed.
 #include <hip/hip_ext.h>
 #include "renderer.h"
 #include "device_math.h"
@@ -72,7 +74,7 @@ __global__ void __launch_bounds__(64) k_trace_primary(SceneView s, FrameParams f
     float4 *__restrict__ hits_s = hits + (size_t)sub * fp.capacity;
     int x, y;
     if (!slot_to_pixel(fp, slot, x, y)) {
-        if ((int)(slot >> 6) < fp.tiles_local) hits_s[slot] = make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
+        if ((int)(slot >> 6) < fp.tiles_local) hits_s[slot] = miss_record();
         return;
     }
     f3 org, dir;
@@ -114,7 +116,7 @@ __global__ void __launch_bounds__(64) k_trace_primary(SceneView s, FrameParams f
         if (h.pk != guess) hint[pixel] = h.pk;
     }
     else hit = TWO_LEVEL ? traverse_instanced<false>(s, org, dir, 0.0f, __builtin_inff(), h) : traverse<false>(s, org, dir, 0.0f, __builtin_inff(), h);
-    qstore(&hits_s[slot], hit ? make_float4(h.t, h.U / h.ad, h.V / h.ad, __uint_as_float(h.gid)) : make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)));
+    qstore(&hits_s[slot], hit_record(hit, h));
 }
 
 template <bool TWO_LEVEL>
@@ -138,7 +140,7 @@ __global__ void __launch_bounds__(64) k_trace_mixed(SceneView s, const float4 *_
             sample[pix] = make_float4(a.x + cc.x, a.y + cc.y, a.z + cc.z, 0.0f);   // one shadow ray per pixel per bounce: no atomics
         }
     } else {
-        hits[j] = hit ? make_float4(h.t, h.U / h.ad, h.V / h.ad, __uint_as_float(h.gid)) : make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
+        hits[j] = hit_record(hit, h);
     }
 }
 
@@ -171,29 +173,30 @@ __global__ void __launch_bounds__(64, TWO_LEVEL ? MRT_TWO_LEVEL_WAVES : MRT_WIDE
     if (even_waves) rays_per_wave = max(64u, ((n + even_waves - 1u) / even_waves + 63u) & ~63u);
     const uint32_t begin = blockIdx.x * rays_per_wave;
     if (begin >= n) return;
+    const MixedQueue<false, false> q{rayA, rayB, srayA, srayB, scon, hits, sample, lit, n_next};
     traverse_wide_stream<TWO_LEVEL>(s, OneRange{begin, min(n, begin + rays_per_wave)}, stk_dyn,
-        [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) {      // tag = index in the ray's own queue
-            const bool sh = i >= n_next; tag = sh ? i - n_next : i; is_any = sh ? 1u : 0u;
-            A = qload(sh ? &srayA[tag] : &rayA[tag]); B = qload(sh ? &srayB[tag] : &rayB[tag]);
-            if (!sh) A.w = __builtin_inff();          // a bounce ray's tmax word may carry the throughput chain
-            else if (lit) tag = __float_as_uint(B.w);   // shadow planes: the ray reports to its pixel's byte
-        },
-        [&](uint32_t j, bool is_any, bool hit, const TravHit &h) {
-            if (is_any) {
-                if (!hit) {
-                    if (lit) lit[4 * (size_t)j] = 1;          // (lit points at this bounce's byte of pixel 0: four bytes per pixel and frame)
-                    else { const uint32_t pix = __float_as_uint(srayB[j].w); float4 cc = qload(&scon[j]), a = q2load(&sample[pix]); q2store(&sample[pix], make_float4(a.x + cc.x, a.y + cc.y, a.z + cc.z, 0.0f)); }
-                }
-            } else {
-                qstore(&hits[j], hit ? make_float4(h.t, h.U / h.ad, h.V / h.ad, __uint_as_float(h.gid)) : make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)));
-            }
-        });
+        [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) { q.fetch(i, A, B, tag, is_any); },
+        [&](uint32_t j, bool is_any, bool hit, const TravHit &h) { q.emit(j, is_any, hit, h); });
 }
 
 #ifdef MRT_WAVE_TIMES      // diagnostics build (tools/archive/wave_times.py): when does every wave of the first traversal launch of a pass start and end?
 __device__ unsigned long long g_wave_times[2 * 8192];
 __device__ uint32_t g_wave_iters[4 * 8192];      // per wave of that launch: iterations | drain iterations + longest iteration << 12 | live lanes summed over the drain iterations | drain start tick
 __device__ unsigned long long g_drain_probe[2][9];      // StreamStats::dr_*, summed over the waves of that launch: [at most 16 | at most 4 live lanes][6 stack-depth bins, hit children pending, triangles pending, samples]
+// Leaves a wave's record behind when the kernel returns, on whichever path (tag: only the launch tagged 0 reports).  DRAIN: the drain probe's sums too.
+template <bool DRAIN> struct WaveTimes {
+    unsigned long long t0; uint32_t tag; StreamStats &st;
+    __device__ ~WaveTimes() {
+        if ((threadIdx.x & 63) == 0 && tag == 0 && blockIdx.x < 8192) {
+            g_wave_times[2 * blockIdx.x] = t0; g_wave_times[2 * blockIdx.x + 1] = wall_clock64();
+            g_wave_iters[4 * blockIdx.x] = st.iters | (st.drain_le8 << 16); g_wave_iters[4 * blockIdx.x + 1] = st.drain_iters | (st.maxdt << 12); g_wave_iters[4 * blockIdx.x + 2] = st.drain_live; g_wave_iters[4 * blockIdx.x + 3] = (uint32_t)st.drain_t0;
+        }
+        if (DRAIN && (threadIdx.x & 63) == 0 && tag == 0) for (int c_ = 0; c_ < 2; c_++) {
+            for (int d_ = 0; d_ < 6; d_++) atomicAdd(&g_drain_probe[c_][d_], (unsigned long long)st.dr_hist[c_][d_]);
+            atomicAdd(&g_drain_probe[c_][6], (unsigned long long)st.dr_kids[c_]); atomicAdd(&g_drain_probe[c_][7], (unsigned long long)st.dr_tris[c_]); atomicAdd(&g_drain_probe[c_][8], (unsigned long long)st.dr_n[c_]);
+        }
+    }
+};
 #endif
 // Persistent variant: the grid is the number of wave slots of the chip (or fewer for a small queue) and every wave pulls
 // `chunk` consecutive rays of the combined queue at a time from `work` (zeroed by k_accumulate at the end of the previous pass).
@@ -208,27 +211,12 @@ __global__ void __launch_bounds__(64, TWO_LEVEL ? MRT_TWO_LEVEL_WAVES : MRT_WIDE
     const uint32_t wt_tag = chunk >> 24; chunk &= 0xFFFFFFu;
     const unsigned long long wt0 = wall_clock64();
     StreamStats wst{0, 0, 0, 0, 0, 0};
-    struct WT { unsigned long long t0; uint32_t tag; StreamStats &st; __device__ ~WT() { if ((threadIdx.x & 63) == 0 && tag == 0 && blockIdx.x < 8192) {
-        g_wave_times[2 * blockIdx.x] = t0; g_wave_times[2 * blockIdx.x + 1] = wall_clock64();
-        g_wave_iters[4 * blockIdx.x] = st.iters | (st.drain_le8 << 16); g_wave_iters[4 * blockIdx.x + 1] = st.drain_iters | (st.maxdt << 12); g_wave_iters[4 * blockIdx.x + 2] = st.drain_live; g_wave_iters[4 * blockIdx.x + 3] = (uint32_t)st.drain_t0; } } } wt{wt0, wt_tag, wst};
+    const WaveTimes<false> wt{wt0, wt_tag, wst};
 #endif
     if (blockIdx.x * chunk >= n) return;            // more waves than chunks (small queue): the surplus leaves at once
-    auto fetch = [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) {
-            const bool sh = i >= n_next; tag = sh ? i - n_next : i; is_any = sh ? 1u : 0u;
-            A = qload(sh ? &srayA[tag] : &rayA[tag]); B = qload(sh ? &srayB[tag] : &rayB[tag]);
-            if (!sh) A.w = __builtin_inff();          // a bounce ray's tmax word may carry the throughput chain
-            else if (lit) tag = __float_as_uint(B.w);   // shadow planes: the ray reports to its pixel's byte
-        };
-    auto emit = [&](uint32_t j, bool is_any, bool hit, const TravHit &h) {
-            if (is_any) {
-                if (!hit) {
-                    if (lit) lit[4 * (size_t)j] = 1;          // (lit points at this bounce's byte of pixel 0: four bytes per pixel and frame)
-                    else { const uint32_t pix = __float_as_uint(srayB[j].w); float4 cc = qload(&scon[j]), a = q2load(&sample[pix]); q2store(&sample[pix], make_float4(a.x + cc.x, a.y + cc.y, a.z + cc.z, 0.0f)); }
-                }
-            } else {
-                qstore(&hits[j], hit ? make_float4(h.t, h.U / h.ad, h.V / h.ad, __uint_as_float(h.gid)) : make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)));
-            }
-        };
+    const MixedQueue<false, false> q{rayA, rayB, srayA, srayB, scon, hits, sample, lit, n_next};
+    const auto fetch = [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) { q.fetch(i, A, B, tag, is_any); };
+    const auto emit = [&](uint32_t j, bool is_any, bool hit, const TravHit &h) { q.emit(j, is_any, hit, h); };
 #ifdef MRT_WAVE_TIMES
     StreamStats *const wss = wt_tag == 0 ? &wst : nullptr;
 #else
@@ -251,16 +239,9 @@ __global__ void __launch_bounds__(64, MRT_WIDE_STREAM_WAVES) k_trace_mixed_wide_
     if (SEG) for (uint32_t x = 1; x < QUEUE_SEGMENTS; x++) c += counts[(size_t)x * SEG_TAIL_STRIDE];          // (neither half carries: a pass queues fewer than 2^31 rays of a kind)
     const uint32_t n_next = (uint32_t)c, n_shadow = (uint32_t)(c >> 32), n = n_next + n_shadow;
     if ((unsigned long long)blockIdx.x * chunk >= (unsigned long long)n + (SEG ? 2ull * QUEUE_SEGMENTS * chunk : 0ull)) return;            // more waves than chunks (small queue; SEG: every segment rounds its two parts up): the surplus leaves at once
-    auto fetch = [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) {
-            const bool sh = SEG ? (i & SEG_SHADOW_BIT) != 0u : i >= n_next; tag = SEG ? i & ~SEG_SHADOW_BIT : sh ? i - n_next : i; is_any = sh ? 1u : 0u;
-            A = qload(sh ? &srayA[tag] : &rayA[tag]); B = qload(sh ? &srayB[tag] : &rayB[tag]);
-            if (!sh) A.w = __builtin_inff();          // a bounce ray's tmax word may carry the throughput chain
-            else tag = __float_as_uint(B.w);          // shadow planes: the ray reports to its pixel's byte
-        };
-    auto emit = [&](uint32_t j, bool is_any, bool hit, const TravHit &h) {
-            if (is_any) { if (!hit) lit[4 * (size_t)j] = 1; }
-            else qstore(&hits[j], hit ? make_float4(h.t, h.U / h.ad, h.V / h.ad, __uint_as_float(h.gid)) : make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)));
-        };
+    const MixedQueue<SEG, true> q{rayA, rayB, srayA, srayB, nullptr, hits, nullptr, lit, n_next};
+    const auto fetch = [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) { q.fetch(i, A, B, tag, is_any); };
+    const auto emit = [&](uint32_t j, bool is_any, bool hit, const TravHit &h) { q.emit(j, is_any, hit, h); };
     StreamExt<true> ext{reinterpret_cast<float *>(lds_dyn), lds_dyn + 256u};
     if constexpr (SEG) traverse_wide_stream<false, false, false, NoPairs, StreamExt<true>>(s, SegRegions{work, counts, subframes, chunk, blockIdx.x & 7u}, lds_dyn + HIT_LDS_WORDS, fetch, emit, nullptr, NoPairs{}, ext);
     else traverse_wide_stream<false, false, false, NoPairs, StreamExt<true>>(s, XcdRegions{work, n_next, n, chunk, subframes, blockIdx.x & 7u}, lds_dyn + HIT_LDS_WORDS, fetch, emit, nullptr, NoPairs{}, ext);
@@ -276,11 +257,7 @@ __global__ void __launch_bounds__(64, MRT_WIDE_STREAM_WAVES) k_trace_mixed_wide_
 #ifdef MRT_WAVE_TIMES
     const uint32_t wt_tag = rays_per_wave >> 24; rays_per_wave &= 0xFFFFFFu;
     StreamStats wst{0, 0, 0, 0, 0, 0};
-    struct WT { unsigned long long t0; uint32_t tag; StreamStats &st; __device__ ~WT() { if ((threadIdx.x & 63) == 0 && tag == 0 && blockIdx.x < 8192) {
-        g_wave_times[2 * blockIdx.x] = t0; g_wave_times[2 * blockIdx.x + 1] = wall_clock64();
-        g_wave_iters[4 * blockIdx.x] = st.iters | (st.drain_le8 << 16); g_wave_iters[4 * blockIdx.x + 1] = st.drain_iters | (st.maxdt << 12); g_wave_iters[4 * blockIdx.x + 2] = st.drain_live; g_wave_iters[4 * blockIdx.x + 3] = (uint32_t)st.drain_t0; }
-        if ((threadIdx.x & 63) == 0 && tag == 0) for (int c_ = 0; c_ < 2; c_++) { for (int d_ = 0; d_ < 6; d_++) atomicAdd(&g_drain_probe[c_][d_], (unsigned long long)st.dr_hist[c_][d_]);
-            atomicAdd(&g_drain_probe[c_][6], (unsigned long long)st.dr_kids[c_]); atomicAdd(&g_drain_probe[c_][7], (unsigned long long)st.dr_tris[c_]); atomicAdd(&g_drain_probe[c_][8], (unsigned long long)st.dr_n[c_]); } } } wt{(unsigned long long)wall_clock64(), wt_tag, wst};
+    const WaveTimes<true> wt{(unsigned long long)wall_clock64(), wt_tag, wst};
     StreamStats *const wss = wt_tag == 0 ? &wst : nullptr;
 #else
     StreamStats *const wss = nullptr;
@@ -292,17 +269,10 @@ __global__ void __launch_bounds__(64, MRT_WIDE_STREAM_WAVES) k_trace_mixed_wide_
     StreamExt<true> ext{reinterpret_cast<float *>(lds_dyn), lds_dyn + 256u};
     // stream_stride: the (n + rays_per_wave - 1) / rays_per_wave waves that have work take the queue's 64-ray batches round-robin instead of one contiguous range each
     const BatchStride src = strided ? BatchStride{blockIdx.x * 64u, 64u * ((n + rays_per_wave - 1u) / rays_per_wave), n} : BatchStride{begin, 64u, min(n, begin + rays_per_wave)};
+    const MixedQueue<false, true> q{rayA, rayB, srayA, srayB, nullptr, hits, nullptr, lit, n_next};
     traverse_wide_stream<false, false, false, NoPairs, StreamExt<true>>(s, src, lds_dyn + HIT_LDS_WORDS,
-        [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) {
-            const bool sh = i >= n_next; tag = sh ? i - n_next : i; is_any = sh ? 1u : 0u;
-            A = qload(sh ? &srayA[tag] : &rayA[tag]); B = qload(sh ? &srayB[tag] : &rayB[tag]);
-            if (!sh) A.w = __builtin_inff();          // a bounce ray's tmax word may carry the throughput chain
-            else tag = __float_as_uint(B.w);          // shadow planes: the ray reports to its pixel's byte
-        },
-        [&](uint32_t j, bool is_any, bool hit, const TravHit &h) {
-            if (is_any) { if (!hit) lit[4 * (size_t)j] = 1; }
-            else qstore(&hits[j], hit ? make_float4(h.t, h.U / h.ad, h.V / h.ad, __uint_as_float(h.gid)) : make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)));
-        }, wss, NoPairs{}, ext);
+        [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) { q.fetch(i, A, B, tag, is_any); },
+        [&](uint32_t j, bool is_any, bool hit, const TravHit &h) { q.emit(j, is_any, hit, h); }, wss, NoPairs{}, ext);
 }
 
 #include "megakernel.h"            // k_megakernel: one launch per frame
@@ -354,7 +324,7 @@ __global__ void __launch_bounds__(64, 5) k_trace_primary_wide_stream(SceneView s
                 }
             },
             [&](uint32_t slot, bool, bool hit, const TravHit &h) {
-                hits[slot] = hit ? make_float4(h.t, h.U / h.ad, h.V / h.ad, __uint_as_float(h.gid)) : make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
+                hits[slot] = hit_record(hit, h);
                 int x, y;
                 if (hit && slot_to_pixel(fp, slot, x, y)) hint[(uint32_t)y * (uint32_t)fp.width + (uint32_t)x] = h.pk;
             });
@@ -362,7 +332,7 @@ __global__ void __launch_bounds__(64, 5) k_trace_primary_wide_stream(SceneView s
         traverse_wide_stream<TWO_LEVEL>(s, OneRange{begin, min(capacity, begin + rays_per_wave)}, stk_dyn,
             [&](uint32_t slot, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) { f3 org, dir; int x, y; (void)make_ray(slot, A, B, tag, is_any, org, dir, x, y); },
             [&](uint32_t slot, bool, bool hit, const TravHit &h) {
-                hits[slot] = hit ? make_float4(h.t, h.U / h.ad, h.V / h.ad, __uint_as_float(h.gid)) : make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
+                hits[slot] = hit_record(hit, h);
             });
     }
 }
@@ -525,158 +495,6 @@ __global__ void k_tonemap(const float4 *__restrict__ accum, int w, int h, uchar4
     out[(size_t)y * w + x] = make_uchar4(o[0], o[1], o[2], 255);
 }
 
-// ------------------------------------------------------------------ query kernels (C-ABI intersect_*)
-// the record of a closest-hit query: ids by hit_ids, u = U / |det|, v = V / |det|; a miss is {0, -1.0f, -1, -1, -1, 0, 0}
-MRT_DEV MRTIntersection closest_record(const SceneView &s, bool two_level, bool hit, const TravHit &h) {
-    MRTIntersection o;
-    o._pad = 0; o.type = 0; o.distance = -1.0f; o.instance_id = o.geometry_id = o.primitive_id = -1; o.u = o.v = 0.0f;
-    if (hit) {
-        uint32_t inst, geom, prim;
-        hit_ids(s, two_level, h.gid, inst, geom, prim);
-        o.type = 1; o.distance = h.t; o.instance_id = (int32_t)inst; o.geometry_id = (int32_t)geom; o.primitive_id = (int32_t)prim;
-        o.u = h.U / h.ad; o.v = h.V / h.ad;
-    }
-    return o;
-}
-template <bool WIDE>
-__global__ void __launch_bounds__(64) k_query_closest(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, MRTIntersection *__restrict__ out) {
-    extern __shared__ uint32_t stk[];      // WIDE: the scene's wide-tree depth x WIDE_STACK_LEVEL_BYTES, sized by the host
-    uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    MRTRay r = rays[i];
-    TravHit h;
-    const f3 ro = mk3(r.origin[0], r.origin[1], r.origin[2]), rd = mk3(r.direction[0], r.direction[1], r.direction[2]);
-    bool hit = s.num_inst ? traverse_instanced<false>(s, ro, rd, r.min_distance, r.max_distance, h)
-             : WIDE ? traverse_wide<false>(s, ro, rd, r.min_distance, r.max_distance, h, stk) : traverse<false>(s, ro, rd, r.min_distance, r.max_distance, h);
-    out[i] = closest_record(s, s.num_inst != 0, hit, h);
-}
-template <bool WIDE>
-__global__ void __launch_bounds__(64) k_query_any(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, int32_t *__restrict__ out) {
-    extern __shared__ uint32_t stk[];      // WIDE: the scene's wide-tree depth x WIDE_STACK_LEVEL_BYTES, sized by the host
-    uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    MRTRay r = rays[i];
-    TravHit h;
-    const f3 ro = mk3(r.origin[0], r.origin[1], r.origin[2]), rd = mk3(r.direction[0], r.direction[1], r.direction[2]);
-    out[i] = (s.num_inst ? traverse_instanced<true>(s, ro, rd, r.min_distance, r.max_distance, h)
-              : WIDE ? traverse_wide<true>(s, ro, rd, r.min_distance, r.max_distance, h, stk) : traverse<true>(s, ro, rd, r.min_distance, r.max_distance, h)) ? 1 : 0;
-}
-
-// per-ray traversal statistics (steps, leaf visits, triangle tests) — diagnostics only
-template <bool WIDE>
-__global__ void __launch_bounds__(64) k_query_stats(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, int any, uint32_t *__restrict__ out) {
-    extern __shared__ uint32_t stk[];      // WIDE: the scene's wide-tree depth x WIDE_STACK_LEVEL_BYTES, sized by the host
-    uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    MRTRay r = rays[i];
-    TravHit h; TravCounters tc{0, 0, 0, 0};
-    tc.alu_dup = (any >> 8) & 0xFF; tc.mem_dup = (any >> 16) & 0xFF; any &= 1;
-    f3 o = mk3(r.origin[0], r.origin[1], r.origin[2]), d = mk3(r.direction[0], r.direction[1], r.direction[2]);
-    unsigned long long t0 = wall_clock64();
-    if (WIDE) { if (any) traverse_wide<true, true>(s, o, d, r.min_distance, r.max_distance, h, stk, &tc); else traverse_wide<false, true>(s, o, d, r.min_distance, r.max_distance, h, stk, &tc); }
-    else { if (any) traverse<true, true>(s, o, d, r.min_distance, r.max_distance, h, &tc); else traverse<false, true>(s, o, d, r.min_distance, r.max_distance, h, &tc); }
-    unsigned long long t1 = wall_clock64();
-    out[8 * i + 0] = tc.steps; out[8 * i + 1] = tc.leaves; out[8 * i + 2] = tc.tris; out[8 * i + 3] = h.gid;
-    out[8 * i + 4] = (uint32_t)t0; out[8 * i + 5] = (uint32_t)t1; out[8 * i + 6] = tc.wave_iters;   // 100 MHz ticks
-    out[8 * i + 7] = (tc.alu_dup | tc.mem_dup) ? __float_as_uint(tc.sink) : (tc.empty & 0xFFFFu) | (tc.stale << 16);    // 8-wide layout: empty visits | stale visits << 16
-}
-
-// stream-traversal lane accounting (diagnostics): per wave {iterations, sum of live lanes, node lanes, tri lanes, refills, refilled lanes}
-template <bool TWO_LEVEL>
-__global__ void __launch_bounds__(64) k_query_stream_stats(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, int any, uint32_t per_wave, uint32_t depth, uint32_t *__restrict__ out) {
-    extern __shared__ uint32_t stk_dyn[];
-    const uint32_t begin = blockIdx.x * per_wave;
-    if (begin >= n) return;
-    const uint32_t end = min(n, begin + per_wave);
-    StreamStats ss{0, 0, 0, 0, 0, 0};
-    uint32_t sink = 0;
-#if defined(MRT_STATS_PROBE) && MRT_STATS_PROBE == 1
-    {   // BFS numbering, children contiguous: level L + 1 starts where level L ends and holds the internal children (imask bits) of level L's nodes
-        uint32_t lo = 0, hi = 1;
-        for (int L = 0; L < 3; L++) {
-            uint32_t kids = 0;
-            for (uint32_t i = lo; i < hi; i++) kids += (uint32_t)__popc(__float_as_uint(s.wnodes[WNODE_STRIDE * (size_t)i].w) >> 24);
-            lo = hi; hi += kids; ss.level_end[L] = hi;
-        }
-    }
-#endif
-    traverse_wide_stream<TWO_LEVEL>(s, OneRange{begin, end}, stk_dyn,
-        [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) {
-            MRTRay r = rays[i]; tag = i & 0x7FFFFFFFu;
-            A = make_float4(r.origin[0], r.origin[1], r.origin[2], r.max_distance); B = make_float4(r.direction[0], r.direction[1], r.direction[2], 0.0f); is_any = (uint32_t)any;
-        },
-        [&](uint32_t, bool, bool hit, const TravHit &) { sink += hit ? 1u : 0u; }, &ss);
-    if ((threadIdx.x & 63) == 0) {
-        uint32_t *o = out + 8 * (size_t)blockIdx.x;
-        o[0] = ss.iters; o[1] = ss.live_sum; o[2] = ss.node_sum; o[3] = ss.tri_sum; o[4] = ss.refills; o[5] = ss.refill_lanes; o[6] = sink; o[7] = end - begin;
-#ifdef MRT_STATS_PROBE
-        o[4] = ss.probe[0]; o[5] = ss.probe[1]; o[6] = ss.probe[2];
-#endif
-    }
-}
-
-// the render kernels' traversal (8-wide stream with lane refill; both levels of an instanced scene) on caller rays — parity tests of that path
-template <bool TWO_LEVEL>
-__global__ void __launch_bounds__(64) k_query_stream(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, int any, uint32_t per_wave, MRTIntersection *__restrict__ out) {
-    extern __shared__ uint32_t stk_dyn[];
-    const uint32_t begin = blockIdx.x * per_wave;
-    if (begin >= n) return;
-    traverse_wide_stream<TWO_LEVEL>(s, OneRange{begin, min(n, begin + per_wave)}, stk_dyn,
-        [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) {
-            MRTRay r = rays[i]; tag = i & 0x7FFFFFFFu; is_any = (uint32_t)any;
-            A = make_float4(r.origin[0], r.origin[1], r.origin[2], r.max_distance); B = make_float4(r.direction[0], r.direction[1], r.direction[2], 0.0f);
-        },
-        [&](uint32_t i, bool is_any, bool hit, const TravHit &h) {
-            MRTIntersection o = closest_record(s, TWO_LEVEL, hit && !is_any, h);
-            o.type = hit ? 1 : 0;
-            out[i] = o;
-        });
-}
-
-// ------------------------------------------------------------------ stream-ordered queries on caller buffers (mrt_scene_intersect_*_device)
-// Two launches on the caller's stream, no allocation, no copy, no synchronisation.  Every ray is answered by exactly one of them, and both decide with the same
-// expression (min_distance != 0), so every record is written exactly once whatever the rays hold:
-//   k_query_stream_device   rays with min_distance == 0 on the 8-wide layout: the render kernels' walk (traverse_wide_stream, lane refill, both levels of a two-level
-//                           scene on one stack).  Its scaled node test has tmin = 0 built in, so a ray with another min_distance enters the loop as the inert ray of a
-//                           partial-tile slot (tmax < 0 -> miss: one refill slot, no node visit) and its result is not written.
-//   k_query_lane_device     the other rays — and all rays of a scene without the 8-wide layout — one per lane with the walks of mrt_scene_intersect_closest / _any,
-//                           which carry tmin.  A lane whose ray the stream kernel answered leaves after reading min_distance.
-constexpr uint32_t QUERY_STREAM_RAYS = 256;      // rays per wave of the static split, as k_query_stream
-template <bool TWO_LEVEL, bool ANY>
-__global__ void __launch_bounds__(64, TWO_LEVEL ? MRT_TWO_LEVEL_WAVES : MRT_WIDE_STREAM_WAVES) k_query_stream_device(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, const uint32_t *__restrict__ count, void *__restrict__ out) {
-    extern __shared__ uint32_t stk_dyn[];
-    if (count) n = min(n, *count);      // the caller's device-side ray count (null: every ray), read once as a uniform scalar load: the rays at and past it are not touched
-    const uint32_t begin = blockIdx.x * QUERY_STREAM_RAYS;
-    if (begin >= n) return;
-    traverse_wide_stream<TWO_LEVEL>(s, OneRange{begin, min(n, begin + QUERY_STREAM_RAYS)}, stk_dyn,
-        [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) {
-            const MRTRay r = rays[i]; tag = i; is_any = ANY ? 1u : 0u;
-            if (r.min_distance != 0.0f) { A = make_float4(0.0f, 0.0f, 0.0f, -1.0f); B = make_float4(0.0f, 0.0f, 1.0f, 0.0f); }      // the lane kernel's ray: inert here (tmax < 0 -> miss)
-            else { A = make_float4(r.origin[0], r.origin[1], r.origin[2], r.max_distance); B = make_float4(r.direction[0], r.direction[1], r.direction[2], 0.0f); }
-        },
-        [&](uint32_t i, bool, bool hit, const TravHit &h) {
-            if (rays[i].min_distance != 0.0f) return;
-            if (ANY) static_cast<int32_t *>(out)[i] = hit ? 1 : 0;
-            else static_cast<MRTIntersection *>(out)[i] = closest_record(s, TWO_LEVEL, hit, h);
-        });
-}
-template <bool WIDE, bool ANY>
-__global__ void __launch_bounds__(64) k_query_lane_device(SceneView s, const MRTRay *__restrict__ rays, uint32_t n, const uint32_t *__restrict__ count, void *__restrict__ out) {
-    extern __shared__ uint32_t stk[];      // WIDE: the scene's wide-tree depth x WIDE_STACK_LEVEL_BYTES, sized by the host
-    if (count) n = min(n, *count);      // (as k_query_stream_device)
-    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    const bool mine = i < n && (s.num_wnodes == 0 || rays[i].min_distance != 0.0f);      // without the 8-wide layout no stream kernel ran: every ray is answered here
-    if (__ballot(mine) == 0ull) return;      // nothing for this wave: a uniform branch to the end
-    if (!mine) return;
-    const MRTRay r = rays[i];
-    TravHit h;
-    const f3 ro = mk3(r.origin[0], r.origin[1], r.origin[2]), rd = mk3(r.direction[0], r.direction[1], r.direction[2]);
-    const bool hit = s.num_inst ? traverse_instanced<ANY>(s, ro, rd, r.min_distance, r.max_distance, h)
-                   : WIDE ? traverse_wide<ANY>(s, ro, rd, r.min_distance, r.max_distance, h, stk) : traverse<ANY>(s, ro, rd, r.min_distance, r.max_distance, h);
-    if (ANY) static_cast<int32_t *>(out)[i] = hit ? 1 : 0;
-    else static_cast<MRTIntersection *>(out)[i] = closest_record(s, s.num_inst != 0, hit, h);
-}
-
 // ------------------------------------------------------------------ device-function probes
 __global__ void k_probe_halton(const int32_t *i, const int32_t *d, uint32_t n, float *out) {
     uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -688,8 +506,6 @@ __global__ void k_probe_hemisphere(const float *u2, const float *n3, uint32_t n,
     f3 v = align_hemisphere_dev(sample_cosine_hemisphere_dev(u2[2 * k], u2[2 * k + 1]), mk3(n3[3 * k], n3[3 * k + 1], n3[3 * k + 2]));
     out3[3 * k] = v.x; out3[3 * k + 1] = v.y; out3[3 * k + 2] = v.z;
 }
-
-static inline uint32_t cdiv(size_t a, size_t b) { return (uint32_t)((a + b - 1) / b); }
 
 // Launch with the kernel's own start/stop events when `ev` is given (bench.py's live roofline measurement).
 template <class... KArgs, class... Args>
@@ -1555,22 +1371,6 @@ int Renderer::render(int n_frames) {
     return MRT_OK;
 }
 
-#ifdef MRT_DEBUG_BOUNDS
-static int check_bounds_record() {
-    uint32_t v = 0;
-    MRT_HIP(hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_bounds_violation), 4));
-    if (v) {
-        static const char *kinds[] = {"?", "8-wide node", "triangle packet", "wtlas_index slot", "instance id"};
-        const uint32_t zero = 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bounds_violation), &zero, 4);
-        set_error(std::string("MRT_DEBUG_BOUNDS: the stream traversal followed an index outside its array: ") + kinds[std::min(v >> 28, 4u)] + " " + std::to_string(v & 0x0FFFFFFFu));
-        return MRT_ERR_STATE;
-    }
-    return MRT_OK;
-}
-#else
-static int check_bounds_record() { return MRT_OK; }
-#endif
-
 int Renderer::wait() {
     MRT_HIP(hipStreamSynchronize(stream));
     if (int rc = check_bounds_record()) return rc;
@@ -1663,98 +1463,7 @@ int Renderer::reset_stats() {
     return MRT_OK;
 }
 
-// ---- scene queries
-int query_closest(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, MRTIntersection *out) {
-    if (n == 0) return MRT_OK;
-    DevBuf<MRTRay> d_r; DevBuf<MRTIntersection> d_o;
-    MRT_HIP(d_r.alloc(n)); MRT_HIP(d_o.alloc(n));
-    MRT_HIP(hipMemcpyAsync(d_r.p, rays, n * sizeof(MRTRay), hipMemcpyHostToDevice, stream));
-    if (sc.num_wnodes) hipLaunchKernelGGL(k_query_closest<true>, dim3(cdiv(n, 64)), dim3(64), (size_t)sc.wide_depth * WIDE_STACK_LEVEL_BYTES, stream, sc.view(), d_r.p, (uint32_t)n, d_o.p);
-    else hipLaunchKernelGGL(k_query_closest<false>, dim3(cdiv(n, 64)), dim3(64), 0, stream, sc.view(), d_r.p, (uint32_t)n, d_o.p);
-    MRT_HIP(hipMemcpyAsync(out, d_o.p, n * sizeof(MRTIntersection), hipMemcpyDeviceToHost, stream));
-    MRT_HIP(hipStreamSynchronize(stream));
-    MRT_HIP(hipGetLastError());
-    return MRT_OK;
-}
-int query_any(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, int32_t *out) {
-    if (n == 0) return MRT_OK;
-    DevBuf<MRTRay> d_r; DevBuf<int32_t> d_o;
-    MRT_HIP(d_r.alloc(n)); MRT_HIP(d_o.alloc(n));
-    MRT_HIP(hipMemcpyAsync(d_r.p, rays, n * sizeof(MRTRay), hipMemcpyHostToDevice, stream));
-    if (sc.num_wnodes) hipLaunchKernelGGL(k_query_any<true>, dim3(cdiv(n, 64)), dim3(64), (size_t)sc.wide_depth * WIDE_STACK_LEVEL_BYTES, stream, sc.view(), d_r.p, (uint32_t)n, d_o.p);
-    else hipLaunchKernelGGL(k_query_any<false>, dim3(cdiv(n, 64)), dim3(64), 0, stream, sc.view(), d_r.p, (uint32_t)n, d_o.p);
-    MRT_HIP(hipMemcpyAsync(out, d_o.p, n * 4, hipMemcpyDeviceToHost, stream));
-    MRT_HIP(hipStreamSynchronize(stream));
-    MRT_HIP(hipGetLastError());
-    return MRT_OK;
-}
-
-int query_stats(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, int any, uint32_t *out4) {
-    if (n == 0) return MRT_OK;
-    DevBuf<MRTRay> d_r; DevBuf<uint32_t> d_o;
-    MRT_HIP(d_r.alloc(n)); MRT_HIP(d_o.alloc(8 * n));
-    MRT_HIP(hipMemcpyAsync(d_r.p, rays, n * sizeof(MRTRay), hipMemcpyHostToDevice, stream));
-    if (sc.num_wnodes) hipLaunchKernelGGL(k_query_stats<true>, dim3(cdiv(n, 64)), dim3(64), (size_t)sc.wide_depth * WIDE_STACK_LEVEL_BYTES, stream, sc.view(), d_r.p, (uint32_t)n, any, d_o.p);
-    else hipLaunchKernelGGL(k_query_stats<false>, dim3(cdiv(n, 64)), dim3(64), 0, stream, sc.view(), d_r.p, (uint32_t)n, any, d_o.p);
-    MRT_HIP(hipMemcpyAsync(out4, d_o.p, n * 32, hipMemcpyDeviceToHost, stream));
-    MRT_HIP(hipStreamSynchronize(stream));
-    MRT_HIP(hipGetLastError());
-    return MRT_OK;
-}
-
-int query_stream_stats(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, int any, uint32_t per_wave, uint32_t *out8, size_t nwaves) {
-    if (n == 0 || sc.num_wnodes == 0) return MRT_OK;
-    DevBuf<MRTRay> d_r; DevBuf<uint32_t> d_o;
-    MRT_HIP(d_r.alloc(n)); MRT_HIP(d_o.alloc(8 * nwaves));
-    MRT_HIP(hipMemsetAsync(d_o.p, 0, 32 * nwaves, stream));
-    MRT_HIP(hipMemcpyAsync(d_r.p, rays, n * sizeof(MRTRay), hipMemcpyHostToDevice, stream));
-    const size_t lds = (size_t)sc.wide_depth * WIDE_STACK_LEVEL_BYTES + (sc.num_inst ? WIDE_WORLD_RAY_BYTES : 0);
-    if (sc.num_inst) hipLaunchKernelGGL(k_query_stream_stats<true>, dim3((uint32_t)nwaves), dim3(64), lds, stream, sc.view(), d_r.p, (uint32_t)n, any, per_wave, (uint32_t)sc.wide_depth, d_o.p);
-    else hipLaunchKernelGGL(k_query_stream_stats<false>, dim3((uint32_t)nwaves), dim3(64), lds, stream, sc.view(), d_r.p, (uint32_t)n, any, per_wave, (uint32_t)sc.wide_depth, d_o.p);
-    MRT_HIP(hipMemcpyAsync(out8, d_o.p, 32 * nwaves, hipMemcpyDeviceToHost, stream));
-    MRT_HIP(hipStreamSynchronize(stream));
-    MRT_HIP(hipGetLastError());
-    return MRT_OK;
-}
-
-int query_stream(const DeviceScene &sc, hipStream_t stream, const MRTRay *rays, size_t n, int any, MRTIntersection *out) {
-    if (n == 0) return MRT_OK;
-    if (sc.num_wnodes == 0) { set_error("the scene has no 8-wide layout"); return MRT_ERR_UNSUPPORTED; }
-    for (size_t i = 0; i < n; i++) if (rays[i].min_distance != 0.0f) { set_error("the stream traversal starts every ray at distance 0 (min_distance must be 0)"); return MRT_ERR_INVALID_ARGUMENT; }
-    if (n >= (size_t(1) << 31)) { set_error("too many rays"); return MRT_ERR_INVALID_ARGUMENT; }
-    DevBuf<MRTRay> d_r; DevBuf<MRTIntersection> d_o;
-    MRT_HIP(d_r.alloc(n)); MRT_HIP(d_o.alloc(n));
-    MRT_HIP(hipMemcpyAsync(d_r.p, rays, n * sizeof(MRTRay), hipMemcpyHostToDevice, stream));
-    const uint32_t per_wave = 256;
-    const size_t lds = (size_t)sc.wide_depth * WIDE_STACK_LEVEL_BYTES + (sc.num_inst ? WIDE_WORLD_RAY_BYTES : 0);
-    if (sc.num_inst) hipLaunchKernelGGL(k_query_stream<true>, dim3(cdiv(n, per_wave)), dim3(64), lds, stream, sc.view(), d_r.p, (uint32_t)n, any, per_wave, d_o.p);
-    else hipLaunchKernelGGL(k_query_stream<false>, dim3(cdiv(n, per_wave)), dim3(64), lds, stream, sc.view(), d_r.p, (uint32_t)n, any, per_wave, d_o.p);
-    MRT_HIP(hipMemcpyAsync(out, d_o.p, n * sizeof(MRTIntersection), hipMemcpyDeviceToHost, stream));
-    MRT_HIP(hipStreamSynchronize(stream));
-    MRT_HIP(hipGetLastError());
-    return check_bounds_record();
-}
-
-// The stream-ordered entries (mrt_scene_intersect_closest_device / _any_device): both launches on the caller's stream, nothing else.
-template <bool ANY>
-static int query_device_t(const DeviceScene &sc, hipStream_t stream, const MRTRay *d_rays, size_t n, void *d_out, const void *d_count) {
-    const SceneView sv = sc.view();
-    const uint32_t *const cnt = static_cast<const uint32_t *>(d_count);      // (grids are sized by n, the capacity: a workgroup past the count leaves at once)
-    const uint32_t n32 = (uint32_t)n;
-    if (sc.num_wnodes) {
-        const size_t lds = (size_t)sc.wide_depth * WIDE_STACK_LEVEL_BYTES + (sc.num_inst ? WIDE_WORLD_RAY_BYTES : 0);
-        if (sc.num_inst) hipLaunchKernelGGL((k_query_stream_device<true, ANY>), dim3(cdiv(n, QUERY_STREAM_RAYS)), dim3(64), lds, stream, sv, d_rays, n32, cnt, d_out);
-        else hipLaunchKernelGGL((k_query_stream_device<false, ANY>), dim3(cdiv(n, QUERY_STREAM_RAYS)), dim3(64), lds, stream, sv, d_rays, n32, cnt, d_out);
-        MRT_HIP(hipGetLastError());
-    }
-    if (sc.num_wnodes) hipLaunchKernelGGL((k_query_lane_device<true, ANY>), dim3(cdiv(n, 64)), dim3(64), (size_t)sc.wide_depth * WIDE_STACK_LEVEL_BYTES, stream, sv, d_rays, n32, cnt, d_out);
-    else hipLaunchKernelGGL((k_query_lane_device<false, ANY>), dim3(cdiv(n, 64)), dim3(64), 0, stream, sv, d_rays, n32, cnt, d_out);
-    MRT_HIP(hipGetLastError());
-    return MRT_OK;
-}
-int query_closest_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_out, const void *d_count) { return query_device_t<false>(sc, stream, static_cast<const MRTRay *>(d_rays), n, d_out, d_count); }
-int query_any_device(const DeviceScene &sc, hipStream_t stream, const void *d_rays, size_t n, void *d_occluded, const void *d_count) { return query_device_t<true>(sc, stream, static_cast<const MRTRay *>(d_rays), n, d_occluded, d_count); }
-
+// ---- device-function probes
 int probe_halton(hipStream_t stream, const int32_t *i, const int32_t *d, size_t n, float *out) {
     if (n == 0) return MRT_OK;
     DevBuf<int32_t> di, dd; DevBuf<float> dout;

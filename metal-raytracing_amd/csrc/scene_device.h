@@ -165,6 +165,7 @@ template <class T> struct DevBuf {
     }
     size_t bytes() const { return n * sizeof(T); }
 };
+static inline uint32_t cdiv(size_t a, size_t b) { return (uint32_t)((a + b - 1) / b); }      // grid sizes
 
 // Pinned host memory that only grows: the staging area of a scene's uploads.  A commit concatenates the caller's arrays straight into it (one pass, no zero fill)
 // and the copies to the device are DMA from pinned pages; it stays with the scene, so the commits of an animated scene pay no allocation.

@@ -150,7 +150,7 @@ struct ShadeShared { uint32_t w_next[SHADE_WAVES], w_shadow[SHADE_WAVES], w_spec
 // TLAS / BLAS passes becomes a hit record — the barycentrics come from re-testing the winning triangle in its instance's
 // object space (the traversal's own test of the winner: the same U, V, |det|)
 MRT_DEV float4 pairs_hit(const SceneView &s, const ShadeIO &io, const uint32_t i, const unsigned long long key) {
-    if (key == ~0ull) return make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
+    if (key == ~0ull) return miss_record();
     const uint32_t g = (uint32_t)key;
     const InstanceDev &I = s.inst[instance_of_gid(s, g)];
     const uint32_t pk = s.tri_packet[I.ts_base + (g - I.gid_base)];
@@ -317,7 +317,7 @@ __global__ void __launch_bounds__(SHADE_THREADS, WALK >= 2 ? MRT_SHADE_WIDE_WAVE
     const uint32_t spix = sub * io.capacity + slot;          // sample index (seed table, sample buffer, contribution planes)
     int px_x = 0, px_y = 0;
     const bool active = slot < io.capacity && in_batch && slot_to_pixel(fp, slot, px_x, px_y);
-    float4 H = make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)), Bprim = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
+    float4 H = miss_record(), Bprim = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
     if (active) {
         f3 org, dir;
         primary_ray(fp, io.seeds, spix, px_x, px_y, org, dir);
@@ -379,7 +379,7 @@ __global__ void __launch_bounds__(SHADE_THREADS, WALK >= 2 ? MRT_SHADE_WIDE_WAVE
             if (h.pk != guess) io.hint[pixel] = h.pk;
         }
         else hit = traverse<false>(s, org, dir, 0.0f, __builtin_inff(), h);
-        if (hit) H = make_float4(h.t, h.U / h.ad, h.V / h.ad, __uint_as_float(h.gid));
+        if (hit) H = hit_record(true, h);
     }
     shade_entry<false, true, true, true>(s, fp, io, sh, spix, H, active, Bprim);
 }
@@ -396,7 +396,7 @@ __global__ void __launch_bounds__(SHADE_THREADS, MRT_SHADE_WAVES) k_shade_pack(S
     // segmented queues: block j is range j / segs of segment j % segs — it reads that segment and (shade_entry) writes the same one; a range at or beyond its segment's count is empty
     const uint32_t seg = fp.segs > 1u ? blockIdx.x & (QUEUE_SEGMENTS - 1u) : 0u, range = fp.segs > 1u ? blockIdx.x / QUEUE_SEGMENTS : blockIdx.x, first = seg * fp.seg_cap;
     const uint32_t n = io.count_in ? (uint32_t)io.count_in[(size_t)seg * SEG_TAIL_STRIDE] : io.capacity;
-    const float4 miss = make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)), noB = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
+    const float4 miss = miss_record(), noB = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
     const uint32_t begin = first + min(n, range * fp.pack_range), end = first + min(n, (range + 1u) * fp.pack_range);
     const uint32_t lane_ = threadIdx.x & 63, wv_ = threadIdx.x >> 6;
     uint32_t head = 0, tail = 0, cur = begin;                  // the ring's positions only ever grow; entry k lives in slot k & (2 * SHADE_THREADS - 1); all three are workgroup-uniform
@@ -448,7 +448,7 @@ __global__ void __launch_bounds__(SHADE_THREADS, MRT_SHADE_WAVES) k_shade(SceneV
         active = active && slot_to_pixel(fp, slot, px_x, px_y);
         if (active && !PLANES) q2store(&io.sample_primary[i], make_float4(0.0f, 0.0f, 0.0f, 0.0f));   // Raytracing.metal:227 (sample index = sub * capacity + slot)
     }
-    float4 H = make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
+    float4 H = miss_record();
     if (active && PAIRS) H = pairs_hit(s, io, i, __builtin_nontemporal_load(reinterpret_cast<const unsigned long long *>(io.hits) + i));
     else if (active) H = qload(&io.hits[i]);
     shade_entry<MATERIALS, CHAIN, PLANES, false>(s, fp, io, sh, i, H, active, make_float4(0.0f, 0.0f, 1.0f, 0.0f));

@@ -9,6 +9,9 @@ namespace mrt {
 namespace {
 
 struct TravHit { float t, U, V, ad; uint32_t gid; uint32_t pk = 0xFFFFFFFFu; };      // pk: packet of the hit (read after traverse<SEED> and the lane walks only)
+// The 16-byte hit record of the pipeline's `hits` queues: {t, u = U / |det|, v = V / |det|, global triangle id (bits)}; a miss is {-1, 0, 0, ~0}.
+MRT_DEV float4 miss_record() { return make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu)); }
+MRT_DEV float4 hit_record(bool hit, const TravHit &h) { return hit ? make_float4(h.t, h.U / h.ad, h.V / h.ad, __uint_as_float(h.gid)) : miss_record(); }
 
 MRT_DEV float safe_inv(float d) {
     float a = fabsf(d) < 1e-20f ? copysignf(1e-20f, d) : d;

@@ -35,13 +35,26 @@ namespace {
 #endif
 // -DMRT_DEBUG_BOUNDS (tools/build_variant.sh bounds "-DMRT_DEBUG_BOUNDS"): every node, packet and instance index the stream traversal is about
 // to follow is checked against its array; the first violation is recorded (kind << 28 | index) and the index replaced by 0, and the host
-// turns a non-zero record into MRT_ERR_STATE at the next wait (renderer.hip).  The release build has no such checks: the commit-time
+// turns a non-zero record into MRT_ERR_STATE at the next wait (check_bounds_record: Renderer::wait, query_stream).  The record belongs to the translation
+// unit — every unit that includes this header has its own, and reads its own kernels' violations.  The release build has no such checks: the commit-time
 // validator (two_level.hip validate_layout) is what keeps bad indices out of the arrays.
 #ifdef MRT_DEBUG_BOUNDS
 __device__ uint32_t g_bounds_violation = 0;
 #define MRT_BOUND(idx, limit, kind) do { if ((idx) >= (limit)) { atomicMax(&g_bounds_violation, ((uint32_t)(kind) << 28) | min((uint32_t)(idx), 0x0FFFFFFFu)); (idx) = 0; } } while (0)
+template <class = void> int check_bounds_record() {      // (a template: only a unit that calls it refers to its record from the host, which changes how its kernels address it)
+    uint32_t v = 0;
+    MRT_HIP(hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_bounds_violation), 4));
+    if (v) {
+        static const char *kinds[] = {"?", "8-wide node", "triangle packet", "wtlas_index slot", "instance id"};
+        const uint32_t zero = 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bounds_violation), &zero, 4);
+        set_error(std::string("MRT_DEBUG_BOUNDS: the stream traversal followed an index outside its array: ") + kinds[v >> 28 < 4u ? v >> 28 : 4u] + " " + std::to_string(v & 0x0FFFFFFFu));
+        return MRT_ERR_STATE;
+    }
+    return MRT_OK;
+}
 #else
 #define MRT_BOUND(idx, limit, kind) do { } while (0)
+inline int check_bounds_record() { return MRT_OK; }
 #endif
 // ((1 << width) - 1) << offset in one instruction (width, offset taken mod 32)
 MRT_DEV uint32_t bfm_b32(uint32_t width, uint32_t offset) { uint32_t r; asm("v_bfm_b32 %0, %1, %2" : "=v"(r) : "v"(width), "v"(offset)); return r; }
@@ -568,6 +581,28 @@ struct SegRegions {
             return true;
         }
         return false;
+    }
+};
+
+// The combined queue of a bounce, [next-bounce rays | shadow rays], as the fetch and emit of traverse_wide_stream.  SEG: the index is physical and carries SEG_SHADOW_BIT
+// (SegRegions); otherwise the shadow rays follow the n_next bounce rays.  PLANES_ONLY: shadow planes are known to be on (`lit` is not null; scon and sample are not read).
+template <bool SEG, bool PLANES_ONLY>
+struct MixedQueue {
+    const float4 *__restrict__ rayA, *__restrict__ rayB, *__restrict__ srayA, *__restrict__ srayB, *__restrict__ scon;
+    float4 *__restrict__ hits, *__restrict__ sample; uint8_t *__restrict__ lit; uint32_t n_next;
+    MRT_DEV void fetch(uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) const {      // tag = index in the ray's own queue
+        const bool sh = SEG ? (i & SEG_SHADOW_BIT) != 0u : i >= n_next; tag = SEG ? i & ~SEG_SHADOW_BIT : sh ? i - n_next : i; is_any = sh ? 1u : 0u;
+        A = qload(sh ? &srayA[tag] : &rayA[tag]); B = qload(sh ? &srayB[tag] : &rayB[tag]);
+        if (!sh) A.w = __builtin_inff();          // a bounce ray's tmax word may carry the throughput chain
+        else if (PLANES_ONLY || lit) tag = __float_as_uint(B.w);   // shadow planes: the ray reports to its pixel's byte
+    }
+    MRT_DEV void emit(uint32_t j, bool is_any, bool hit, const TravHit &h) const {
+        if (is_any) {
+            if (!hit) {
+                if (PLANES_ONLY || lit) lit[4 * (size_t)j] = 1;          // (lit points at this bounce's byte of pixel 0: four bytes per pixel and frame)
+                else { const uint32_t pix = __float_as_uint(srayB[j].w); float4 cc = qload(&scon[j]), a = q2load(&sample[pix]); q2store(&sample[pix], make_float4(a.x + cc.x, a.y + cc.y, a.z + cc.z, 0.0f)); }
+            }
+        } else qstore(&hits[j], hit_record(hit, h));
     }
 };
 

@@ -25,13 +25,9 @@ __global__ void __launch_bounds__(64, MRT_TWO_LEVEL_WAVES) k_tl_top(SceneView s,
     uint32_t *const cursor = stk_dyn + stack_words;          // two words behind the wave's stack: its block of the pair queue
     cursor[0] = 0; cursor[1] = 0;
     const PairQueue pq{pairs, pair_count, pair_cap, cursor};
+    const MixedQueue<false, true> q{rayA, rayB, srayA, srayB, nullptr, nullptr, nullptr, lit, n_next};      // (the fetch half: a bounce ray's result here is a key, not a hit record)
     traverse_wide_stream<true, false, false, PairQueue>(s, SharedCounter{work, n, chunk}, stk_dyn,
-        [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) {
-            const bool sh = i >= n_next; tag = sh ? i - n_next : i; is_any = sh ? 1u : 0u;
-            A = qload(sh ? &srayA[tag] : &rayA[tag]); B = qload(sh ? &srayB[tag] : &rayB[tag]);
-            if (!sh) A.w = __builtin_inff();          // a bounce ray's tmax word carries the throughput chain
-            else tag = __float_as_uint(B.w);            // a shadow ray reports to its pixel's byte
-        },
+        [&](uint32_t i, float4 &A, float4 &B, uint32_t &tag, uint32_t &is_any) { q.fetch(i, A, B, tag, is_any); },
         [&](uint32_t j, bool is_any, bool hit, const TravHit &h) {
             if (is_any) { if (!hit) lit[4 * (size_t)j] = 1; }          // not occluded at the TLAS level: lit unless one of its pairs finds an occluder
             else {

@@ -85,6 +85,54 @@ def test_uniforms_block_as_input(mrt, orc, gpu_ctx):
     r.close()
 
 
+@pytest.fixture(scope="module")
+def query_cases(mrt, orc, gpu_ctx):
+    """The Cornell box flattened and two-level, on the device and in the oracle, and 65 rays into it — one past a wave — with the oracle's answers (computed once)."""
+    sc = mrt.CornellScene((8, 8))
+    rng = np.random.default_rng(65)
+    o = np.array([0.0, 1.0, 2.5]) + rng.normal(size=(65, 3)) * 0.1
+    d = np.c_[rng.uniform(-0.9, 0.9, 65), rng.uniform(0.1, 1.9, 65), rng.uniform(-0.9, 0.9, 65)] - o
+    rays = np.zeros((65, 8), np.float32); rays[:, 0:3] = o; rays[:, 4:7] = d / np.linalg.norm(d, axis=1, keepdims=True); rays[:, 7] = np.inf
+    short = rays.copy(); short[:, 7] = rng.uniform(1.5, 4.0, 65)      # shadow-ray style: some end before the box's walls, some do not
+    out = {}
+    for form, opts, osc in (("flattened", {}, orc.OracleScene(mrt.flatten_scene(sc), sc.lights)),
+                            ("two_level", {"instancing": 1}, orc.OracleScene(mrt.flatten_scene(sc, share=True), sc.lights, instancing=True))):
+        ds = mrt.DeviceScene(gpu_ctx, sc, opts)
+        assert ds.stats.wide_layout == 1 and ds.stats.instances == 6          # (which form it is shows in the test: per-ray statistics are refused on a two-level scene)
+        out[form] = (ds, osc.intersect_closest(rays), osc.intersect_any(short))
+    yield rays, short, out
+    for ds, _, _ in out.values(): ds.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [0, 1, 65])
+@pytest.mark.parametrize("form", ["flattened", "two_level"])
+def test_host_ray_queries_at_the_sizes_around_a_wave(mrt, query_cases, form, n):
+    """The five entries that take rays from host memory (query.hip: one round trip for all of them), none, one and one past a wave of rays, both scene forms: the oracle's bits."""
+    rays, short, cases = query_cases
+    ds, closest, occluded = cases[form]
+    for g in (ds.intersect_closest(rays[:n]), ds.intersect_stream(rays[:n])):
+        assert len(g) == n
+        for f in ("type", "instance_id", "geometry_id", "primitive_id"):
+            assert np.array_equal(g[f], closest[f][:n]), f
+        for f in ("distance", "u", "v"):
+            assert np.array_equal(g[f].view(np.uint32), closest[f][:n].view(np.uint32)), f
+    assert np.array_equal(ds.intersect_any(short[:n]), occluded[:n])
+    assert np.array_equal(ds.intersect_stream(short[:n], any_hit=True)["type"], occluded[:n])
+    if n == 65: assert closest["type"].all() and 0 < occluded.sum() < 65          # the box is closed towards the rays; the short rays are of both kinds
+    for per_wave in (64, 256):          # lane accounting of the stream walk: word 7 is the wave's share of the rays; words 1-3 count lanes per iteration (word 0), 64 at most in each
+        st = ds.stream_stats(rays[:n], per_wave=per_wave)
+        assert st[:, 7].tolist() == [min(per_wave, n - b) for b in range(0, n, per_wave)]
+        assert (st[:, 0] >= 1).all() and (st[:, 1:4] <= 64 * st[:, 0:1]).all()
+    if form == "flattened":
+        st = ds.traversal_stats(rays[:n])
+        assert st.shape == (n, 8) and (st[:, 3] < ds.stats.triangles).all()          # every ray hits; word 3 is the hit's global triangle id: one id per (instance, geometry, primitive) of the oracle's hits
+        pairs = set(zip(st[:, 3].tolist(), closest["instance_id"][:n].tolist(), closest["geometry_id"][:n].tolist(), closest["primitive_id"][:n].tolist()))
+        assert len(pairs) == len({p[0] for p in pairs}) == len({p[1:] for p in pairs})
+    else:
+        with pytest.raises(mrt.MRTError): ds.traversal_stats(rays[:max(n, 1)])          # the per-lane counters exist for flattened scenes only
+
+
 @pytest.mark.gpu
 def test_frames_completed_never_blocks_and_ends_at_the_total(mrt, gpu_ctx):
     w, h = 640, 360
