@@ -261,6 +261,18 @@ struct Scene {                                                       // Scene.sw
         check(mrt_context_reproject_device(ctx, width, height, &camera, &prevCamera, deviceSurfaces, devicePrevPosition, devicePrevNormalDepth, devicePrevIds, devicePrevHistory,
                                            deviceSample, deviceOut, params, hipStream));
     }
+    // The variance-guided a-trous filter and the sample image of its moments (mrt_context_moments_sample_device / _denoise_variance_device).
+    // momentsSampleDevice writes {l, l * l, 0, 0} of a sample; a second reprojectDevice call of the frame with that image as deviceSample and its own previous output as
+    // devicePrevHistory accumulates it into deviceMoments {m1, m2, ., length}.  denoiseVarianceDevice filters deviceImage (the colour's reprojectDevice output) with a
+    // colour term in standard deviations (params->sigma_color; nullptr = the defaults); workspace and deviceOut as denoiseDevice.  On hipStream; no allocation, copy or wait.
+    static void momentsSampleDevice(MRTContext ctx, int width, int height, const void *deviceSample, const void *deviceAlbedo, bool demodulate, void *deviceOut, void *hipStream) {
+        check(mrt_context_moments_sample_device(ctx, width, height, deviceSample, deviceAlbedo, demodulate ? 1 : 0, deviceOut, hipStream));
+    }
+    static void denoiseVarianceDevice(MRTContext ctx, int width, int height, const void *deviceImage, const void *deviceMoments, const void *deviceNormalDepth, const void *deviceAlbedo,
+                                      void *deviceWorkspace, size_t workspaceBytes, void *deviceOut, const MRTDenoiseParams *params, void *hipStream) {
+        check(mrt_context_denoise_variance_device(ctx, width, height, deviceImage, deviceMoments, deviceNormalDepth, deviceAlbedo, deviceWorkspace, workspaceBytes, deviceOut, params,
+                                                  hipStream));
+    }
     // each mesh's first attribute row (an instance reports its source's) and, last, the number of rows: meshCount + 1 entries
     static std::vector<uint64_t> vertexOffsets(MRTScene scene, size_t meshCount) {
         std::vector<uint64_t> o(meshCount + 1); check(mrt_scene_vertex_offsets(scene, o.data(), o.size())); return o;
@@ -414,6 +426,14 @@ class Renderer {                                                     // Renderer
                          const void *devicePrevIds, const void *devicePrevHistory, const void *deviceSample, void *deviceOut, const MRTReprojectParams *params, void *hipStream) {
         Scene::reprojectDevice(ctx_, w_, h_, camera, prevCamera, deviceSurfaces, devicePrevPosition, devicePrevNormalDepth, devicePrevIds, devicePrevHistory, deviceSample, deviceOut,
                                params, hipStream);
+    }
+    // the moments' sample image and the variance-guided filter (Scene::momentsSampleDevice / denoiseVarianceDevice): images of this renderer's size
+    void momentsSampleDevice(const void *deviceSample, const void *deviceAlbedo, bool demodulate, void *deviceOut, void *hipStream) {
+        Scene::momentsSampleDevice(ctx_, w_, h_, deviceSample, deviceAlbedo, demodulate, deviceOut, hipStream);
+    }
+    void denoiseVarianceDevice(const void *deviceImage, const void *deviceMoments, const void *deviceNormalDepth, const void *deviceAlbedo, void *deviceWorkspace, size_t workspaceBytes,
+                               void *deviceOut, const MRTDenoiseParams *params, void *hipStream) {
+        Scene::denoiseVarianceDevice(ctx_, w_, h_, deviceImage, deviceMoments, deviceNormalDepth, deviceAlbedo, deviceWorkspace, workspaceBytes, deviceOut, params, hipStream);
     }
     MRTRenderStats stats() { MRTRenderStats s; check(mrt_renderer_stats(r_, &s)); return s; }
     MRTSceneStats sceneStats() { MRTSceneStats s; check(mrt_scene_stats(scene_, &s)); return s; }

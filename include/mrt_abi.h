@@ -808,6 +808,55 @@ int mrt_context_reproject_device(MRTContext ctx, int32_t width, int32_t height, 
                                  const void *d_prev_position, const void *d_prev_normal_depth, const void *d_prev_ids, const void *d_prev_history, const void *d_sample,
                                  void *d_out, const MRTReprojectParams *params, void *hip_stream);
 
+/* Variance-guided a-trous filter on DEVICE buffers, with moments, ordered on a stream of the caller's: the spatial step of SVGF (Schied et al. 2017)
+ * after the temporal one above.  mrt_context_denoise_device filters every pixel with one sigma_color / step, whatever its history; this filter measures the colour
+ * difference of a tap in standard deviations of the pixel's own luminance, estimated from the two accumulated luminance moments where the history is long enough and
+ * from the moments of the pixel's neighbourhood where it is not, and carries that variance through its levels.  The common rules of the image stages above hold: buffers
+ * of the context's device, hip_stream taken literally, nothing allocated, copied from host memory or waited for; plain arguments checked first, each message naming its
+ * argument, a NULL context refused last; every refusal leaves the outputs untouched.  Neither entry reads a scene.  Images are width * height entries of 16 bytes, pixel
+ * p = y * width + x, row 0 = bottom.  Arithmetic: float32, one rounding per operation, no fused multiply-add, IEEE divide, correctly rounded sqrt.  k(x) = max(0, 1 - x),
+ * max(a, b) = fmaxf, lum(c) = (0.2126 c.x + 0.7152 c.y) + 0.0722 c.z, A_p = max(albedo_p.rgb, 1e-3) per channel if demodulate and albedo_p.w != 0, else 1 — the A of
+ * mrt_renderer_denoise.
+ *   The temporal accumulation of the moments is DEFINED as a second call of mrt_context_reproject_device on the same stream, with the same cameras, surfaces, previous
+ *   guide entries, previous positions and parameters: d_sample = the image mrt_context_moments_sample_device wrote and d_prev_history = the previous frame's output of
+ *   that same second call (zeros at the start).  Its output is {m1, m2, 0, len}: the reprojected first and second luminance moment, blended with the taps, weights and
+ *   length of the colour's call.  No reprojection kernel is added.
+ *   mrt_context_moments_sample_device: d_out_p = {l, l * l, 0, 0} with c = sample_p.rgb / A_p, l = lum(c); demodulate != 0 divides by the albedo.  sample_p.w is ignored.
+ *     With the albedo buffer the filter is given, the moments are in the units of the signal the filter works on.  ONE kernel: one 16-byte load per input, one 16-byte store.
+ *     MRT_ERR_INVALID_ARGUMENT: width or height <= 0, width * height >= 2^30, a NULL or not 16-byte aligned buffer, d_out overlapping an input (byte ranges).
+ *   mrt_context_denoise_variance_device: d_image float4, rgb = the accumulated colour (mrt_context_reproject_device's output; w ignored); d_moments float4 {m1, m2, ., len}
+ *     (the second call's output); d_normal_depth, d_albedo, d_workspace (mrt_denoise_workspace_bytes: two images), d_out, the order of the checks, the overlap rules and the
+ *     1 + iterations launches exactly as mrt_context_denoise_device.  params == NULL = the MRT_DENOISE_DEFAULT_* values, but sigma_color is IN STANDARD DEVIATIONS and is not
+ *     divided by the step.  The inputs are not modified; the output alpha is 1.
+ *     A working entry is {I.rgb, v}, 16 bytes: the variance rides in the word where mrt_renderer_denoise keeps coverage.  A pixel that is not covered (albedo.w == 0) stores
+ *     v = -1.  A tap is skipped iff its v < 0 or it lies outside the image.  A covered pixel's v is never negative: every v below ends in max(0, .) or is a sum of
+ *     non-negative terms.  A pixel that is not covered is copied through every level to the bit and is never a tap; its d_out is image.rgb, alpha 1.  Skipped taps are
+ *     branched over or selected away, never multiplied by 0: a NaN in an entry that is not covered or lies outside does not reach a covered output.
+ *     Prepass: I_p = image_p.rgb / A_p.  Covered and len_p >= MRT_VARIANCE_MIN_HISTORY: v_p = max(0, m2 - m1 * m1).  Covered with a shorter history (a NaN len counts as
+ *       shorter): the spatial estimate over the 7 x 7 window at distance 1, row-major from (-3, -3) — taps q inside the image with albedo_q.w != 0 take
+ *       w = k(xn)^2 * k(xz)^2 with xn = (1 - max(0, (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z)) / sigma_normal, xz = |t_p - t_q| / (sigma_depth * t_p), the centre takes
+ *       w = 1;  s1 += w * m1_q; s2 += w * m2_q; sw += w;  M1 = s1 / sw, M2 = s2 / sw;  v_p = max(0, M2 - M1 * M1) * (4 / max(len_p, 1)) — SVGF's boost for young pixels.
+ *     Iteration it (step = 1 << it), for a covered pixel p:
+ *       1. g = the 3 x 3 Gaussian of v over the ADJACENT pixels, at distance 1 at every level: weights 1/4 centre, 1/8 edges, 1/16 corners; taps inside the image with
+ *          v_q >= 0, row-major from (-1, -1): gs += weight * v_q; gw += weight;  g = gs / gw.
+ *       2. den = sigma_color * sqrt(g) + MRT_VARIANCE_EPSILON.
+ *       3. The 25 taps q = p + step * (dx, dy) in mrt_renderer_denoise's order with its h, xn and xz (xz = |t_p - t_q| / ((sigma_depth * t_p) * step)) and
+ *          xc = |lum(I_p) - lum(I_q)| / den:  w = ((h * k(xn)^2) * k(xz)^2) * k(xc)^2, the centre takes w = h;  sum += w * I_q; vs += (w * w) * v_q; wsum += w.
+ *       4. I'_p = sum / wsum, v'_p = vs / (wsum * wsum).
+ *     The last iteration writes {I' * A_p, 1} to d_out.
+ *     MRT_ERR_INVALID_ARGUMENT: as mrt_context_denoise_device, d_moments being a fourth input; and height > MRT_VARIANCE_MAX_HEIGHT — a workgroup of the prepass and of
+ *     the larger steps covers 8 rows and a launch has at most 65535 workgroups in y.  (mrt_context_denoise_device has the same launch shape and no such check: an image
+ *     taller than that fails there with MRT_ERR_HIP.)
+ * Not provided: Renderer.draw does neither (mrt_renderer_denoise is the fixed-sigma filter); no stage makes d_prev_position; the first level's output is not fed back into
+ * the colour history as SVGF does; the two reprojection calls of a frame are not fused into one launch.                                                                 */
+#define MRT_VARIANCE_MIN_HISTORY 4.0f     /* frames of history from which a pixel's own two moments give its variance                     */
+#define MRT_VARIANCE_MAX_HEIGHT  524280   /* 65535 * 8: the tallest image mrt_context_denoise_variance_device takes                      */
+#define MRT_VARIANCE_EPSILON     1e-6f    /* added to sigma_color * sqrt(g): a pixel of variance 0 accepts taps of its own luminance only */
+int mrt_context_moments_sample_device(MRTContext ctx, int32_t width, int32_t height, const void *d_sample, const void *d_albedo, int32_t demodulate, void *d_out,
+                                      void *hip_stream);
+int mrt_context_denoise_variance_device(MRTContext ctx, int32_t width, int32_t height, const void *d_image, const void *d_moments, const void *d_normal_depth,
+                                        const void *d_albedo, void *d_workspace, size_t workspace_bytes, void *d_out, const MRTDenoiseParams *params, void *hip_stream);
+
 /* ---------------------------------------------------------------- device group (multi-GPU, one process)
  * The reference creates ONE device and ONE queue (MTLCreateSystemDefaultDevice + makeCommandQueue, Renderer.swift:46-59); this is that
  * seam widened to the n GPUs of a node.  The scene and its BVH are replicated on every device; the image is sharded by 8x8 screen tile

@@ -256,6 +256,8 @@ SIGNATURES = {
     "mrt_context_denoise_device": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _SZ, _P, C.POINTER(DenoiseParams), _P]),
     "mrt_context_tonemap_device": (C.c_int, [_P, _I32, _I32, _P, _P, _P]),
     "mrt_context_reproject_device": (C.c_int, [_P, _I32, _I32, C.POINTER(Camera), C.POINTER(Camera), _P, _P, _P, _P, _P, _P, _P, C.POINTER(ReprojectParams), _P]),
+    "mrt_context_moments_sample_device": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _P, _P]),
+    "mrt_context_denoise_variance_device": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P, C.POINTER(DenoiseParams), _P]),
     "mrt_renderer_stats": (C.c_int, [_P, C.POINTER(RenderStats)]),
     "mrt_renderer_reset_stats": (C.c_int, [_P]),
     "mrt_renderer_kernel_times": (C.c_int, [_P, C.POINTER(KernelTimes)]),

@@ -6,6 +6,7 @@
 #include "paths.h"
 #include "image.h"
 #include "temporal.h"
+#include "variance.h"
 #include "../../include/mrt_debug.h"
 #include <algorithm>
 #include <cstring>
@@ -989,6 +990,54 @@ int mrt_context_reproject_device(MRTContext ctx, int32_t width, int32_t height, 
     if (int rc = bind_device(ctx)) return rc;
     return mrt::reproject_device((hipStream_t)hip_stream, width, height, *camera, *prev_camera, d_surfaces, d_prev_position, d_prev_normal_depth, d_prev_ids, d_prev_history, d_sample,
                                  d_out, p);
+    MRT_CATCH
+}
+// The variance-guided filter and the sample image of its moments (variance.hip).  The same order again; the filter's checks are
+// mrt_context_denoise_device's with d_moments a fourth input.
+int mrt_context_moments_sample_device(MRTContext ctx, int32_t width, int32_t height, const void *d_sample, const void *d_albedo, int32_t demodulate, void *d_out, void *hip_stream) {
+    MRT_TRY
+    const std::string who = "mrt_context_moments_sample_device";
+    REQUIRE_IMAGE_SIZE();
+    const size_t n = (size_t)width * (size_t)height, image_bytes = n * 16;
+    REQUIRE_GIVEN(d_sample); REQUIRE_GIVEN(d_albedo); REQUIRE_GIVEN(d_out);
+    REQUIRE_ALIGNED(d_sample, 16); REQUIRE_ALIGNED(d_albedo, 16); REQUIRE_ALIGNED(d_out, 16);
+    const ByteRange inputs[2] = {byte_range(d_sample, image_bytes, "d_sample"), byte_range(d_albedo, image_bytes, "d_albedo")};
+    const ByteRange out = byte_range(d_out, image_bytes, "d_out");
+    for (const ByteRange &in : inputs) REQUIRE(!ranges_overlap(out, in), who + ": d_out overlaps " + in.what);
+    REQUIRE(ctx, who + ": ctx is NULL");
+    if (int rc = bind_device(ctx)) return rc;
+    return mrt::moments_sample_device((hipStream_t)hip_stream, width, height, d_sample, d_albedo, demodulate != 0, d_out);
+    MRT_CATCH
+}
+int mrt_context_denoise_variance_device(MRTContext ctx, int32_t width, int32_t height, const void *d_image, const void *d_moments, const void *d_normal_depth, const void *d_albedo,
+                                        void *d_workspace, size_t workspace_bytes, void *d_out, const MRTDenoiseParams *params, void *hip_stream) {
+    MRT_TRY
+    const std::string who = "mrt_context_denoise_variance_device";
+    REQUIRE_IMAGE_SIZE();
+    REQUIRE(height <= MRT_VARIANCE_MAX_HEIGHT, who + ": height must be at most 524280 (rows of 8 pixels per workgroup, 65535 workgroups in y)");
+    MRTDenoiseParams p{};
+    if (params) p = *params;
+    else { p.iterations = MRT_DENOISE_DEFAULT_ITERATIONS; p.sigma_color = MRT_DENOISE_DEFAULT_SIGMA_COLOR; p.sigma_normal = MRT_DENOISE_DEFAULT_SIGMA_NORMAL; p.sigma_depth = MRT_DENOISE_DEFAULT_SIGMA_DEPTH; p.demodulate = 1; }
+    REQUIRE(p.iterations >= 1 && p.iterations <= 8, who + ": denoise: iterations must be in [1,8]");
+    const float big = 3.0e38f;
+    REQUIRE((p.sigma_color > 0.0f && p.sigma_color < big) && (p.sigma_normal > 0.0f && p.sigma_normal < big) && (p.sigma_depth > 0.0f && p.sigma_depth < big),
+            who + ": denoise: sigma_color, sigma_normal and sigma_depth must be finite and > 0");
+    REQUIRE(p.demodulate == 0 || p.demodulate == 1, who + ": denoise: demodulate must be 0 or 1");
+    const size_t n = (size_t)width * (size_t)height, image_bytes = n * 16, need = mrt::denoise_workspace_bytes(width, height);
+    REQUIRE_GIVEN(d_image); REQUIRE_GIVEN(d_moments); REQUIRE_GIVEN(d_normal_depth); REQUIRE_GIVEN(d_albedo); REQUIRE_GIVEN(d_workspace); REQUIRE_GIVEN(d_out);
+    REQUIRE_ALIGNED(d_image, 16); REQUIRE_ALIGNED(d_moments, 16); REQUIRE_ALIGNED(d_normal_depth, 16); REQUIRE_ALIGNED(d_albedo, 16); REQUIRE_ALIGNED(d_workspace, 16); REQUIRE_ALIGNED(d_out, 16);
+    REQUIRE(workspace_bytes >= need, who + ": workspace_bytes is below mrt_denoise_workspace_bytes(width, height)");
+    const ByteRange inputs[4] = {byte_range(d_image, image_bytes, "d_image"), byte_range(d_moments, image_bytes, "d_moments"), byte_range(d_normal_depth, image_bytes, "d_normal_depth"),
+                                 byte_range(d_albedo, image_bytes, "d_albedo")};
+    const ByteRange work = byte_range(d_workspace, need, "d_workspace"), out = byte_range(d_out, image_bytes, "d_out");
+    for (const ByteRange &in : inputs) {
+        REQUIRE(!ranges_overlap(out, in), who + ": d_out overlaps " + in.what);
+        REQUIRE(!ranges_overlap(work, in), who + ": d_workspace overlaps " + in.what);
+    }
+    REQUIRE(!ranges_overlap(out, work), who + ": d_out overlaps d_workspace");
+    REQUIRE(ctx, who + ": ctx is NULL");
+    if (int rc = bind_device(ctx)) return rc;
+    return mrt::denoise_variance_device((hipStream_t)hip_stream, width, height, d_image, d_moments, d_normal_depth, d_albedo, d_workspace, d_out, p);
     MRT_CATCH
 }
 #undef REQUIRE_IMAGE_SIZE

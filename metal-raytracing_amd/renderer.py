@@ -587,6 +587,71 @@ class DeviceScene:
                                              C.c_void_p(self._stream_handle(stream))))
         return out
 
+    def _images(self, size, **tensors):
+        """size = (width, height) and named image tensors -> (w, h, the device): each a contiguous float32 tensor of shape (h, w, 4) or (h * w, 4) on the context's device"""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        w, h = int(size[0]), int(size[1])
+        self.denoise_workspace_bytes((w, h))                                                            # (refuses a size that is not positive or too large)
+        shapes = ((h, w, 4), (h * w, 4))
+        for what, t in tensors.items():
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or tuple(t.shape) not in shapes or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous torch.float32 tensor of shape {shapes[0]} or {shapes[1]} on {dev}")
+        return w, h, dev
+
+    def moments_sample_device(self, sample, albedo, size, demodulate=None, out=None, stream=None):
+        """The sample image of the luminance moments, on the GPU and ordered on a stream: sample and albedo float32 tensors of width x height x 4 elements — (h, w, 4) or
+        (h * w, 4), row 0 = bottom — size = (width, height) -> float32 of sample's shape, {l, l * l, 0, 0} per pixel with l the luminance of sample.rgb / A and A the
+        albedo term of denoise_device (demodulate, default 1; 0: A = 1).  A second reproject_device call of the frame — the same surfaces, previous guide entries, cameras,
+        previous positions and parameters, this image as its sample and its own previous output as prev_history — accumulates it into the moments {m1, m2, 0, length}
+        denoise_variance_device reads.  out: the tensor to write (sample's shape; it may not overlap an input), allocated when None.  Otherwise nothing is allocated,
+        copied or synchronised.  stream: as intersect_closest_device takes it."""
+        import torch
+        from ._ffi import DENOISE_DEFAULTS
+        w, h, _ = self._images(size, sample=sample, albedo=albedo)
+        if out is None:
+            out = torch.empty_like(sample)
+        else:
+            self._images(size, out=out)
+            if tuple(out.shape) != tuple(sample.shape):
+                raise ValueError("out must have sample's shape")
+        demodulate = int(DENOISE_DEFAULTS["demodulate"] if demodulate is None else demodulate)
+        check(lib.mrt_context_moments_sample_device(self.ctx.handle, w, h, C.c_void_p(sample.data_ptr()), C.c_void_p(albedo.data_ptr()), demodulate, C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(self._stream_handle(stream))))
+        return out
+
+    def denoise_variance_device(self, image, moments, normal_depth, albedo, size, iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None, demodulate=None, out=None,
+                                workspace=None, stream=None):
+        """The variance-guided a-trous filter (the spatial step of SVGF) of an image the caller holds, on the GPU and ordered on a stream: image, moments, normal_depth and
+        albedo are float32 tensors of width x height x 4 elements — (h, w, 4) or (h * w, 4), row 0 = bottom — size = (width, height) -> the filtered image, float32 of
+        image's shape, alpha 1.  image: rgb = the accumulated colour, reproject_device's output (image[..., 3] is ignored); moments: {m1, m2, ., length}, the output of the
+        frame's second reproject_device call on moments_sample_device's image.  A pixel with a history of at least 4 frames takes its variance from its own two moments,
+        a younger one from the moments of its 7 x 7 neighbourhood, boosted by 4 / length; every level measures a tap's luminance difference in standard deviations of
+        the pixel (sigma_color, default 4, is in standard deviations here and is not divided by the step) and carries the variance on.  The other parameters and their
+        defaults are denoise_device's, and so are out and workspace (denoise_workspace_bytes(size) bytes).  The definition is include/mrt_abi.h's.  No input is modified.
+        Nothing is allocated (but out and workspace when None), copied or synchronised.  stream: as intersect_closest_device takes it."""
+        import torch
+        from ._ffi import DENOISE_DEFAULTS, DenoiseParams
+        w, h, dev = self._images(size, image=image, moments=moments, normal_depth=normal_depth, albedo=albedo)
+        need = self.denoise_workspace_bytes((w, h))
+        if out is None:
+            out = torch.empty_like(image)
+        else:
+            self._images(size, out=out)
+            if tuple(out.shape) != tuple(image.shape):
+                raise ValueError("out must have image's shape")
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        elif not isinstance(workspace, torch.Tensor) or workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+            raise ValueError(f"workspace must be a contiguous torch.uint8 tensor on {dev} (denoise_workspace_bytes(size) bytes)")
+        given = dict(iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_depth=sigma_depth, demodulate=demodulate)
+        v = {k: (DENOISE_DEFAULTS[k] if x is None else x) for k, x in given.items()}
+        p = DenoiseParams(int(v["iterations"]), float(v["sigma_color"]), float(v["sigma_normal"]), float(v["sigma_depth"]), int(v["demodulate"]))
+        check(lib.mrt_context_denoise_variance_device(self.ctx.handle, w, h, C.c_void_p(image.data_ptr()), C.c_void_p(moments.data_ptr()), C.c_void_p(normal_depth.data_ptr()),
+                                                      C.c_void_p(albedo.data_ptr()), C.c_void_p(workspace.data_ptr() if workspace.numel() else None), workspace.numel(),
+                                                      C.c_void_p(out.data_ptr()), C.byref(p), C.c_void_p(self._stream_handle(stream))))
+        return out
+
     def tonemap_device(self, image, size, out=None, stream=None):
         """Renderer.tonemapped() of an image the caller holds, left on the GPU and ordered on a stream: image a float32 tensor of shape (h, w, 4) or (h * w, 4), row 0 =
         bottom, size = (width, height) -> torch.uint8 (h, w, 4), top row first: Reinhard, saturate, round to 8 bits, alpha 255.  out: the tensor to write, allocated
